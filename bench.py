@@ -89,6 +89,31 @@ def attach_profile(path, kernel_name, fingerprint, root=None):
     return dict(j, source=rel), None
 
 
+DUMP_LIMIT_BYTES = 64_000_000      # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: write the per-user arrays of one scoring pass (first axis: the pass's user rows) as out_dir/<name>.npy
+    -- float32 / float64 arrays as they are, integer ones as float64 (exact) -- and rows.npy, the user rows they hold.  A pass
+    too large for `limit` bytes keeps a fixed, seeded sample of its rows (sorted), the same sample for the same arguments.
+    Arrays that are None are not written.  Returns the names written."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items() if v is not None}
+    arrays = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    assert all(v.shape[0] == n for v in arrays.values()), "arrays of one pass must have one row per user"
+    per_row = 8 + sum(v.dtype.itemsize * int(np.prod(v.shape[1:])) for v in arrays.values())    # (+ 8: rows.npy)
+    room = limit - 256 * (len(arrays) + 1)                                                         # (.npy headers)
+    if per_row * n <= room:
+        rows = np.arange(n)
+    else:
+        rows = np.sort(np.random.default_rng(seed).choice(n, room // per_row, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(v[rows]))
+    return ["rows"] + list(arrays)
+
+
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
@@ -370,7 +395,13 @@ def main() -> None:
     ap.add_argument("--no-c4", action="store_true",
                     help="skip the `c4` leg of the default (c3) line: BASELINE config 4's shape (1 M x 500k, 100 M interactions), "
                          "sharded fit + all-users scoring at this --gpus N (about 45 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned -- top-k ids, scores (when the pass "
+                         "returns them) and list lengths of every user -- as DIR/<name>.npy, plus DIR/rows.npy, the user rows "
+                         "they cover (all of them, or a fixed seeded sample when that would exceed 64 MB); same inputs every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     shard_auto = args.score_shard == "auto" and not args.shard_w
     if args.shard_w:
         args.score_shard = "columns"
@@ -631,6 +662,11 @@ def main() -> None:
     ms_per_step = dt / args.steps * 1e3
     value = U * args.steps / dt
     crc_main = zlib.crc32(out[0].cpu().numpy().tobytes())
+    if args.dump_outputs and rank == 0:         # what the last timed step handed back (every rank holds the full lists)
+        names = dump_outputs(args.dump_outputs, {"topk_ids": out[0].cpu().numpy(),
+                                                  "topk_scores": None if out[1] is None else out[1].cpu().numpy(),
+                                                  "topk_counts": out[2].cpu().numpy()})
+        log(f"[bench] last timed step's outputs written to {args.dump_outputs}: {', '.join(n + '.npy' for n in names)}")
     if out[1] is None:          # the timed exchange carried ids + counts only: the bookkeeping below reads the scores too
         out = eng.score_topk_device(None, U, top_k, True, _native.TOPK_SPARSE, d_rows=d_rows, xb=xb, with_scores=True)
 

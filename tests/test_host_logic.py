@@ -1009,6 +1009,41 @@ def test_bench_attaches_a_profile_summary_only_for_the_build_it_times(tmp_path):
     assert not build.same_build({"lib_sha256": "x", "src_sha256": "y"}, f) and not build.same_build({}, f) and not build.same_build(None, None)
 
 
+def test_bench_dump_outputs_writes_exact_float_arrays_within_the_size_limit(tmp_path):
+    """bench.py --dump-outputs: integer arrays become exact float64, float32 stays float32 bit for bit, a pass too large for the
+    limit keeps the same seeded, sorted sample of rows every time, and no file set exceeds the limit."""
+    import bench
+    rng = np.random.default_rng(4)
+    U, k = 5000, 10
+    ids = rng.integers(-1, 1 << 30, (U, k), dtype=np.int32)
+    sc = rng.standard_normal((U, k)).astype(np.float32)
+    cnt = rng.integers(0, k + 1, U).astype(np.int32)
+    arrays = {"topk_ids": ids, "topk_scores": sc, "topk_counts": cnt}
+
+    def load(d):
+        return {p.stem: np.load(p) for p in d.iterdir()}
+    full = tmp_path / "full"
+    assert bench.dump_outputs(str(full), arrays) == ["rows", "topk_ids", "topk_scores", "topk_counts"]
+    f = load(full)
+    assert f["rows"].dtype == np.float64 and np.array_equal(f["rows"], np.arange(U))
+    assert f["topk_ids"].dtype == np.float64 and np.array_equal(f["topk_ids"].astype(np.int64), ids)
+    assert f["topk_scores"].dtype == np.float32 and np.array_equal(f["topk_scores"].view(np.uint32), sc.view(np.uint32))
+    assert f["topk_counts"].dtype == np.float64 and np.array_equal(f["topk_counts"], cnt)
+    limit = 200_000
+    runs = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        bench.dump_outputs(str(d), arrays, limit=limit)
+        assert sum(p.stat().st_size for p in d.iterdir()) <= limit
+        runs.append(load(d))
+    rows = runs[0]["rows"].astype(np.int64)
+    assert 0 < len(rows) < U and np.all(np.diff(rows) > 0)
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name])
+    assert np.array_equal(runs[0]["topk_ids"], ids[rows]) and np.array_equal(runs[0]["topk_counts"], cnt[rows])
+    assert bench.dump_outputs(str(tmp_path / "ids_only"), dict(arrays, topk_scores=None)) == ["rows", "topk_ids", "topk_counts"]
+
+
 # ---- the scoring dispatch as pure functions (rtrec_amd/score_plan.py): explicit table + invariants over the cross product ----
 def _facts(**kw):
     from rtrec_amd import score_plan as sp_
