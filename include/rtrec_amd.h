@@ -266,7 +266,9 @@ typedef struct {
      * last << 25, d_fr_tile_rows[g * 2 + h] bit f = 1 iff the fragment holds row 64 h + f, d_fr_tile_off[g] = its byte
      * offset inside its super-tile.  Consecutive fragments (at most 64) form fr_n_super super-tiles, fragments
      * d_fr_super_tile[s] .. d_fr_super_tile[s + 1] - 1, each staged as one piece: d_fr_w holds the super-tiles back
-     * to back, each a whole number of KiB starting at KiB d_fr_super_kb[s] (fr_n_super + 1 entries both).
+     * to back, each a whole number of KiB starting at KiB d_fr_super_kb[s] (fr_n_super + 1 entries both), and then, at
+     * float d_fr_super_kb[fr_n_super] * 256, fr_n_frags floats: per fragment 1.0001 * max |w| over its whole tile
+     * (float32-rounded), the kernel's first-level tile bound.
      * fr_buf_bytes (a multiple of 1024, >= the largest super-tile) is the size of one LDS staging buffer.  Two forms:
      *   streaming  fr_buf_bytes >= 32 KiB and 2 * (2 * fr_buf_bytes + 5136) <= 160 KiB: two 8-wave workgroups per CU,
      *              two buffers each (a tile may continue in the next super-tile: its sums stay in registers);

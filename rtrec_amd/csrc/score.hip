@@ -1032,7 +1032,8 @@ struct FrArgs {
     const int *col_map;     // [n_items] item -> layout column, or -1
     const int *col_ids;     // [n_cols]  layout column -> item id (ascending)
     int n_cols, R, n_tiles;
-    const float *wd;        // the tiles' slices, super-tile after super-tile: per tile its rows that hold a weight, ascending
+    const float *wd;        // the tiles' slices, super-tile after super-tile: per tile its rows that hold a weight, ascending;
+                            // then [n_frags]: 1.0001 * max |w| over the fragment's tile (the first-level tile bound)
     const unsigned long long *tile_rows;   // [n_frags][2]: bit f of word h set <=> the fragment holds row 64 h + f of its tile's slice
     const int *tile_off;    // [n_frags]: byte offset of the fragment inside its super-tile
     const int *frag_tile;   // [n_frags]: tile | first << 24 | last << 25 (a slice may be cut into consecutive fragments)
@@ -1188,6 +1189,7 @@ __device__ __forceinline__ void fr_static_for(F &&f) {
 }
 
 typedef const __attribute__((address_space(4))) unsigned long long fr_const_u64;
+typedef const __attribute__((address_space(4))) float fr_const_f32;
 
 // First-touch row of layout column c for a user who rates the rows own0 / own1 (bit f: row f / 64 + f of W): the lowest
 // such row with a weight in that column -- scipy's csr_matmat meets the user's items in ascending order, and rows of W
@@ -1255,6 +1257,8 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
     uint32_t *xs_wave = reinterpret_cast<uint32_t *>(sc_wave);
     unsigned long long *ms_wave = sc_wave + kFrUsers * kFrUserWords / 2;
     const uint32_t lane16 = static_cast<uint32_t>(lane) * (REGS * 4);         // byte offset of this lane in a row
+    // behind the super-tiles: per fragment, 1.0001 * the largest max|w| of its tile's rows (the first-level bound below)
+    fr_const_f32 *frag_wtop = (fr_const_f32 *)(a.wd + (static_cast<size_t>(a.st_kb[a.n_super]) << 8));
 
     // super-tile s = tiles [st_tile[s], st_tile[s + 1]): their rows that hold a weight, tile after tile, st_kb[s + 1] - st_kb[s] KiB
     auto load_super = [&](int sidx, unsigned char *dst) {
@@ -1481,27 +1485,21 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                     //      list only by BEATING the user's (k+1)-th best: when B_u <= that for all eight users the
                     //      sweep, the selection and the tile's further fragments are skipped -- after the heavy first
                     //      tiles that is the fate of nine tiles in ten (ML-20M shape). ----
-                    float wm[XR];
-                    fr_static_for<XR>([&](auto H) {
-                        wm[H()] = *reinterpret_cast<const float *>(wb + toff - kFrTileHeaderBytes + (H() * 64 + lane) * 4);
-                    });
                     // first level, all eight users in one compare: (sum_f |x_uf|) * max_f max|w_f| -- decides 86 % of
-                    // the (wave, tile) pairs on the ML-20M shape; only the others pay the per-user reductions below
-                    float wmm = wm[0];
-                    if constexpr (XR == 2) wmm = fmaxf(wmm, wm[1]);
-                    wmm = fmaxf(wmm, fr_dpp_f<0x111>(wmm, 0.0f));
-                    wmm = fmaxf(wmm, fr_dpp_f<0x112>(wmm, 0.0f));
-                    wmm = fmaxf(wmm, fr_dpp_f<0x114>(wmm, 0.0f));
-                    wmm = fmaxf(wmm, fr_dpp_f<0x118>(wmm, 0.0f));
-                    wmm = fmaxf(wmm, fr_dpp_f<0x142>(wmm, 0.0f));
-                    wmm = fmaxf(wmm, fr_dpp_f<0x143>(wmm, 0.0f));
-                    const float wtop = __fmul_rn(readlane_f(wmm, 63), 1.0001f);
+                    // the (wave, tile) pairs on the ML-20M shape; only the others read the header and pay the per-user
+                    // reductions below.  max_f max|w_f| (times the margin) is a constant of W: the layout stores it
+                    // per fragment (frag_wtop) instead of every wave reducing the header again for every job
+                    const float wtop = frag_wtop[g];                 // scalar load
                     // (a user with NO rating on a row of W -- an empty row, a position past the end of the batch in the last job --
                     // has bound 0: every sum is +0, no candidate; it must not hold the tile open while its list is empty.  Such a
                     // slot used to keep its wave sweeping EVERY tile: a batch whose size is no multiple of the job size paid one
                     // unpruned wave at its end, 0.06-0.09 ms whatever its size -- tools/row_slice_probe.py, round 4)
                     const unsigned long long open1 = __ballot(lane < UW && l1v > 0.0f && !(thrv >= 0.0f && __fmul_rn(l1v, wtop) <= thrv));
                     bool all_skip = true;
+                    float wm[XR];
+                    if (open1) fr_static_for<XR>([&](auto H) {
+                        wm[H()] = *reinterpret_cast<const float *>(wb + toff - kFrTileHeaderBytes + (H() * 64 + lane) * 4);
+                    });
                     if (open1) fr_static_for<UW>([&](auto Uc) {
                         constexpr int u = decltype(Uc)::value;
                         float b = __fmul_rn(fabsf(xr[u][0]), wm[0]);

@@ -156,13 +156,18 @@ def build_feature_rows(W_csc: sp.csc_matrix, col_lo: int, col_hi: int, col_ids: 
     P = _pack_fragments(n_rows_t.astype(np.int64), tc)           # slices -> fragments -> super-tiles staged in LDS
     k_of = local[t_of, f_of]                                     # rank of the weight's row among its tile's stored rows
     g_of = P["frag_of"][t_of, k_of]                              # ... and the fragment that holds it
-    wd = np.zeros(max(int(P["super_kb"][-1]) * 256, 256), dtype=np.float32)
+    wd = np.zeros(int(P["super_kb"][-1]) * 256 + P["n_frags"], dtype=np.float32)     # the super-tiles, then frag_wtop
     base = P["super_kb"][P["frag_super"][g_of]] * 256 + P["frag_off"][g_of] // 4
     wd[base + (k_of - P["frag_k0"][g_of]) * tc + lc % tc] = vals
     # tile headers: max |w| per row -- the kernel skips a tile for a wave when sum_f |x_f| max|w_f| cannot beat any of
     # its users' current (k+1)-th best scores
     hbase = P["super_kb"][P["frag_super"][P["first_frag"]]] * 256 + (P["frag_off"][P["first_frag"]] - FR_TILE_HEADER_BYTES) // 4
     np.maximum.at(wd, hbase[t_of] + f_of, np.abs(vals))
+    # behind the super-tiles, per fragment: 1.0001 * max |w| over its whole tile (float32-rounded) -- the kernel's first-level
+    # test, a constant of W that would otherwise be reduced from the header by every wave for every job
+    tmax = np.zeros(n_tiles, dtype=np.float32)
+    np.maximum.at(tmax, t_of, np.abs(vals))
+    wd[int(P["super_kb"][-1]) * 256:] = (tmax * np.float32(1.0001))[P["frag_tile"]]
     frag_rows = np.zeros((P["n_frags"], 2), dtype=np.uint64)
     np.bitwise_or.at(frag_rows, (g_of, f_of // 64), np.uint64(1) << (f_of % 64).astype(np.uint64))
     tile_rows = np.zeros((n_tiles, 2), dtype=np.uint64)
@@ -300,11 +305,13 @@ def build_feature_rows_device(torch, rows, cols, vals, n_items: int, col_lo: int
     dv = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     k_of = local[t_of, f_of]
     g_of = dv(P["frag_of"])[t_of, k_of]
-    wd = torch.zeros(max(int(P["super_kb"][-1]) * 256, 256), dtype=torch.float32, device=dev)
+    wd = torch.zeros(int(P["super_kb"][-1]) * 256 + P["n_frags"], dtype=torch.float32, device=dev)
     base = dv(P["super_kb"])[dv(P["frag_super"])[g_of]] * 256 + dv(P["frag_off"])[g_of] // 4
     wd[base + (k_of - dv(P["frag_k0"])[g_of]) * tc + lc % tc] = v
     hbase = dv(P["super_kb"][P["frag_super"][P["first_frag"]]] * 256 + (P["frag_off"][P["first_frag"]] - FR_TILE_HEADER_BYTES) // 4)
     wd.scatter_reduce_(0, hbase[t_of] + f_of, v.abs(), reduce="amax")             # tile headers: max |w| per row
+    tmax = torch.zeros(n_tiles, dtype=torch.float32, device=dev).scatter_reduce_(0, t_of, v.abs(), reduce="amax")
+    wd[int(P["super_kb"][-1]) * 256:] = (tmax * torch.tensor(1.0001, dtype=torch.float32, device=dev))[dv(P["frag_tile"])]
     # one bit per (row, fragment) / (row, tile) block that holds a weight
     blk_key = torch.unique(g_of * 128 + f_of)
     bg, bf = blk_key // 128, blk_key % 128
