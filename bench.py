@@ -6,6 +6,11 @@ Contract (one JSON line on rank 0):
           (interactions/sec) is reported in the `fit` object of the same line.
   step    one pass of the fused SpMV + interacted filter + top-k path over ALL users of the
           workload, inputs (X in CSR, W tiles) already resident in HBM.
+  --full  a run without it does only what the headline needs: generate the workload, fit W, build the layouts, the cold
+          step and the work order, warm up, time the K steps, write --dump-outputs, print.  With it the line also carries
+          alt_sharding, roofline and cpu_baseline (below), fit.tolerance_modes, fit.roofline, pcie_inclusive_users_per_sec,
+          c4, streaming, api, structured and fit.all_features; the tolerance-mode fits run before the timed steps,
+          everything else after them.
   N > 1   the fit is sharded by item column (each rank fits its own columns, the coefficients are all-gathered
           on the device, every rank holds W).  Scoring is divided over the ranks either by USER ROWS (default:
           W is ~1 MB and replicated, a rank scores every N-th user, only the final lists are all-gathered)
@@ -371,29 +376,33 @@ def main() -> None:
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--tile-cols", type=int, default=4096)
     ap.add_argument("--top-k", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline too: the tolerance-mode fits, the other division of "
+                         "the pass, the PCIe-inclusive pass, the rooflines, the c4 / streaming / api / structured legs, the "
+                         "K=None fit and the cpu_baseline (the --no-* switches below leave out single ones of them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fast-fit", action="store_true", help="skip the second (tolerance-mode) fit")
     ap.add_argument("--stream-batches", type=int, default=8,
-                    help="streaming leg (N = 1 only): this many 1,000-interaction SLIM.fit mini-batches per fit mode, each "
-                         "followed by a 100-user recommend_batch, on a model bulk-fitted at the same workload shape (0 = skip)")
+                    help="streaming leg (--full, N = 1 only): this many 1,000-interaction SLIM.fit mini-batches per fit mode, "
+                         "each followed by a 100-user recommend_batch, on a model bulk-fitted at the same workload shape (0 = skip)")
     ap.add_argument("--score-shard", default="auto", choices=["auto", "columns", "rows"],
                     help="multi-GPU scoring: item-column shards of W + list exchange (BASELINE.json's configuration), or "
                          "user-row shards with W replicated.  auto = rows unless W is too large to replicate (the single-GPU shard "
                          "models of round 4 favour rows for the feature-row AND the segment kernel: DESIGN.md section 6); the other "
-                         "division is timed right after and reported as `alt_sharding`, and the line says which was chosen and why "
+                         "division is timed right after with --full and reported as `alt_sharding`; the line says which was chosen and why "
                          "(`score_shard_choice`)")
     ap.add_argument("--shard-w", action="store_true",
                     help="multi-GPU, column shards: every rank fits and KEEPS only its own column block of W (no all-gather of the "
                          "coefficients; SlimEngine.shard_w).  Implies --score-shard columns and no alt_sharding leg")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU time budget per cpu_baseline leg (4 legs)")
     ap.add_argument("--no-structured", action="store_true",
-                    help="skip the `structured` leg of the default (c3) line: the same shape with item-item structure (c3s), "
+                    help="skip the `structured` leg of a --full c3 line: the same shape with item-item structure (c3s), "
                          "fit + all-users scoring through the general-W kernel")
-    ap.add_argument("--no-api", action="store_true", help="skip the `api` leg (Recommender.bulk_fit / recommend_batch through the DataFrame API)")
+    ap.add_argument("--no-api", action="store_true", help="skip the `api` leg of a --full line (Recommender.bulk_fit / recommend_batch through the DataFrame API)")
     ap.add_argument("--exchange-scores", action="store_true",
                     help="several ranks, user-row shards: all-gather the float32 scores with the ids (84 instead of 44 bytes per user)")
     ap.add_argument("--no-c4", action="store_true",
-                    help="skip the `c4` leg of the default (c3) line: BASELINE config 4's shape (1 M x 500k, 100 M interactions), "
+                    help="skip the `c4` leg of a --full c3 line: BASELINE config 4's shape (1 M x 500k, 100 M interactions), "
                          "sharded fit + all-users scoring at this --gpus N (about 45 s)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned -- top-k ids, scores (when the pass "
@@ -522,20 +531,21 @@ def main() -> None:
     eng._layout(compact=True, top_k=top_k)
     torch.cuda.synchronize()
     layout_s = time.time() - t1
-    tg, items, coef, count = (t.cpu().numpy() for t in (d_tg, d_items, d_coef, d_count))
-    tg = tg.astype(np.int64)
-    # algorithmic bytes of this rank's fit (every datum once per target column):
-    # y (8 nnz_j) + the co-occurring user rows that form X^T y (8 |I_u| per u in U_j) + the K selected
-    # feature columns (8 nnz(c)) + the written coefficients (8 |S_j|)
-    col_nnz_all = np.diff(Xc.indptr).astype(np.float64)
-    row_nnz_all = np.diff(X.indptr).astype(np.float64)
-    owned = np.zeros(I, dtype=bool)
-    owned[mine] = True
-    # sum over owned targets j of sum_{u in U_j} |I_u|  ==  sum over interactions (u, j owned) of |I_u|
-    cooc = float(np.repeat(row_nnz_all, np.diff(X.indptr))[owned[X.indices]].sum())
-    sel_mask = np.arange(items.shape[1])[None, :] < count[:, None]
-    feat = float(col_nnz_all[items[sel_mask]].sum())
-    fit_algo_bytes = 8.0 * float(col_nnz_all[mine].sum()) + 8.0 * cooc + 8.0 * feat + 8.0 * float(count.sum())
+    if args.full:
+        tg, items, coef, count = (t.cpu().numpy() for t in (d_tg, d_items, d_coef, d_count))
+        tg = tg.astype(np.int64)
+        # algorithmic bytes of this rank's fit (every datum once per target column):
+        # y (8 nnz_j) + the co-occurring user rows that form X^T y (8 |I_u| per u in U_j) + the K selected
+        # feature columns (8 nnz(c)) + the written coefficients (8 |S_j|)
+        col_nnz_all = np.diff(Xc.indptr).astype(np.float64)
+        row_nnz_all = np.diff(X.indptr).astype(np.float64)
+        owned = np.zeros(I, dtype=bool)
+        owned[mine] = True
+        # sum over owned targets j of sum_{u in U_j} |I_u|  ==  sum over interactions (u, j owned) of |I_u|
+        cooc = float(np.repeat(row_nnz_all, np.diff(X.indptr))[owned[X.indices]].sum())
+        sel_mask = np.arange(items.shape[1])[None, :] < count[:, None]
+        feat = float(col_nnz_all[items[sel_mask]].sum())
+        fit_algo_bytes = 8.0 * float(col_nnz_all[mine].sum()) + 8.0 * cooc + 8.0 * feat + 8.0 * float(count.sum())
     if world > 1:
         t = torch.tensor([fit_local], device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -549,7 +559,7 @@ def main() -> None:
     # the same fit in the tolerance mode (exact=False: Gram-form CD / tree-reduced dots), timed beside the exact one;
     # the scored W is the exact one
     fit_fast = None
-    if not args.no_fast_fit:
+    if args.full and not args.no_fast_fit:
         We = merge_coefficients(None, I, *coefficients_to_updates(tg, items, coef, count))
         fit_fast = {"note": "rank 0's columns, same call as the exact fit with mode=... (rtrec_fit_opts.fast): same features, "
                             "coordinate sequence and stopping rules, dot products not in scikit-learn's left-to-right order"}
@@ -667,6 +677,43 @@ def main() -> None:
                                                   "topk_scores": None if out[1] is None else out[1].cpu().numpy(),
                                                   "topk_counts": out[2].cpu().numpy()})
         log(f"[bench] last timed step's outputs written to {args.dump_outputs}: {', '.join(n + '.npy' for n in names)}")
+
+    lay = eng._layout(True) or {"tile_cols": None, "n_tiles": 0, "n_cols": 0}
+    fr = lay.get("fr_host")
+    line = {
+        "metric": "users-scored/sec top-10 (SLIM recommend, int ids, filter_interacted) + fit interactions/sec in `fit`",
+        "value": value, "unit": "users/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.workload}: {wl['desc']}", "n_users": U, "n_items": I, "nnz": nnz,
+                   "nn_feature_selection": K, "top_k": top_k, "tile_cols": lay["tile_cols"], "n_tiles": lay["n_tiles"],
+                   "active_columns": lay["n_cols"],
+                   "w_rows": (fr["fr_rows"] if fr is not None else (int(lay["sg"]["sg_rows"]) if lay.get("sg") else None)),
+                   "score_layout": ("feature rows" if fr is not None else "segments" if lay.get("sg") else "tiled CSR"),
+                   "parallelism": ("single GPU" if world == 1 else f"item-column shard x{world}" if args.score_shard == "columns"
+                                   else f"user-row shard x{world}, W replicated"),
+                   "exchange": (None if world == 1 else "per-shard records, all-to-all + all-gather of the final lists" if args.score_shard == "columns"
+                                else ("ids + scores + counts, 84 B per user" if args.exchange_scores else "ids + counts, 44 B per user") +
+                                f", all-gather in chunks of >= {eng.row_chunk_rows} slots per rank overlapped with the next chunk's kernel")},
+        "ranks_seen": ranks_seen, "rank_devices": rank_devices, "backend": backend,
+        "score_shard_choice": dict(shard_choice, w_column_sharded=bool(args.shard_w)),
+        "topk_ids_crc32": crc_main, "rows_rescored_by_exact_tie_pass": n_rescored,
+        "fit": {"seconds": fit_s, "interactions_per_sec": nnz / fit_s, "columns_per_sec": I / fit_s,
+                "W_nnz": int(W.nnz), "mean_sweeps": float(n_iter.mean()), "mode": "exact",
+                "to_score": {"write_back_ms": merge_s * 1e3, "layouts_ms": layout_s * 1e3,
+                             "note": "fit output -> W merge -> score layouts, all on the device (engine.merge_fit, "
+                                     "build_tiled_w_device / build_feature_rows_device); no host copy of W is on this path"}},
+        "step_accounting": {"cold_step_ms": cold_step_ms, "row_order_ms": row_order_ms, "warm_ms_per_step": ms_per_step,
+                            "note": "cold = the first pass after a new X / W: it builds the work order of the rows (an index of X for the "
+                                    "layout in use: argsort by row length, or by feature-row pattern for the feature-row kernel), which the "
+                                    "timed steps reuse; row_order_ms is that build alone (the length order of the first pass plus, where the layout wants one, the pattern-grouped order a row set gets when it is scored a second time).  The layouts themselves are fit.to_score.layouts_ms"},
+    }
+    if not args.full:           # a plain run ends with its headline; what follows measures and checks everything else
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     if out[1] is None:          # the timed exchange carried ids + counts only: the bookkeeping below reads the scores too
         out = eng.score_topk_device(None, U, top_k, True, _native.TOPK_SPARSE, d_rows=d_rows, xb=xb, with_scores=True)
 
@@ -728,14 +775,12 @@ def main() -> None:
         n_scored = U
     kern_ms = tot_ms.value / max(n_launch.value, 1)
     kern_s = kern_ms * 1e-3
-    lay = eng._layout(True) or {"tile_cols": None, "n_tiles": 0, "n_cols": 0}
     VALU_PEAK_TFLOPS = 78.6        # 256 CUs x 4 SIMD x 32 lanes x 2.4 GHz, one flop per lane-op: the sums are NOT fused
                                    # (x * w is rounded before it is added, like scipy's) so FMA's factor 2 does not apply
     LDS_READ_PEAK_GBS = 150_000.0  # MI355X_MICROARCH.md: ~150 TB/s aggregate for ds_read_b64/b128
     L2_PEAK_GBS = 34_500.0         # MI355X_MICROARCH.md: ~34.5 TB/s
     bounds, kernel_name, bound = {}, "score_sparse_kernel<float,false>", "l2"
     compulsory_hbm = 8.0 * (nnz if n_scored == U else int(Xs.nnz)) + 4.0 * (n_scored + 1) + (8.0 * top_k + 4.0) * n_scored
-    fr = lay.get("fr_host")
 
     def tiled_model():
             l2_bytes = 6.0 * gathered_entries + 24.0 * (nnz if n_scored == U else int(Xs.nnz)) * max(lay["n_tiles"], 1)
@@ -929,48 +974,22 @@ def main() -> None:
                            "how": "SQ_ACTIVE_INST_VALU (quad-cycles, all SIMDs) x 4 / 1024 SIMDs / (kernel_ms_avg x 2.4 GHz)",
                            "wait_any_frac_of_wave_cycles": (counters.get("derived") or {}).get("wait_any_frac")}
     best = bounds[bound]
-    line = {
-        "metric": "users-scored/sec top-10 (SLIM recommend, int ids, filter_interacted) + fit interactions/sec in `fit`",
-        "value": value, "unit": "users/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{args.workload}: {wl['desc']}", "n_users": U, "n_items": I, "nnz": nnz,
-                   "nn_feature_selection": K, "top_k": top_k, "tile_cols": lay["tile_cols"], "n_tiles": lay["n_tiles"],
-                   "active_columns": lay["n_cols"],
-                   "w_rows": (fr["fr_rows"] if fr is not None else (int(lay["sg"]["sg_rows"]) if lay.get("sg") else None)),
-                   "score_layout": ("feature rows" if fr is not None else "segments" if lay.get("sg") else "tiled CSR"),
-                   "parallelism": ("single GPU" if world == 1 else f"item-column shard x{world}" if args.score_shard == "columns"
-                                   else f"user-row shard x{world}, W replicated"),
-                   "exchange": (None if world == 1 else "per-shard records, all-to-all + all-gather of the final lists" if args.score_shard == "columns"
-                                else ("ids + scores + counts, 84 B per user" if args.exchange_scores else "ids + counts, 44 B per user") +
-                                f", all-gather in chunks of >= {eng.row_chunk_rows} slots per rank overlapped with the next chunk's kernel")},
-        "ranks_seen": ranks_seen, "rank_devices": rank_devices, "backend": backend, "alt_sharding": alt_sharding,
-        "score_shard_choice": dict(shard_choice, w_column_sharded=bool(args.shard_w)),
-        "pcie_inclusive_users_per_sec": pcie_users_per_s, "topk_ids_crc32": topk_crc, "rows_rescored_by_exact_tie_pass": n_rescored,
-        "fit": {"seconds": fit_s, "interactions_per_sec": nnz / fit_s, "columns_per_sec": I / fit_s,
-                "W_nnz": int(W.nnz), "mean_sweeps": float(n_iter.mean()), "mode": "exact", "tolerance_modes": fit_fast,
-                "to_score": {"write_back_ms": merge_s * 1e3, "layouts_ms": layout_s * 1e3,
-                             "note": "fit output -> W merge -> score layouts, all on the device (engine.merge_fit, "
-                                     "build_tiled_w_device / build_feature_rows_device); no host copy of W is on this path"},
-                "roofline": {"kernel": "fit_columns_kernel<false> (+ fit_columns_mw_kernel for the heaviest targets)",
-                             "bound": "hbm", "achieved": fit_algo_bytes / fit_local / 1e9, "peak": HBM_PEAK_GBS,
-                             "unit": "GB/s", "frac": fit_algo_bytes / fit_local / 1e9 / HBM_PEAK_GBS,
-                             "algorithmic_bytes": fit_algo_bytes, "seconds": fit_local, "traffic": fit_traffic,
-                             "note": "rank 0's columns; compulsory bytes only (SURVEY 8d): the coordinate-descent sweeps "
-                                     "re-read the K feature columns and stream the per-target residual, which is what "
-                                     "`traffic` (PMC, profiles/) measures"}},
-        "roofline": {"kernel": kernel_name, "bound": ("hbm" if bound.startswith("hbm") else bound), "achieved": best["achieved"], "peak": best["peak"],
-                     "unit": best["unit"], "frac": best["frac"], "traffic": traffic, "traffic_source": traffic_src,
-                     "traffic_measured_in_run": False, "traffic_stale": (stale or None), "build": fp,
-                     "traffic_vs_compulsory": (traffic / compulsory_hbm if traffic else None),
-                     "kernel_ms_avg": kern_ms, "launches": int(n_launch.value), "bounds": bounds,
-                     "algorithmic": algorithmic, "counters": counters, "valu_issue_busy": valu_issue_busy, "score_path": score_path},
-        "c4": c4_leg,
-        "step_accounting": {"cold_step_ms": cold_step_ms, "row_order_ms": row_order_ms, "warm_ms_per_step": ms_per_step,
-                            "note": "cold = the first pass after a new X / W: it builds the work order of the rows (an index of X for the "
-                                    "layout in use: argsort by row length, or by feature-row pattern for the feature-row kernel), which the "
-                                    "timed steps reuse; row_order_ms is that build alone (the length order of the first pass plus, where the layout wants one, the pattern-grouped order a row set gets when it is scored a second time).  The layouts themselves are fit.to_score.layouts_ms"},
-    }
+    line.update({"alt_sharding": alt_sharding, "pcie_inclusive_users_per_sec": pcie_users_per_s, "topk_ids_crc32": topk_crc,
+                 "roofline": {"kernel": kernel_name, "bound": ("hbm" if bound.startswith("hbm") else bound), "achieved": best["achieved"],
+                              "peak": best["peak"], "unit": best["unit"], "frac": best["frac"], "traffic": traffic, "traffic_source": traffic_src,
+                              "traffic_measured_in_run": False, "traffic_stale": (stale or None), "build": fp,
+                              "traffic_vs_compulsory": (traffic / compulsory_hbm if traffic else None),
+                              "kernel_ms_avg": kern_ms, "launches": int(n_launch.value), "bounds": bounds,
+                              "algorithmic": algorithmic, "counters": counters, "valu_issue_busy": valu_issue_busy, "score_path": score_path},
+                 "c4": c4_leg})
+    line["fit"].update({"tolerance_modes": fit_fast,
+                        "roofline": {"kernel": "fit_columns_kernel<false> (+ fit_columns_mw_kernel for the heaviest targets)",
+                                     "bound": "hbm", "achieved": fit_algo_bytes / fit_local / 1e9, "peak": HBM_PEAK_GBS,
+                                     "unit": "GB/s", "frac": fit_algo_bytes / fit_local / 1e9 / HBM_PEAK_GBS,
+                                     "algorithmic_bytes": fit_algo_bytes, "seconds": fit_local, "traffic": fit_traffic,
+                                     "note": "rank 0's columns; compulsory bytes only (SURVEY 8d): the coordinate-descent sweeps "
+                                             "re-read the K feature columns and stream the per-target residual, which is what "
+                                             "`traffic` (PMC, profiles/) measures"}})
 
     # ------------------------------------------------------------------ streaming leg (SURVEY 8 row S1 / BASELINE config 4 pattern)
     if world == 1 and args.stream_batches > 0:

@@ -17,7 +17,7 @@ for C in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU S
          "TCC_REQ_sum TCC_HIT_sum TCC_MISS_sum TCC_READ_sum" \
          "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $C --kernel-trace -d $O -o p$i --output-format csv -- python3 bench.py --workload $WL --steps 3 --no-cpu-baseline > $O/p$i.log 2>&1
+  timeout 600 rocprofv3 --pmc $C --kernel-trace -d $O -o p$i --output-format csv -- python3 bench.py --full --workload $WL --steps 3 --no-cpu-baseline > $O/p$i.log 2>&1
   echo "pass $i rc=$?"
 done
 python3 tools/pmc_summary.py $O/*_counter_collection.csv --match "score_sparse_kernel<float, false>" > $O/summary.json

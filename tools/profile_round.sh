@@ -10,9 +10,9 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 cd $R
-python3 bench.py --workload $WL > $O/bench_$WL.json 2> $O/bench_$WL.log
+python3 bench.py --full --workload $WL > $O/bench_$WL.json 2> $O/bench_$WL.log
 echo "bench rc=$?"
-rocprofv3 --kernel-trace --stats -d $O -o stats_$WL --output-format csv -- python3 bench.py --workload $WL --no-cpu-baseline --no-api --no-structured --no-c4 --stream-batches 0 > $O/bench_${WL}_under_rocprof.json 2> $O/rocprof_stats.log
+rocprofv3 --kernel-trace --stats -d $O -o stats_$WL --output-format csv -- python3 bench.py --full --workload $WL --no-cpu-baseline --no-api --no-structured --no-c4 --stream-batches 0 > $O/bench_${WL}_under_rocprof.json 2> $O/rocprof_stats.log
 echo "stats rc=$?"
 i=0
 for C in "FETCH_SIZE" "WRITE_SIZE TCC_HIT_sum TCC_MISS_sum" \

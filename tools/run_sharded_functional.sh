@@ -2,7 +2,7 @@
 # every N must equal the single-rank CRC, for the division of record (user rows) and the other one (item columns:
 # `alt_sharding`, or --score-shard columns).  bench.py launches its ranks itself (torch.distributed.run child).
 cd $GRAFT_REPO_ROOT
-F="--no-cpu-baseline --no-fast-fit --stream-batches 0"
+F="--full --no-cpu-baseline --no-fast-fit --stream-batches 0"
 python bench.py --workload small $F > gpurun_out/bench_small_n1.json 2> gpurun_out/bench_small_n1.log
 RTREC_BENCH_SAME_GPU=1 timeout 600 python bench.py --gpus 2 --workload small $F > gpurun_out/bench_small_n2.json 2> gpurun_out/bench_small_n2.log
 python bench.py --workload c2 $F > gpurun_out/bench_c2_n1.json 2> gpurun_out/bench_c2_n1.log

@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-F="--no-cpu-baseline --no-fast-fit --stream-batches 0 --no-api --no-structured --steps 5"
+F="--full --no-cpu-baseline --no-fast-fit --stream-batches 0 --no-api --no-structured --steps 5"
 python bench.py --workload small $F > gpurun_out/f_small_n1.json 2> gpurun_out/f_small_n1.log
 RTREC_BENCH_SAME_GPU=1 timeout 300 python bench.py --gpus 2 --workload small $F > gpurun_out/f_small_n2.json 2> gpurun_out/f_small_n2.log
 RTREC_BENCH_SAME_GPU=1 timeout 300 python bench.py --gpus 2 --workload small $F --shard-w > gpurun_out/f_small_n2_sw.json 2> gpurun_out/f_small_n2_sw.log

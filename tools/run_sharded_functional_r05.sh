@@ -2,7 +2,7 @@
 # the ids CRC of every N must equal the single-rank one, for the main workload and for the c4 leg.
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05_sharded; mkdir -p $O
-F="--no-cpu-baseline --no-fast-fit --stream-batches 0 --no-api --no-structured --steps 3"
+F="--full --no-cpu-baseline --no-fast-fit --stream-batches 0 --no-api --no-structured --steps 3"
 python bench.py --workload small $F --no-c4 > $O/small_n1.json 2> $O/small_n1.log
 RTREC_BENCH_SAME_GPU=1 timeout 300 python bench.py --gpus 2 --workload small $F --no-c4 > $O/small_n2.json 2> $O/small_n2.log
 RTREC_BENCH_SAME_GPU=1 timeout 300 python bench.py --gpus 4 --workload small $F --no-c4 --exchange-scores > $O/small_n4_scores.json 2> $O/small_n4_scores.log

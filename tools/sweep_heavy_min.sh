@@ -4,5 +4,5 @@
 cd $GRAFT_REPO_ROOT
 python -m pytest tests/test_gpu_seg.py -m gpu -x -q > gpurun_out/r04_seg_tests.log 2>&1; tail -2 gpurun_out/r04_seg_tests.log
 for HM in ${1:-0 385 257 193}; do
-RTREC_AMD_SG_HEAVY_MIN=$HM python bench.py --workload c3s --no-cpu-baseline --steps 5 --no-api --no-structured --stream-batches 0 --no-fast-fit 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('hm=$HM c3s', round(d['roofline']['kernel_ms_avg'],3), round(d['ms_per_step'],3), d['topk_ids_crc32'])"
+RTREC_AMD_SG_HEAVY_MIN=$HM python bench.py --full --workload c3s --no-cpu-baseline --steps 5 --no-api --no-structured --stream-batches 0 --no-fast-fit 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('hm=$HM c3s', round(d['roofline']['kernel_ms_avg'],3), round(d['ms_per_step'],3), d['topk_ids_crc32'])"
 done
