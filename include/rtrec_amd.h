@@ -661,6 +661,27 @@ int rtrec_slim_fit_sgd_epochs(int32_t n_users, int32_t n_items, const int32_t *d
                               float *d_w, float *d_q, double *d_best_loss, int32_t *d_no_improve,
                               int32_t *d_n_iter, int32_t *d_unfinished, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * RANKING METRICS OF Recommender.evaluate  (replaces rtrec/utils/metrics.py:5-313 -- precision, recall, f1_score, ndcg, hit,
+ * reciprocal_rank, average_precision, auc, true_positives per (ranked list, ground truth) pair -- as rtrec/recommender.py:163-200
+ * drives them, for top-k lists that are already on the device).
+ * d_ids[n_rows][stride] / d_counts[n_rows]: the lists of rtrec_slim_score_topk(_opt) (row r valid up to d_counts[r]); the first
+ * k = min(d_counts[r], size) entries are judged, 1 <= size <= 64 (RTREC_ERR_UNSUPPORTED otherwise), stride >= size.
+ * Ground truth as CSR over the same rows: d_truth_ptr[n_rows + 1] into d_truth_items[n_truth], SORTED AND UNIQUE within a row
+ * (membership is a binary search; offsets are clamped to [0, n_truth]), and d_truth_len[n_rows] = the number every "/ len(ground
+ * truth)" of the reference divides by -- the length of its Python list, which also counts duplicated rows and items the model
+ * has never seen, so it may exceed the row's CSR length.
+ * d_discount[size] = 1 / log2(i + 2) and d_ideal[size + 1] = its left-to-right prefix sums (d_ideal[0] = 0), made on the host
+ * with the libm the reference uses: the device then performs only float64 additions and correctly rounded divisions, in the
+ * reference's order, and the figures equal CPython's bit for bit.
+ * Out, per row: d_rel (bit i = the i-th recommendation is relevant, i < k), d_tp = popcount(d_rel), d_metrics[n_rows][8] =
+ * precision, recall, f1, ndcg, hit_rate, mrr, map, auc.
+ * ------------------------------------------------------------------------------------- */
+int rtrec_rank_metrics(int32_t n_rows, int32_t size, const int32_t *d_ids, int32_t stride, const int32_t *d_counts,
+                       const int64_t *d_truth_ptr, const int32_t *d_truth_items, int64_t n_truth,
+                       const int32_t *d_truth_len, const double *d_discount, const double *d_ideal,
+                       uint64_t *d_rel, int32_t *d_tp, double *d_metrics, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ EXPORTS = [
     "rtrec_slim_dense_fill",
     "rtrec_slim_first_touch_aux",
     "rtrec_slim_ordered_sums",
+    "rtrec_rank_metrics",
 ]
 
 
@@ -183,6 +184,8 @@ def load() -> C.CDLL:
     L.rtrec_store_fold_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_double, C.c_double, i32, vp, vp, vp, vp]
     L.rtrec_slim_ordered_sums.restype = C.c_int
     L.rtrec_slim_ordered_sums.argtypes = [vp, vp, i32, i32, vp, vp]
+    L.rtrec_rank_metrics.restype = C.c_int
+    L.rtrec_rank_metrics.argtypes = [i32, i32, vp, i32, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -46,6 +46,7 @@ struct Abi {
     decltype(&rtrec_slim_seg_plan) seg_plan = nullptr;
     decltype(&rtrec_slim_seg_fill) seg_fill = nullptr;
     decltype(&rtrec_slim_ordered_sums) ordered_sums = nullptr;
+    decltype(&rtrec_rank_metrics) rank_metrics = nullptr;
 };
 Abi g_abi;
 
@@ -370,6 +371,30 @@ void ordered_sums(const at::Tensor &values, const at::Tensor &offsets, int64_t m
                              static_cast<int32_t>(mode), ptr<float>(out), stream_of(out)), "rtrec_slim_ordered_sums");
 }
 
+// ids / counts: the lists of score_topk; truth_* the ground truth as CSR over the same rows (include/rtrec_amd.h).  rel is an
+// int64 tensor that receives the uint64 relevance words.
+void rank_metrics(const at::Tensor &ids, const at::Tensor &counts, const at::Tensor &truth_ptr, const at::Tensor &truth_items,
+                  const at::Tensor &truth_len, const at::Tensor &discount, const at::Tensor &ideal, int64_t size, at::Tensor metrics,
+                  at::Tensor tp, at::Tensor rel) {
+    TORCH_CHECK(size >= 1 && size <= 64, "rank_metrics: size must lie in 1..64, got ", size);
+    TORCH_CHECK(ids.dim() == 2 && ids.size(1) >= size, "rank_metrics: ids must be [n_rows, >= size]");
+    const int64_t n = ids.size(0);
+    TORCH_CHECK(n <= INT32_MAX, "rank_metrics: too many rows");
+    TORCH_CHECK(truth_ptr.numel() == n + 1, "rank_metrics: truth_ptr must hold n_rows + 1 entries, got ", truth_ptr.numel());
+    TORCH_CHECK(counts.numel() == n && truth_len.numel() == n, "rank_metrics: counts and truth_len must hold one entry per row");
+    TORCH_CHECK(discount.numel() == size && ideal.numel() == size + 1, "rank_metrics: discount[size] and ideal[size + 1] expected");
+    TORCH_CHECK(metrics.numel() == n * 8 && tp.numel() == n && rel.numel() == n, "rank_metrics: outputs must be metrics[n_rows, 8], tp[n_rows], rel[n_rows]");
+    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
+    check_tensor<const int32_t>(ids); check_tensor<const int32_t>(counts); check_tensor<const int64_t>(truth_ptr);
+    check_tensor<const int32_t>(truth_items); check_tensor<const int32_t>(truth_len); check_tensor<const double>(discount);
+    check_tensor<const double>(ideal); check_tensor<double>(metrics); check_tensor<int32_t>(tp); check_tensor<int64_t>(rel);
+    check(abi().rank_metrics(static_cast<int32_t>(n), static_cast<int32_t>(size), ptr<const int32_t>(ids), static_cast<int32_t>(ids.size(1)),
+                             ptr<const int32_t>(counts), ptr<const int64_t>(truth_ptr), ptr<const int32_t>(truth_items), truth_items.numel(),
+                             ptr<const int32_t>(truth_len), ptr<const double>(discount), ptr<const double>(ideal),
+                             reinterpret_cast<uint64_t *>(ptr<int64_t>(rel)), ptr<int32_t>(tp), ptr<double>(metrics), stream_of(metrics)),
+          "rtrec_rank_metrics");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -398,6 +423,7 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.seg_plan, "rtrec_slim_seg_plan");
         bind_one(h, a.seg_fill, "rtrec_slim_seg_fill");
         bind_one(h, a.ordered_sums, "rtrec_slim_ordered_sums");
+        bind_one(h, a.rank_metrics, "rtrec_rank_metrics");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -452,6 +478,8 @@ TORCH_LIBRARY(rtrec_amd, m) {
           "int tile_cols, int n_tiles, Tensor(a!) ws, Tensor(b!) info, Tensor(c!) seg_ptr, Tensor(d!) ent, Tensor(e!) bound, "
           "Tensor(f!) col_ids, Tensor(g!) trow_ptr, Tensor(h!) trow) -> ()");
     m.def("ordered_sums(Tensor values, Tensor offsets, int mode, Tensor(a!) out) -> ()");
+    m.def("rank_metrics(Tensor ids, Tensor counts, Tensor truth_ptr, Tensor truth_items, Tensor truth_len, Tensor discount, Tensor ideal, "
+          "int size, Tensor(a!) metrics, Tensor(b!) tp, Tensor(c!) rel) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -473,4 +501,5 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("seg_plan", &seg_plan);
     m.impl("seg_fill", &seg_fill);
     m.impl("ordered_sums", &ordered_sums);
+    m.impl("rank_metrics", &rank_metrics);
 }

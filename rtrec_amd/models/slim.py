@@ -268,6 +268,106 @@ class SLIM(BaseModel):
                 out[p] = list(range(n_items - 1, n_items - 1 - k, -1))
         return out
 
+    # ------------------------------------------------------------ evaluate on the device
+    @staticmethod
+    def _internal_ids(ident, values: np.ndarray, what: str) -> np.ndarray:
+        """Identifier.get_id over the distinct raw ids of an evaluation frame's column: int64 internal ids, -1 for a value
+        the identifier has never seen.  Integer pass-through ids are returned as they are (one vectorised step)."""
+        if ident.pass_through and not ident.force_identify:
+            if values.dtype.kind not in "iu":
+                raw = values.tolist()
+                if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in raw):
+                    raise ValueError(f"on_device evaluation: the {what} column mixes integer ids with other values")
+                values = np.fromiter((int(v) for v in raw), dtype=np.int64, count=len(raw))
+            return values.astype(np.int64)
+        # items are only tested for membership (an id of another kind is in no recommendation); users go through get_id
+        # like recommend_batch's own loop, with its "mixed types" error
+        get = ident.obj_to_id.get if what == "item" else ident.get_id
+        return np.fromiter((-1 if (i := get(v)) is None else i for v in values.tolist()), dtype=np.int64, count=len(values))
+
+    def _evaluate_device(self, users: np.ndarray, items: np.ndarray, size: int, filter_interacted: bool,
+                         want_rel: bool = False):
+        """Recommender.evaluate without leaving the device: every user of the frame scored in ONE pass whose lists stay in
+        HBM, rank_metrics_kernel (csrc/rank_metrics.hip) on (lists, ground truth), and only the per-user figures come back.
+        Returns (users in evaluation order, metrics[n, 8] float64 in utils.metrics.METRIC_COLUMNS order, tp[n] int32,
+        rel[n] uint64 or None).  Known users get recommend_batch's hot lists, unknown ones its cold-start list.  What this
+        path does not serve is refused with ValueError -- the caller evaluates on the host instead.  With several ranks the
+        scoring pass is the usual collective and every rank computes the same figures."""
+        from .._native import TOPK_DENSE, TOPK_SPARSE
+        from ..backend import HipBackend
+        from ..utils.metrics import discount_tables, ground_truth_csr
+        eng = self.model.engine
+        be = eng.be
+        if not isinstance(be, HipBackend):
+            raise ValueError("on_device evaluation needs the HIP backend; this model scores through another one")
+        if not 1 <= size <= 64:
+            raise ValueError(f"on_device evaluation serves recommend_size 1..64, got {size}")
+        if (type(self).handle_unknown_user is not BaseModel.handle_unknown_user
+                or type(self)._recommend_cold_batch is not BaseModel._recommend_cold_batch):
+            raise ValueError("on_device evaluation: this model serves unknown users through hooks of its own")
+        for name, col in (("user", users), ("item", items)):
+            if col.dtype.kind not in "iuO":
+                raise ValueError(f"on_device evaluation takes integer or object id columns; the {name} column is {col.dtype}")
+        if not self.model.is_fitted:
+            raise RuntimeError("Model must be fitted before calling batch_recommend.")
+        n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
+
+        def user_index(values: np.ndarray) -> np.ndarray:
+            ids = self._internal_ids(self.user_ids, values, "user")
+            if self.user_ids.pass_through:
+                if (ids < 0).any():
+                    raise ValueError("on_device evaluation: negative integer user ids are served by the host path only")
+                ids = np.where(ids > self.interactions.max_user_id, -1, ids)     # BaseModel._known_user_id: a cold-start user
+            return ids
+
+        def item_index(values: np.ndarray) -> np.ndarray:
+            ids = self._internal_ids(self.item_ids, values, "item")
+            return np.where((ids >= 0) & (ids < 2 ** 31), ids, -1)          # (beyond int32: no list can hold it)
+
+        eval_users, rows, truth_ptr, truth_items, truth_len = ground_truth_csr(users, items, user_index, item_index)
+        n = len(eval_users)
+        if n == 0:
+            return eval_users, np.empty((0, 8), np.float64), np.empty(0, np.int32), (np.empty(0, np.uint64) if want_rel else None)
+        hot = rows >= 0
+        hot_rows = rows[hot]
+        if len(hot_rows) and int(hot_rows.max()) >= n_users:
+            raise ValueError("on_device evaluation: a user known only through register_user_feature is served by the host path only")
+        mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+        top_k = min(size, n_items)
+        self.model._sync_weights()
+        if top_k < 1 or not eng.topk_supported(top_k, mode):
+            raise ValueError(f"on_device evaluation: the fused top-k kernels do not serve recommend_size {size} for this model")
+        torch = be.torch
+        ids = cnt = None
+        if len(hot_rows):
+            self._sync_interactions()
+            ids, _, cnt = eng.score_topk_device(hot_rows.astype(np.int32), len(hot_rows), top_k, filter_interacted, mode,
+                                                with_scores=False)
+        if len(hot_rows) < n or top_k < size or not ids.is_contiguous():
+            # the rows of unknown users (recommend_batch gives them all the hot-items list) and lists narrower than `size`
+            # are placed on the device
+            all_ids = torch.full((n, size), -1, dtype=torch.int32, device=be.device)
+            all_cnt = be.zeros((n,), torch.int32)
+            if ids is not None:
+                pos = be.to_dev(np.flatnonzero(hot))
+                all_ids[pos, :top_k] = ids
+                all_cnt[pos] = cnt
+            if len(hot_rows) < n:
+                cold_list = self._recommend_cold_batch([None], top_k=size)[0][:size]
+                if cold_list:
+                    pos = be.to_dev(np.flatnonzero(~hot))
+                    all_ids[pos, :len(cold_list)] = be.to_dev(np.asarray(cold_list, dtype=np.int32))[None, :]
+                    all_cnt[pos] = len(cold_list)
+            ids, cnt = all_ids, all_cnt
+        discount, ideal = discount_tables(size)
+        d_metrics = be.empty((n, 8), torch.float64)
+        d_tp = be.empty((n,), torch.int32)
+        d_rel = be.empty((n,), torch.int64)
+        be.ops.rank_metrics(ids, cnt.contiguous(), be.to_dev(truth_ptr), be.to_dev(truth_items), be.to_dev(truth_len),
+                            be.to_dev(discount), be.to_dev(ideal), size, d_metrics, d_tp, d_rel)
+        rel = d_rel.cpu().numpy().view(np.uint64) if want_rel else None
+        return eval_users, d_metrics.cpu().numpy(), d_tp.cpu().numpy(), rel
+
     def _similar_items(self, query_item_id: int, query_item_tags: Optional[List[str]] = None, top_k: int = 10
                        ) -> List[Tuple[int, float]]:
         return self.model.similar_items(query_item_id, top_k=top_k, ret_ndarrays=False)  # type: ignore

@@ -12,10 +12,11 @@ import math
 import time
 from typing import Any, Dict, Iterable, Iterator, List, Optional, Tuple
 
+import numpy as np
 import pandas as pd
 
 from .models.base import BaseModel
-from .utils.metrics import compute_scores
+from .utils.metrics import METRIC_COLUMNS, RESULT_KEYS, _query_metrics, compute_scores, scores_from_columns
 
 _COLUMNS = ["user", "item", "tstamp", "rating"]
 _COLUMNAR_CHUNK = 1 << 22
@@ -109,8 +110,20 @@ class Recommender:
         return [self.model.similar_items(item, query_item_tags, top_k, ret_scores) for item in query_items]
 
     def evaluate(self, test_data: pd.DataFrame, user_tags: Optional[Dict[Any, List[str]]] = None,
-                 recommend_size: int = 10, batch_size=100, filter_interacted: bool = True) -> Dict[str, float]:
-        """Average ranking metrics over the users of test_data (columns user, item)."""
+                 recommend_size: int = 10, batch_size=100, filter_interacted: bool = True,
+                 on_device: bool = False, per_user: bool = False) -> Any:
+        """Average ranking metrics over the users of test_data (columns user, item).
+
+        `on_device=True` (extension) evaluates without leaving the GPU: the held-out items go up once, all users are scored
+        in one pass, csrc/rank_metrics.hip turns (lists, ground truth) into the per-user figures and only those come back;
+        the dict equals the host path's bit for bit.  `batch_size` has no effect there.  What that path does not serve --
+        `user_tags`, a `recommend_size` outside 1..64 or beyond the fused top-k kernels, a model without the device hook, id
+        columns that are neither integer nor object dtype, users that only the host path can place -- raises ValueError
+        naming the reason: drop `on_device` then.
+        `per_user=True` (extension, either path) returns `(dict, frame)`: the frame holds the nine figures per user, indexed
+        by user in evaluation order (the order the means are summed in)."""
+        if on_device:
+            return self._evaluate_on_device(test_data, user_tags, recommend_size, filter_interacted, per_user)
         truth = test_data.groupby("user")["item"].apply(list).to_dict()
         users = list(truth.keys())
 
@@ -122,7 +135,33 @@ class Recommender:
                                             filter_interacted=filter_interacted)
                 for u, rec in zip(chunk, recs):
                     yield rec, truth[u]
-        return compute_scores(pairs(), recommend_size)
+        if not per_user:
+            return compute_scores(pairs(), recommend_size)
+        rows = [_query_metrics(rec, tru, recommend_size) for rec, tru in pairs()]
+        frame = pd.DataFrame(rows, index=pd.Index(users, name="user"), columns=list(RESULT_KEYS))
+        return self._scores_and_frame(frame[list(METRIC_COLUMNS)].to_numpy(dtype=np.float64).reshape(len(users), 8),
+                                      frame["tp"].to_numpy(dtype=np.int64), frame.index)
+
+    @staticmethod
+    def _scores_and_frame(metrics: np.ndarray, tp: np.ndarray, index: pd.Index) -> Tuple[Dict[str, float], pd.DataFrame]:
+        frame = pd.DataFrame(metrics, index=index, columns=list(METRIC_COLUMNS))
+        frame.insert(RESULT_KEYS.index("tp"), "tp", np.asarray(tp, dtype=np.int64))
+        return scores_from_columns(metrics, tp), frame
+
+    def _evaluate_on_device(self, test_data: pd.DataFrame, user_tags, recommend_size, filter_interacted: bool,
+                            per_user: bool) -> Any:
+        if user_tags:
+            raise ValueError("on_device evaluation does not take user_tags")
+        if isinstance(recommend_size, bool) or not isinstance(recommend_size, (int, np.integer)) or not 1 <= recommend_size <= 64:
+            raise ValueError(f"on_device evaluation serves an integer recommend_size in 1..64, got {recommend_size!r}")
+        hook = getattr(self.model, "_evaluate_device", None)
+        if hook is None:
+            raise ValueError(f"on_device evaluation: {type(self.model).__name__} has no device evaluation hook")
+        users, metrics, tp, _ = hook(test_data["user"].to_numpy(), test_data["item"].to_numpy(), int(recommend_size),
+                                     bool(filter_interacted))
+        if per_user:
+            return self._scores_and_frame(metrics, tp, pd.Index(users, name="user"))
+        return scores_from_columns(metrics, tp)
 
     @staticmethod
     def generate_batches(df: pd.DataFrame, batch_size: int = 1_000, as_generator: bool = False

@@ -9,7 +9,12 @@ from __future__ import annotations
 
 from collections import defaultdict
 from math import log2
-from typing import Any, Dict, Iterable, List, Sequence, Tuple
+from typing import Any, Callable, Dict, Iterable, List, Sequence, Tuple
+
+import numpy as np
+
+METRIC_COLUMNS = ("precision", "recall", "f1", "ndcg", "hit_rate", "mrr", "map", "auc")     # rank_metrics_kernel's order
+RESULT_KEYS = ("precision", "recall", "f1", "ndcg", "hit_rate", "mrr", "map", "tp", "auc")   # _query_metrics' order
 
 
 def _relevance(ranked_list: Sequence[Any], ground_truth: Sequence[Any], size: int) -> List[int]:
@@ -87,3 +92,95 @@ def compute_scores(evaluation_pairs: Iterable[Tuple[List[Any], List[Any]]], reco
     if n == 0:
         return defaultdict(float)
     return {name: (int(total) if name == "tp" else total / n) for name, total in totals.items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Array forms for Recommender.evaluate: the ground truth as CSR (what rank_metrics_kernel reads), the discount tables the
+# device cannot compute itself (no libm there), and compute_scores' means over per-user columns.
+
+def discount_tables(size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(discount[size], ideal[size + 1]): discount[i] = 1 / log2(i + 2) with Python's math.log2 -- the addends of dcg --
+    and ideal[m] = the idcg of min(len(ground_truth), size) == m, summed left to right from 0 like `sum(...)` does."""
+    discount = [1.0 / log2(pos + 2) for pos in range(size)]
+    ideal = [0.0]
+    for d in discount:
+        ideal.append(ideal[-1] + d)
+    return np.asarray(discount, dtype=np.float64), np.asarray(ideal, dtype=np.float64)
+
+
+def sequential_sum(values: np.ndarray) -> float:
+    """((0 + v[0]) + v[1]) + ... in float64: compute_scores' `totals[name] += value` loop.  np.cumsum accumulates in
+    order; np.sum adds pairwise and differs in the last bits."""
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    return float(np.cumsum(values)[-1]) if len(values) else 0.0
+
+
+def _missing(column: np.ndarray) -> np.ndarray:
+    """The keys pandas' groupby drops: NaN, and None in an object column."""
+    if column.dtype.kind == "f":
+        return np.isnan(column)
+    if column.dtype.kind == "O":
+        return np.not_equal(column, column).astype(bool) | np.equal(column, None).astype(bool)
+    return np.zeros(len(column), dtype=bool)
+
+
+def _distinct(values: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """np.unique(values, return_inverse=True).  Small non-negative integers -- pass-through ids -- are counted instead of
+    sorted (a bincount and a gather instead of an argsort over every row of the frame)."""
+    if values.dtype.kind in "iu" and len(values):
+        lo, hi = int(values.min()), int(values.max())
+        if lo >= 0 and hi <= 4 * len(values) + 65536:
+            seen = np.bincount(values, minlength=hi + 1) > 0
+            return np.flatnonzero(seen).astype(values.dtype), (np.cumsum(seen) - 1)[values]
+    return np.unique(values, return_inverse=True)
+
+
+def ground_truth_csr(users: np.ndarray, items: np.ndarray, user_index: Callable[[np.ndarray], np.ndarray],
+                     item_index: Callable[[np.ndarray], np.ndarray]):
+    """The dict `frame.groupby("user")["item"].apply(list).to_dict()` of Recommender.evaluate as arrays.
+
+    `users` / `items` are the two id columns; `user_index(distinct users)` / `item_index(distinct items)` return the
+    internal int64 id of every distinct value, -1 for one the model does not know.  Returns
+        eval_users   the distinct users in evaluation order (groupby sorts its keys and drops missing ones)
+        user_rows    their internal ids (-1: unknown user)
+        truth_ptr    int64[n + 1], truth_items int32: per user the KNOWN items of its list, sorted and unique
+        truth_len    int32[n]: len() of the user's list -- duplicated rows and unknown items included, which is what the
+                     reference divides by while it tests membership against the list's distinct values
+    One sort per column and one over the (user, item) pairs; no Python object per row."""
+    users, items = np.asarray(users), np.asarray(items)
+    if users.shape != items.shape or users.ndim != 1:
+        raise ValueError("users and items must be two columns of one length")
+    drop = _missing(users)
+    if drop.any():
+        users, items = users[~drop], items[~drop]
+    eval_users, u_pos = _distinct(users)
+    n = len(eval_users)
+    user_rows = np.asarray(user_index(eval_users), dtype=np.int64) if n else np.empty(0, np.int64)
+    truth_len = np.bincount(u_pos, minlength=n).astype(np.int32)
+    ok = ~_missing(items)                       # a missing item is in the list (it counts) but equals no recommendation
+    distinct, i_pos = _distinct(items if ok.all() else items[ok])
+    ids = np.asarray(item_index(distinct), dtype=np.int64) if len(distinct) else np.empty(0, np.int64)
+    item_ids, rows = ids[i_pos], (u_pos if ok.all() else u_pos[ok])
+    known = item_ids >= 0
+    if known.any():
+        if not known.all():
+            rows, item_ids = rows[known], item_ids[known]
+        bound = int(item_ids.max()) + 1
+        rows, truth_items = np.divmod(np.unique(rows.astype(np.int64, copy=False) * bound + item_ids), bound)
+        truth_items = truth_items.astype(np.int32)
+    else:
+        rows, truth_items = np.empty(0, np.int64), np.empty(0, np.int32)
+    truth_ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=n), out=truth_ptr[1:])
+    return eval_users, user_rows, truth_ptr, truth_items, truth_len
+
+
+def scores_from_columns(metrics: np.ndarray, tp: np.ndarray) -> Dict[str, float]:
+    """compute_scores over per-user columns (metrics[n, 8] in METRIC_COLUMNS order, tp[n]): sequential float64 sums in row
+    order divided by n, tp an integer sum; the same dict, key order included."""
+    n = len(tp)
+    if n == 0:
+        return defaultdict(float)
+    col = {name: sequential_sum(metrics[:, j]) / n for j, name in enumerate(METRIC_COLUMNS)}
+    col["tp"] = int(np.asarray(tp, dtype=np.int64).sum())
+    return {name: col[name] for name in RESULT_KEYS}
