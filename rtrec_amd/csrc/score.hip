@@ -1190,6 +1190,14 @@ __device__ __forceinline__ void fr_static_for(F &&f) {
 
 typedef const __attribute__((address_space(4))) unsigned long long fr_const_u64;
 typedef const __attribute__((address_space(4))) float fr_const_f32;
+typedef const __attribute__((address_space(4))) int fr_const_i32;
+
+// One fragment's constants of W (tile_rows, tile_off, frag_tile, frag_wtop), held in scalar registers.
+struct FrFrag {
+    unsigned long long nz[2];   // rows of the tile's slice the fragment holds
+    int toff, ft;               // byte offset inside the super-tile; tile | first << 24 | last << 25
+    float wtop;                 // 1.0001 * max |w| over the fragment's tile
+};
 
 // First-touch row of layout column c for a user who rates the rows own0 / own1 (bit f: row f / 64 + f of W): the lowest
 // such row with a weight in that column -- scipy's csr_matmat meets the user's items in ascending order, and rows of W
@@ -1233,7 +1241,8 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
     constexpr int TC = 64 * REGS;
     constexpr int ROWB = TC * 4;                            // bytes of one row of a tile
     constexpr int NL = (UW + 3) / 4;                        // list registers: four users per 64 lanes, 16 lanes each
-    const int tid = static_cast<int>(threadIdx.x), wave = tid >> 6, lane = tid & 63;
+    // (the wave index is uniform: said so, everything derived from it -- the wave's scratch, its LDS slices -- is scalar)
+    const int tid = static_cast<int>(threadIdx.x), wave = readfirst_i(tid >> 6), lane = tid & 63;
     const int NW = static_cast<int>(blockDim.x) >> 6;       // waves of this workgroup: 16 (resident layout) or 8 (streaming)
     const int kk = a.kk;                                    // <= 16
     unsigned char *buf0 = smem;
@@ -1258,11 +1267,25 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
     unsigned long long *ms_wave = sc_wave + kFrUsers * kFrUserWords / 2;
     const uint32_t lane16 = static_cast<uint32_t>(lane) * (REGS * 4);         // byte offset of this lane in a row
     // behind the super-tiles: per fragment, 1.0001 * the largest max|w| of its tile's rows (the first-level bound below)
-    fr_const_f32 *frag_wtop = (fr_const_f32 *)(a.wd + (static_cast<size_t>(a.st_kb[a.n_super]) << 8));
+    // W's tables (st_kb, st_tile, tile_rows, tile_off, frag_tile, frag_wtop) are written before the launch and never
+    // during it.  They are read through the constant address space from wave-uniform addresses, i.e. by SCALAR loads:
+    // those count on lgkmcnt, so waiting for one never waits for the LDS-DMA prefetch in flight on vmcnt, and each is
+    // requested one super-tile / one fragment ahead of its use.
+    fr_const_i32 *c_st_kb = (fr_const_i32 *)a.st_kb, *c_st_tile = (fr_const_i32 *)a.st_tile;
+    fr_const_f32 *frag_wtop = (fr_const_f32 *)(a.wd + (static_cast<size_t>(c_st_kb[a.n_super]) << 8));
+    const int n_frags = c_st_tile[a.n_super];
+    auto load_frag = [&](int g) {
+        FrFrag r;
+        r.nz[0] = ((fr_const_u64 *)a.tile_rows)[2 * g];
+        r.nz[1] = ((fr_const_u64 *)a.tile_rows)[2 * g + 1];
+        r.toff = ((fr_const_i32 *)a.tile_off)[g];
+        r.ft = ((fr_const_i32 *)a.frag_tile)[g];
+        r.wtop = frag_wtop[g];
+        return r;
+    };
 
-    // super-tile s = tiles [st_tile[s], st_tile[s + 1]): their rows that hold a weight, tile after tile, st_kb[s + 1] - st_kb[s] KiB
-    auto load_super = [&](int sidx, unsigned char *dst) {
-        const int kb0 = a.st_kb[sidx], kb1 = a.st_kb[sidx + 1];
+    // super-tile s = fragments [st_tile[s], st_tile[s + 1]): their rows that hold a weight, tile after tile, KiB [kb0, kb1) of wd
+    auto load_super = [&](int kb0, int kb1, unsigned char *dst) {
         const unsigned char *src = reinterpret_cast<const unsigned char *>(a.wd) + (static_cast<size_t>(kb0) << 10);
         for (int c = wave; c < kb1 - kb0; c += NW)
             __builtin_amdgcn_global_load_lds((fr_glb_void *)(src + (static_cast<size_t>(c) << 10) + lane * 16),
@@ -1274,7 +1297,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
     const unsigned long long pf_start_ = pf_t_;
 #endif
     if (resident) {                                         // all of W's slices: once per workgroup
-        load_super(0, buf0);
+        load_super(c_st_kb[0], c_st_kb[1], buf0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     // Streaming layout: a job = 128 users of the whole workgroup (the waves share the staged slices and meet at its
@@ -1300,7 +1323,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
             __syncthreads();
             const int job = *s_job;
             if (job >= n_jobs) break;
-            load_super(0, buf0);
+            load_super(c_st_kb[0], c_st_kb[1], buf0);
             // position p of the job's users goes to wave p % NW, so that with rows handed over longest-first (a.order)
             // every wave of the workgroup gets the same mix of long and short rows and the barriers find the waves level
             base = job * NW * UW + (a.consecutive ? wave * UW : wave); pstride = a.consecutive ? 1 : NW;
@@ -1409,6 +1432,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
         });
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_dcache_inv();                   // dense masks are read back through the scalar cache
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // running top-kk of every user, in registers: user u = lanes (u & 3) * 16 .. + kk - 1 of register u >> 2,
         // lane offset j = rank j (a DPP row is 16 lanes, so a list shifts with row_shr:1)
         float ls4[NL];
@@ -1451,25 +1475,22 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
             const float tot = readlane_f(b, 63);
             l1v = lane == u ? tot : l1v;
         });
+        // what the loop below holds one step ahead: the KiB extent of super-tile sidx + 1 (kb_a, kb_b), the fragments of
+        // super-tile sidx ([t_lo, t_hi)), fragment g's constants (fr); fragment numbers run on across super-tiles
+        int kb_a = c_st_kb[min(1, a.n_super)], kb_b = c_st_kb[min(2, a.n_super)];
+        int t_lo = c_st_tile[0], t_hi = c_st_tile[min(1, a.n_super)];
+        FrFrag fr = load_frag(min(t_lo, max(n_frags - 1, 0))), fr_next = fr;
         for (int sidx = 0; sidx < a.n_super; ++sidx) {
             const unsigned char *wb = (sidx & 1) ? buf1 : buf0;
-            if (sidx + 1 < a.n_super) load_super(sidx + 1, (sidx & 1) ? buf0 : buf1);
-            const int t_lo = a.st_tile[sidx], t_hi = a.st_tile[sidx + 1];      // fragments of this super-tile
-            // the fragments' row masks, offsets and tiles, lane g = fragment t_lo + g: one load per super-tile, read
-            // back with v_readlane below (no memory latency inside the loop)
-            unsigned long long nzv[2] = {0ull, 0ull};
-            int toffv = 0, ftilev = 0;
-            if (lane < t_hi - t_lo) {
-                nzv[0] = a.tile_rows[(t_lo + lane) * 2];
-                nzv[1] = a.tile_rows[(t_lo + lane) * 2 + 1];
-                toffv = a.tile_off[t_lo + lane];
-                ftilev = a.frag_tile[t_lo + lane];
-            }
+            if (sidx + 1 < a.n_super) load_super(kb_a, kb_b, (sidx & 1) ? buf0 : buf1);
+            // the next super-tile's extents: requested now, needed at the hand-over
+            const int kb_c = c_st_kb[min(sidx + 3, a.n_super)], t_hi_next = c_st_tile[min(sidx + 2, a.n_super)];
             const unsigned char *wlane = wb + lane16;             // this lane's columns in a slice row
             const unsigned char *wzero = zrow + lane16;           // a row of +0.0: what a step reads past the last row
 
-            for (int g = t_lo; g < t_hi; ++g) {
-                const int ft = readlane_i(ftilev, g - t_lo);
+            for (int g = t_lo; g < t_hi; ++g, fr = fr_next) {
+                fr_next = load_frag(min(g + 1, n_frags - 1));     // in flight while fragment g is worked on
+                const int ft = fr.ft;
                 const int t = ft & 0xffffff;                     // the tile this fragment belongs to
                 // ---- tile-major sweep: every row of W that holds a weight in this tile (and that one of the wave's
                 //      users rates) is read from LDS ONCE and applied to all eight users: acc_u += x_u * w, one
@@ -1477,7 +1498,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                 //      and 256 columns), rows ascending = scipy's order.  A user that does not rate the row has
                 //      x_u = 0: x * w = +-0 changes no sum (a sum that starts at +0 never becomes -0), and the same
                 //      holds for rows and blocks that are skipped altogether. ----
-                const int toff = readlane_i(toffv, g - t_lo);
+                const int toff = fr.toff;
                 if (ft & (1 << 24)) {                            // first fragment of a tile
                     // ---- can this tile matter at all?  Its header holds max |w| of every row of W over the tile's
                     //      columns (lane f = row 64 h + f), so  B_u = sum_f |x_uf| max|w_f|  bounds every score user u
@@ -1489,7 +1510,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                     // the (wave, tile) pairs on the ML-20M shape; only the others read the header and pay the per-user
                     // reductions below.  max_f max|w_f| (times the margin) is a constant of W: the layout stores it
                     // per fragment (frag_wtop) instead of every wave reducing the header again for every job
-                    const float wtop = frag_wtop[g];                 // scalar load
+                    const float wtop = fr.wtop;
                     // (a user with NO rating on a row of W -- an empty row, a position past the end of the batch in the last job --
                     // has bound 0: every sum is +0, no candidate; it must not hold the tile open while its list is empty.  Such a
                     // slot used to keep its wave sweeping EVERY tile: a batch whose size is no multiple of the job size paid one
@@ -1521,9 +1542,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                 int below = 0;                                   // rows of this tile's slice before half h
                 fr_static_for<XR>([&](auto H) {
                     constexpr int h = decltype(H)::value;
-                    const unsigned long long nz =
-                        (static_cast<unsigned long long>(readlane_u(static_cast<uint32_t>(nzv[h] >> 32), g - t_lo)) << 32) |
-                        readlane_u(static_cast<uint32_t>(nzv[h]), g - t_lo);
+                    const unsigned long long nz = fr.nz[h];
                     unsigned long long rows = nz & own_or[h];
                     while (rows) {
                         // two rows per step: their LDS reads go out together; eight users' applies (80 vector
@@ -1669,6 +1688,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                 __syncthreads();                                    // ... and every wave has left super-tile s
             }
             PF_MARK(PF_GROUP)
+            kb_a = kb_b; kb_b = kb_c; t_lo = t_hi; t_hi = t_hi_next;
         }
 
         // ---- the lists are the rows' answers: lane lb + j of list register g = rank j of user 4 g + lb / 16 ----
