@@ -698,27 +698,15 @@ class SlimEngine:
         """The LIL write-back of slim_elastic.py:271-274 / 371-374 / 554-557 on the device: start from `old`, then for
         every fitted (i, j) a non-zero value overwrites W[i, j] and an explicit zero deletes it; entries of column j
         that the new solution does not mention survive.  The arguments are this rank's
-        fit_columns(device_out=True) tensors; with several ranks the triples are exchanged with all_gather_into_tensor
-        (int64 keys + float32 values, padded to the longest part) -- nothing is pickled and nothing visits the host."""
+        fit_columns(device_out=True) tensors; with several ranks the triples are exchanged on the device
+        (_all_gather_triples) -- nothing is pickled and nothing visits the host."""
         torch = self.be.torch
         n, cap = d_items.shape
         mask = torch.arange(cap, device=d_items.device)[None, :] < d_count[:, None]
         key = (d_targets.to(torch.int64)[:, None] * n_items + d_items.to(torch.int64))[mask]
         val = d_coef[mask]
         if self.world_size > 1 and not self.shard_w:
-            import torch.distributed as dist
-            sizes = torch.zeros(self.world_size, dtype=torch.int64, device=key.device)
-            dist.all_gather_into_tensor(sizes, torch.tensor([key.numel()], dtype=torch.int64, device=key.device), group=self.group)
-            sizes = sizes.cpu().tolist()
-            m = max(max(sizes), 1)
-            kp = torch.zeros(m, dtype=torch.int64, device=key.device); kp[:key.numel()] = key
-            vp = torch.zeros(m, dtype=torch.float32, device=key.device); vp[:val.numel()] = val
-            ka = torch.empty(m * self.world_size, dtype=torch.int64, device=key.device)
-            va = torch.empty(m * self.world_size, dtype=torch.float32, device=key.device)
-            dist.all_gather_into_tensor(ka, kp, group=self.group)
-            dist.all_gather_into_tensor(va, vp, group=self.group)
-            key = torch.cat([ka[r * m:r * m + s] for r, s in enumerate(sizes)])
-            val = torch.cat([va[r * m:r * m + s] for r, s in enumerate(sizes)])
+            key, val = self._all_gather_triples(key, val)
         if self.shard_w and old is not None and (getattr(old, "shard", None) is None or old.n_items != n_items):
             # the catalogue grew (the block boundaries moved) or the old W was not sharded: every rank keeps the old entries
             # of ITS columns under the new boundaries
@@ -741,28 +729,30 @@ class SlimEngine:
             dw.shard = (self.rank, self.world_size)
         return dw
 
+    def _all_gather_triples(self, key, val):
+        """Every rank's (int64 key, float32 value) triples, concatenated in rank order: all_gather_into_tensor of the parts,
+        each padded to the longest one (only the part sizes visit the host).  A COLLECTIVE: every rank calls it."""
+        import torch.distributed as dist
+        torch, G, dev = self.be.torch, self.world_size, key.device
+        sizes = torch.zeros(G, dtype=torch.int64, device=dev)
+        dist.all_gather_into_tensor(sizes, torch.tensor([key.numel()], dtype=torch.int64, device=dev), group=self.group)
+        sizes = sizes.cpu().tolist()
+        m = max(max(sizes), 1)
+        out = []
+        for part in (key, val):
+            padded = torch.zeros(m, dtype=part.dtype, device=dev); padded[:part.numel()] = part
+            every = torch.empty(m * G, dtype=part.dtype, device=dev)
+            dist.all_gather_into_tensor(every, padded, group=self.group)
+            out.append(torch.cat([every[r * m:r * m + n] for r, n in enumerate(sizes)]))
+        return tuple(out)
+
     def gather_weights(self, dw: "DeviceWeights") -> "DeviceWeights":
         """All of W from its column shards (shard_w): the ranks' triples concatenated in rank order = (column, row) order,
         because the shards are contiguous column blocks.  A COLLECTIVE: every rank calls it (reading `item_similarity`,
         pickling).  A W that is not sharded is returned as it is."""
         if getattr(dw, "shard", None) is None or self.world_size == 1:
             return dw
-        import torch.distributed as dist
-        torch = self.be.torch
-        dev = dw.vals.device
-        sizes = torch.zeros(self.world_size, dtype=torch.int64, device=dev)
-        dist.all_gather_into_tensor(sizes, torch.tensor([dw.nnz], dtype=torch.int64, device=dev), group=self.group)
-        sizes = sizes.cpu().tolist()
-        m = max(max(sizes), 1)
-        key = dw.cols * dw.n_items + dw.rows
-        kp = torch.zeros(m, dtype=torch.int64, device=dev); kp[:dw.nnz] = key
-        vp = torch.zeros(m, dtype=torch.float32, device=dev); vp[:dw.nnz] = dw.vals
-        ka = torch.empty(m * self.world_size, dtype=torch.int64, device=dev)
-        va = torch.empty(m * self.world_size, dtype=torch.float32, device=dev)
-        dist.all_gather_into_tensor(ka, kp, group=self.group)
-        dist.all_gather_into_tensor(va, vp, group=self.group)
-        key = torch.cat([ka[r * m:r * m + n] for r, n in enumerate(sizes)])
-        val = torch.cat([va[r * m:r * m + n] for r, n in enumerate(sizes)])
+        key, val = self._all_gather_triples(dw.cols * dw.n_items + dw.rows, dw.vals)
         return DeviceWeights(key % dw.n_items, key // dw.n_items, val.contiguous(), dw.n_items, dw.f64)
 
     def _fast_layout(self) -> Optional[Dict[str, Any]]:
@@ -1041,124 +1031,125 @@ class SlimEngine:
         plan = score_plan.choose_path(facts, req, has_fr=bool(fast is not None and fast.get("fr_w") is not None),
                                       has_sg=bool(fast is not None and fast.get("sg") is not None),
                                       tiled_exists=tiled_key in W["layouts"])
-        use_fr, use_sg, dense_fast = plan.use_fr, plan.use_sg, req.dense_fast
-        if plan.path is score_plan.Path.FAST_F64:
-            return self._local_topk_f64(d_row_ids, n_rows, xb, top_k, filter_interacted, d_col_rank, fast, use_fr, use_sg,
-                                        ids, sc, sc64, aux, cnt, mode, signed=plan.f64_signed)
-        if plan.path is score_plan.Path.FAST and plan.lazy:
-            need = be.score_workspace_bytes(n_rows, 1, top_k)
-            if self._score_ws is None or self._score_ws.numel() < need:
-                self._score_ws = be.empty((need,), torch.uint8)
-            order = self._row_order(d_row_ids, n_rows, xb, fast, allow_grouped=use_fr)
-            self.last_score_path = "feature_rows" if use_fr else "segments"
-            flagged = pack[2 * nk + cap:] if flag_words else be.empty((n_rows + 1,), torch.int32)
-            fill = plan.fill
-            flagged_fast = be.empty((n_rows + 1,), torch.int32) if fill else flagged
-            be.score_topk(n_rows, d_row_ids, xb, W["n_items"], W["col_lo"], fast, d_col_rank, top_k, filter_interacted,
-                          mode, False, ids, sc, None, aux, cnt, self._score_ws, timer=self.score_timer,
-                          diagnostics=self.diagnostics | ((self.fr_users_per_wave & 0xf) << 8) | ((self.sg_heavy_min & 0xfff) << 12), use_fr=use_fr, row_order=order,
-                          rescored=None, row_order_grouped=(order is not None and use_fr and self._order_grouped),
-                          use_sg=use_sg, use_sg_heavy=self.use_seg_heavy, flagged=flagged_fast)
-            if fill:          # DENSE mode: short all-positive lists are completed with the zero-score columns, the rest stays flagged
-                be.ops.dense_fill(d_row_ids, xb[0], xb[1], n_rows, int(W["col_lo"]), int(W["col_hi"]), top_k, bool(filter_interacted),
-                                  ids, sc, aux, cnt, flagged_fast, flagged)
-            if flag_words:                # one download: the lists and the counter
-                h = pack.cpu().numpy()
-                n_flag = int(h[2 * nk + cap])
-                if n_flag == 0:
-                    ids._rtrec_host = h
-            else:
-                n_flag = int(flagged[0].item())
-            if self.rescored is not None:
-                self.rescored.fill_(n_flag)
-            if n_flag:
-                # exact ties: those rows again, against the tiled layout (built now) -- its exact-tie pass orders them
-                lay = self._layout(compact=not dense_fast, top_k=top_k)
-                rows_f = flagged[1:1 + n_flag].long()
-                sub_ids = d_row_ids[rows_f].contiguous() if d_row_ids is not None else rows_f.to(torch.int32)
-                t_ids, t_sc, t_aux = (be.empty((n_flag, top_k), dt) for dt in (torch.int32, torch.float32, torch.int32))
-                t_cnt = be.empty((n_flag,), torch.int32)
-                need = be.score_workspace_bytes(n_flag, lay["n_tiles"], top_k)
-                if self._score_ws.numel() < need:
-                    self._score_ws = be.empty((need,), torch.uint8)
-                be.score_topk(n_flag, sub_ids, xb, W["n_items"], W["col_lo"], lay, d_col_rank, top_k, filter_interacted,
-                              mode, False, t_ids, t_sc, None, t_aux, t_cnt, self._score_ws, use_fr=False, use_sg=False)
-                ids[rows_f] = t_ids; sc[rows_f] = t_sc; aux[rows_f] = t_aux; cnt[rows_f] = t_cnt
-            return ids, sc, sc64, aux, cnt
+        out = (ids, sc, sc64, aux, cnt)
+        if plan.lazy:             # the fast pass alone; the tiled layout only for the rows it flags (float64 W: always)
+            return self._local_topk_lazy(plan, fast, d_row_ids, n_rows, xb, top_k, filter_interacted, mode, d_col_rank, out,
+                                         host_pack=pack if flag_words else None)
         lay = self._layout(compact=sparse, top_k=top_k)
         if lay is None:
             ids.fill_(-1); sc.fill_(float("-inf")); aux.zero_(); cnt.zero_()
             if sc64 is not None:
                 sc64.fill_(float("-inf"))
-            return ids, sc, sc64, aux, cnt
-        need = be.score_workspace_bytes(n_rows, lay["n_tiles"], top_k)
+            return out
+        if plan.use_sg and lay.get("sg") is None:          # a small batch against a feature-row W: its segment form
+            lay = dict(lay, sg=fast["sg"])
+        self._launch_score(lay, d_row_ids, n_rows, xb, top_k, filter_interacted, mode, d_col_rank, out, plan.use_fr, plan.use_sg,
+                           rescored=self.rescored, acc_f64=W["acc_f64"])
+        return out
+
+    def _score_workspace(self, need: int):
+        """The score kernels' scratch (self._score_ws), grown to at least `need` bytes."""
         if self._score_ws is None or self._score_ws.numel() < need:
-            self._score_ws = be.empty((need,), torch.uint8)
-        if hip:
-            if use_sg and lay.get("sg") is None:          # a small batch against a feature-row W: its segment form
-                lay = dict(lay, sg=fast["sg"])
-            order = self._row_order(d_row_ids, n_rows, xb, lay, allow_grouped=use_fr) if (use_fr or use_sg) else None
-            self.last_score_path = "feature_rows" if use_fr else ("segments" if use_sg else "tiled")
-            be.score_topk(n_rows, d_row_ids, xb, W["n_items"], W["col_lo"], lay, d_col_rank, top_k, filter_interacted,
-                          mode, W["acc_f64"], ids, sc, sc64, aux, cnt, self._score_ws, timer=self.score_timer,
-                          diagnostics=self.diagnostics | ((self.fr_users_per_wave & 0xf) << 8) | ((self.sg_heavy_min & 0xfff) << 12), use_fr=use_fr, row_order=order,
-                          rescored=self.rescored,
-                          row_order_grouped=(order is not None and use_fr and self._order_grouped), use_sg=use_sg,
-                          use_sg_heavy=self.use_seg_heavy)
-        else:
-            be.score_topk(n_rows, d_row_ids, xb, W["n_items"], W["col_lo"], lay, d_col_rank, top_k, filter_interacted,
-                          mode, W["acc_f64"], ids, sc, sc64, aux, cnt, self._score_ws)
-        return ids, sc, sc64, aux, cnt
+            self._score_ws = self.be.empty((need,), self.be.torch.uint8)
+        return self._score_ws
+
+    def _launch_score(self, lay, d_row_ids, n_rows: int, xb, top_k: int, filter_interacted: bool, mode: int, d_col_rank, out,
+                      use_fr: bool = False, use_sg: bool = False, flagged=None, rescored=None, acc_f64: bool = False,
+                      dominant: bool = True, path_suffix: str = "") -> None:
+        """THE launch of rtrec_slim_score_topk: `n_rows` rows of the batch `xb` against the layout `lay` into `out` = (ids,
+        scores, float64 scores or None, tie keys, counts).  What every launch needs is derived here and nowhere else: the
+        scratch, the work order (only when a fast kernel runs; the pattern-grouped one only for the feature-row kernel -- the
+        segment kernels rely on the length order), the flag that says which order it is, the diagnostics word.
+        `dominant`: the kernel that does the bulk of the call's work -- it alone is bracketed by score_timer (bench.py reads
+        it), looks at the diagnostics and names last_score_path; the tiled re-score of a few flagged rows is not."""
+        be, W = self.be, self._W
+        # (a fast form alone has no tiles of its own: its kernels need the scratch of one)
+        ws = self._score_workspace(be.score_workspace_bytes(n_rows, lay.get("n_tiles", 1), top_k))
+        args = (n_rows, d_row_ids, xb, W["n_items"], W["col_lo"], lay, d_col_rank, top_k, filter_interacted, mode, acc_f64,
+                *out, ws)
+        if not isinstance(be, HipBackend):          # the tests' stand-in (tests/cpu_backend.py): the tiled kernel only
+            be.score_topk(*args)
+            return
+        order = self._row_order(d_row_ids, n_rows, xb, lay, allow_grouped=use_fr) if (use_fr or use_sg) else None
+        timer = diagnostics = 0
+        if dominant:
+            timer = self.score_timer
+            diagnostics = self.diagnostics | ((self.fr_users_per_wave & 0xf) << 8) | ((self.sg_heavy_min & 0xfff) << 12)
+            self.last_score_path = ("feature_rows" if use_fr else ("segments" if use_sg else "tiled")) + path_suffix
+        be.score_topk(*args, timer=timer, diagnostics=diagnostics, use_fr=use_fr, row_order=order, rescored=rescored,
+                      row_order_grouped=(order is not None and use_fr and self._order_grouped), use_sg=use_sg,
+                      use_sg_heavy=self.use_seg_heavy, flagged=flagged)
+
+    def _rescore_flagged(self, rows_f, d_row_ids, xb, top_k: int, filter_interacted: bool, mode: int, d_col_rank, out) -> None:
+        """The flagged rows of a fast pass (`rows_f`: int64 positions in the batch) again, against the tiled layout (built
+        now, if this is the first call that needs it) -- its exact-tie pass orders them like the reference -- and scattered
+        into `out`; float64 accumulators when `out` carries float64 scores."""
+        be, torch = self.be, self.be.torch
+        n_f = int(rows_f.numel())
+        lay = self._layout(compact=(mode == _native.TOPK_SPARSE), top_k=top_k)
+        sub_ids = d_row_ids[rows_f].contiguous() if d_row_ids is not None else rows_f.to(torch.int32)
+        f64 = out[2] is not None
+        tmp = (be.empty((n_f, top_k), torch.int32), be.empty((n_f, top_k), torch.float32),
+               be.empty((n_f, top_k), torch.float64) if f64 else None, be.empty((n_f, top_k), torch.int32),
+               be.empty((n_f,), torch.int32))
+        self._launch_score(lay, sub_ids, n_f, xb, top_k, filter_interacted, mode, d_col_rank, tmp, acc_f64=f64, dominant=False)
+        for dst, src in zip(out, tmp):
+            if src is not None:
+                dst[rows_f] = src
 
     F64_REFINE_MIN_VALUE = 1e-18     # ratings and weights at least this large: a product is a normal float32 number
 
-    def _local_topk_f64(self, d_row_ids, n_rows: int, xb, top_k: int, filter_interacted: bool, d_col_rank, fast, use_fr: bool,
-                        use_sg: bool, ids, sc, sc64, aux, cnt, mode: int = _native.TOPK_SPARSE, signed: bool = False):
-        """SPARSE mode, float64 W with positive float32-valued weights, positive ratings: the float32 fast pass for top_k + 1
+    def _local_topk_lazy(self, plan, fast, d_row_ids, n_rows: int, xb, top_k: int, filter_interacted: bool, mode: int,
+                         d_col_rank, out, host_pack=None):
+        """The fast pass against `fast` alone, its post-step, and the tiled kernel for the rows the two flag.
+        float32 W (Path.FAST): the flagged rows hold an exact score tie.  `host_pack`: the caller downloads the lists (the
+        buffer they are views of, flag words at its end), so the flag counter is read out of the same copy.
+        float64 W (Path.FAST_F64) with positive float32-valued weights, positive ratings: the float32 fast pass for top_k + 1
         columns, the float64 scores of those candidates (csrc/score_refine.hip), and the float64 tiled kernel for the rows
         either step flags (float32 ties; a top_k-th float64 score too close to what a column outside the list could reach;
         float64 ties).  DENSE mode likewise: its fast pass also flags the rows with fewer than top_k + 1 positive scores (every
-        non-zero score is positive here), which the DENSE float64 tiled kernel then scores."""
-        dense = mode == _native.TOPK_DENSE
+        non-zero score is positive here), which the DENSE float64 tiled kernel then scores.  plan.f64_signed (SPARSE): signed
+        weights, with the absolute per-user slack of _f64_abs_slack."""
         be, W = self.be, self._W
         torch = be.torch
-        k1 = top_k + 1
-        ids1, sc1 = be.empty((n_rows, k1), torch.int32), be.empty((n_rows, k1), torch.float32)
-        aux1, cnt1 = be.empty((n_rows, k1), torch.int32), be.empty((n_rows,), torch.int32)
-        flagged = be.empty((2 * n_rows + 2,), torch.int32)
-        need = be.score_workspace_bytes(n_rows, 1, k1)
-        if self._score_ws is None or self._score_ws.numel() < need:
-            self._score_ws = be.empty((need,), torch.uint8)
-        order = self._row_order(d_row_ids, n_rows, xb, fast, allow_grouped=use_fr)
-        self.last_score_path = ("feature_rows" if use_fr else "segments") + "+f64"
-        be.score_topk(n_rows, d_row_ids, xb, W["n_items"], W["col_lo"], fast, d_col_rank, k1, filter_interacted,
-                      mode, False, ids1, sc1, None, aux1, cnt1, self._score_ws, timer=self.score_timer,
-                      diagnostics=self.diagnostics | ((self.fr_users_per_wave & 0xf) << 8) | ((self.sg_heavy_min & 0xfff) << 12),
-                      use_fr=use_fr, row_order=order, rescored=None,
-                      row_order_grouped=(order is not None and use_fr and self._order_grouped),
-                      use_sg=use_sg, use_sg_heavy=self.use_seg_heavy, flagged=flagged)
-        wc_ptr, wc_row, wc_val = W["dw"].csc_arrays(torch)
-        margin = 2.0 * (W["col_nnz_max"] + 2) * 2.0 ** -24
-        be.ops.refine_topk_f64(d_row_ids, xb[0], xb[1], xb[2], n_rows, W["n_items"], wc_ptr, wc_row, wc_val, top_k, ids1, sc1, cnt1,
-                               float(margin), self._f64_abs_slack(xb) if signed else None, ids, sc, sc64, cnt, flagged)
-        aux.zero_()
-        n_flag = int(flagged[0].item())
+        ids, sc, sc64, aux, cnt = out
+        f64 = plan.path is score_plan.Path.FAST_F64
+        k_fast = plan.k_fast
+        if f64:
+            host_pack = None
+            fast_out = (be.empty((n_rows, k_fast), torch.int32), be.empty((n_rows, k_fast), torch.float32), None,
+                        be.empty((n_rows, k_fast), torch.int32), be.empty((n_rows,), torch.int32))
+            flagged = be.empty((2 * n_rows + 2,), torch.int32)          # a row can be flagged by both steps
+        else:
+            fast_out = (ids, sc, None, aux, cnt)
+            flagged = host_pack[-(n_rows + 1):] if host_pack is not None else be.empty((n_rows + 1,), torch.int32)
+        flagged_fast = be.empty((n_rows + 1,), torch.int32) if plan.fill else flagged
+        self._launch_score(fast, d_row_ids, n_rows, xb, k_fast, filter_interacted, mode, d_col_rank, fast_out, plan.use_fr,
+                           plan.use_sg, flagged=flagged_fast, path_suffix="+f64" if f64 else "")
+        if f64:
+            ids1, sc1, _, _, cnt1 = fast_out
+            wc_ptr, wc_row, wc_val = W["dw"].csc_arrays(torch)
+            margin = 2.0 * (W["col_nnz_max"] + 2) * 2.0 ** -24
+            be.ops.refine_topk_f64(d_row_ids, xb[0], xb[1], xb[2], n_rows, W["n_items"], wc_ptr, wc_row, wc_val, top_k, ids1, sc1, cnt1,
+                                   float(margin), self._f64_abs_slack(xb) if plan.f64_signed else None, ids, sc, sc64, cnt, flagged)
+            aux.zero_()
+        elif plan.fill:          # DENSE mode: short all-positive lists are completed with the zero-score columns, the rest stays flagged
+            be.ops.dense_fill(d_row_ids, xb[0], xb[1], n_rows, int(W["col_lo"]), int(W["col_hi"]), top_k, bool(filter_interacted),
+                              ids, sc, aux, cnt, flagged_fast, flagged)
+        if host_pack is not None:                # one download: the lists and the counter
+            h = host_pack.cpu().numpy()
+            n_flag = int(h[-(n_rows + 1)])
+            if n_flag == 0:
+                ids._rtrec_host = h
+        else:
+            n_flag = int(flagged[0].item())
         if self.rescored is not None:
             self.rescored.fill_(n_flag)
         if n_flag:
-            rows_f = torch.unique(flagged[1:1 + n_flag].long())
-            n_f = int(rows_f.numel())
-            lay = self._layout(compact=not dense, top_k=top_k)
-            sub_ids = d_row_ids[rows_f].contiguous() if d_row_ids is not None else rows_f.to(torch.int32)
-            t_ids, t_sc, t_aux = (be.empty((n_f, top_k), dt) for dt in (torch.int32, torch.float32, torch.int32))
-            t_sc64, t_cnt = be.empty((n_f, top_k), torch.float64), be.empty((n_f,), torch.int32)
-            need = be.score_workspace_bytes(n_f, lay["n_tiles"], top_k)
-            if self._score_ws.numel() < need:
-                self._score_ws = be.empty((need,), torch.uint8)
-            be.score_topk(n_f, sub_ids, xb, W["n_items"], W["col_lo"], lay, d_col_rank, top_k, filter_interacted,
-                          mode, True, t_ids, t_sc, t_sc64, t_aux, t_cnt, self._score_ws, use_fr=False, use_sg=False)
-            ids[rows_f] = t_ids; sc[rows_f] = t_sc; sc64[rows_f] = t_sc64; aux[rows_f] = t_aux; cnt[rows_f] = t_cnt
-        return ids, sc, sc64, aux, cnt
+            rows_f = flagged[1:1 + n_flag].long()
+            self._rescore_flagged(torch.unique(rows_f) if f64 else rows_f, d_row_ids, xb, top_k, filter_interacted, mode,
+                                  d_col_rank, out)
+        return out
 
     ROW_ORDER_MIN = 2048        # batches below this are one or two waves of jobs: nothing to level
     GROUPED_ORDER_MIN = 32768   # the pattern-grouped order (~1 ms to compute, kept per row set) pays for bulk passes only
@@ -1274,16 +1265,8 @@ class SlimEngine:
                           candidates: Optional[np.ndarray] = None, with_scores: bool = True):
         """Device tensors (ids, scores, counts) of the GLOBAL top-k for the given rows of X
         (or of the CSR batch `xb` = (ptr, col, val) device tensors).  `d_rows` may pass the row ids
-        as a device tensor that is already resident (bench.py reuses it across steps).
-
-        Multi-GPU: every rank scores the rows against its own column shard and packs its per-shard lists
-        into ONE int32 record per user -- [scores | ids | first-touch aux | count] (float64 scores in
-        front when W is float64).  The exchange is sized for xGMI's point-to-point mesh rather than for
-        a switch: an ALL-TO-ALL hands rank r the records of ITS slice of the users from every shard
-        (B/G * 124 B from each peer instead of all B * 124 B of an all-gather), merge_topk_kernel merges
-        that slice in place through strides, and only the final k-lists (84 B per user) are all-gathered.
-        Rows are processed in chunks whose exchanges (RCCL, asynchronous on its own stream) overlap the
-        scoring kernel of the next chunk.
+        as a device tensor that is already resident (bench.py reuses it across steps).  Multi-GPU: the exchange of the
+        column shards (_score_column_sharded) or of the row shards (_score_row_sharded).
         with_scores=False (row shards): only ids and counts travel -- what `recommend_batch` returns (the reference hands out
         item ids, base.py:188-269) -- 44 instead of 84 bytes per user at k = 10; the score tensor is then None."""
         be = self.be
@@ -1305,28 +1288,47 @@ class SlimEngine:
         if self.world_size == 1 and not self.force_exchange:
             ids, sc, sc64, aux, cnt = self._local_topk(d_rows, n_rows, xb, top_k, filter_interacted, mode, d_rank, host=host)
             return ids, sc, cnt
-        import torch.distributed as dist
-        torch = be.torch
-        G, k = self.world_size, top_k
-        f64 = bool(self._W["acc_f64"])
         if d_rows is None:
-            d_rows = torch.arange(n_rows, dtype=torch.int32, device=xb[0].device)
+            d_rows = be.torch.arange(n_rows, dtype=be.torch.int32, device=xb[0].device)
         if self.score_shard == "rows":
-            return self._score_row_sharded(d_rows, n_rows, xb, k, filter_interacted, mode, d_rank, with_scores)
+            return self._score_row_sharded(d_rows, n_rows, xb, top_k, filter_interacted, mode, d_rank, with_scores)
+        return self._score_column_sharded(d_rows, n_rows, xb, top_k, filter_interacted, mode, d_rank)
+
+    def _score_column_sharded(self, d_rows, n_rows: int, xb, k: int, filter_interacted: bool, mode: int, d_rank):
+        """score_shard == "columns": every rank scores the rows against its own column shard and packs its per-shard lists
+        into ONE int32 record per user -- [scores | ids | first-touch aux | count] (float64 scores in
+        front when W is float64).  The exchange is sized for xGMI's point-to-point mesh rather than for
+        a switch: an ALL-TO-ALL hands rank r the records of ITS slice of the users from every shard
+        (B/G * 124 B from each peer instead of all B * 124 B of an all-gather), merge_topk_kernel merges
+        that slice in place through strides, and only the final k-lists (84 B per user) are all-gathered.
+        Rows are processed in chunks whose exchanges (RCCL, asynchronous on its own stream) overlap the
+        scoring kernel of the next chunk."""
+        import torch.distributed as dist
+        be = self.be
+        torch = be.torch
+        G = self.world_size
+        f64 = bool(self._W["acc_f64"])
         # chunks exist so that one chunk's exchange overlaps the next chunk's kernel; a chunk must still be large enough to
         # fill the chip (GATHER_CHUNK_ROWS), so passes of up to ~200k rows are one chunk
         per = max(1, int(self.gather_chunk_rows))
         n_chunks = max(1, min(MAX_GATHER_CHUNKS, (n_rows + per // 2) // per))
         per = -(-n_rows // n_chunks)
-        # exchanged record (int32 words): [2k float64 scores]? | k scores | k ids | k aux | count | pad to even
+        # The two record layouts (offsets and widths in int32 words; a record is padded to an even number of them):
+        # exchanged: [2k float64 scores]? | k scores | k ids | k aux | count | pad;  final: k scores | k ids | count | pad
         o_sc = 2 * k if f64 else 0
-        width = o_sc + 3 * k + 1
-        width += width & 1
-        fwidth = 2 * k + 1          # final record: k scores | k ids | count | pad to even
-        fwidth += fwidth & 1
-        o_ids = be.empty((n_rows, k), torch.int32)
-        o_scs = be.empty((n_rows, k), torch.float32)
-        o_cnt = be.empty((n_rows,), torch.int32)
+        o_ids, o_aux, o_cnt = o_sc + k, o_sc + 2 * k, o_sc + 3 * k
+        f_ids, f_cnt = k, 2 * k
+        width, fwidth = (n + 1 + ((n + 1) & 1) for n in (o_cnt, f_cnt))
+
+        def record(m: int, n_words: int, parts):
+            """The column blocks `parts` side by side as [m, n_words] int32 records (a zero pad word where the layout has one)."""
+            if sum(int(p.shape[1]) for p in parts) < n_words:
+                parts = parts + [torch.zeros((m, 1), dtype=torch.int32, device=parts[0].device)]
+            return torch.cat(parts, dim=1)
+
+        res_ids = be.empty((n_rows, k), torch.int32)
+        res_sc = be.empty((n_rows, k), torch.float32)
+        res_cnt = be.empty((n_rows,), torch.int32)
         pending = []
         for c in range(n_chunks):
             a, b = c * per, min(n_rows, (c + 1) * per)
@@ -1334,16 +1336,13 @@ class SlimEngine:
             if m <= 0:
                 break
             ids, sc, sc64, aux, cnt = self._local_topk(d_rows[a:b], m, xb, k, filter_interacted, mode, d_rank)
-            parts = ([sc64.view(torch.int32)] if f64 else []) + [sc.view(torch.int32), ids, aux.view(torch.int32),
-                                                                 cnt.view(m, 1)]
-            if (o_sc + 3 * k + 1) & 1:
-                parts.append(torch.zeros((m, 1), dtype=torch.int32, device=ids.device))
+            packed = record(m, width, ([sc64.view(torch.int32)] if f64 else []) + [sc.view(torch.int32), ids, aux.view(torch.int32),
+                                                                                   cnt.view(m, 1)])
             q = -(-m // G)                      # rows of this chunk each rank merges
-            if q * G == m:
-                packed = torch.cat(parts, dim=1)
-            else:                               # pad to G equal slices; padded rows carry count 0
-                packed = torch.zeros((q * G, width), dtype=torch.int32, device=ids.device)
-                packed[:m] = torch.cat(parts, dim=1)
+            if q * G != m:                      # pad to G equal slices; padded rows carry count 0
+                padded = torch.zeros((q * G, width), dtype=torch.int32, device=ids.device)
+                padded[:m] = packed
+                packed = padded
             recv = be.empty((G * q, width), torch.int32)
             work = dist.all_to_all_single(recv, packed, group=self.group, async_op=True)
             pending.append((a, b, q, recv, packed, work))
@@ -1351,29 +1350,23 @@ class SlimEngine:
         for a, b, q, recv, packed, work in pending:
             work.wait()
             g3 = recv.view(G, q, width)         # [source shard, row of my slice, record]
-            g_sc = g3[:, :, o_sc:o_sc + k].view(torch.float32)
-            g_ids = g3[:, :, o_sc + k:o_sc + 2 * k]
-            g_aux = g3[:, :, o_sc + 2 * k:o_sc + 3 * k]
-            g_cnt = g3[:, :, o_sc + 3 * k]
             g_sc64 = recv.view(torch.float64).view(G, q, width // 2)[:, :, :k] if f64 else None
             s_ids = be.empty((q, k), torch.int32)
             s_sc = be.empty((q, k), torch.float32)
             s_cnt = be.empty((q,), torch.int32)
-            be.merge_topk(q, G, k, g_ids, g_sc, g_sc64, g_aux, g_cnt, s_ids, s_sc, s_cnt)
-            fparts = [s_sc.view(torch.int32), s_ids, s_cnt.view(q, 1)]
-            if (2 * k + 1) & 1:
-                fparts.append(torch.zeros((q, 1), dtype=torch.int32, device=s_ids.device))
-            fin = torch.cat(fparts, dim=1)
+            be.merge_topk(q, G, k, g3[:, :, o_ids:o_aux], g3[:, :, o_sc:o_ids].view(torch.float32), g_sc64, g3[:, :, o_aux:o_cnt],
+                          g3[:, :, o_cnt], s_ids, s_sc, s_cnt)
+            fin = record(q, fwidth, [s_sc.view(torch.int32), s_ids, s_cnt.view(q, 1)])
             out = be.empty((G * q, fwidth), torch.int32)
             work2 = dist.all_gather_into_tensor(out, fin, group=self.group, async_op=True)
             finals.append((a, b, out, fin, work2))
         for a, b, out, fin, work2 in finals:
             work2.wait()
             m = b - a
-            o_scs[a:b] = out[:m, :k].view(torch.float32)
-            o_ids[a:b] = out[:m, k:2 * k]
-            o_cnt[a:b] = out[:m, 2 * k]
-        return o_ids, o_scs, o_cnt
+            res_sc[a:b] = out[:m, :f_ids].view(torch.float32)
+            res_ids[a:b] = out[:m, f_ids:f_cnt]
+            res_cnt[a:b] = out[:m, f_cnt]
+        return res_ids, res_sc, res_cnt
 
     def _score_row_sharded(self, d_rows, n_rows: int, xb, k: int, filter_interacted: bool, mode: int, d_rank,
                            with_scores: bool = True):
@@ -1560,7 +1553,7 @@ class SlimEngine:
         rank array `col_rank` (n_items entries, -1 = not a candidate) or the list `candidates` itself."""
         row_ids = np.asarray(row_ids, dtype=np.int64)
         if len(row_ids) == 0:
-            return (np.empty((0, top_k), np.int32), np.empty((0, top_k), np.float32), np.empty((0,), np.int32))
+            return self._empty_lists(top_k)
         self._check_rows(row_ids)
         row_ids = row_ids.astype(np.int32)
         return self._download(*self.score_topk_device(row_ids, len(row_ids), top_k, filter_interacted, mode, col_rank, host=True,
@@ -1582,15 +1575,24 @@ class SlimEngine:
                       mode: int = _native.TOPK_SPARSE, col_rank: Optional[np.ndarray] = None,
                       candidates: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Top-k for the rows of a host CSR batch (the SLIMElastic.recommend_batch boundary)."""
-        be = self.be
         B = Xb.shape[0]
         if B == 0:
-            return (np.empty((0, top_k), np.int32), np.empty((0, top_k), np.float32), np.empty((0,), np.int32))
+            return self._empty_lists(top_k)
+        return self._download(*self.score_topk_device(None, B, top_k, filter_interacted, mode, col_rank, xb=self._upload_csr(Xb),
+                                                      candidates=candidates))
+
+    @staticmethod
+    def _empty_lists(top_k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(ids, scores, counts) of a call without rows."""
+        return np.empty((0, top_k), np.int32), np.empty((0, top_k), np.float32), np.empty((0,), np.int32)
+
+    def _upload_csr(self, Xb: sp.csr_matrix):
+        """A host CSR batch as the (ptr, col, val) device tensors the score kernels read (sorted indices, int32 / float32)."""
+        be = self.be
         if not Xb.has_sorted_indices:
             Xb = Xb.sorted_indices()
-        xb = (be.to_dev(np.asarray(Xb.indptr, dtype=np.int32)), be.to_dev(np.asarray(Xb.indices, dtype=np.int32)),
-              be.to_dev(np.asarray(Xb.data, dtype=np.float32)))
-        return self._download(*self.score_topk_device(None, B, top_k, filter_interacted, mode, col_rank, xb=xb, candidates=candidates))
+        return (be.to_dev(np.asarray(Xb.indptr, dtype=np.int32)), be.to_dev(np.asarray(Xb.indices, dtype=np.int32)),
+                be.to_dev(np.asarray(Xb.data, dtype=np.float32)))
 
     # ------------------------------------------------------------------------------ score vectors
     def predict_csr(self, Xb: sp.csr_matrix) -> np.ndarray:
@@ -1602,10 +1604,7 @@ class SlimEngine:
             raise RuntimeError("Model must be fitted before calling predict.")
         torch = be.torch
         B = Xb.shape[0]
-        if not Xb.has_sorted_indices:
-            Xb = Xb.sorted_indices()
-        xb = (be.to_dev(np.asarray(Xb.indptr, dtype=np.int32)), be.to_dev(np.asarray(Xb.indices, dtype=np.int32)),
-              be.to_dev(np.asarray(Xb.data, dtype=np.float32)))
+        xb = self._upload_csr(Xb)
         lay = self._layout(compact=False)
         dt = torch.float64 if W["acc_f64"] else torch.float32
         n_local = W["col_hi"] - W["col_lo"]
@@ -1629,7 +1628,7 @@ class SlimEngine:
         q = np.asarray(queries, dtype=np.int32)
         n = len(q)
         if n == 0:
-            return (np.empty((0, top_k), np.int32), np.empty((0, top_k), np.float32), np.empty((0,), np.int32))
+            return self._empty_lists(top_k)
         d_q = be.to_dev(q)
         ids = be.empty((n, top_k), torch.int32)
         sc = be.empty((n, top_k), torch.float32)
