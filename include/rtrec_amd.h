@@ -682,6 +682,36 @@ int rtrec_rank_metrics(int32_t n_rows, int32_t size, const int32_t *d_ids, int32
                        const int32_t *d_truth_len, const double *d_discount, const double *d_ideal,
                        uint64_t *d_rel, int32_t *d_tp, double *d_metrics, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * EXPLANATIONS  (an extension: the reference has no such call.  In SLIM score(u, i) = sum_j X[u, j] * W[j, i] is a short sum
+ * over the items the user rated; its largest terms are the "because you interacted with ..." of a recommendation.)
+ * Job r explains the list d_ids[r * ids_stride + 0 .. list_k) (item ids; valid up to d_counts[r], clamped to [0, list_k]) for
+ * CSR row d_row_ids[r] of d_xb_* (row r when d_row_ids is NULL; columns ascending; xb_nnz = length of d_xb_col / d_xb_val)
+ * against W in CSC form d_wc_* (d_wc_ptr[n_items + 1], rows ascending per column, float32 values; wc_nnz = length of d_wc_row /
+ * d_wc_val).  Per (row u, item i):
+ *   contributing items  the j stored in both row u of X and column i of W
+ *   contribution        c(j) = fl32(x_uj * w_ji): one float32 multiply, one rounding, fused with nothing.  A W that is float64
+ *                       on the host (serial fit) holds float32 values on the device; the float64 product of two float32
+ *                       numbers is exact, so its float32 rounding is the same number
+ *   support             the number of contributing items -> d_out_support[n_rows][list_k]
+ *   reasons             the top_m contributing items by c descending, among equal c the LOWER item id first; every stored
+ *                       intersection takes part, negative ones included -> d_out_items / d_out_contrib [n_rows][list_k][top_m],
+ *                       unused slots -1 / -inf (the padding of rtrec_slim_score_topk)
+ * Invariant for a float32 W: adding all contributions of a pair in ascending j, sequentially in float32 from 0.0f, gives
+ * exactly the score rtrec_slim_score_topk reports for the pair (scipy's csr_matmat order).
+ * A list slot at or beyond d_counts[r], an item id outside [0, n_items) (-1 included) and a row id outside [0, n_x_rows) (a
+ * user without a row) get support 0 and only padding.  CSR / CSC offsets are clamped to [0, xb_nnz] / [0, wc_nnz], so a
+ * malformed matrix gives wrong answers, never an out-of-range read.
+ * list_k in 1..64 and top_m in 1..32 (RTREC_ERR_UNSUPPORTED otherwise); NULL or negative arguments and ids_stride < list_k:
+ * RTREC_ERR_INVALID_ARG; n_rows == 0: RTREC_OK.  One wave per row (csrc/explain.hip, explain_topk_kernel).
+ * ------------------------------------------------------------------------------------- */
+int rtrec_slim_explain_topk(int32_t n_rows, const int32_t *d_row_ids, const int32_t *d_xb_ptr, const int32_t *d_xb_col,
+                            const float *d_xb_val, int32_t n_x_rows, int64_t xb_nnz, int32_t n_items,
+                            const int32_t *d_wc_ptr, const int32_t *d_wc_row, const float *d_wc_val, int64_t wc_nnz,
+                            const int32_t *d_ids, int64_t ids_stride, int32_t list_k, const int32_t *d_counts,
+                            int32_t top_m, int32_t *d_out_items, float *d_out_contrib, int32_t *d_out_support,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ EXPORTS = [
     "rtrec_slim_first_touch_aux",
     "rtrec_slim_ordered_sums",
     "rtrec_rank_metrics",
+    "rtrec_slim_explain_topk",
 ]
 
 
@@ -186,6 +187,9 @@ def load() -> C.CDLL:
     L.rtrec_slim_ordered_sums.argtypes = [vp, vp, i32, i32, vp, vp]
     L.rtrec_rank_metrics.restype = C.c_int
     L.rtrec_rank_metrics.argtypes = [i32, i32, vp, i32, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
+    L.rtrec_slim_explain_topk.restype = C.c_int
+    L.rtrec_slim_explain_topk.argtypes = [i32, vp, vp, vp, vp, i32, C.c_int64, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, i32, vp,
+                                          i32, vp, vp, vp, vp]
     _lib = L
     return L
 

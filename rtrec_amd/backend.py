@@ -279,3 +279,9 @@ class HipBackend:
 
     def similar_topk(self, queries, W, top_k, ids, sc, cnt):
         self.ops.similar_topk(queries, W["cptr"], W["crow"], W["cval"], top_k, ids, sc, cnt)
+
+    def explain_topk(self, row_ids, xb, n_items, W, ids, counts, list_k, top_m, items, contrib, support):
+        """Per (row, list item): the top_m terms x_uj * w_ji of the score and their number (csrc/explain.hip); W as the CSC
+        view of DeviceWeights.csc_arrays, ids [n_rows, >= list_k]."""
+        self.ops.explain_topk(row_ids, xb[0], xb[1], xb[2], n_items, W["cptr"], W["crow"], W["cval"], ids, counts, list_k, top_m,
+                              items, contrib, support)

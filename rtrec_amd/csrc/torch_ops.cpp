@@ -47,6 +47,7 @@ struct Abi {
     decltype(&rtrec_slim_seg_fill) seg_fill = nullptr;
     decltype(&rtrec_slim_ordered_sums) ordered_sums = nullptr;
     decltype(&rtrec_rank_metrics) rank_metrics = nullptr;
+    decltype(&rtrec_slim_explain_topk) explain_topk = nullptr;
 };
 Abi g_abi;
 
@@ -395,6 +396,36 @@ void rank_metrics(const at::Tensor &ids, const at::Tensor &counts, const at::Ten
           "rtrec_rank_metrics");
 }
 
+// ids [n_rows, >= list_k] / counts [n_rows]: lists of item ids (score_topk's, or any the caller brings); the outputs are
+// items / contrib [n_rows, list_k, top_m] and support [n_rows, list_k] (include/rtrec_amd.h, "EXPLANATIONS").
+void explain_topk(const OT &row_ids, const at::Tensor &xb_ptr, const at::Tensor &xb_col, const at::Tensor &xb_val, int64_t n_items,
+                  const at::Tensor &wc_ptr, const at::Tensor &wc_row, const at::Tensor &wc_val, const at::Tensor &ids,
+                  const at::Tensor &counts, int64_t list_k, int64_t top_m, at::Tensor items, at::Tensor contrib, at::Tensor support) {
+    TORCH_CHECK(list_k >= 1 && list_k <= 64, "explain_topk: list_k must lie in 1..64, got ", list_k);
+    TORCH_CHECK(top_m >= 1 && top_m <= 32, "explain_topk: top_m must lie in 1..32, got ", top_m);
+    TORCH_CHECK(ids.dim() == 2 && ids.size(1) >= list_k, "explain_topk: ids must be [n_rows, >= list_k]");
+    const int64_t n = ids.size(0);
+    TORCH_CHECK(n <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, "explain_topk: too many rows or items");
+    TORCH_CHECK(counts.numel() == n, "explain_topk: counts must hold one entry per row");
+    TORCH_CHECK(!(row_ids.has_value() && row_ids->defined()) || row_ids->numel() == n, "explain_topk: row_ids must hold one entry per row");
+    TORCH_CHECK(xb_ptr.numel() >= 1 && xb_val.numel() == xb_col.numel(), "explain_topk: xb_ptr / xb_col / xb_val are not one CSR matrix");
+    TORCH_CHECK(wc_ptr.numel() == n_items + 1 && wc_val.numel() == wc_row.numel(), "explain_topk: wc_ptr must hold n_items + 1 entries, wc_row and wc_val one length");
+    TORCH_CHECK(items.numel() == n * list_k * top_m && contrib.numel() == n * list_k * top_m && support.numel() == n * list_k,
+                "explain_topk: outputs must be items[n_rows, list_k, top_m], contrib[same], support[n_rows, list_k]");
+    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
+    if (row_ids.has_value() && row_ids->defined()) check_tensor<const int32_t>(*row_ids);
+    check_tensor<const int32_t>(xb_ptr); check_tensor<const int32_t>(xb_col); check_tensor<const float>(xb_val);
+    check_tensor<const int32_t>(wc_ptr); check_tensor<const int32_t>(wc_row); check_tensor<const float>(wc_val);
+    check_tensor<const int32_t>(ids); check_tensor<const int32_t>(counts);
+    check_tensor<int32_t>(items); check_tensor<float>(contrib); check_tensor<int32_t>(support);
+    check(abi().explain_topk(static_cast<int32_t>(n), ptr<const int32_t>(row_ids), ptr<const int32_t>(xb_ptr), ptr<const int32_t>(xb_col),
+                             ptr<const float>(xb_val), static_cast<int32_t>(xb_ptr.numel() - 1), xb_col.numel(), static_cast<int32_t>(n_items),
+                             ptr<const int32_t>(wc_ptr), ptr<const int32_t>(wc_row), ptr<const float>(wc_val), wc_row.numel(),
+                             ptr<const int32_t>(ids), ids.size(1), static_cast<int32_t>(list_k), ptr<const int32_t>(counts),
+                             static_cast<int32_t>(top_m), ptr<int32_t>(items), ptr<float>(contrib), ptr<int32_t>(support), stream_of(items)),
+          "rtrec_slim_explain_topk");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -424,6 +455,7 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.seg_fill, "rtrec_slim_seg_fill");
         bind_one(h, a.ordered_sums, "rtrec_slim_ordered_sums");
         bind_one(h, a.rank_metrics, "rtrec_rank_metrics");
+        bind_one(h, a.explain_topk, "rtrec_slim_explain_topk");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -480,6 +512,8 @@ TORCH_LIBRARY(rtrec_amd, m) {
     m.def("ordered_sums(Tensor values, Tensor offsets, int mode, Tensor(a!) out) -> ()");
     m.def("rank_metrics(Tensor ids, Tensor counts, Tensor truth_ptr, Tensor truth_items, Tensor truth_len, Tensor discount, Tensor ideal, "
           "int size, Tensor(a!) metrics, Tensor(b!) tp, Tensor(c!) rel) -> ()");
+    m.def("explain_topk(Tensor? row_ids, Tensor xb_ptr, Tensor xb_col, Tensor xb_val, int n_items, Tensor wc_ptr, Tensor wc_row, "
+          "Tensor wc_val, Tensor ids, Tensor counts, int list_k, int top_m, Tensor(a!) items, Tensor(b!) contrib, Tensor(c!) support) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -502,4 +536,5 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("seg_fill", &seg_fill);
     m.impl("ordered_sums", &ordered_sums);
     m.impl("rank_metrics", &rank_metrics);
+    m.impl("explain_topk", &explain_topk);
 }

@@ -1649,6 +1649,70 @@ class SlimEngine:
             ids, sc, cnt = mine[:, :top_k], mine[:, top_k:2 * top_k].view(torch.float32), mine[:, 2 * top_k]
         return ids.cpu().numpy(), sc.cpu().numpy(), cnt.cpu().numpy()
 
+    # ------------------------------------------------------------------------------ explanations
+    EXPLAIN_MAX_LIST = 64       # list_k / top_m limits of rtrec_slim_explain_topk
+    EXPLAIN_MAX_TOP_M = 32
+
+    def _explain_weights(self) -> DeviceWeights:
+        """The W an explanation reads: all of it, with the float32 values the scores were computed from."""
+        if not self._W:
+            raise RuntimeError("Model must be fitted before calling explain.")
+        dw: DeviceWeights = self._W["dw"]
+        if getattr(dw, "shard", None) is not None and self.world_size > 1:
+            raise ValueError("explanations need the whole of W on this rank, and W is column-sharded (shard_w): "
+                             "gather it with gather_item_similarity() and explain from the gathered model")
+        if dw.lossy:
+            raise ValueError("explanations are exact float32 products; this W was uploaded from a float64 matrix whose values "
+                             "are not float32 numbers (DeviceWeights.lossy)")
+        return dw
+
+    def explain_device(self, d_rows, n_rows: int, xb, ids, counts, top_m: int):
+        """Device tensors (reason_items[n_rows, k, top_m], contributions[same], support[n_rows, k]) for the lists `ids`
+        [n_rows, k] / `counts` [n_rows] (int32 device tensors, e.g. what score_topk_device returned: they never leave HBM) of
+        the rows `d_rows` (int32 device tensor, or None = rows 0 .. n_rows-1) of `xb` = (ptr, col, val) device tensors (None:
+        the resident X).  The contract is the comment of rtrec_slim_explain_topk in include/rtrec_amd.h.  Every rank that
+        holds the whole W answers locally: there is no collective."""
+        be, torch = self.be, self.be.torch
+        dw = self._explain_weights()
+        k = int(ids.shape[-1])
+        if not 1 <= k <= self.EXPLAIN_MAX_LIST or not 1 <= int(top_m) <= self.EXPLAIN_MAX_TOP_M:
+            raise ValueError(f"explain: lists of 1..{self.EXPLAIN_MAX_LIST} items and top_m in 1..{self.EXPLAIN_MAX_TOP_M} "
+                             f"are supported, got {k} and {top_m}")
+        if xb is None:
+            xb = (self._X["rptr"], self._X["rcol"], self._X["rval"])
+        items = be.empty((n_rows, k, int(top_m)), torch.int32)
+        contrib = be.empty((n_rows, k, int(top_m)), torch.float32)
+        support = be.empty((n_rows, k), torch.int32)
+        if n_rows == 0:
+            return items, contrib, support
+        cptr, crow, cval = dw.csc_arrays(torch)
+        be.explain_topk(d_rows, xb, dw.n_items, {"cptr": cptr, "crow": crow, "cval": cval}, ids.contiguous(), counts.contiguous(),
+                        k, int(top_m), items, contrib, support)
+        return items, contrib, support
+
+    def explain_rows(self, row_ids: Sequence[int], item_ids: np.ndarray, counts: Optional[np.ndarray] = None, top_m: int = 3,
+                     xb=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """explain_device for lists the caller brings: numpy (reason_items[B, k, top_m], contributions, support[B, k]) for
+        `item_ids` [B, k] (-1 = no item) of the rows `row_ids` of the resident X -- or of the device CSR batch `xb`.  A row id
+        outside the matrix is a user without a row: support 0 everywhere."""
+        be = self.be
+        row_ids = np.asarray(row_ids, dtype=np.int64)
+        item_ids = np.ascontiguousarray(item_ids, dtype=np.int32)
+        if item_ids.ndim != 2 or item_ids.shape[0] != len(row_ids):
+            raise ValueError("item_ids must be [len(row_ids), k]")
+        B, k = item_ids.shape
+        counts = np.full(B, k, dtype=np.int32) if counts is None else np.asarray(counts, dtype=np.int32)
+        if counts.shape != (B,):
+            raise ValueError("counts must hold one entry per row")
+        n_x = self.n_users if xb is None else int(xb[0].shape[0]) - 1
+        rows32 = np.where((row_ids >= 0) & (row_ids < n_x), row_ids, -1).astype(np.int32)
+        if B == 0:
+            self._explain_weights()
+            return (np.empty((0, k, top_m), np.int32), np.empty((0, k, top_m), np.float32), np.empty((0, k), np.int32))
+        up = getattr(be, "to_dev_small", be.to_dev)
+        out = self.explain_device(up(rows32), B, xb, up(item_ids), up(counts), top_m)
+        return tuple(t.cpu().numpy() for t in out)
+
 
 def coefficients_to_updates(targets: np.ndarray, items: np.ndarray, coef: np.ndarray, count: np.ndarray
                             ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

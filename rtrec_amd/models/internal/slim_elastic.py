@@ -378,6 +378,30 @@ class SLIMElastic:
         ids, scores, counts = self._topk(Xb, candidate_item_ids, top_k, filter_interacted, dense_output)
         return self._format(ids, scores, counts, ret_scores)
 
+    def explain_batch(self, user_ids: List[int], interaction_matrix: sp.csr_matrix, item_ids: Sequence[Sequence[int]],
+                      top_m: int = 3) -> Tuple[ndarray, ndarray, ndarray]:
+        """An extension (the reference has none): for every (user, item) of `item_ids` -- one list of item ids per user, at
+        most 64 each, -1 or an id outside W = no item -- the `top_m` largest terms X[u, j] * W[j, i] of the score
+        (csrc/explain.hip; the contract is the comment of rtrec_slim_explain_topk in include/rtrec_amd.h).  Returns
+        (reason_items[B, k, top_m], contributions[B, k, top_m], support[B, k]), k = the longest list, -1 / -inf padded."""
+        if not self.is_fitted:
+            raise RuntimeError("Model must be fitted before calling explain_batch.")
+        rows = [list(r) for r in item_ids]
+        if len(rows) != len(user_ids):
+            raise ValueError("item_ids must hold one list per user")
+        k = max([len(r) for r in rows] + [1])
+        ids = np.full((len(rows), k), -1, dtype=np.int32)
+        for b, r in enumerate(rows):
+            ids[b, :len(r)] = r
+        counts = np.array([len(r) for r in rows], dtype=np.int32)
+        self._sync_weights()
+        n_items = self.n_items_fitted
+        Xb = interaction_matrix[user_ids, :].tocsr() if len(rows) else sp.csr_matrix((0, n_items), dtype=np.float32)
+        if Xb.shape[1] != n_items:
+            Xb = Xb.copy()
+            Xb.resize((Xb.shape[0], n_items))
+        return self.engine.explain_rows(np.arange(len(rows)), ids, counts, top_m, xb=self.engine._upload_csr(Xb))
+
     @staticmethod
     def _format(ids: ndarray, scores: ndarray, counts: ndarray, ret_scores: bool):
         rows = ids.tolist()                                # one conversion for the whole batch

@@ -368,6 +368,124 @@ class SLIM(BaseModel):
         rel = d_rel.cpu().numpy().view(np.uint64) if want_rel else None
         return eval_users, d_metrics.cpu().numpy(), d_tp.cpu().numpy(), rel
 
+    # ------------------------------------------------------------ explanations (an extension: the reference has none)
+    def explain_batch(self, users: List[Any], items: Optional[List[List[Any]]] = None, top_k: int = 10, top_m: int = 3,
+                      filter_interacted: bool = True, as_arrays: bool = False) -> Any:
+        """Why each item is recommended: in SLIM score(u, i) = sum_j X[u, j] * W[j, i] over the items j the user interacted
+        with, and the largest terms are the "because you interacted with ..." of a recommendation (csrc/explain.hip).
+
+        `items=None`: recommend `top_k` items per user and explain them in one device pass over the resident X -- the lists
+        go from the scoring kernels to the explanation kernel without visiting the host.  `items` = one list of raw item ids
+        per user (at most 64 each): explain those instead, e.g. a list that was served earlier; an item the model does not
+        know gets an empty explanation.
+
+        Per (user, item) the contributing items are the j stored in both the user's row of X and column i of W, the
+        contribution of j is the float32 product x_uj * w_ji (one rounding), and the reasons are the `top_m` (1..32)
+        contributing items by contribution descending, the lower item id first among equal ones; negative contributions take
+        part (filter by sign if only positive reasons are wanted).  For a float32 W, adding ALL contributions of a pair in
+        ascending item order in float32 gives exactly the score `recommend` ranks it by.  Unknown users get their cold-start
+        list with empty reasons; users outside the matrix follow `recommend_batch`'s rules for the list and get empty reasons.
+
+        Returns, per user, [(item, [(reason_item, contribution), ...]), ...] with raw ids and float contributions -- or with
+        `as_arrays=True` (ids[B, k], counts[B], reason_ids[B, k, top_m], contributions[B, k, top_m], support[B, k]): row b is
+        valid up to counts[b], support = the number of contributing items of the pair (it may exceed top_m), unused slots
+        hold -1 / -inf.  The id arrays hold INTERNAL item ids: for integer ids those are the raw ids, for a model with string
+        ids map them with `model.item_ids.get`."""
+        from .._native import TOPK_DENSE, TOPK_SPARSE
+        if not self.model.is_fitted:
+            raise RuntimeError("Model must be fitted before calling explain_batch.")
+        arr = self._int_user_array(users)          # integer pass-through ids: the hot / cold split is one compare
+        if arr is None:
+            users = list(users)
+        B, m = len(users), int(top_m)
+        if items is not None:
+            items = [list(row) for row in items]
+            if len(items) != B:
+                raise ValueError(f"items must hold one list per user: {len(items)} lists for {B} users")
+            K = max([len(row) for row in items] + [1])
+        else:
+            K = int(top_k)
+        if not 1 <= K <= 64 or not 1 <= m <= 32:
+            raise ValueError(f"explain_batch serves lists of 1..64 items and top_m in 1..32, got {K} and {m}")
+        ids = np.full((B, K), -1, dtype=np.int64)
+        counts = np.zeros(B, dtype=np.int32)
+        r_ids = np.full((B, K, m), -1, dtype=np.int64)
+        contrib = np.full((B, K, m), -np.inf, dtype=np.float32)
+        support = np.zeros((B, K), dtype=np.int32)
+        eng = self.model.engine
+        n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
+        if arr is not None:
+            uid, cold = arr, arr > self.interactions.max_user_id
+        else:
+            known = [self._known_user_id(u) for u in users]
+            cold = np.fromiter((u is None for u in known), dtype=bool, count=B)
+            uid = np.fromiter((0 if u is None else u for u in known), dtype=np.int64, count=B)
+        regular = ~cold & (uid >= 0) & (uid < n_users)
+        if B:
+            self.model._sync_weights()
+            eng._explain_weights()               # a W that cannot be explained is refused whatever the batch holds
+        if items is not None:
+            for b, row in enumerate(items):
+                counts[b] = len(row)
+                for p_, raw in enumerate(row):
+                    try:
+                        i = self.item_ids.get_id(raw)
+                    except (ValueError, TypeError):       # an id of the other kind: no such item
+                        i = None
+                    ids[b, p_] = i if (i is not None and 0 <= i < n_items) else -1
+            if regular.any():
+                self._sync_interactions()
+                r_ids[:], contrib[:], support[:] = eng.explain_rows(np.where(regular, uid, -1), ids, counts, m)
+        elif B:
+            if cold.any():
+                cold_list = self._recommend_cold_batch([None], top_k=K)[0][:K]
+                ids[cold, :len(cold_list)] = np.asarray(cold_list, dtype=np.int64)[None, :]
+                counts[cold] = len(cold_list)
+            odd = ~cold & ~regular
+            if odd.any():
+                lists = self._recommend_odd_ids(uid[~cold], n_users, None, K, filter_interacted)
+                for b, row in zip(np.flatnonzero(~cold).tolist(), lists):
+                    if odd[b]:
+                        ids[b, :len(row)] = row
+                        counts[b] = len(row)
+            k = min(K, n_items)
+            if regular.any() and k >= 1:
+                self._sync_interactions()
+                rows = uid[regular].astype(np.int32)
+                mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+                if eng.topk_supported(k, mode):
+                    be = eng.be
+                    d_rows = getattr(be, "to_dev_small", be.to_dev)(rows)
+                    d_ids, _, d_cnt = eng.score_topk_device(None, len(rows), k, filter_interacted, mode, d_rows=d_rows)
+                    out = eng.explain_device(d_rows, len(rows), None, d_ids, d_cnt, m)
+                    h_ids, h_cnt = d_ids.cpu().numpy(), d_cnt.cpu().numpy()
+                    h_r, h_c, h_s = (t.cpu().numpy() for t in out)
+                else:                            # a catalogue the fused top-k does not serve: lists selected on the host
+                    h_ids, _, h_cnt = self.model._topk(None, None, k, filter_interacted, not self.item_ids.pass_through, row_ids=rows)
+                    h_r, h_c, h_s = eng.explain_rows(rows, h_ids, h_cnt, m)
+                pos = np.flatnonzero(regular)
+                ids[pos, :k], counts[pos] = h_ids, h_cnt
+                r_ids[pos, :k], contrib[pos, :k], support[pos, :k] = h_r, h_c, h_s
+        if as_arrays:
+            return ids, counts, r_ids, contrib, support
+        raw_of = (lambda i: i) if self.item_ids.pass_through else self.item_ids.get
+        id_rows, cnts, reason_rows, contrib_rows = ids.tolist(), counts.tolist(), r_ids.tolist(), contrib.tolist()
+        n_reasons = np.minimum(support, m).tolist()
+        out_rows: List[List[Tuple[Any, List[Tuple[Any, float]]]]] = []
+        for b in range(B):
+            row = []
+            for p_ in range(cnts[b]):
+                item = items[b][p_] if items is not None else raw_of(id_rows[b][p_])
+                row.append((item, [(raw_of(reason_rows[b][p_][q]), contrib_rows[b][p_][q]) for q in range(n_reasons[b][p_])]))
+            out_rows.append(row)
+        return out_rows
+
+    def explain(self, user: Any, items: Optional[List[Any]] = None, top_k: int = 10, top_m: int = 3,
+                filter_interacted: bool = True) -> List[Tuple[Any, List[Tuple[Any, float]]]]:
+        """explain_batch for one user: [(item, [(reason_item, contribution), ...]), ...]."""
+        return self.explain_batch([user], None if items is None else [list(items)], top_k=top_k, top_m=top_m,
+                                  filter_interacted=filter_interacted)[0]
+
     def _similar_items(self, query_item_id: int, query_item_tags: Optional[List[str]] = None, top_k: int = 10
                        ) -> List[Tuple[int, float]]:
         return self.model.similar_items(query_item_id, top_k=top_k, ret_ndarrays=False)  # type: ignore

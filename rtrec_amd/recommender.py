@@ -102,6 +102,17 @@ class Recommender:
             return self.model.recommend_batch(users, candidate_items, users_tags, top_k, filter_interacted, as_arrays=True)
         return self.model.recommend_batch(users, candidate_items, users_tags, top_k, filter_interacted)
 
+    def explain(self, user: Any, items: Optional[List[Any]] = None, top_k: int = 10, top_m: int = 3,
+                filter_interacted: bool = True) -> Any:
+        """An extension (the reference has none): [(item, [(reason_item, contribution), ...]), ...] -- SLIM.explain."""
+        return self.model.explain(user, items, top_k=top_k, top_m=top_m, filter_interacted=filter_interacted)
+
+    def explain_batch(self, users: List[Any], items: Optional[List[List[Any]]] = None, top_k: int = 10, top_m: int = 3,
+                      filter_interacted: bool = True, as_arrays: bool = False) -> Any:
+        """SLIM.explain_batch: recommend and explain in one device pass (`items=None`), or explain the given lists."""
+        return self.model.explain_batch(users, items, top_k=top_k, top_m=top_m, filter_interacted=filter_interacted,
+                                        as_arrays=as_arrays)
+
     def similar_items(self, query_items: List[Any], query_item_tags: Optional[List[str]] = None, top_k: int = 10,
                       ret_scores: bool = False):
         batch = getattr(self.model, "similar_items_batch", None)

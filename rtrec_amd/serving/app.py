@@ -10,6 +10,9 @@ the GPU), POST /recommend (one user's top-k).  Differences, all forced by the de
     not stall the event loop;
   * POST /recommend_batch is an addition for callers that can batch (one kernel launch per request
     instead of one per user): {"users": [...]} -> {"users": [...], "recommendations": [[...], ...]};
+  * POST /explain is an addition (the reference cannot say why it recommended something): {"user": ..., "items": [...] or
+    absent, "top_k", "top_m", "filter_interacted"} -> {"user": ..., "explanations": [{"item": ..., "reasons": [{"item": ...,
+    "contribution": ...}, ...]}, ...]} (SLIM.explain); same token check as /recommend, not coalesced;
   * concurrent POST /recommend calls are coalesced (`RecommendCoalescer`): requests that arrive within a bounded
     wait (RTREC_AMD_COALESCE_MS, default 1 ms; 0 = only what queued up behind the model lock) share ONE
     recommend_batch launch per (top_k, filter_interacted) group; each caller gets exactly what its own
@@ -50,6 +53,12 @@ class RecommendationRequest(_TopKOptions):
 
 class BatchRecommendationRequest(_TopKOptions):
     users: List[Any]
+
+
+class ExplanationRequest(_TopKOptions):
+    user: Any
+    items: Optional[List[Any]] = None
+    top_m: int = 3
 
 
 class RecommendationResponse(BaseModel):
@@ -237,6 +246,15 @@ def build_router(gate: ModelGate) -> APIRouter:
         lists = gate.call("Recommendation", lambda m: m.recommend_batch(
             request.users, top_k=request.top_k, filter_interacted=request.filter_interacted))
         return BatchRecommendationResponse(users=request.users, recommendations=lists)
+
+    @api.post("/explain")
+    def explain(request: ExplanationRequest, x_token: str = Header()):
+        _authorise(x_token)
+        rows = gate.call("Explanation", lambda m: m.explain(request.user, request.items, top_k=request.top_k, top_m=request.top_m,
+                                                            filter_interacted=request.filter_interacted))
+        return {"user": request.user,
+                "explanations": [{"item": item, "reasons": [{"item": j, "contribution": c} for j, c in reasons]}
+                                 for item, reasons in rows]}
 
     return api
 
