@@ -712,6 +712,44 @@ int rtrec_slim_explain_topk(int32_t n_rows, const int32_t *d_row_ids, const int3
                             int32_t top_m, int32_t *d_out_items, float *d_out_contrib, int32_t *d_out_support,
                             void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * AUDIENCE OF AN ITEM  (an extension: the reference has no such call.  Every scoring path answers "which items for this user";
+ * this one answers "which users for this item": a release, a restock, a campaign of 200 titles.)
+ * X is read in CSC form d_xc_* (d_xc_ptr[n_items + 1], rows ascending per column, xc_nnz = length of d_xc_row / d_xc_val, below
+ * 2^31), W in CSC form d_wc_* (d_wc_ptr[n_items + 1], rows ascending per column, float32 values, wc_nnz = length of d_wc_row /
+ * d_wc_val).  For a query item i = d_items[q] (internal id) and a user row u of X:
+ *   contributing items  the j stored in both row u of X and column i of W
+ *   support             their number
+ *   score(u, i)         the float32 sum of the products fl32(x_uj * w_ji): each product is one multiply with one rounding, never
+ *                       fused; the products are added sequentially in float32 from 0.0f, in ascending j.  This is the invariant
+ *                       of rtrec_slim_explain_topk read the other way round, hence the score rtrec_slim_score_topk ranks the pair
+ *                       by for a float32 W.  A W that is float64 on the host with float32-representable values is served with
+ *                       those float32 numbers: the float32 model's scores
+ *   eligible users      support >= 1 (the reference's sparse rule: structural entries compete whatever their value; zero and
+ *                       negative scores take part); with filter_interacted != 0, u is not stored in column i of X; with
+ *                       d_user_mask != NULL (int32 words, bit u & 31 of word u >> 5, (n_users + 31) / 32 words), its bit is set
+ *   audience            the top_n eligible users by score descending, among equal scores the LOWER user row first
+ * Per query item: d_out_users[q][top_n] (unused slots -1), d_out_scores[q][top_n] (unused slots -inf), d_out_count[q] =
+ * min(top_n, eligible), d_out_eligible[q] = the full number of eligible users, the reach of the item (it may exceed top_n).
+ * A query id outside [0, n_items) has no column: count 0, eligible 0.  Repeated query items are answered independently.  CSC
+ * offsets are clamped to [0, xc_nnz] / [0, wc_nnz] and rows outside [0, n_users) are skipped, so a malformed matrix gives wrong
+ * answers, never an out-of-range read.  A score whose bit pattern is 0xffffffff (a NaN payload float32 arithmetic does not
+ * produce) counts as no support.
+ * top_n in 1..1024 (RTREC_ERR_UNSUPPORTED otherwise, as are xc_nnz / wc_nnz >= 2^31); negative sizes and NULL arrays:
+ * RTREC_ERR_INVALID_ARG; n_q == 0: RTREC_OK, nothing launched; these checks run before anything touches the device.
+ * d_workspace: rtrec_slim_audience_workspace_bytes(n_users, n_q, top_n) bytes (0 for arguments outside the limits) -- at most
+ * 256 MiB unless one query item needs more; with less than n_q items' worth the call works through the items in passes;
+ * less than one item's worth: RTREC_ERR_WORKSPACE.  A column of W of any length works (K = None fits).
+ * csrc/audience.hip: audience_tile_kernel (one workgroup per tile of 8,192 users and query item) + audience_merge_kernel.
+ * ------------------------------------------------------------------------------------- */
+size_t rtrec_slim_audience_workspace_bytes(int32_t n_users, int32_t n_q, int32_t top_n);
+int rtrec_slim_audience_topk(int32_t n_q, const int32_t *d_items, int32_t n_users, int32_t n_items,
+                             const int32_t *d_xc_ptr, const int32_t *d_xc_row, const float *d_xc_val, int64_t xc_nnz,
+                             const int32_t *d_wc_ptr, const int32_t *d_wc_row, const float *d_wc_val, int64_t wc_nnz,
+                             int32_t top_n, int32_t filter_interacted, const int32_t *d_user_mask,
+                             int32_t *d_out_users, float *d_out_scores, int32_t *d_out_count, int32_t *d_out_eligible,
+                             void *d_workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,8 @@ EXPORTS = [
     "rtrec_slim_ordered_sums",
     "rtrec_rank_metrics",
     "rtrec_slim_explain_topk",
+    "rtrec_slim_audience_workspace_bytes",
+    "rtrec_slim_audience_topk",
 ]
 
 
@@ -190,6 +192,11 @@ def load() -> C.CDLL:
     L.rtrec_slim_explain_topk.restype = C.c_int
     L.rtrec_slim_explain_topk.argtypes = [i32, vp, vp, vp, vp, i32, C.c_int64, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, i32, vp,
                                           i32, vp, vp, vp, vp]
+    L.rtrec_slim_audience_workspace_bytes.restype = C.c_size_t
+    L.rtrec_slim_audience_workspace_bytes.argtypes = [i32, i32, i32]
+    L.rtrec_slim_audience_topk.restype = C.c_int
+    L.rtrec_slim_audience_topk.argtypes = [i32, vp, i32, i32, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp, vp, vp,
+                                           vp, C.c_size_t, vp]
     _lib = L
     return L
 

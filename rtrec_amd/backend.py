@@ -285,3 +285,13 @@ class HipBackend:
         view of DeviceWeights.csc_arrays, ids [n_rows, >= list_k]."""
         self.ops.explain_topk(row_ids, xb[0], xb[1], xb[2], n_items, W["cptr"], W["crow"], W["cval"], ids, counts, list_k, top_m,
                               items, contrib, support)
+
+    def audience_workspace_bytes(self, n_users, n_q, top_n):
+        return int(self.lib.rtrec_slim_audience_workspace_bytes(n_users, n_q, top_n))
+
+    def audience_topk(self, items, n_users, X, W, top_n, filter_interacted, user_mask, users, scores, count, eligible):
+        """Per query item: the top_n users by score, their number and the item's reach (csrc/audience.hip); X = (cptr, crow, cval), its CSC
+        orientation with as many columns as W, W as the CSC view of DeviceWeights.csc_arrays, user_mask an int32 bitmap or None."""
+        ws = self.empty((max(self.audience_workspace_bytes(n_users, int(items.numel()), top_n), 8),), self.torch.uint8)
+        self.ops.audience_topk(items, n_users, X[0], X[1], X[2], W["cptr"], W["crow"], W["cval"], top_n,
+                               bool(filter_interacted), user_mask, users, scores, count, eligible, ws)

@@ -48,6 +48,7 @@ struct Abi {
     decltype(&rtrec_slim_ordered_sums) ordered_sums = nullptr;
     decltype(&rtrec_rank_metrics) rank_metrics = nullptr;
     decltype(&rtrec_slim_explain_topk) explain_topk = nullptr;
+    decltype(&rtrec_slim_audience_topk) audience_topk = nullptr;
 };
 Abi g_abi;
 
@@ -426,6 +427,42 @@ void explain_topk(const OT &row_ids, const at::Tensor &xb_ptr, const at::Tensor 
           "rtrec_slim_explain_topk");
 }
 
+// items [n_q] query item ids; X and W in CSC form; user_mask: optional bitmap of (n_users + 31) / 32 int32 words; the outputs are
+// users / scores [n_q, top_n] and count / eligible [n_q]; ws: rtrec_slim_audience_workspace_bytes (include/rtrec_amd.h,
+// "AUDIENCE OF AN ITEM").
+void audience_topk(const at::Tensor &items, int64_t n_users, const at::Tensor &xc_ptr, const at::Tensor &xc_row, const at::Tensor &xc_val,
+                   const at::Tensor &wc_ptr, const at::Tensor &wc_row, const at::Tensor &wc_val, int64_t top_n, bool filter_interacted,
+                   const OT &user_mask, at::Tensor users, at::Tensor scores, at::Tensor count, at::Tensor eligible, at::Tensor ws) {
+    TORCH_CHECK(top_n >= 1 && top_n <= 1024, "audience_topk: top_n must lie in 1..1024, got ", top_n);
+    const int64_t n = items.numel(), n_items = wc_ptr.numel() - 1;
+    TORCH_CHECK(items.dim() == 1 && n <= INT32_MAX, "audience_topk: items must be one list of query item ids");
+    TORCH_CHECK(n_users >= 0 && n_users < INT32_MAX && n_items >= 0, "audience_topk: n_users out of range or wc_ptr empty");
+    TORCH_CHECK(xc_ptr.numel() == n_items + 1 && xc_val.numel() == xc_row.numel() && xc_row.numel() <= INT32_MAX,
+                "audience_topk: xc_ptr must hold n_items + 1 entries like wc_ptr, xc_row and xc_val one length below 2^31");
+    TORCH_CHECK(wc_val.numel() == wc_row.numel() && wc_row.numel() <= INT32_MAX, "audience_topk: wc_row and wc_val must have one length below 2^31");
+    const bool masked = user_mask.has_value() && user_mask->defined();
+    TORCH_CHECK(!masked || user_mask->numel() == (n_users + 31) / 32, "audience_topk: user_mask must hold (n_users + 31) / 32 words");
+    TORCH_CHECK(users.numel() == n * top_n && scores.numel() == n * top_n && count.numel() == n && eligible.numel() == n,
+                "audience_topk: outputs must be users[n_q, top_n], scores[same], count[n_q], eligible[n_q]");
+    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
+    check_tensor<const int32_t>(items);
+    check_tensor<const int32_t>(xc_ptr); check_tensor<const int32_t>(xc_row); check_tensor<const float>(xc_val);
+    check_tensor<const int32_t>(wc_ptr); check_tensor<const int32_t>(wc_row); check_tensor<const float>(wc_val);
+    if (masked) check_tensor<const int32_t>(*user_mask);
+    check_tensor<int32_t>(users); check_tensor<float>(scores); check_tensor<int32_t>(count); check_tensor<int32_t>(eligible);
+    check_tensor<void>(ws);
+    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&xc_ptr, &xc_row, &xc_val, &wc_ptr, &wc_row, &wc_val, &users, &scores, &count, &eligible, &ws})
+        TORCH_CHECK(t->device() == items.device(), "audience_topk: all tensors must live on one device");
+    TORCH_CHECK(!masked || user_mask->device() == items.device(), "audience_topk: all tensors must live on one device");
+    check(abi().audience_topk(static_cast<int32_t>(n), ptr<const int32_t>(items), static_cast<int32_t>(n_users), static_cast<int32_t>(n_items),
+                              ptr<const int32_t>(xc_ptr), ptr<const int32_t>(xc_row), ptr<const float>(xc_val), xc_row.numel(),
+                              ptr<const int32_t>(wc_ptr), ptr<const int32_t>(wc_row), ptr<const float>(wc_val), wc_row.numel(),
+                              static_cast<int32_t>(top_n), filter_interacted ? 1 : 0, ptr<const int32_t>(user_mask), ptr<int32_t>(users),
+                              ptr<float>(scores), ptr<int32_t>(count), ptr<int32_t>(eligible), ptr<void>(ws),
+                              static_cast<size_t>(ws.numel() * ws.element_size()), stream_of(users)),
+          "rtrec_slim_audience_topk");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -456,6 +493,7 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.ordered_sums, "rtrec_slim_ordered_sums");
         bind_one(h, a.rank_metrics, "rtrec_rank_metrics");
         bind_one(h, a.explain_topk, "rtrec_slim_explain_topk");
+        bind_one(h, a.audience_topk, "rtrec_slim_audience_topk");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -514,6 +552,9 @@ TORCH_LIBRARY(rtrec_amd, m) {
           "int size, Tensor(a!) metrics, Tensor(b!) tp, Tensor(c!) rel) -> ()");
     m.def("explain_topk(Tensor? row_ids, Tensor xb_ptr, Tensor xb_col, Tensor xb_val, int n_items, Tensor wc_ptr, Tensor wc_row, "
           "Tensor wc_val, Tensor ids, Tensor counts, int list_k, int top_m, Tensor(a!) items, Tensor(b!) contrib, Tensor(c!) support) -> ()");
+    m.def("audience_topk(Tensor items, int n_users, Tensor xc_ptr, Tensor xc_row, Tensor xc_val, Tensor wc_ptr, Tensor wc_row, "
+          "Tensor wc_val, int top_n, bool filter_interacted, Tensor? user_mask, Tensor(a!) users, Tensor(b!) scores, "
+          "Tensor(c!) count, Tensor(d!) eligible, Tensor(e!) ws) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -537,4 +578,5 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("ordered_sums", &ordered_sums);
     m.impl("rank_metrics", &rank_metrics);
     m.impl("explain_topk", &explain_topk);
+    m.impl("audience_topk", &audience_topk);
 }

@@ -1713,6 +1713,97 @@ class SlimEngine:
         out = self.explain_device(up(rows32), B, xb, up(item_ids), up(counts), top_m)
         return tuple(t.cpu().numpy() for t in out)
 
+    # ------------------------------------------------------------------------------ audience of an item
+    AUDIENCE_MAX_TOP_N = 1024   # top_n limit of rtrec_slim_audience_topk
+
+    def _audience_check(self, top_n: int) -> DeviceWeights:
+        """The one argument check of the audience calls: the W an audience is scored from -- all of it, with the float32 values
+        the scores are computed from (a float64 W whose values are float32 numbers is served with those numbers: the float32
+        model's scores) -- and top_n within the kernel's range."""
+        if not self._W:
+            raise RuntimeError("Model must be fitted before calling recommend_users.")
+        dw: DeviceWeights = self._W["dw"]
+        if getattr(dw, "shard", None) is not None and self.world_size > 1:
+            raise ValueError("an audience needs the whole of W on this rank, and W is column-sharded (shard_w): "
+                             "gather it with gather_item_similarity() and serve audiences from the gathered model")
+        if dw.lossy:
+            raise ValueError("audience scores are exact float32 sums; this W was uploaded from a float64 matrix whose values "
+                             "are not float32 numbers (DeviceWeights.lossy)")
+        if not 1 <= int(top_n) <= self.AUDIENCE_MAX_TOP_N:
+            raise ValueError(f"recommend_users: top_n in 1..{self.AUDIENCE_MAX_TOP_N} is supported, got {top_n}")
+        return dw
+
+    def has_csc(self) -> bool:
+        """Whether the resident X carries its CSC orientation (set_interactions(need_csc=False) leaves it out)."""
+        return "cptr" in self._X
+
+    def _attach_csc(self, X_csc: sp.csc_matrix) -> None:
+        """Add the CSC orientation of the resident X (the same matrix, sorted indices): the keys set_interactions(need_csc=True)
+        would have left -- cptr / crow / cval and, because the fit reads them beside those, col_nnz and nonneg.  The CSR side
+        is not touched, and the next set_interactions replaces the whole dict."""
+        be = self.be
+        if X_csc.shape != (self.n_users, self.n_items):
+            raise ValueError(f"the CSC orientation is {X_csc.shape}, the resident X {(self.n_users, self.n_items)}")
+        if not X_csc.has_sorted_indices:
+            X_csc = X_csc.sorted_indices()
+        X = self._X
+        X["cptr"] = be.to_dev(np.asarray(X_csc.indptr, dtype=np.int32))
+        X["crow"] = be.to_dev(np.asarray(X_csc.indices, dtype=np.int32))
+        X["cval"] = be.to_dev(np.asarray(X_csc.data, dtype=np.float32))
+        X["col_nnz"] = np.diff(np.asarray(X_csc.indptr, dtype=np.int64))
+        X["nonneg"] = bool(X_csc.nnz == 0 or float(X_csc.data.min()) >= 0.0)
+
+    def audience_device(self, d_items, n_q: int, top_n: int, filter_interacted: bool = True, d_user_mask=None):
+        """Device tensors (users[n_q, top_n], scores[n_q, top_n], count[n_q], eligible[n_q]) for the query items `d_items`
+        (int32 device tensor of internal item ids) against the resident X: the top_n users by score per item, the lower row
+        first among equal scores, and the item's reach.  `d_user_mask`: int32 bitmap over the user rows (bit u & 31 of word
+        u >> 5), None = everyone.  The contract is the comment of rtrec_slim_audience_topk in include/rtrec_amd.h.  The
+        results stay in HBM.  Every rank that holds the whole W and X answers locally: there is no collective."""
+        be, torch = self.be, self.be.torch
+        dw = self._audience_check(top_n)
+        top_n = int(top_n)
+        if not self.has_csc():
+            raise RuntimeError("set_interactions() with the CSC orientation must be called before audience_device()")
+        users = be.empty((n_q, top_n), torch.int32)
+        scores = be.empty((n_q, top_n), torch.float32)
+        count = be.empty((n_q,), torch.int32)
+        eligible = be.empty((n_q,), torch.int32)
+        if n_q == 0:
+            return users, scores, count, eligible
+        cptr, crow, cval = dw.csc_arrays(torch)
+        X = self._X
+        xptr, n_w = X["cptr"], dw.n_items          # the kernel reads the columns of X that W knows: X may have grown since the fit
+        if xptr.numel() > n_w + 1:
+            xptr = xptr[:n_w + 1]
+        elif xptr.numel() < n_w + 1:
+            xptr = torch.cat([xptr, xptr[-1:].expand(n_w + 1 - xptr.numel())])
+        be.audience_topk(d_items, self.n_users, (xptr, X["crow"], X["cval"]), {"cptr": cptr, "crow": crow, "cval": cval}, top_n,
+                         bool(filter_interacted), d_user_mask, users, scores, count, eligible)
+        return users, scores, count, eligible
+
+    def audience_items(self, item_ids: Sequence[int], top_n: int = 100, filter_interacted: bool = True,
+                       candidate_rows: Optional[Sequence[int]] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """audience_device from the host: numpy (users[n_q, top_n], scores, count[n_q], eligible[n_q]) for the internal item
+        ids `item_ids` (an id outside W: count 0).  `candidate_rows`: only these user rows are eligible (rows outside the
+        matrix are ignored, an empty list leaves nobody); None = everyone."""
+        be = self.be
+        q = np.asarray(item_ids, dtype=np.int64).reshape(-1)
+        top_n = int(top_n)
+        if len(q) == 0:
+            self._audience_check(top_n)
+            return (np.empty((0, top_n), np.int32), np.empty((0, top_n), np.float32), np.empty(0, np.int32), np.empty(0, np.int32))
+        q32 = np.where((q >= 0) & (q < 2 ** 31 - 1), q, -1).astype(np.int32)      # the kernel treats any id outside W as no column
+        d_mask = None
+        if candidate_rows is not None:
+            rows = np.asarray(candidate_rows, dtype=np.int64).reshape(-1)
+            rows = rows[(rows >= 0) & (rows < self.n_users)]
+            bits = np.zeros(((self.n_users + 31) // 32) * 32, dtype=np.uint8)
+            bits[rows] = 1
+            d_mask = be.to_dev(np.packbits(bits, bitorder="little").view(np.int32))
+        up = getattr(be, "to_dev_small", be.to_dev)
+        out = self.audience_device(up(q32), len(q32), top_n, filter_interacted, d_mask)
+        return tuple(t.cpu().numpy() for t in out)
+
 
 def coefficients_to_updates(targets: np.ndarray, items: np.ndarray, coef: np.ndarray, count: np.ndarray
                             ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

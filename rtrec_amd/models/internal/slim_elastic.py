@@ -402,6 +402,18 @@ class SLIMElastic:
             Xb.resize((Xb.shape[0], n_items))
         return self.engine.explain_rows(np.arange(len(rows)), ids, counts, top_m, xb=self.engine._upload_csr(Xb))
 
+    def recommend_users_batch(self, item_ids: Sequence[int], top_n: int = 100, filter_interacted: bool = True,
+                              candidate_rows: Optional[Sequence[int]] = None) -> Tuple[ndarray, ndarray, ndarray, ndarray]:
+        """An extension (the reference has none): the audience of every item of `item_ids` (internal ids; an id outside W
+        has no audience) among the user rows of the X resident in the engine -- the `top_n` (1..1024) users by score
+        descending, the lower row first among equal scores (csrc/audience.hip; the contract is the comment of
+        rtrec_slim_audience_topk in include/rtrec_amd.h).  Returns (users[n, top_n], scores[n, top_n], counts[n],
+        eligible[n]), -1 / -inf padded; eligible = the item's reach, it may exceed top_n."""
+        if not self.is_fitted:
+            raise RuntimeError("Model must be fitted before calling recommend_users_batch.")
+        self._sync_weights()
+        return self.engine.audience_items(item_ids, top_n, filter_interacted, candidate_rows)
+
     @staticmethod
     def _format(ids: ndarray, scores: ndarray, counts: ndarray, ret_scores: bool):
         rows = ids.tolist()                                # one conversion for the whole batch

@@ -486,6 +486,74 @@ class SLIM(BaseModel):
         return self.explain_batch([user], None if items is None else [list(items)], top_k=top_k, top_m=top_m,
                                   filter_interacted=filter_interacted)[0]
 
+    # ------------------------------------------------------------ audience of an item (an extension: the reference has none)
+    def _sync_interactions_csc(self) -> None:
+        """_sync_interactions, and the CSC orientation of the GPU copy too: the device mirror's, or -- on the branch that
+        uploaded the host CSR alone -- one more upload of the store's CSC export (same values, same max_timestamp)."""
+        self._sync_interactions()
+        eng = self.model.engine
+        if not eng.has_csc():
+            eng._attach_csc(self.interactions.to_csc())
+
+    def recommend_users_batch(self, items: List[Any], top_n: int = 100, filter_interacted: bool = True,
+                              candidate_users: Optional[List[Any]] = None, ret_scores: bool = False,
+                              as_arrays: bool = False) -> Any:
+        """Which users should be told about an item: per raw item id of `items` the `top_n` (1..1024) users by
+        score(u, i) = sum_j X[u, j] * W[j, i], the score `recommend` ranks the pair by -- computed on the X the model serves
+        from (decayed to the current max_timestamp) by walking the <= K columns of X that column i of W names
+        (csrc/audience.hip).  Eligible are the users with at least one stored term in that sum (the sparse rule: zero and
+        negative scores take part), not stored in the item's own column when `filter_interacted`, and in `candidate_users`
+        (raw ids; unknown ones are ignored, an empty list leaves nobody) when given.  Among equal scores the user with the
+        lower internal id comes first.  An item the model does not know, or one the fit never reached, gets an empty list;
+        repeated items are answered independently.  A float64 W whose values are float32 numbers is served with those
+        numbers (the float32 model's scores); a W that is not, or a column-sharded one, raises ValueError.
+
+        Returns one list of raw user ids per item -- of (user, score) tuples with `ret_scores` -- or with `as_arrays=True`
+        (users[n, top_n], scores[n, top_n], counts[n], eligible[n]): row b is valid up to counts[b], unused slots hold
+        -1 / -inf, eligible[b] is the item's reach (it may exceed top_n), and the ids are INTERNAL user ids: for integer ids
+        those are the raw ids, for a model with string ids map them with `model.user_ids.get`."""
+        if not self.model.is_fitted:
+            raise RuntimeError("Model must be fitted before calling recommend_users_batch.")
+        items = list(items)
+        n_items = self.model.n_items_fitted
+        q = np.full(len(items), -1, dtype=np.int64)
+        for p_, raw in enumerate(items):
+            try:
+                i = self.item_ids.get_id(raw)
+            except (ValueError, TypeError):       # an id of the other kind: no such item
+                i = None
+            if i is not None and 0 <= i < n_items:
+                q[p_] = i
+        rows = None
+        if candidate_users is not None:
+            known = []
+            for raw in candidate_users:
+                try:
+                    u = self._known_user_id(raw)
+                except (ValueError, TypeError):
+                    u = None
+                if u is not None and u >= 0:
+                    known.append(u)
+            rows = np.asarray(known, dtype=np.int64)
+        self.model._sync_weights()
+        self.model.engine._audience_check(top_n)  # a W or a top_n that cannot be served is refused before X is touched
+        if len(items):
+            self._sync_interactions_csc()
+        users, scores, counts, eligible = self.model.recommend_users_batch(q, top_n, filter_interacted, rows)
+        if as_arrays:
+            return users, scores, counts, eligible
+        raw_of = (lambda u: u) if self.user_ids.pass_through else self.user_ids.get
+        user_rows, score_rows, cnts = users.tolist(), scores.tolist(), counts.tolist()
+        if ret_scores:
+            return [[(raw_of(u), s) for u, s in zip(user_rows[b][:cnts[b]], score_rows[b][:cnts[b]])] for b in range(len(items))]
+        return [[raw_of(u) for u in user_rows[b][:cnts[b]]] for b in range(len(items))]
+
+    def recommend_users(self, item: Any, top_n: int = 100, filter_interacted: bool = True,
+                        candidate_users: Optional[List[Any]] = None, ret_scores: bool = False) -> List[Any]:
+        """recommend_users_batch for one item: its audience as raw user ids, or (user, score) tuples."""
+        return self.recommend_users_batch([item], top_n=top_n, filter_interacted=filter_interacted,
+                                          candidate_users=candidate_users, ret_scores=ret_scores)[0]
+
     def _similar_items(self, query_item_id: int, query_item_tags: Optional[List[str]] = None, top_k: int = 10
                        ) -> List[Tuple[int, float]]:
         return self.model.similar_items(query_item_id, top_k=top_k, ret_ndarrays=False)  # type: ignore

@@ -113,6 +113,18 @@ class Recommender:
         return self.model.explain_batch(users, items, top_k=top_k, top_m=top_m, filter_interacted=filter_interacted,
                                         as_arrays=as_arrays)
 
+    def recommend_users(self, item: Any, top_n: int = 100, filter_interacted: bool = True,
+                        candidate_users: Optional[List[Any]] = None, ret_scores: bool = False) -> Any:
+        """An extension (the reference has none): the audience of an item, its top_n users by score -- SLIM.recommend_users."""
+        return self.model.recommend_users(item, top_n=top_n, filter_interacted=filter_interacted, candidate_users=candidate_users,
+                                          ret_scores=ret_scores)
+
+    def recommend_users_batch(self, items: List[Any], top_n: int = 100, filter_interacted: bool = True,
+                              candidate_users: Optional[List[Any]] = None, ret_scores: bool = False, as_arrays: bool = False) -> Any:
+        """SLIM.recommend_users_batch: the audiences of many items in one device pass."""
+        return self.model.recommend_users_batch(items, top_n=top_n, filter_interacted=filter_interacted,
+                                                candidate_users=candidate_users, ret_scores=ret_scores, as_arrays=as_arrays)
+
     def similar_items(self, query_items: List[Any], query_item_tags: Optional[List[str]] = None, top_k: int = 10,
                       ret_scores: bool = False):
         batch = getattr(self.model, "similar_items_batch", None)

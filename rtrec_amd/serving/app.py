@@ -13,6 +13,9 @@ the GPU), POST /recommend (one user's top-k).  Differences, all forced by the de
   * POST /explain is an addition (the reference cannot say why it recommended something): {"user": ..., "items": [...] or
     absent, "top_k", "top_m", "filter_interacted"} -> {"user": ..., "explanations": [{"item": ..., "reasons": [{"item": ...,
     "contribution": ...}, ...]}, ...]} (SLIM.explain); same token check as /recommend, not coalesced;
+  * POST /recommend_users is an addition (the other direction: which users for this item): {"item": ..., "top_n",
+    "filter_interacted", "candidate_users": [...] or absent} -> {"item": ..., "users": [{"user": ..., "score": ...}, ...]}
+    (SLIM.recommend_users); same token check as /recommend, not coalesced;
   * concurrent POST /recommend calls are coalesced (`RecommendCoalescer`): requests that arrive within a bounded
     wait (RTREC_AMD_COALESCE_MS, default 1 ms; 0 = only what queued up behind the model lock) share ONE
     recommend_batch launch per (top_k, filter_interacted) group; each caller gets exactly what its own
@@ -59,6 +62,13 @@ class ExplanationRequest(_TopKOptions):
     user: Any
     items: Optional[List[Any]] = None
     top_m: int = 3
+
+
+class AudienceRequest(BaseModel):
+    item: Any
+    top_n: int = 100
+    filter_interacted: bool = True
+    candidate_users: Optional[List[Any]] = None
 
 
 class RecommendationResponse(BaseModel):
@@ -255,6 +265,14 @@ def build_router(gate: ModelGate) -> APIRouter:
         return {"user": request.user,
                 "explanations": [{"item": item, "reasons": [{"item": j, "contribution": c} for j, c in reasons]}
                                  for item, reasons in rows]}
+
+    @api.post("/recommend_users")
+    def recommend_users(request: AudienceRequest, x_token: str = Header()):
+        _authorise(x_token)
+        pairs = gate.call("Audience", lambda m: m.recommend_users(request.item, top_n=request.top_n,
+                                                                  filter_interacted=request.filter_interacted,
+                                                                  candidate_users=request.candidate_users, ret_scores=True))
+        return {"item": request.item, "users": [{"user": u, "score": s} for u, s in pairs]}
 
     return api
 
