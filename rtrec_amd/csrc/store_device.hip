@@ -13,6 +13,16 @@
 // within that error of a float32 rounding boundary -- about one value in 2^29 / margin.  The kernel therefore
 // flags every entry whose product is closer than kMarginUlps float64 ulps to a boundary; the host re-evaluates
 // just those with libm (rtrec_store_decay) and patches them.  Every other float32 is provably the reference's.
+// With margin = kMarginUlps * 2^-52 the distance test flags a share between 2^-16 and 2^-15 of random entries (two
+// boundaries per float32 spacing of 2^-24..2^-23 |v|, a band of 2 * margin |v| around each).
+// The spacing test needs both neighbours of the float32 to be finite and non-zero numbers; where they are not, the
+// host decides every entry:
+//   * underflow: a product that rounds to 0, or lies below 2^-148 (float32 rounds to 0 or to its smallest denormals);
+//   * overflow: a finite product whose float32 is +-FLT_MAX or +-inf (|v| >= 2^128 - 2^104 or so, the boundary being
+//     2^128 - 2^103; reachable only with a max_value beyond the float32 range).  The upper neighbour of FLT_MAX is inf
+//     and inf has none, so the distance test would see inf / NaN there and never flag.
+// An infinite or NaN product, an exact zero and |v| >= 1e300 are not flagged: float32(v) is the same for any pow within
+// a few ulps (a finite |v| >= 1e300 is inf in float32 either way; inf / NaN / 0 come from val or an overflowed pow).
 #include "common.hip.h"
 #include "../../include/rtrec_amd.h"
 
@@ -32,9 +42,10 @@ __global__ __launch_bounds__(256) void decay_kernel(const double *__restrict__ v
         // distance of v to the nearest float32 rounding boundary (the midpoints between f and its neighbours)
         const double fd = static_cast<double>(f);
         if (!(fabs(v) < 1e300) || v == 0.0) continue;                        // inf / nan / an exact zero: nothing to decide
-        if (fd == 0.0 || fabs(v) < 0x1p-148) {
-            // at the underflow boundary (|v| around 2^-150: float32 rounds to 0 or to its smallest denormal): the spacing
-            // test below does not apply, the host decides with libm
+        if (fd == 0.0 || fabs(v) < 0x1p-148 || !(fabsf(f) < 0x1.fffffep+127f)) {
+            // at the underflow boundary (|v| around 2^-150: float32 rounds to 0 or to its smallest denormal) and at the
+            // overflow boundary (f is +-FLT_MAX or +-inf: |v| around 2^128 - 2^103): the spacing test below does not apply,
+            // the host decides with libm
             const int slot = atomicAdd(unsafe_count, 1);
             if (slot < cap) unsafe_idx[slot] = static_cast<int>(k);
             continue;

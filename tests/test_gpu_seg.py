@@ -400,6 +400,145 @@ def test_float64_w_through_the_fast_pass_and_the_refine_step(oracle, shape):
         assert all(np.array_equal(x.view(np.int32), y.view(np.int32)) for x, y in zip(a, b))
 
 
+U24 = 2.0 ** -24
+
+
+def near_tie_case(g, signed, seed=3, jitter=0.0):
+    """(X, W, col_nnz_max) for the refine step's near ties: 4 clusters, each one base column of 12 weights in [0.1, 1] on its own
+    "feature" items, copied into 40 columns as float32(b * (1 + c * g)), c = 0..39 in a random order of the column ids --
+    adjacent copies score a factor 1 + g apart in exact arithmetic.  The copies' ids are disjoint from the feature items (filter_interacted removes no copy); a background
+    of weights <= 0.05, at most 5 per column, in the other columns (signed: 40 of them negative).  2,000 users rate 8 of
+    their cluster's 12 features with non-dyadic float ratings, plus one item of the background.
+    jitter > 0: every weight of every copy is moved by its own random factor 1 + jitter * [-1, 1] as well.  Plain copies are
+    monotone in c weight by weight, and so are their float32 scores: the float32 order can only TIE where the float64 order
+    decides, and the fast pass flags an exact tie by itself.  With the jitter the float32 order of two copies can be the
+    reverse of the float64 order without a tie, and only the margin test stands between such a row and a wrong list."""
+    rng = np.random.default_rng(seed)
+    rng_j = np.random.default_rng(seed + 1000)
+    I, U, Q, F, C = 1200, 2000, 4, 12, 40
+    rows, cols, vals = [], [], []
+    for q in range(Q):
+        b = rng.uniform(0.1, 1.0, F)
+        place = rng.permutation(C)          # not in id order: float32 sums are monotone in the weights, so copies in id order
+        for c in range(C):                  # could only TIE in float32, and ties go by id -- the float64 order by accident
+            rows += list(range(q * F, (q + 1) * F))
+            cols += [100 + q * C + int(place[c])] * F
+            vals += (b * (1.0 + c * g) * (1.0 + jitter * rng_j.uniform(-1.0, 1.0, F))).astype(np.float32).tolist()
+    n_copy = len(vals)
+    pool = np.concatenate([np.arange(Q * F), np.arange(300, I)])
+    for col in range(300, I):
+        r = rng.choice(pool[pool != col], 5, replace=False)
+        rows += r.tolist()
+        cols += [col] * 5
+        vals += rng.uniform(0.005, 0.05, 5).astype(np.float32).tolist()
+    vals = np.array(vals, np.float32)
+    if signed:
+        vals[n_copy + rng.choice(len(vals) - n_copy, 40, replace=False)] *= -1
+    W = sp.csc_matrix((vals, (rows, cols)), shape=(I, I))
+    W.sort_indices()
+    assert W.nnz == len(vals) and int(np.diff(W.indptr).max()) == F
+    xr, xc, xv = [], [], []
+    for u in range(U):
+        q = u % Q
+        its = np.concatenate([q * F + rng.choice(F, 8, replace=False), rng.integers(300, I, 1)])
+        xr += [u] * len(its)
+        xc += its.tolist()
+        xv += rng.uniform(1.0, 5.0, len(its)).astype(np.float32).tolist()
+    X = sp.csr_matrix((np.array(xv, np.float32), (xr, xc)), shape=(U, I))
+    X.sort_indices()
+    return X, W, F
+
+
+def margin_model(oracle, X, W, col_nnz_max, top_k, filt, signed):
+    """The refine step's margin test stated in numpy on the ORACLE's float32 lists (never on a GPU result): per row, does the
+    top_k-th best float64 score among the float32 top-(top_k + 1) beat what a column outside the list could reach --
+    m32 * (1 + 2 (col_nnz_max + 2) 2^-24) for positive weights (SlimEngine._local_topk_lazy), max(m32, 0) + the per-user slack
+    2 (n_u + 2) 2^-24 B_u (1 + 1e-6) + 1e-30 for signed ones (SlimEngine._f64_abs_slack).  Also: is the oracle's float64
+    top_k inside that float32 list at all."""
+    Wr = W.tocsr()
+    ids32, sc32, cnt32 = oracle.recommend_batch(X, Wr, top_k=top_k + 1, filter_interacted=filt)
+    ids64, _, cnt64 = oracle.recommend_batch(X, Wr, top_k=top_k, filter_interacted=filt, use_f64=True)
+    assert (cnt32 == top_k + 1).all() and (cnt64 == top_k).all()
+    S = np.asarray((X.astype(np.float64) @ W.astype(np.float64)).todense())
+    e = np.take_along_axis(S, ids32.astype(np.int64), axis=1)
+    e_k = -np.sort(-e, axis=1)[:, top_k - 1]
+    m32 = sc32[:, top_k].astype(np.float64)
+    if signed:
+        rmax = np.asarray(abs(W).max(axis=1).todense()).ravel().astype(np.float64)
+        B = np.asarray(abs(X).astype(np.float64) @ rmax).ravel()
+        n_u = np.diff(X.indptr).astype(np.float64)
+        passes = (e_k > np.maximum(m32, 0.0) + 2.0 * (n_u + 2.0) * U24 * B * (1.0 + 1e-6) + 1e-30) & (e != 0).all(axis=1)
+    else:
+        passes = e_k > m32 * (1.0 + 2.0 * (col_nnz_max + 2) * U24)
+    inside = np.array([set(a.tolist()) <= set(b.tolist()) for a, b in zip(ids64, ids32)])
+    return passes, inside
+
+
+@pytest.mark.parametrize("signed", [False, True])
+@pytest.mark.parametrize("gap", [0.5, 1.0, 2.0, 32.0, 128.0])
+def test_float64_refine_near_tie_clusters(oracle, gap, signed):
+    """refine_f64_kernel's net, both ways.  Columns of W that are copies of one another a factor 1 + g apart (g = gap * 2^-24):
+    for g <= 2u the float32 order of the copies is noise, the float32 top-(k + 1) need not even hold the float64 top-k, and the
+    margin test must hand every user to the float64 tiled kernel -- a margin that is not applied shows in the re-scored count
+    at g = u and 2u (measured with rel_margin = 0: 1739 and 411 of 2000 rows re-scored; the lists stay right because these
+    copies can only tie in float32, see the next test); for g >= 32u the margin test passes and the refined lists are final.  ids,
+    float32 casts of the float64 scores and counts equal the oracle's use_f64 mode on every row, SPARSE and DENSE."""
+    near_tie_run(oracle, gap, signed)
+
+
+def test_float64_refine_near_ties_that_only_the_margin_catches(oracle):
+    """The copies of near_tie_case are monotone in c, so their float32 scores can only tie where the float64 order decides,
+    and the fast pass flags a tie by itself: with the margin test switched off (rel_margin = 0) the lists of the case above
+    still come out right, only the re-scored count gives it away.  Here every weight of every copy also carries its own
+    jitter of +-4u: the float32 order of two copies can be the reverse of the float64 order with no tie anywhere, and on the
+    rows the guard counts (a few per cent at top_k = 1) only the margin test keeps a wrong list from being final."""
+    near_tie_run(oracle, 0.5, False, jitter=4.0)
+
+
+def near_tie_run(oracle, gap, signed, jitter=0.0):
+    import torch
+    g = gap * U24
+    X, W, col_nnz_max = near_tie_case(g, signed, jitter=jitter * U24)
+    eng = SlimEngine(device="cuda:0")
+    eng.set_interactions(None, X, need_csc=False)
+    eng.set_weights(W.astype(np.float64), acc_f64=True)
+    Wr, rows = W.tocsr(), np.arange(X.shape[0])
+    for top_k in (1, 10, 31):
+        for filt in (True, False):
+            passes, inside = margin_model(oracle, X, W, col_nnz_max, top_k, filt, signed)
+            if gap <= 2.0:          # input guards, from the oracle and numpy alone
+                assert not passes.any(), f"the margin model passes on {int(passes.sum())} rows at g = {gap} u"
+                if gap == 0.5:
+                    assert (~inside).any(), f"float64 top-{top_k} outside the float32 top-{top_k + 1} on {(~inside).mean():.1%} of rows"
+                if jitter and top_k == 1:       # rows that nothing but the margin test protects: a wrong list, no tie in sight
+                    ids32, sc32, _ = oracle.recommend_batch(X, Wr, top_k=2, filter_interacted=filt)
+                    e = np.take_along_axis(np.asarray((X.astype(np.float64) @ W.astype(np.float64)).todense()), ids32.astype(np.int64), axis=1)
+                    alone = ~inside & (e.max(axis=1) > sc32[:, 1]) & (sc32[:, 0] != sc32[:, 1]) & (e[:, 0] != e[:, 1])
+                    assert alone.mean() > 0.01, f"only the margin test protects {alone.mean():.1%} of the rows"
+            else:
+                assert passes.all(), f"the margin model fails on {int((~passes).sum())} rows at g = {gap} u"
+                assert inside.all()
+            eng.rescored = torch.zeros(1, dtype=torch.int32, device="cuda:0")
+            ids, sc, cnt = eng.recommend_rows(rows, top_k=top_k, filter_interacted=filt, mode=_native.TOPK_SPARSE)
+            n_rescored = int(eng.rescored.item())
+            eng.rescored = None
+            assert eng.last_score_path.endswith("+f64"), eng.last_score_path
+            o_ids, o_sc, o_cnt = oracle.recommend_batch(X, Wr, top_k=top_k, filter_interacted=filt, use_f64=True)
+            assert np.array_equal(cnt, o_cnt)
+            bad = np.flatnonzero((ids != o_ids).any(axis=1))
+            assert bad.size == 0, (f"g = {gap} u, top_k {top_k}, filter {filt}: ids differ on {bad.size} rows, first {bad[0]}: "
+                                   f"{ids[bad[0]]} vs {o_ids[bad[0]]}; float64 top-k outside the float32 list on {(~inside).mean():.1%}")
+            assert np.array_equal(bits(sc), bits(o_sc))
+            if gap <= 2.0:
+                assert n_rescored >= len(rows), (n_rescored, len(rows))
+            else:
+                assert n_rescored < len(rows) // 4, (n_rescored, len(rows))
+        ids, sc, cnt = eng.recommend_rows(rows, top_k=top_k, filter_interacted=True, mode=_native.TOPK_DENSE)
+        o_ids, o_sc, o_cnt = oracle.recommend_batch(X, Wr, top_k=top_k, filter_interacted=True, dense=True, use_f64=True)
+        assert np.array_equal(cnt, o_cnt) and np.array_equal(ids, o_ids) and np.array_equal(bits(sc), bits(o_sc))
+        assert signed == (eng.last_score_path == "tiled"), eng.last_score_path
+
+
 def test_seg_exact_ties_go_through_the_exact_pass(oracle):
     """Integer ratings and duplicated columns of W: exact score ties inside and at the edge of the list; the flagged rows
     are re-scored by the first-touch kernel and come out in the reference's order."""
