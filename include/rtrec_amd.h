@@ -270,10 +270,12 @@ typedef struct {
      * float d_fr_super_kb[fr_n_super] * 256, fr_n_frags floats: per fragment 1.0001 * max |w| over its whole tile
      * (float32-rounded), the kernel's first-level tile bound.
      * fr_buf_bytes (a multiple of 1024, >= the largest super-tile) is the size of one LDS staging buffer.  Two forms:
-     *   streaming  fr_buf_bytes >= 32 KiB and 2 * (2 * fr_buf_bytes + 5136) <= 160 KiB: two 8-wave workgroups per CU,
-     *              two buffers each (a tile may continue in the next super-tile: its sums stay in registers);
+     *   streaming  fr_buf_bytes >= 32 KiB and 2 * (2 * fr_buf_bytes + 7696) <= 160 KiB: two 8-wave workgroups per CU,
+     *              two buffers each (a tile may continue in the next super-tile: its sums stay in registers).  7696 =
+     *              8 * 576 (candidate buffers) + 1024 (zero row) + 16 + 2048 (early exit: a suffix bound and a vote word per
+     *              super-tile; a W of 256 or more super-tiles is scored without the early exit);
      *   resident   fr_n_super == 1, fr_n_tiles <= 64 and everything fits next to the per-wave setup scratch
-     *              (fr_buf_bytes + 16 * ceil256(fr_n_tiles * fr_tile_cols / 8 + 768) + 9232 <= 160 KiB): one 16-wave
+     *              (fr_buf_bytes + 16 * ceil256(fr_n_tiles * fr_tile_cols / 8 + 768) + 10256 <= 160 KiB): one 16-wave
      *              workgroup per CU loads W once and keeps it.
      * d_fr_scratch: rtrec_slim_score_fr_scratch_bytes() bytes of device scratch.  Scores and ids are identical to
      * the tiled-CSR path; accumulators live in registers and the matrix is streamed through LDS

@@ -79,6 +79,7 @@ struct ScoreArgs {
 enum { PF_JOBS, PF_ROWPTR, PF_HDR, PF_GROUP, PF_DENSE, PF_SPARSE, PF_SELECT, PF_EMIT, PF_RESET, PF_QUEUE,
        PF_N_DENSE, PF_N_SPARSE_ROWS, PF_N_SPARSE_CHUNKS, PF_N_OVERFLOW, PF_TOTAL, PF_COUNT };
 __device__ unsigned long long g_score_prof[16];
+__device__ unsigned int g_fr_exit_depth[257];     // score_frows_kernel: histogram of the depth at which a job ended
 #define PF_DECL unsigned long long pf_[16] = {0}; unsigned long long pf_t_ = __builtin_amdgcn_s_memtime();
 #define PF_MARK(slot) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); pf_[slot] += n_ - pf_t_; pf_t_ = n_; }
 #define PF_ADD(slot, v) { pf_[slot] += (v); }
@@ -1087,10 +1088,16 @@ __host__ __device__ constexpr int fr_setup_scratch(int mask_words) { return ((ma
 // Streaming layout: two slice buffers (the second doubles as setup scratch).  RESIDENT layout (all of W's slices in ONE
 // super-tile that fits next to the setup scratch): one buffer, loaded once per workgroup and kept across its jobs.
 constexpr int kFrWavesStream = 8;            // streaming layout: two 8-wave workgroups per CU
+// Early exit of a job (streaming layout): sfx[s] = max of frag_wtop over the fragments of super-tiles s, s + 1, ... (sfx[n_super]
+// = 0), a constant of W that every workgroup derives once, and one vote word per super-tile -- 8 bytes of LDS per super-tile.
+// A W of kFrExitSlots or more super-tiles runs without the early exit (as if every sfx were +inf).
+constexpr int kFrExitSlots = 256;
+constexpr int kFrExitBytes = kFrExitSlots * 8;
 __host__ __device__ constexpr size_t fr_lds_bytes(int buf_bytes, bool resident = false, int mask_words = kFrMaskWords) {
     return resident ? static_cast<size_t>(buf_bytes) + kFrWaves * fr_setup_scratch(mask_words) + kFrWaves * fr_wave_extra_bytes() +
                           kFrZeroRowBytes + 16
-                    : 2 * static_cast<size_t>(buf_bytes) + kFrWavesStream * fr_wave_extra_bytes() + kFrZeroRowBytes + 16;
+                    : 2 * static_cast<size_t>(buf_bytes) + kFrWavesStream * fr_wave_extra_bytes() + kFrZeroRowBytes + 16 +
+                          kFrExitBytes;
 }
 
 typedef __attribute__((address_space(3))) void fr_lds_void;
@@ -1292,6 +1299,33 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                                              (fr_lds_void *)(dst + (c << 10)), 16, 0, 0);
     };
 
+    // ---- leaving a job early.  The layout visits the heavy tiles first, so after a few super-tiles no user of a job can
+    //      open any tile that is still to come: with sfx = the largest first-level bound (frag_wtop) from some point of W
+    //      on, a user whose first-level test fails against sfx fails it against every later fragment too (__fmul_rn is
+    //      monotone in the bound, the (k+1)-th best never falls), so every later tile would be skipped for it anyway.
+    //      Streaming: sfx per super-tile in LDS; the waves vote at the hand-over and leave the job together (below).
+    //      Resident: sfx per fragment (at most 64: one super-tile) in lane g of one register; a wave leaves on its own. ----
+    float *s_sfx = reinterpret_cast<float *>(smem + lds_front + NW * fr_wave_extra_bytes() + kFrZeroRowBytes + 16);
+    int *s_vote = reinterpret_cast<int *>(s_sfx + kFrExitSlots);
+    const bool exit_on = resident ? n_frags <= 64 : a.n_super < kFrExitSlots;
+    float sfx_frag = 0.0f;
+    if (resident) {
+        if (exit_on) {
+            sfx_frag = lane < n_frags ? frag_wtop[lane] : 0.0f;
+            for (int d = 1; d < 64; d <<= 1) {              // suffix maximum over the lanes
+                const float o = __shfl_down(sfx_frag, d, 64);
+                sfx_frag = (lane + d < 64 && o > sfx_frag) ? o : sfx_frag;
+            }
+        }
+    } else if (exit_on) {
+        for (int s = wave; s <= a.n_super; s += NW) {       // (the job loop starts with a barrier)
+            float m = 0.0f;
+            for (int g = c_st_tile[s] + lane; g < n_frags; g += 64) { const float v = frag_wtop[g]; m = v > m ? v : m; }
+            for (int d = 1; d < 64; d <<= 1) { const float o = shfl_xor_t(m, d); m = o > m ? o : m; }
+            if (lane == 0) s_sfx[s] = m;
+        }
+    }
+
     PF_DECL
 #ifdef SCORE_PROFILE
     const unsigned long long pf_start_ = pf_t_;
@@ -1320,6 +1354,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
             __syncthreads();                                // the previous job has left both buffers
             PF_MARK(PF_QUEUE)
             if (tid == 0) *s_job = atomicAdd(a.queue, 1);
+            if (exit_on) for (int s = tid; s < a.n_super; s += NW * 64) s_vote[s] = 0;   // (every wave has read the last job's)
             __syncthreads();
             const int job = *s_job;
             if (job >= n_jobs) break;
@@ -1480,17 +1515,27 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
         int kb_a = c_st_kb[min(1, a.n_super)], kb_b = c_st_kb[min(2, a.n_super)];
         int t_lo = c_st_tile[0], t_hi = c_st_tile[min(1, a.n_super)];
         FrFrag fr = load_frag(min(t_lo, max(n_frags - 1, 0))), fr_next = fr;
+        bool wave_done = false;    // streaming: none of this wave's users can open anything from the next super-tile on
+        bool stage_next = true;    // streaming: some wave may still need the super-tile after the next one
+        int ft_last = 1 << 25;     // flags of the last fragment this wave has passed
+#ifdef SCORE_PROFILE
+        int pf_depth_ = resident ? -1 : a.n_super;
+#endif
         for (int sidx = 0; sidx < a.n_super; ++sidx) {
             const unsigned char *wb = (sidx & 1) ? buf1 : buf0;
-            if (sidx + 1 < a.n_super) load_super(kb_a, kb_b, (sidx & 1) ? buf0 : buf1);
+            // (stage_next false: the vote at the end of this super-tile ends the job -- nobody will read the next one)
+            if (sidx + 1 < a.n_super && stage_next) load_super(kb_a, kb_b, (sidx & 1) ? buf0 : buf1);
             // the next super-tile's extents: requested now, needed at the hand-over
             const int kb_c = c_st_kb[min(sidx + 3, a.n_super)], t_hi_next = c_st_tile[min(sidx + 2, a.n_super)];
             const unsigned char *wlane = wb + lane16;             // this lane's columns in a slice row
             const unsigned char *wzero = zrow + lane16;           // a row of +0.0: what a step reads past the last row
 
-            for (int g = t_lo; g < t_hi; ++g, fr = fr_next) {
+            // (a wave that is done only helps to stage and meets the others at the barriers: its fragments' constants are
+            // no longer loaded, nothing reads them)
+            if (!wave_done) for (int g = t_lo; g < t_hi; ++g, fr = fr_next) {
                 fr_next = load_frag(min(g + 1, n_frags - 1));     // in flight while fragment g is worked on
                 const int ft = fr.ft;
+                ft_last = ft;
                 const int t = ft & 0xffffff;                     // the tile this fragment belongs to
                 // ---- tile-major sweep: every row of W that holds a weight in this tile (and that one of the wave's
                 //      users rates) is read from LDS ONCE and applied to all eight users: acc_u += x_u * w, one
@@ -1535,6 +1580,17 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                         const float thr_u = readlane_f(ls4[u >> 2], (u & 3) * 16 + kk - 1);
                         if (bound > 0.0f && !(thr_u >= 0.0f && bound <= thr_u)) all_skip = false;
                     });
+                    // resident layout: a tile that is closed at the first level for all of the wave's users -- when every
+                    // fragment from here on is, too (sfx_frag), the wave's lists are final
+                    if (!open1 && resident && exit_on) {
+                        const float sfx = readlane_f(sfx_frag, g);
+                        if (!__ballot(lane < UW && l1v > 0.0f && !(thrv >= 0.0f && __fmul_rn(l1v, sfx) <= thrv))) {
+#ifdef SCORE_PROFILE
+                            pf_depth_ = g;
+#endif
+                            break;
+                        }
+                    }
                     tile_skip = all_skip;
                     if (!tile_skip) fr_static_for<UW>([&](auto Uc) { acc[decltype(Uc)::value] = vec(0.0f); });
                 }
@@ -1684,12 +1740,47 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
             }
             PF_MARK(PF_DENSE)
             if (!resident) {
+                // ---- the vote: does this wave need super-tile s+1 (bit 0), s+2 (bit 1) or anything behind them?  The first-level
+                //      test of the tile loop with the suffix bound in place of a tile's own; a wave whose open tile continues
+                //      in s+1 needs both.  A list that never fills (thrv = -inf) keeps the job running to the end of W, a slot
+                //      without ratings (l1v = 0) never does.  One word per super-tile, OR-ed before the barrier that is here
+                //      anyway and read by every wave after it: all of them take the same decision.  Bit 1 decides whether
+                //      s+2 is staged at all: when no wave sets it, none can set bit 0 at the end of s+1 (sfx[s+2] covers the
+                //      continuation of every tile that starts in s+1, thresholds only rise), so the job ends there with no
+                //      LDS-DMA in flight.  When only the thresholds of s itself close the job, s+1 has been staged for
+                //      nothing; the wait below covers it. ----
+                if (exit_on && !wave_done) {
+                    const bool cont = !tile_skip && !(ft_last & (1 << 25));
+                    const float sfx1 = s_sfx[sidx + 1], sfx2 = s_sfx[min(sidx + 2, a.n_super)];
+                    const bool live = lane < UW && l1v > 0.0f;
+                    const bool need1 = cont || __ballot(live && !(thrv >= 0.0f && __fmul_rn(l1v, sfx1) <= thrv)) != 0ull;
+                    const bool need2 = cont || __ballot(live && !(thrv >= 0.0f && __fmul_rn(l1v, sfx2) <= thrv)) != 0ull;
+                    if (need1 && lane == 0) atomicOr(&s_vote[sidx], need2 ? 3 : 1);
+                    wave_done = !need1;
+                }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // super-tile s+1 has landed ...
                 __syncthreads();                                    // ... and every wave has left super-tile s
             }
             PF_MARK(PF_GROUP)
+            if (!resident && exit_on) {
+                const int vote = readfirst_i(s_vote[sidx]);
+                if (!(vote & 1)) {
+#ifdef SCORE_PROFILE
+                    pf_depth_ = sidx + 1;
+#endif
+                    break;
+                }
+                stage_next = (vote & 2) != 0;
+            }
             kb_a = kb_b; kb_b = kb_c; t_lo = t_hi; t_hi = t_hi_next;
         }
+#ifdef SCORE_PROFILE
+        // super-tiles a streaming job worked on / fragment at which a resident wave left (n_frags: it went to the end)
+        if (lane == 0 && (resident || wave == 0)) {
+            if (pf_depth_ < 0) pf_depth_ = n_frags;
+            atomicAdd(&g_fr_exit_depth[min(pf_depth_, kFrExitSlots)], 1u);
+        }
+#endif
 
         // ---- the lists are the rows' answers: lane lb + j of list register g = rank j of user 4 g + lb / 16 ----
         int gid[NL], orow = 0;
@@ -2202,6 +2293,11 @@ extern "C" int rtrec_amd_seg_heavy_profile(unsigned long long *out16, int reset)
 extern "C" int rtrec_amd_seg_profile(unsigned long long *out16, int reset) {
     if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_seg_prof), 16 * sizeof(unsigned long long)) != hipSuccess) return -4;
     if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_seg_prof), z, sizeof(z)) != hipSuccess) return -4; }
+    return 0;
+}
+extern "C" int rtrec_amd_fr_exit_depth(unsigned int *out257, int reset) {
+    if (out257 && hipMemcpyFromSymbol(out257, HIP_SYMBOL(rtrec::g_fr_exit_depth), 257 * sizeof(unsigned int)) != hipSuccess) return 1;
+    if (reset) { static const unsigned int z[257] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(rtrec::g_fr_exit_depth), z, sizeof(z)) != hipSuccess) return 1; }
     return 0;
 }
 extern "C" int rtrec_amd_score_profile(unsigned long long *out16, int reset) {

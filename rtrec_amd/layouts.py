@@ -386,3 +386,82 @@ def build_tiled_w_device(torch, rows, cols, vals, n_items: int, col_lo: int, col
                 n_dense=0 if dense_idx is None else int(dense_val.numel() // S),
                 tile_ptr=tile_ptr.view(-1), w_col=kl.to(torch.int16), w_val=vl.contiguous(),
                 col_ids=None if col_ids is None else col_ids.to(torch.int32), col_map=col_map, row_hdr=hdr)
+
+
+# ---- host model of score_frows_kernel's early exit (csrc/score.hip): the suffix bound and the depth a job needs ----
+def fr_exit_suffix_bound(L: Dict[str, Any]) -> np.ndarray:
+    """sfx[s] = max(frag_wtop[g] for g >= fr_super_tile[s]) for s = 0 .. n_super, sfx[n_super] = 0: the largest first-level
+    bound any fragment from super-tile s on carries (a continuation fragment carries its tile's).  float32, as the kernel
+    derives it from the tail of fr_w."""
+    kb, st = np.asarray(L["fr_super_kb"]), np.asarray(L["fr_super_tile"])
+    tail = np.asarray(L["fr_w"])[int(kb[-1]) * 256:].astype(np.float32)
+    run = np.append(np.maximum.accumulate(tail[::-1])[::-1], np.float32(0)).astype(np.float32)
+    return run[st]
+
+
+def fr_exit_model(L: Dict[str, Any], W: sp.spmatrix, X: sp.csr_matrix, top_k: int, filter_interacted: bool = True) -> Dict[str, Any]:
+    """What the kernel's running (k+1)-th best scores look like, super-tile by super-tile, for the users of X (host layout L
+    of W from build_feature_rows).  Scores are float32 sums over the rows of W in ascending order, one rounded product and
+    one rounded add each, like the kernel's; a user's threshold after a tile is the (top_k + 1)-th largest admissible score
+    (non-zero, not interacted when filtering) of the tiles so far, -inf while there are fewer.
+      scores[u, c]   float32 score of layout column c
+      l1[u]          float32 sum of |ratings| over the feature rows (summed in row order; the kernel sums a tree)
+      thr_end[u, s]  the threshold at the hand-over that ends super-tile s (tiles whose last fragment lies in 0 .. s)
+      closed[u, s]   the exit predicate at that hand-over: l1 == 0, or thr >= 0 and fl(l1 * sfx[s + 1]) <= thr
+      depth[u]       super-tiles the user needs by the predicate alone (first closed s, plus one; n_super: never closes)
+      depth_open[u]  ... and counting every tile that is first-level-open for the user to its last fragment: no job runs
+                     deeper than the largest depth_open of its users
+      later_tiles[s] tiles with a fragment in a super-tile > s"""
+    tc, n_tiles, kk = int(L["fr_tile_cols"]), int(L["fr_n_tiles"]), int(top_k) + 1
+    st, ftile = np.asarray(L["fr_super_tile"]), np.asarray(L["fr_frag_tile"])
+    n_super, n_frags = len(st) - 1, len(ftile)
+    sfx = fr_exit_suffix_bound(L)
+    kb = np.asarray(L["fr_super_kb"])
+    tail = np.asarray(L["fr_w"])[int(kb[-1]) * 256:].astype(np.float32)
+    f_super = np.searchsorted(st, np.arange(n_frags), side="right") - 1
+    t_of_frag = ftile & 0xFFFFFF
+    last_super = np.full(n_tiles, -1, dtype=np.int64)           # super-tile of a tile's last fragment (-1: no stored row)
+    wtop = np.zeros(n_tiles, dtype=np.float32)
+    np.maximum.at(last_super, t_of_frag, f_super)
+    wtop[t_of_frag] = tail
+    F = np.flatnonzero(np.asarray(L["fr_map"]) >= 0)
+    col_ids = np.asarray(L["fr_col_ids"])
+    dense = W.tocsr()[F][:, col_ids].toarray().astype(np.float32)       # R x n_cols, layout order
+    Xf = X.tocsr()[:, F].toarray().astype(np.float32)                    # U x R
+    U, n_cols = Xf.shape[0], dense.shape[1]
+    scores = np.zeros((U, n_cols), dtype=np.float32)
+    l1 = np.zeros(U, dtype=np.float32)
+    for f in range(len(F)):
+        scores = (scores + (Xf[:, f:f + 1] * dense[f][None, :]).astype(np.float32)).astype(np.float32)
+        l1 = (l1 + np.abs(Xf[:, f])).astype(np.float32)
+    ok = scores != 0
+    if filter_interacted:                       # every stored entry of the user's row, a stored zero included
+        Xr = X.tocsr()
+        seen = sp.csr_matrix((np.ones(Xr.nnz, dtype=np.int8), Xr.indices, Xr.indptr), shape=Xr.shape)[:, col_ids].toarray()
+        ok &= seen == 0
+    adm = np.where(ok, scores, -np.inf).astype(np.float32)
+    thr_tile = np.full((U, n_tiles), -np.inf, dtype=np.float32)           # threshold after tile t
+    top = np.full((U, kk), -np.inf, dtype=np.float32)
+    for t in range(n_tiles):
+        top = -np.sort(-np.concatenate([top, adm[:, t * tc:(t + 1) * tc]], axis=1), axis=1)[:, :kk]
+        thr_tile[:, t] = top[:, kk - 1]
+    ninf = np.full(U, -np.inf, dtype=np.float32)
+    thr_end = np.empty((U, n_super), dtype=np.float32)
+    closed = np.empty((U, n_super), dtype=bool)
+    for s in range(n_super):
+        done = np.flatnonzero(last_super <= s)                              # (tiles complete in layout order)
+        n_done = int(done.max()) + 1 if len(done) else 0
+        thr = thr_tile[:, n_done - 1] if n_done else ninf
+        thr_end[:, s] = thr
+        closed[:, s] = (l1 == 0) | ((thr >= 0) & ((l1 * sfx[s + 1]).astype(np.float32) <= thr))
+    depth = np.where(closed.any(axis=1), closed.argmax(axis=1) + 1, n_super)
+    depth_open = depth.copy()
+    for t in range(n_tiles):
+        if last_super[t] < 0:
+            continue
+        before = thr_tile[:, t - 1] if t else ninf
+        open1 = (l1 > 0) & ~((before >= 0) & ((l1 * wtop[t]).astype(np.float32) <= before))
+        depth_open = np.where(open1, np.maximum(depth_open, last_super[t] + 1), depth_open)
+    later_tiles = [np.flatnonzero(last_super > s) for s in range(n_super)]
+    return dict(scores=scores, l1=l1, sfx=sfx, thr_end=thr_end, closed=closed, depth=depth, depth_open=np.minimum(depth_open, n_super),
+                later_tiles=later_tiles, n_super=n_super, wtop=wtop, last_super=last_super)
