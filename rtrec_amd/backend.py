@@ -14,9 +14,9 @@ import scipy.sparse as sp
 
 from . import _native
 from . import settings
+from .fit_plan import FitKnobs, FIT_MW_MAX_TARGETS  # noqa: F401  (the latter for importers of old)
 
-FIT_MW_MAX_TARGETS = 2048   # kMwMaxTargets of csrc/fit.hip: calls up to this size run the multi-wave kernel
-XTY_SCRATCH_MAX_BYTES = 32 << 30   # such calls get the one-pass X^T y (rtrec_fit_opts.d_xty_ws) while its scratch stays below this
+XTY_SCRATCH_MAX_BYTES = 32 << 30   # a small fit call gets the one-pass X^T y (rtrec_fit_opts.d_xty_ws) while its scratch stays below this
 
 
 class DeviceWeights:
@@ -123,30 +123,17 @@ class HipBackend:
 
     supports_gram = True
     supports_device_store = True     # X can stay resident as sorted COO (utils/device_store.py)
-
-    @staticmethod
-    def fit_knobs() -> Dict[str, int]:
-        """Tuning / test knobs of rtrec_fit_opts, read from the environment HERE (the library itself reads none):
-        RTREC_AMD_FIT_MODE=sw|mw, RTREC_AMD_COLWALK_MIN, RTREC_AMD_SCREEN_MIN, RTREC_AMD_LANE_MAX,
-        RTREC_AMD_FOLD=chain|spec|spec-all (how ordered dot products are evaluated; bit-identical results)."""
-        mode = settings.raw("RTREC_AMD_FIT_MODE", "")
-        lane_max = settings.raw("RTREC_AMD_LANE_MAX")
-        return dict(kernel=2 if mode.startswith("m") else 1 if mode.startswith("s") else 0,
-                    colwalk_min_rows=int(settings.raw("RTREC_AMD_COLWALK_MIN", 0)),
-                    screen_min=int(settings.raw("RTREC_AMD_SCREEN_MIN", 0)),
-                    lane_max=0 if lane_max is None else (-1 if int(lane_max) == 0 else int(lane_max)),
-                    fold={"": 0, "chain": 1, "spec-all": 2, "spec": 3}[settings.raw("RTREC_AMD_FOLD", "")])
+    fit_launch_options = True        # fit_columns takes fast / one_pass_xty / knobs (SlimEngine._launch_fit)
 
     def fit_columns(self, n_users, n_items, X, targets, cfg, out_items, out_coef, out_count, out_niter, cap,
-                    ws, queue, slots, trace=None, gram=None, fast=False, one_pass_xty=True):
+                    ws, queue, slots, trace=None, gram=None, fast=0, one_pass_xty=False, knobs=FitKnobs()):
+        """One launch of rtrec_slim_fit_columns_opt.  What to launch is the caller's decision (fit_plan.plan_fit: `fast`,
+        `one_pass_xty`, and `knobs` for the tuning fields of rtrec_fit_opts); here only the scratch of the one-pass X^T y
+        of all targets is sized, grown on demand, and given up where it would pass XTY_SCRATCH_MAX_BYTES."""
         g = gram or {}
-        k = self.fit_knobs()
-        # small calls with feature selection (online partial_fit): scratch for the one-pass X^T y of all targets
         xty = None
-        n_t, nnz = int(targets.shape[0]), int(X["rcol"].shape[0])
-        if (one_pass_xty and 0 < n_t <= FIT_MW_MAX_TARGETS and int(cfg.top_features) > 0 and int(fast) != 1 and k["kernel"] != 1 and nnz > 0
-                and settings.raw("RTREC_AMD_XTY_BATCH", "1") != "0"):
-            need = int(self.lib.rtrec_slim_xty_workspace_bytes(n_users, n_items, nnz, n_t))
+        if one_pass_xty:
+            need = int(self.lib.rtrec_slim_xty_workspace_bytes(n_users, n_items, int(X["rcol"].shape[0]), int(targets.shape[0])))
             if 0 < need <= XTY_SCRATCH_MAX_BYTES:
                 if self._xty_ws is None or self._xty_ws.numel() < need:
                     self._xty_ws = None
@@ -159,7 +146,8 @@ class HipBackend:
                              int(cfg.seed), bool(cfg.positive), int(cfg.top_features),
                              out_items, out_coef, out_count, out_niter, cap, ws, slots, queue, trace,
                              g.get("G"), g.get("index"), int(g.get("n", 0)), float(g.get("rel_err", 0.0)),
-                             int(fast), k["kernel"], k["colwalk_min_rows"], k["screen_min"], k["lane_max"], xty, X.get("col_order") if xty is not None else None, k["fold"])
+                             int(fast), knobs.kernel, knobs.colwalk_min_rows, knobs.screen_min, knobs.lane_max, xty,
+                             X.get("col_order") if xty is not None else None, knobs.fold)
 
     def gram_matrix(self, X, n_users, n_items, n_top):
         """Gram matrix X_P^T X_P of the n_top most popular items in float64 for the fit kernel's Gram

@@ -26,27 +26,23 @@ import scipy.sparse as sp
 from . import _native
 from . import settings
 # (round 4: the layout builders and the backend live in modules of their own; the names stay importable from here)
-from .backend import DeviceWeights, HipBackend, FIT_MW_MAX_TARGETS, XTY_SCRATCH_MAX_BYTES  # noqa: F401
-from . import score_plan
+from .backend import DeviceWeights, HipBackend, XTY_SCRATCH_MAX_BYTES  # noqa: F401
+from . import fit_plan, score_plan
+# (the fit's constants live with the decision that uses them, in fit_plan.py; the names stay importable from here)
+from .fit_plan import (FitFacts, FitKnobs, MAX_SLOTS, ALLF_OUTPUT_CAP, GRAM_ITEMS, GRAM_ITEMS_MAX, FIT_SCRATCH_GIB,  # noqa: F401
+                       XTY_MIN_WALK_ENTRIES, FIT_HEAVY_TARGETS, FIT_HEAVY_SLOTS, FIT_HEAVY_MIN_ROWS, FIT_MW_MAX_TARGETS,
+                       FIT_SLOTS_SPARSE, FIT_SPARSE_FEATURES, FIT_DENSE_FEATURES)
 from .layouts import (TiledW, build_tiled_w, row_header_table, build_feature_rows, build_feature_rows_device,  # noqa: F401
                       build_tiled_w_device, _heavy_tiles_first, _pack_fragments, FR_MAX_ROWS, FR_MIN_FILL,
                       FR_TILE_HEADER_BYTES, FR_STREAM_BUF_BYTES)
 
 DEFAULT_TILE_COLS = 4096   # 16 KB of float accumulators: 8 persistent waves per CU (2 per SIMD) hide each other's latency
 DENSE_ROW_FILL = 1.0 / 3.0   # W row segments at least this full are stored dense (sparse layout)
-MAX_SLOTS = 4096   # 4 single-wave workgroups per SIMD; with Gram tracking the sweet spot moved down from 5120 (C3: 2.16 s vs 2.3 s)
 GATHER_CHUNK_ROWS = 131072  # rows per exchange chunk of a column-sharded scoring call: a launch of the score kernel needs this
                             # many users to fill the chip a few times over (32k-row chunks: 6.4 ms per ML-20M pass against 2.6)
 MAX_GATHER_CHUNKS = 8
 ROW_CHUNK_ROWS = 49152     # least slots per exchange chunk of a row-sharded scoring call (each rank's launch per chunk): C4 at 8
                            # ranks (125k slots per rank) runs as two chunks, the gather of the first beside the kernel of the second
-ALLF_OUTPUT_CAP = 2048      # coefficients per target the K=None output block holds before a refit with cap = I
-GRAM_ITEMS = 512            # most popular items whose pairwise dot products the fit kernel may look up
-FIT_SCRATCH_GIB = 16.0      # total per-slot scratch of a bulk fit is kept near this (see fit_columns)
-XTY_MIN_WALK_ENTRIES = 1e9         # ... and the per-target column walks it replaces would visit at least this many entries
-FIT_HEAVY_TARGETS = 256     # head of a bulk call sent to the multi-wave kernel (one workgroup per CU)
-FIT_HEAVY_SLOTS = 256
-FIT_HEAVY_MIN_ROWS = 2048   # ... as long as the target has at least this many users
 
 
 def sklearn_seed(random_state: Optional[int]) -> int:
@@ -285,24 +281,20 @@ class SlimEngine:
         row t describes model.sparse_coef_ of target t (see rtrec_slim_fit_columns).  device_out=True (feature
         selection only) leaves the first four on the device -- int32 targets, the kernels' output blocks -- for
         merge_fit(); only n_iter (one int per target) is downloaded.
+
+        What the call asks of the device is decided by fit_plan.plan_fit; this method runs that plan.
         """
         be, X = self.be, self._X
         if "cptr" not in X:
             raise RuntimeError("set_interactions() with the CSC orientation must be called before fit_columns()")
         U, I = self.n_users, self.n_items
         targets = np.asarray(targets, dtype=np.int64)
-        # the one-pass X^T y of small calls maps a target to ONE slot of the call (xty_tmap_kernel): a repeated target would lose
-        # its candidates there, so such a call takes the per-target walks (same results; ADVICE round 2)
         distinct_targets = len(np.unique(targets)) == len(targets)
         # longest columns first: the device work queue then ends on short jobs
-        order = np.argsort(-X["col_nnz"][targets], kind="stable")
-        targets = targets[order]
+        targets = targets[np.argsort(-X["col_nnz"][targets], kind="stable")]
         K = int(nn_feature_selection) if nn_feature_selection is not None else 0
         if nn_feature_selection is not None and K <= 0:
             raise AssertionError(f"n_neighbors must be a positive integer: {K}")
-        # K = None: a column's solution is sparse, so the output block is sized for ALLF_OUTPUT_CAP
-        # coefficients per target and the rare target that has more is refitted with room for all I
-        cap = min(K, I) if K > 0 else min(I, int(settings.raw("RTREC_AMD_ALLF_CAP", ALLF_OUTPUT_CAP)))
         cfg = _native.FitCfg(np.float32(alpha * l1_ratio * U), np.float32(alpha * (1.0 - l1_ratio) * U),
                              np.float32(tol), int(max_iter), sklearn_seed(random_state), int(bool(positive)), K)
         torch = be.torch
@@ -310,148 +302,113 @@ class SlimEngine:
             X["sqn"] = be.empty((I,), torch.float32)
             be.column_sqnorms(I, X["cptr"], X["cval"], X["sqn"])
         n = len(targets)
-        slots = int(n_slots or min(int(settings.raw("RTREC_AMD_FIT_SLOTS", self._fit_slots_for(targets, cfg, cap, K))), max(1, n)))
-        # Per-slot scratch is R (U floats) + s/touched/candidates (I each).  The X^T y step is a random
-        # read-modify-write over s, i.e. bound by cache lines moved, and measured faster with FEWER
-        # targets in flight once a slot is several MB (C4: 1024 slots 7.3 s, 5120 slots 9.2 s): keep
-        # the total near 16 GiB but never below 1024 slots.
-        per_slot = 4 * (U + (5 if K <= 0 else 4) * I)
-        scratch_gib = float(settings.raw("RTREC_AMD_FIT_SCRATCH_GIB", FIT_SCRATCH_GIB))
-        slots = max(1, min(slots, max(1024, int(scratch_gib * (1 << 30)) // max(per_slot, 1))))
-
-        # Bulk calls end on their heaviest targets: a popular item's X^T y is a walk over tens of
-        # thousands of user rows and one wave does it strictly row after row.  The head of the
-        # (length-sorted) list therefore goes to the multi-wave latency kernel on a side stream while
-        # the single-wave throughput kernel works through the rest; the C-ABI picks the kernel by
-        # call size (<= FIT_MW_MAX_TARGETS targets -> multi-wave), so this is two plain calls.
-        n_heavy = 0
-        heavy_slots = FIT_HEAVY_SLOTS
-        if K > 0 and n > FIT_MW_MAX_TARGETS:
-            # A call of a few thousand targets (one rank's share of a sharded fit, a large incremental fit)
-            # ends with its slowest target: more of it goes to the multi-wave kernel, two workgroups per CU
-            # (C3, an eighth of the targets: 0.77 -> 0.59 s; tools/fit_shard_model.py).
-            small_call = n <= 2 * FIT_MW_MAX_TARGETS
-            want = int(settings.raw("RTREC_AMD_FIT_HEAVY", 4 * FIT_HEAVY_TARGETS if small_call else FIT_HEAVY_TARGETS))
-            heavy_slots = 2 * FIT_HEAVY_SLOTS if small_call else FIT_HEAVY_SLOTS
-            heavy_min_rows = FIT_HEAVY_MIN_ROWS // 8 if small_call else FIT_HEAVY_MIN_ROWS
-            nnz_sorted = X["col_nnz"][targets]
-            n_heavy = int(min(want, n - FIT_MW_MAX_TARGETS - 1, np.searchsorted(-nnz_sorted, -int(settings.raw("RTREC_AMD_FIT_HEAVY_MIN_ROWS", heavy_min_rows)),
-                                                                                 side="right")))
-            n_heavy = max(n_heavy, 0)
-
-        # Gram tracking (csrc/fit.hip): bulk calls on a non-negative X get the Gram matrix of the most
-        # popular items, which lets the kernel decide most zero coordinates without a pass over memory.
+        knobs = FitKnobs.from_settings()
+        plan = fit_plan.plan_fit(FitFacts(
+            n_users=U, n_items=I, n_targets=n, col_nnz=X["col_nnz"][targets], nnz=int(X["col_nnz"].sum()), K=K,
+            mode=mode or ("exact" if exact else "gram"), n_slots=n_slots, device_out=device_out, nonneg=bool(X.get("nonneg")),
+            hip=isinstance(be, HipBackend), supports_gram=getattr(be, "supports_gram", False), distinct_targets=distinct_targets,
+            pilot_density=lambda: self._pilot_feature_density(targets, cfg, knobs)), knobs)
+        cap = plan.cap
         gram = None
-        gmode = settings.raw("RTREC_AMD_GRAM", "auto")
-        mode_ = mode or ("exact" if exact else "gram")
-        if mode_ not in ("exact", "shuffle", "gram"):
-            raise ValueError(f"fit mode must be 'exact', 'shuffle' or 'gram': {mode_}")
-        fast = {"exact": 0, "shuffle": 1, "gram": 2}[mode_] if K > 0 else 0
-        if fast == 1:
-            n_heavy = 0            # tree-reduced dots: single-wave kernel only, one launch
-        # exact mode: Gram TRACKING needs a non-negative X and pays on bulk calls; tolerance mode: Gram-form CD, any X
-        if (K > 0 and min(K, I) <= 64 and getattr(be, "supports_gram", False) and gmode != "0"
-                and (fast == 2 or (fast == 0 and X.get("nonneg") and (n > FIT_MW_MAX_TARGETS or gmode == "force")))):
-            n_top = self._gram_items(targets, cfg, cap)
+        if plan.use_gram:
+            n_top = self._gram_items(targets, cfg, knobs)
             if X.get("gram_n") != n_top:
                 X["gram"], X["gram_n"] = be.gram_matrix(X, U, I, n_top), n_top
             gram = X["gram"]
 
-        def workspace(n_slots_: int, role: str = "main"):
-            """(scratch, queue, slots of the scratch layout); `role` keeps the side-stream launch of the
-            heavy targets on a scratch of its own (the two kernels run concurrently).  A cached scratch of the same problem shape
-            with at least n_slots_ slots is reused as it is -- the kernel launches min(slots, targets)
-            workgroups, so extra slots are simply idle -- which keeps mini-batches of varying size
-            (online partial_fit) from re-allocating and re-initialising it every call."""
-            kk = K if K > 0 else 0
-            fits = [k for k in self._fit_ws
-                    if k[0] == U and k[1] == I and k[3] == kk and k[2] >= n_slots_ and k[4] == role]
-            if fits:
-                key = min(fits, key=lambda k: k[2])
-            else:
-                want = 1 << max(0, int(n_slots_ - 1).bit_length())          # next power of two
-                key = (U, I, int(min(max(want, n_slots_), max(slots, n_slots_))), kk, role)
-                if len(self._fit_ws) >= 4:
-                    self._fit_ws.clear()
-                self._fit_ws[key] = be.fit_workspace(U, I, key[2], K)
-            ws_, queue_ = self._fit_ws[key]
-            return ws_, queue_, key[2]
-
-        # chunk so that the output block stays below ~1 GiB (matters for K=None, cap = I)
-        chunk = max(1, min(n, int((1 << 30) // max(cap * 8, 1)))) if n else 1
-        if device_out and K <= 0:
-            raise ValueError("device_out needs nn_feature_selection (the all-features output block is host-sized)")
-        kept: List[Dict[str, Any]] = []
-        items_out = np.empty((0 if device_out else n, cap), dtype=np.int32)
-        coef_out = np.empty((0 if device_out else n, cap), dtype=np.float32)
-        count_out = np.empty((n,), dtype=np.int32)
-        niter_out = np.empty((n,), dtype=np.int32)
+        # device_out keeps the launches' blocks (`kept`), otherwise each is downloaded into `host` before the next launch
+        kept: List[Tuple[int, Dict[str, Any]]] = []
+        host = None if device_out else dict(items=np.empty((n, cap), dtype=np.int32), coef=np.empty((n, cap), dtype=np.float32),
+                                            count=np.empty((n,), dtype=np.int32), niter=np.empty((n,), dtype=np.int32))
         trace_out = np.zeros((n, 8), dtype=np.int64) if trace else None
-
-        def launch(lo_: int, hi_: int, n_slots_: int, role: str = "main"):
-            tg = targets[lo_:hi_]
-            m = len(tg)
-            ws, queue, ws_slots = workspace(n_slots_, role)
-            d = dict(lo=lo_, hi=hi_, t=be.to_dev(tg.astype(np.int32)), items=be.empty((m, cap), torch.int32),
-                     coef=be.empty((m, cap), torch.float32), count=be.empty((m,), torch.int32),
-                     niter=be.empty((m,), torch.int32), trace=be.zeros((m, 8), torch.int64) if trace else None,
-                     ws=(ws, queue))   # keeps the scratch alive while the kernel runs
-            if isinstance(be, HipBackend):
-                be.fit_columns(U, I, X, d["t"], cfg, d["items"], d["coef"], d["count"], d["niter"], cap, ws, queue,
-                               ws_slots, d["trace"], gram, fast=fast,
-                               # the heavy head of a bulk call starts its long ordered folds at once: its targets' own
-                               # multi-wave walks overlap them, a one-pass X^T y up front would only delay the chain
-                               one_pass_xty=(role != "heavy" and distinct_targets and self._one_pass_xty_pays(tg)))
+        heavy = side = None
+        for ln in plan.launches:
+            args = (targets[ln.lo:ln.hi], cfg, cap, ln.n_slots, ln.role, knobs, plan.slots, trace, gram, plan.fast, ln.one_pass_xty)
+            if ln.role == "heavy":      # on the side stream, beside the chunks; collected after them
+                side = self._side_stream = getattr(self, "_side_stream", None) or torch.cuda.Stream(be.device)
+                side.wait_stream(torch.cuda.current_stream(be.device))
+                with torch.cuda.stream(side):
+                    heavy = (ln, self._launch_fit(*args))
             else:
-                be.fit_columns(U, I, X, d["t"], cfg, d["items"], d["coef"], d["count"], d["niter"], cap, ws, queue,
-                               ws_slots, d["trace"], gram)
-            return d
-
-        def collect(d):
-            lo_, hi_ = d["lo"], d["hi"]
-            if device_out:
-                kept.append(d)
-                if trace:
-                    trace_out[lo_:hi_] = d["trace"].cpu().numpy()
-                return
-            items_out[lo_:hi_] = d["items"].cpu().numpy()
-            coef_out[lo_:hi_] = d["coef"].cpu().numpy()
-            count_out[lo_:hi_] = d["count"].cpu().numpy()
-            niter_out[lo_:hi_] = d["niter"].cpu().numpy()
-            if trace:
-                trace_out[lo_:hi_] = d["trace"].cpu().numpy()
-
-        heavy = None
-        if n_heavy > 0:
-            main = torch.cuda.current_stream(be.device)
-            side = self._side_stream = getattr(self, "_side_stream", None) or torch.cuda.Stream(be.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                heavy = launch(0, n_heavy, min(n_heavy, int(settings.raw("RTREC_AMD_FIT_HEAVY_SLOTS", heavy_slots))), role="heavy")
-        for s in range(n_heavy, n, chunk):
-            collect(launch(s, min(n, s + chunk), min(slots, max(1, min(n, s + chunk) - s))))
+                self._collect_fit(ln, self._launch_fit(*args), host, kept, trace_out)
         if heavy is not None:
             torch.cuda.current_stream(be.device).wait_stream(side)
-            collect(heavy)
+            self._collect_fit(*heavy, host, kept, trace_out)
         if K <= 0 and cap < I:
-            over = np.flatnonzero(count_out > cap)
-            if over.size:      # refit these with room for every item, then widen the block
-                full = self._fit_overflow(targets[over], cfg, U, I, slots)
-                wide = int(max(int(full[2].max()), cap))
-                items_w = np.zeros((n, wide), dtype=np.int32); items_w[:, :cap] = items_out
-                coef_w = np.zeros((n, wide), dtype=np.float32); coef_w[:, :cap] = coef_out
-                items_w[over] = full[0][:, :wide]; coef_w[over] = full[1][:, :wide]
-                niter_out[over] = full[3]
-                items_out, coef_out = items_w, coef_w
-        self.last_fit_stats = {"n_targets": n, "slots": slots, "cap": cap, "trace": trace_out, "n_heavy": n_heavy}
+            over = np.flatnonzero(host["count"] > cap)
+            if over.size:      # K = None targets whose solution did not fit the output block: refit these with room for every item, then widen the block
+                d = self._launch_fit(targets[over], cfg, I, max(1, min(plan.slots, len(over))), "overflow", knobs)
+                full = {k: d[k].cpu().numpy() for k in ("items", "coef", "count", "niter")}
+                wide = int(max(int(full["count"].max()), cap))
+                items_w = np.zeros((n, wide), dtype=np.int32); items_w[:, :cap] = host["items"]
+                coef_w = np.zeros((n, wide), dtype=np.float32); coef_w[:, :cap] = host["coef"]
+                items_w[over] = full["items"][:, :wide]; coef_w[over] = full["coef"][:, :wide]
+                host["niter"][over] = full["niter"]
+                host["items"], host["coef"] = items_w, coef_w
+        self.last_fit_stats = {"n_targets": n, "slots": plan.slots, "cap": cap, "trace": trace_out, "n_heavy": plan.n_heavy,
+                               "plan": plan}
         self.last_fit_targets = targets
         if device_out:
-            kept.sort(key=lambda d: d["lo"])
-            cat = (lambda k, shape, dt: torch.cat([d[k] for d in kept]) if kept else be.empty(shape, dt))
+            kept.sort(key=lambda e: e[0])
+            cat = (lambda k, shape, dt: torch.cat([d[k] for _, d in kept]) if kept else be.empty(shape, dt))
             d_niter = cat("niter", (0,), torch.int32)
             return (cat("t", (0,), torch.int32), cat("items", (0, cap), torch.int32), cat("coef", (0, cap), torch.float32),
                     cat("count", (0,), torch.int32), d_niter.cpu().numpy())
-        return targets, items_out, coef_out, count_out, niter_out
+        return targets, host["items"], host["coef"], host["count"], host["niter"]
+
+    def _fit_workspace(self, n_slots: int, K: int, role: str = "main", limit: int = 0):
+        """(scratch, queue, slots of the scratch layout) -- the one scratch cache of the fit.  `role` keeps the side-stream
+        launch of the heavy targets on a scratch of its own (the two kernels run concurrently).  main / heavy: a cached scratch
+        of the same problem shape with at least n_slots slots is reused as it is -- the kernel launches min(slots, targets)
+        workgroups, so extra slots are simply idle -- which keeps mini-batches of varying size (online partial_fit) from
+        re-allocating and re-initialising it every call; a new one is rounded up to a power of two, but not beyond `limit`
+        (the call's slots in flight).  The overflow refit's is sized exactly; the pilot's too, and is not kept."""
+        be, U, I = self.be, self.n_users, self.n_items
+        if role == "pilot":
+            return (*be.fit_workspace(U, I, n_slots, K), n_slots)
+        if role == "overflow":
+            key = (U, I, n_slots, K, role)
+            if key not in self._fit_ws:
+                self._fit_ws[key] = be.fit_workspace(U, I, n_slots, K)
+        else:
+            fits = [k for k in self._fit_ws if k[0] == U and k[1] == I and k[3] == K and k[2] >= n_slots and k[4] == role]
+            if fits:
+                key = min(fits, key=lambda k: k[2])
+            else:
+                want = 1 << max(0, int(n_slots - 1).bit_length())          # next power of two
+                key = (U, I, int(min(max(want, n_slots), max(limit, n_slots))), K, role)
+                if len(self._fit_ws) >= 4:
+                    self._fit_ws.clear()
+                self._fit_ws[key] = be.fit_workspace(U, I, key[2], K)
+        ws, queue = self._fit_ws[key]
+        return ws, queue, key[2]
+
+    def _launch_fit(self, tg: np.ndarray, cfg, cap: int, n_slots: int, role: str, knobs: FitKnobs, limit: int = 0,
+                    trace: bool = False, gram=None, fast: int = 0, one_pass_xty: bool = False) -> Dict[str, Any]:
+        """The only caller of be.fit_columns: allocates the output block of targets `tg`, fetches the scratch of `role`
+        and launches on the current stream.  A new kernel option is an argument here and nowhere else.  Returns the device block."""
+        be, torch = self.be, self.be.torch
+        m = len(tg)
+        ws, queue, ws_slots = self._fit_workspace(n_slots, int(cfg.top_features), role, limit)
+        d = dict(t=be.to_dev(tg.astype(np.int32)), items=be.empty((m, cap), torch.int32),
+                 coef=be.empty((m, cap), torch.float32), count=be.empty((m,), torch.int32),
+                 niter=be.empty((m,), torch.int32), trace=be.zeros((m, 8), torch.int64) if trace else None,
+                 ws=(ws, queue))   # keeps the scratch alive while the kernel runs
+        # how the HIP kernels are to go about it; the tests' CPU stand-in solves target by target and takes none of these
+        opts = dict(fast=fast, one_pass_xty=one_pass_xty, knobs=knobs) if getattr(be, "fit_launch_options", False) else {}
+        be.fit_columns(self.n_users, self.n_items, self._X, d["t"], cfg, d["items"], d["coef"], d["count"], d["niter"], cap, ws, queue,
+                       ws_slots, d["trace"], gram, **opts)
+        return d
+
+    @staticmethod
+    def _collect_fit(ln, d: Dict[str, Any], host, kept, trace_out) -> None:
+        if trace_out is not None:
+            trace_out[ln.lo:ln.hi] = d["trace"].cpu().numpy()
+        if host is None:
+            kept.append((ln.lo, d))
+            return
+        for k in ("items", "coef", "count", "niter"):
+            host[k][ln.lo:ln.hi] = d[k].cpu().numpy()
 
     SGD_EPOCH_BLOCK_BYTES = 2 << 30   # time-sorted copies of X held at once by fit_columns_sgd (8 B per stored entry and epoch)
 
@@ -540,127 +497,51 @@ class SlimEngine:
 
     SGD_MAX_FEATURES = 256           # csrc/fit_sgd.hip: kSgdMaxFeatures
 
-    FIT_SLOTS_SPARSE = 1024          # targets in flight when the folded columns are sparse (see _fit_slots_for)
-    FIT_SPARSE_FEATURES = 0.08       # mean density of the selected feature columns up to which FIT_SLOTS_SPARSE are used (c3s: 0.058)
-    FIT_DENSE_FEATURES = 0.25        # ... and from which the full MAX_SLOTS are (C3: 0.39; C2: 0.13 -> 2048, flat there)
+    GRAM_PILOT_TARGETS = fit_plan.GRAM_PILOT_TARGETS
+    GRAM_PILOT_MIN_NNZ = fit_plan.GRAM_PILOT_MIN_NNZ      # (an attribute so that a test can reach the pilot on a small matrix)
 
-    def _fit_slots_for(self, targets: np.ndarray, cfg, cap: int, K: int) -> int:
-        """Targets in flight (work-queue slots) of a bulk fit with feature selection.  Every target owns a residual of U floats
-        and its waves gather from it at the rows of the columns they fold.  Where those columns are DENSE (popularity-only
-        data: the features of every target are the ~100 most popular items, 30-70 % of all users each) a fold streams its
-        residual nearly sequentially, the kernel is bound by the dependent-add chains and the fabric's streaming rate, and more
-        targets in flight are better up to 4 per SIMD (C3: 4096 slots 2.05 s, 2048 2.3 s, 1024 3.6 s).  Where they are SPARSE
-        (item clusters: ~8k-entry columns, 6 % of the users) every gather is a 64-byte sector of its own, the memory system
-        serves a fixed number of such sectors per second whatever the number of waves asking (Little's law: a wave's step
-        took ~100 us with 4096 waves in flight), and what helps is residuals that stay in L2 + Infinity Cache: c3s 4096 slots
-        1.43-1.52 s, 2048 1.30 s, 1024 0.91 s, 768 0.97-1.03 s, 512 1.03 s (tools/fit_sweep.py, profiles/r04_fit_sweep_*.jsonl;
-        W bits and sweep counts identical for every slot count -- the slots only decide who runs when).  The density comes
-        from the Gram pilot's feature selection (_gram_items); in between the count is interpolated (C2, 0.13: flat)."""
-        if K <= 0 or len(targets) <= FIT_MW_MAX_TARGETS:
-            return MAX_SLOTS
+    def _pilot_feature_density(self, targets: np.ndarray, cfg, knobs: FitKnobs) -> Optional[float]:
+        """Mean density of the feature columns the Gram pilot selected (fit_plan.fit_slots_for_density); None: no pilot."""
         if "pilot_feature_density" not in self._X:
-            self._gram_items(targets, cfg, cap)            # runs the pilot when the call is large enough for one
-        d = self._X.get("pilot_feature_density")
-        if d is None:
-            return MAX_SLOTS
-        f = min(1.0, max(0.0, (d - self.FIT_SPARSE_FEATURES) / (self.FIT_DENSE_FEATURES - self.FIT_SPARSE_FEATURES)))
-        lo = self.FIT_SLOTS_SPARSE
-        return int(-(-(lo + f * (MAX_SLOTS - lo)) // 256) * 256) if f < 1.0 else MAX_SLOTS
+            self._gram_items(targets, cfg, knobs)            # runs the pilot when the call is large enough for one
+        return self._X.get("pilot_feature_density")
 
-    GRAM_ITEMS_MAX = 4096       # rtrec_slim_gram_matrix's limit
-    GRAM_PILOT_TARGETS = 64
-    GRAM_PILOT_MIN_NNZ = 8_000_000      # smaller fits take a fraction of a second: the pilot (and a larger G) would not pay
-
-    def _gram_items(self, targets: np.ndarray, cfg, cap: int) -> int:
-        """How many of the most popular item columns the shared Gram matrix covers (RTREC_AMD_GRAM_ITEMS=<n> fixes it).
-        Gram tracking (exact mode) decides a zero coordinate without touching memory only while every UPDATED feature of the
-        target has a row in G, and the Gram-form coordinate descent (tolerance mode) needs ALL of a target's features there.
-        Which items are features depends on the co-occurrence structure, not on the popularity law: on popularity-only data
-        the features of every target are the ~100 most popular items, with item clusters they are each cluster's own
-        popular items and reach down to popularity rank ~5,000 (ML-20M shape, 80 clusters: top-512 holds 23 % of the
-        selected features, top-4096 97 % and every feature that ends up with a non-zero weight).  So the size is read off a
-        PILOT: the feature selection (one sweep) of 64 of the call's targets from the middle of the length-sorted
-        list -- the 90th percentile of the deepest popularity rank a target selects, rounded up to a power of two in
-        [512, 4096].  A matrix with few non-empty columns (a mini-batch's partial matrix, slim.py:33-36) gets them all.
-        The answer is cached with X."""
-        be, X = self.be, self._X
-        env = settings.raw("RTREC_AMD_GRAM_ITEMS", "auto")
-        if env != "auto":
-            return min(self.n_items, int(env))
-        if "gram_auto" in X:
-            return X["gram_auto"]
-        col_nnz = X["col_nnz"]
-        nonempty = int(np.count_nonzero(col_nnz))
-        n_top = GRAM_ITEMS
-        if nonempty <= 1024:
-            n_top = max(64, min(self.n_items, nonempty))
-        elif (len(targets) > FIT_MW_MAX_TARGETS and isinstance(be, HipBackend) and int(cfg.top_features) > 0
-              and int(col_nnz.sum()) >= self.GRAM_PILOT_MIN_NNZ):
-            torch = be.torch
-            live = targets[col_nnz[targets] > 0]
-            # (not the head of the length-sorted list: a popular target's X^T y walks 100k user rows, and what it selects is no
-            # different -- the pilot costs a few ms this way instead of ~100)
-            pick = (live[np.linspace(0.05 * (len(live) - 1), 0.6 * (len(live) - 1), min(self.GRAM_PILOT_TARGETS, len(live))).astype(np.int64)]
-                    if len(live) else live)
-            if len(pick):
-                m = len(pick)
-                pcfg = _native.FitCfg(cfg.l1_reg, cfg.l2_reg, cfg.tol, 1, cfg.seed, cfg.positive, cfg.top_features)
-                key = (self.n_users, self.n_items, m, int(cfg.top_features), "pilot")
-                if key not in self._fit_ws:
-                    self._fit_ws[key] = be.fit_workspace(self.n_users, self.n_items, m, int(cfg.top_features))
-                ws, queue = self._fit_ws[key]
-                items = be.empty((m, cap), torch.int32)
-                coef = be.empty((m, cap), torch.float32)
-                count, niter = be.empty((m,), torch.int32), be.empty((m,), torch.int32)
-                be.fit_columns(self.n_users, self.n_items, X, be.to_dev(pick.astype(np.int32)), pcfg, items, coef, count, niter, cap,
-                               ws, queue, m, None, None, fast=0, one_pass_xty=False)
-                rank = np.empty(self.n_items, dtype=np.int64)
-                rank[np.argsort(-col_nnz, kind="stable")] = np.arange(self.n_items)
-                it, cn = items.cpu().numpy(), count.cpu().numpy()
-                deepest = np.array([rank[it[k, :cn[k]]].max() if cn[k] else 0 for k in range(m)])
-                need = int(np.percentile(deepest, 90)) + 1
-                sel = np.concatenate([it[k, :cn[k]] for k in range(m)]) if cn.sum() else np.empty(0, np.int64)
-                if len(sel):          # how dense the columns a target folds are (_fit_slots_for)
-                    X["pilot_feature_density"] = float(col_nnz[sel].mean()) / max(self.n_users, 1)
-                n_top = GRAM_ITEMS if need <= GRAM_ITEMS else min(self.GRAM_ITEMS_MAX, 1 << int(need - 1).bit_length())
-                self._fit_ws.pop(key, None)
-        X["gram_auto"] = min(self.n_items, n_top)
+    def _gram_items(self, targets: np.ndarray, cfg, knobs: FitKnobs) -> int:
+        """How many of the most popular item columns the shared Gram matrix covers (RTREC_AMD_GRAM_ITEMS=<n> fixes it):
+        fit_plan.gram_items, from a pilot where fit_plan.gram_pilot_pays.  The answer is cached with X."""
+        X = self._X
+        if knobs.gram_items is not None:
+            return min(self.n_items, knobs.gram_items)
+        if "gram_auto" not in X:
+            col_nnz = X["col_nnz"]
+            nonempty = int(np.count_nonzero(col_nnz))
+            pilot = fit_plan.gram_pilot_pays(len(targets), isinstance(self.be, HipBackend), int(cfg.top_features), nonempty,
+                                             int(col_nnz.sum()), self.GRAM_PILOT_MIN_NNZ)
+            X["gram_auto"] = fit_plan.gram_items(self.n_items, nonempty, self._gram_pilot(targets, cfg, knobs) if pilot else None)
         return X["gram_auto"]
 
-    def _one_pass_xty_pays(self, targets: np.ndarray) -> bool:
-        """The one-pass X^T y of a small call (csrc/fit.hip, xty_batch_kernel) replaces one walk per target by one pass
-        over X plus fixed costs (row compaction, per-column scans of the target sums, the latency chain of the longest
-        column).  Targets with >= 1024 users walk all of X each (kColWalkMinRows), so it pays when that traffic is
-        large (targets x entries of the matrix being fitted): measured between C2 (175 such targets x 1.1 M entries: 16 -> 23 ms with
-        it) and C3 (450 x 5.0 M: 58 -> 44 ms)."""
-        if settings.raw("RTREC_AMD_XTY_BATCH") == "force":      # parity tests: small matrices through this path
-            return True
-        col_nnz = self._X["col_nnz"]
-        big = int(np.count_nonzero(col_nnz[targets] >= 1024))
-        walks = big * float(col_nnz.sum())
-        # ... and its own fixed cost is one scan of the target sums per item column: a wide catalogue (C4: 500k columns,
-        # 879 -> 957 ms with it) pays more for that than the walks cost
-        scans = float(self.n_items) * -(-len(targets) // 64)
-        if settings.raw("RTREC_AMD_DEBUG_XTY"):
-            print(f"[xty] targets={len(targets)} big={big} nnz={int(col_nnz.sum())} walks={walks:.3g} scans={scans:.3g}", flush=True)
-        if walks < 2000.0 * scans:
-            return False
-        return walks >= XTY_MIN_WALK_ENTRIES
-
-    def _fit_overflow(self, targets: np.ndarray, cfg, U: int, I: int, slots: int):
-        """K = None targets whose solution did not fit the output block: fit them again with cap = I."""
-        be, X, torch = self.be, self._X, self.be.torch
-        m = len(targets)
-        n_slots = max(1, min(slots, m))
-        key = (U, I, n_slots, 0, "overflow")
-        if key not in self._fit_ws:
-            self._fit_ws[key] = be.fit_workspace(U, I, n_slots, 0)
-        ws, queue = self._fit_ws[key]
-        d_t = be.to_dev(targets.astype(np.int32))
-        items, coef = be.empty((m, I), torch.int32), be.empty((m, I), torch.float32)
-        count, niter = be.empty((m,), torch.int32), be.empty((m,), torch.int32)
-        be.fit_columns(U, I, X, d_t, cfg, items, coef, count, niter, I, ws, queue, n_slots, None, None)
-        return items.cpu().numpy(), coef.cpu().numpy(), count.cpu().numpy(), niter.cpu().numpy()
+    def _gram_pilot(self, targets: np.ndarray, cfg, knobs: FitKnobs) -> Optional[int]:
+        """The feature selection (one sweep) of 64 of the call's targets from the middle of the length-sorted list.  Returns
+        the 90th percentile of the deepest popularity rank a target selects, plus one (None: no target has an entry), and
+        leaves the mean density of the selected columns in X["pilot_feature_density"]."""
+        X, col_nnz = self._X, self._X["col_nnz"]
+        live = targets[col_nnz[targets] > 0]
+        if not len(live):
+            return None
+        # (not the head of the length-sorted list: a popular target's X^T y walks 100k user rows, and what it selects is no
+        # different -- the pilot costs a few ms this way instead of ~100)
+        pick = live[np.linspace(0.05 * (len(live) - 1), 0.6 * (len(live) - 1), min(self.GRAM_PILOT_TARGETS, len(live))).astype(np.int64)]
+        m = len(pick)
+        pcfg = _native.FitCfg(cfg.l1_reg, cfg.l2_reg, cfg.tol, 1, cfg.seed, cfg.positive, cfg.top_features)
+        d = self._launch_fit(pick, pcfg, min(int(cfg.top_features), self.n_items), m, "pilot", knobs)
+        rank = np.empty(self.n_items, dtype=np.int64)
+        rank[np.argsort(-col_nnz, kind="stable")] = np.arange(self.n_items)
+        it, cn = d["items"].cpu().numpy(), d["count"].cpu().numpy()
+        deepest = np.array([rank[it[k, :cn[k]]].max() if cn[k] else 0 for k in range(m)])
+        sel = np.concatenate([it[k, :cn[k]] for k in range(m)]) if cn.sum() else np.empty(0, np.int64)
+        if len(sel):          # how dense the columns a target folds are (fit_plan.fit_slots_for_density)
+            X["pilot_feature_density"] = float(col_nnz[sel].mean()) / max(self.n_users, 1)
+        return int(np.percentile(deepest, 90)) + 1
 
     # ------------------------------------------------------------------------------ W
     def upload_weights(self, W_csc: sp.csc_matrix, acc_f64: Optional[bool] = None) -> DeviceWeights:

@@ -1166,3 +1166,226 @@ def test_score_plan_invariants_over_the_cross_product():
         if mode != D:
             assert "fill" not in calls, ctx
     assert n > 100_000
+
+
+# ---- the fit's decision as pure functions (rtrec_amd/fit_plan.py): explicit table + invariants over a cross product ----
+# "parent" in the comments below: rtrec_amd/engine.py and backend.py at the commit tests/golden/fit_calls.json names, where
+# these formulas stood inside SlimEngine.fit_columns (engine.py:275-454), its helpers (:547-663) and HipBackend.fit_columns
+# (backend.py:140-162).
+def _no_pilot():
+    raise AssertionError("the pilot must not be asked here")
+
+
+def _fit_facts(n, U=4000, I=2600, K=20, col_nnz=None, **kw):
+    from rtrec_amd.fit_plan import FitFacts
+    col_nnz = np.full(n, 300, dtype=np.int64) if col_nnz is None else np.asarray(col_nnz, dtype=np.int64)
+    assert len(col_nnz) == n and (np.diff(col_nnz) <= 0).all()
+    base = dict(n_users=U, n_items=I, n_targets=n, col_nnz=col_nnz, nnz=int(col_nnz.sum()), K=K, mode="exact", n_slots=None,
+                device_out=False, nonneg=True, hip=True, supports_gram=True, distinct_targets=True, pilot_density=lambda: None)
+    base.update(kw)
+    return FitFacts(**base)
+
+
+def _launches(plan):
+    return [(ln.lo, ln.hi, ln.n_slots, ln.role, ln.one_pass_xty) for ln in plan.launches]
+
+
+def test_fit_plan_explicit_table():
+    """One row per branch of plan_fit.  Rows that coincide with a case of tests/test_gpu_fit_plan.py take their expected
+    values from the golden log of the parent commit; the rest are worked out by hand from the parent's formulas."""
+    from rtrec_amd.fit_plan import FitKnobs, plan_fit
+    from tests import fit_call_log as fcl
+    with open(os.path.join(os.path.dirname(__file__), "golden", "fit_calls.json")) as f:
+        golden = json.load(f)["cases"]
+
+    def golden_row(name, plan):
+        g, fits = golden[name]["last_fit_stats"], [c for c in golden[name]["calls"] if c["op"] == "fit_columns" and c["max_iter"] > 1]
+        assert (plan.slots, plan.cap, plan.n_heavy) == (g["slots"], g["cap"], g["n_heavy"]), name
+        first = [ln for ln in plan.launches]
+        assert [ln.hi - ln.lo for ln in first] == [c["n_targets"] for c in fits[:len(first)]], name
+        assert [ln.role == "main" for ln in first] == [c["default_stream"] for c in fits[:len(first)]], name
+        assert [plan.fast] * len(first) == [c["fast"] for c in fits[:len(first)]], name
+        assert [plan.use_gram] * len(first) == [c["gram"] for c in fits[:len(first)]], name
+        # (whether a launch that asks for the one-pass X^T y gets it is the backend's scratch-size test: far below its limit here)
+        assert [ln.one_pass_xty for ln in first] == [c["xty_ws"] for c in fits[:len(first)]], name
+
+    # the bulk matrix of the GPU cases: 163,978 entries, 87 columns with >= 256 users, 500 with >= 64
+    Xc = fcl.matrix(fcl.BULK)[0]
+    bulk_nnz = -np.sort(-np.diff(Xc.indptr).astype(np.int64), kind="stable")
+    bulk = dict(n=2600, col_nnz=bulk_nnz)
+    p = plan_fit(_fit_facts(**bulk), FitKnobs())
+    golden_row("bulk", p)
+    # small call (n <= 4096): wants 4 x 256, minimum rows 2048 / 8, 2 x 256 heavy slots; min(1024, 2600 - 2049, 87) = 87 (parent engine.py:329-340)
+    assert (p.n_heavy, p.heavy_slots, p.use_gram) == (87, 512, True)
+    assert _launches(p) == [(0, 87, 87, "heavy", False), (87, 2600, 2513, "main", False)]
+    golden_row("bulk_shuffle", plan_fit(_fit_facts(mode="shuffle", **bulk), FitKnobs()))
+    golden_row("bulk_gram", plan_fit(_fit_facts(mode="gram", **bulk), FitKnobs()))
+    golden_row("bulk_n_slots_512", plan_fit(_fit_facts(n_slots=512, pilot_density=_no_pilot, **bulk), FitKnobs()))
+    golden_row("bulk_env_slots_768", plan_fit(_fit_facts(**bulk), FitKnobs(fit_slots=768)))
+    golden_row("bulk_heavy_min_rows_64", plan_fit(_fit_facts(**bulk), FitKnobs(heavy_min_rows=64)))
+    golden_row("bulk_heavy_off", plan_fit(_fit_facts(**bulk), FitKnobs(heavy=0)))
+    # the latency matrix: 72,209 entries, 6 columns with >= 1024 users -> 6 x 72,209 walks < 2000 x 800 x 13 scans: does not pay
+    Lc = fcl.matrix(fcl.LATENCY)[0]
+    lat_nnz = -np.sort(-np.diff(Lc.indptr).astype(np.int64), kind="stable")
+    lat = dict(n=800, U=3000, I=800, K=50, col_nnz=lat_nnz)
+    golden_row("latency", plan_fit(_fit_facts(**lat), FitKnobs()))
+    golden_row("latency_xty_force", plan_fit(_fit_facts(**lat), FitKnobs(xty_batch="force")))
+    golden_row("latency_xty_off", plan_fit(_fit_facts(**lat), FitKnobs(xty_batch="0")))
+    four = dict(n=4, U=3000, I=800, K=50, col_nnz=lat_nnz[:4], nnz=int(lat_nnz.sum()), distinct_targets=False)
+    golden_row("repeated_target_xty_force", plan_fit(_fit_facts(**four), FitKnobs(xty_batch="force")))
+    # K = None: cap = min(I, RTREC_AMD_ALLF_CAP) (parent engine.py:305); no head, no Gram, no one-pass X^T y without feature selection
+    p = plan_fit(_fit_facts(200, U=600, I=200, K=0), FitKnobs(allf_cap=8))
+    golden_row("allf_overflow", p)
+    assert (p.cap, p.fast, p.use_gram, _launches(p)) == (8, 0, False, [(0, 200, 200, "main", False)])
+    assert plan_fit(_fit_facts(200, U=600, I=200, K=0), FitKnobs()).cap == 200
+    assert plan_fit(_fit_facts(200, U=600, I=5000, K=0), FitKnobs()).cap == 2048
+    assert plan_fit(_fit_facts(200, U=600, I=10, K=20), FitKnobs()).cap == 10                       # K > I
+
+    # the scratch clamp (parent engine.py:318-320): 4 x (4e6 + 4 x 5e5) = 24 MB per slot, 16 GiB hold 715 -- but never below 1024
+    p = plan_fit(_fit_facts(100000, U=4_000_000, I=500_000, K=50), FitKnobs())
+    assert p.slots == 1024
+    # ... 16 MB per slot: 1073 slots; a budget of 64 GiB: 4294, so MAX_SLOTS; the caller's n_slots is clamped too
+    assert plan_fit(_fit_facts(100000, U=2_000_000, I=500_000, K=50), FitKnobs()).slots == 1073
+    assert plan_fit(_fit_facts(100000, U=2_000_000, I=500_000, K=50), FitKnobs(scratch_gib=64.0)).slots == 4096
+    assert plan_fit(_fit_facts(100000, U=2_000_000, I=500_000, K=50, n_slots=2000), FitKnobs()).slots == 1073
+    # bulk call (n > 4096): wants 256 targets of at least 2048 users, 256 heavy slots (parent engine.py:333-336)
+    nnz = np.r_[np.full(300, 3000), np.full(4700, 300)]
+    p = plan_fit(_fit_facts(5000, I=5000, col_nnz=nnz), FitKnobs())
+    assert (p.n_heavy, p.heavy_slots, p.slots) == (256, 256, 4096)
+    assert _launches(p) == [(0, 256, 256, "heavy", False), (256, 5000, 4096, "main", False)]
+    assert plan_fit(_fit_facts(5000, I=5000), FitKnobs()).n_heavy == 0                              # nobody has 2048 users
+    assert plan_fit(_fit_facts(5000, I=5000, col_nnz=nnz), FitKnobs(heavy_slots=64)).launches[0].n_slots == 64
+    # small call, every column long enough: n - 2049 limits the head, the rest still fills the single-wave kernel (parent engine.py:338)
+    p = plan_fit(_fit_facts(3000, I=3000), FitKnobs())
+    assert (p.n_heavy, p.heavy_slots) == (951, 512)
+    assert _launches(p) == [(0, 951, 512, "heavy", False), (951, 3000, 2049, "main", False)]
+    assert plan_fit(_fit_facts(2048, I=3000), FitKnobs()).n_heavy == 0                              # the whole call is multi-wave already
+    assert plan_fit(_fit_facts(2049, I=3000), FitKnobs()).n_heavy == 0
+    assert plan_fit(_fit_facts(2050, I=3000), FitKnobs()).n_heavy == 1
+    # shuffle: one launch, no Gram (parent engine.py:350-354); a backend that is not HIP has no side stream
+    p = plan_fit(_fit_facts(3000, I=3000, mode="shuffle"), FitKnobs())
+    assert (p.fast, p.n_heavy, p.use_gram, _launches(p)) == (1, 0, False, [(0, 3000, 3000, "main", False)])
+    assert plan_fit(_fit_facts(3000, I=3000, hip=False, supports_gram=False), FitKnobs()).n_heavy == 0
+    # Gram (parent engine.py:353-354): tracking on bulk calls of a non-negative X, or forced; Gram-form CD whatever the size and sign
+    gram = lambda n, knobs=FitKnobs(), **kw: plan_fit(_fit_facts(n, I=3000, **kw), knobs).use_gram      # noqa: E731
+    assert gram(3000) and not gram(800) and gram(800, FitKnobs(gram="force")) and not gram(3000, FitKnobs(gram="0"))
+    assert not gram(3000, nonneg=False) and gram(10, mode="gram", nonneg=False) and not gram(10, FitKnobs(gram="0"), mode="gram")
+    assert not gram(3000, K=100) and gram(3000, K=64) and not gram(3000, supports_gram=False) and not gram(3000, K=0)
+    assert plan_fit(_fit_facts(3000, I=40, K=100), FitKnobs()).use_gram                             # min(K, I) <= 64
+    # K = None, 70,000 targets: 2^30 B / (2048 x 8 B) = 65,536 targets per output block (parent engine.py:381)
+    p = plan_fit(_fit_facts(70000, U=1000, I=70000, K=0), FitKnobs())
+    assert (p.cap, p.slots, _launches(p)) == (2048, 4096, [(0, 65536, 4096, "main", False), (65536, 70000, 4096, "main", False)])
+    # refused (parent engine.py:347-348, 382-383)
+    with pytest.raises(ValueError, match="device_out needs nn_feature_selection"):
+        plan_fit(_fit_facts(10, K=0, device_out=True), FitKnobs())
+    with pytest.raises(ValueError, match="fit mode must be"):
+        plan_fit(_fit_facts(10, mode="fast"), FitKnobs())
+    assert plan_fit(_fit_facts(0), FitKnobs()).launches == ()
+    # slots from the pilot's density (parent engine.py:559-568): only a bulk call with feature selection asks, and not when
+    # the caller names the slots; RTREC_AMD_FIT_SLOTS overrides what it says but the pilot has run (the default argument of
+    # parent engine.py:313 is evaluated)
+    slots = lambda d, n=5000, **kw: plan_fit(_fit_facts(n, I=5000, pilot_density=lambda: d, **kw), FitKnobs()).slots   # noqa: E731
+    assert [slots(d) for d in (None, 0.058, 0.08, 0.13, 0.25, 0.39)] == [4096, 1024, 1024, 2048, 4096, 4096]
+    assert slots(0.058, n=3000) == 1024 and slots(0.39, n=3000) == 3000
+    assert plan_fit(_fit_facts(2048, pilot_density=_no_pilot), FitKnobs()).slots == 2048
+    assert plan_fit(_fit_facts(5000, I=5000, K=0, pilot_density=_no_pilot), FitKnobs()).slots == 4096
+    asked = []
+    assert plan_fit(_fit_facts(5000, I=5000, pilot_density=lambda: asked.append(1)), FitKnobs(fit_slots=768)).slots == 768 and asked
+    # the one-pass X^T y of a small call (parent engine.py:404, 630-648; backend.py:147-148).  C3: 450 targets of >= 1024 users
+    # x 5.0 M entries = 2.25e9 walks >= 1e9 and >= 2000 x (3000 x 8 scans); C4's 500k columns: 2000 x 4e6 scans are more
+    big = dict(col_nnz=np.full(450, 2000), nnz=5_000_000, U=100000)
+    xty = lambda knobs=FitKnobs(), **kw: [ln.one_pass_xty for ln in plan_fit(_fit_facts(450, **{**big, **kw}), knobs).launches]   # noqa: E731
+    assert xty(I=3000) == [True] and xty(I=500_000) == [False] and xty(I=3000, nnz=2_000_000) == [False]
+    assert xty(I=3000, distinct_targets=False) == [False] and xty(I=3000, mode="shuffle") == [False] and xty(I=3000, K=0) == [False]
+    assert xty(FitKnobs(kernel=1), I=3000) == [False] and xty(FitKnobs(kernel=2), I=3000) == [True]
+    assert xty(FitKnobs(xty_batch="0"), I=3000) == [False] and xty(I=3000, mode="gram") == [True]
+    assert xty(FitKnobs(xty_batch="force"), I=3000, nnz=0, col_nnz=np.zeros(450)) == [False]        # an empty matrix
+    assert xty(I=3000, col_nnz=np.full(450, 1023)) == [False]                                       # nobody walks all of X
+
+
+def test_fit_plan_invariants_over_the_cross_product():
+    import itertools
+    from rtrec_amd.fit_plan import FIT_MW_MAX_TARGETS, FitKnobs, plan_fit
+    assert FIT_MW_MAX_TARGETS == 2048
+    rng = np.random.default_rng(3)
+    seen = 0
+    for n, K, mode, distinct, hip, kernel, xb, n_slots, density in itertools.product(
+            (0, 1, 800, 2048, 2049, 3000, 4097, 70000), (0, 8, 100), ("exact", "shuffle", "gram"), (True, False), (True, False),
+            (0, 1, 2), ("1", "0", "force"), (None, 512), (None, 0.1)):
+        col_nnz = -np.sort(-rng.integers(0, 3000, n))
+        f = _fit_facts(n, U=5000, I=max(n, 100), K=K, col_nnz=col_nnz, mode=mode, distinct_targets=distinct, hip=hip, n_slots=n_slots,
+                       pilot_density=lambda: density)
+        p = plan_fit(f, FitKnobs(kernel=kernel, xty_batch=xb))
+        seen += 1
+        # the launches are disjoint and cover [0, n) in order; the head is first and the only one of its role
+        pos = 0
+        for i, ln in enumerate(p.launches):
+            assert ln.lo == pos and ln.hi > ln.lo
+            pos = ln.hi
+            assert (ln.role == "heavy") == (i == 0 and p.n_heavy > 0)
+            assert 1 <= ln.n_slots <= ln.hi - ln.lo
+            if ln.role == "main":
+                assert ln.n_slots <= p.slots
+            if ln.role == "heavy" or not distinct or p.fast == 1 or kernel == 1 or K <= 0 or ln.hi - ln.lo > FIT_MW_MAX_TARGETS:
+                assert not ln.one_pass_xty
+        assert pos == n
+        assert p.launches[0].hi == p.n_heavy if p.n_heavy else True
+        if p.fast == 1 or K <= 0 or n <= FIT_MW_MAX_TARGETS or not hip:
+            assert p.n_heavy == 0
+        assert 0 <= p.n_heavy <= max(0, n - FIT_MW_MAX_TARGETS - 1)
+        assert p.fast == (0 if K <= 0 else {"exact": 0, "shuffle": 1, "gram": 2}[mode])
+        assert p.cap == (min(K, f.n_items) if K > 0 else min(f.n_items, 2048)) and p.slots >= 1
+        if n_slots:
+            assert p.slots == n_slots
+    assert seen == 8 * 3 * 3 * 2 * 2 * 3 * 3 * 2 * 2
+
+
+def test_fit_plan_gram_items_and_pilot():
+    """fit_plan.gram_items (parent engine.py:593-596, 621-627: deepest rank -> a power of two in [512, 4096], never more than
+    the catalogue; few non-empty columns -> all of them, at least 64) and gram_pilot_pays (parent engine.py:595-598)."""
+    from rtrec_amd.fit_plan import gram_items, gram_pilot_pays
+    assert gram_items(5000, 300, None) == 300 and gram_items(5000, 30, None) == 64 and gram_items(40, 30, None) == 40
+    assert gram_items(5000, 1024, 4000) == 1024                # the pilot's answer does not matter there
+    assert [gram_items(50000, 20000, d) for d in (None, 1, 512, 513, 1024, 1025, 4096, 5000, 40000)] == [
+        512, 512, 512, 1024, 1024, 2048, 4096, 4096, 4096]
+    assert gram_items(1500, 1100, 2000) == 1500 and gram_items(1500, 1100, None) == 512
+    pays = dict(n_targets=2049, hip=True, K=20, nonempty=1025, nnz=8_000_000)
+    assert gram_pilot_pays(**pays)
+    for k, v in dict(n_targets=2048, hip=False, K=0, nonempty=1024, nnz=7_999_999).items():
+        assert not gram_pilot_pays(**{**pays, k: v}), k
+    assert gram_pilot_pays(**{**pays, "nnz": 5}, min_nnz=0)
+
+
+def test_fit_knobs_read_every_switch(monkeypatch):
+    """FitKnobs.from_settings is the only reader of the fit's switches: each one round-trips, and no other module of the
+    package asks settings for one."""
+    import glob
+    import re
+    from dataclasses import asdict
+    from rtrec_amd.fit_plan import FitKnobs
+    from tests.fit_call_log import FIT_ENV
+    for k in FIT_ENV:
+        monkeypatch.delenv(k, raising=False)
+    assert FitKnobs.from_settings() == FitKnobs()
+    rows = [("RTREC_AMD_FIT_SLOTS", "768", "fit_slots", 768), ("RTREC_AMD_FIT_SCRATCH_GIB", "2.5", "scratch_gib", 2.5),
+            ("RTREC_AMD_FIT_HEAVY", "0", "heavy", 0), ("RTREC_AMD_FIT_HEAVY_SLOTS", "96", "heavy_slots", 96),
+            ("RTREC_AMD_FIT_HEAVY_MIN_ROWS", "64", "heavy_min_rows", 64), ("RTREC_AMD_ALLF_CAP", "8", "allf_cap", 8),
+            ("RTREC_AMD_GRAM", "force", "gram", "force"), ("RTREC_AMD_GRAM", "0", "gram", "0"),
+            ("RTREC_AMD_GRAM_ITEMS", "2048", "gram_items", 2048), ("RTREC_AMD_GRAM_ITEMS", "auto", "gram_items", None),
+            ("RTREC_AMD_XTY_BATCH", "force", "xty_batch", "force"), ("RTREC_AMD_XTY_BATCH", "0", "xty_batch", "0"),
+            ("RTREC_AMD_FIT_MODE", "sw", "kernel", 1), ("RTREC_AMD_FIT_MODE", "mw", "kernel", 2),
+            ("RTREC_AMD_COLWALK_MIN", "1", "colwalk_min_rows", 1), ("RTREC_AMD_SCREEN_MIN", "1", "screen_min", 1),
+            ("RTREC_AMD_LANE_MAX", "0", "lane_max", -1), ("RTREC_AMD_LANE_MAX", "128", "lane_max", 128),
+            ("RTREC_AMD_FOLD", "chain", "fold", 1), ("RTREC_AMD_FOLD", "spec-all", "fold", 2), ("RTREC_AMD_FOLD", "spec", "fold", 3),
+            ("RTREC_AMD_DEBUG_XTY", "1", "debug_xty", True)]
+    assert {r[0] for r in rows} == set(FIT_ENV) and {r[2] for r in rows} == set(asdict(FitKnobs()))
+    for name, value, field, want in rows:
+        with monkeypatch.context() as mp:
+            mp.setenv(name, value)
+            got = FitKnobs.from_settings()
+            assert getattr(got, field) == want, name
+            assert {k: v for k, v in asdict(got).items() if k != field} == {k: v for k, v in asdict(FitKnobs()).items() if k != field}
+    root = os.path.join(os.path.dirname(os.path.dirname(__file__)), "rtrec_amd")
+    for path in glob.glob(os.path.join(root, "**", "*.py"), recursive=True):
+        if not path.endswith("fit_plan.py"):
+            assert not set(re.findall(r'settings\.raw\("(RTREC_AMD_[A-Z0-9_]+)"', open(path).read())) & set(FIT_ENV), path
