@@ -432,7 +432,14 @@ int rtrec_slim_score_rows(int32_t n_rows, const int32_t *d_row_ids,
 
 /* Merge `n_lists` per-shard top-k lists per row (layout [n_lists][n_rows][top_k], as produced
  * by an all-gather of rtrec_slim_score_topk outputs) into one top-k per row, using the same
- * (score, aux, id) order.  d_in_scores64 may be NULL (then float32 scores are compared). */
+ * (score, aux, id) order.  d_in_scores64 may be NULL (then float32 scores are compared).
+ * Only the first d_in_count[l * n_rows + row] entries of a list are read.  Order: score descending, then aux descending
+ * as UNSIGNED 32-bit, then id descending; with d_in_scores64 the doubles are compared and the returned score is their
+ * float32 rounding.  Outputs beyond d_out_count[row] = min(valid entries, top_k) are id -1 / score -inf.
+ * n_lists * top_k <= 1024 (RTREC_ERR_UNSUPPORTED beyond).
+ * PRECONDITION: the ids of one row are distinct across its lists (column shards and tiles own disjoint columns) and no
+ * score is NaN.  Two candidates of a row with an identical (score, aux, id) triple are outside the contract: they would
+ * share a rank, and the output is then unspecified. */
 int rtrec_slim_merge_topk(int32_t n_rows, int32_t n_lists, int32_t top_k,
                           const int32_t *d_in_ids, const float *d_in_scores, const double *d_in_scores64,
                           const uint32_t *d_in_aux, const int32_t *d_in_count,

@@ -59,6 +59,29 @@ def shard_bounds(n_items: int, world_size: int, rank: int) -> Tuple[int, int]:
     return lo, hi
 
 
+def exchange_record_layout(k: int, f64: bool) -> Dict[str, int]:
+    """The two per-user records of a column-sharded scoring call (_score_column_sharded), as offsets and widths in int32 words;
+    a record is padded to an even number of them, so that consecutive records keep a leading float64 block 8-byte aligned:
+    exchanged: [2k words of float64 scores]? | k scores | k ids | k aux | count | pad  (o_sc, o_ids, o_aux, o_cnt, width);
+    final:     k scores | k ids | count | pad                                          (f_ids, f_cnt, fwidth)."""
+    o_sc = 2 * k if f64 else 0
+    o_ids, o_aux, o_cnt = o_sc + k, o_sc + 2 * k, o_sc + 3 * k
+    f_ids, f_cnt = k, 2 * k
+    width, fwidth = (n + 1 + ((n + 1) & 1) for n in (o_cnt, f_cnt))
+    return {"o_sc": o_sc, "o_ids": o_ids, "o_aux": o_aux, "o_cnt": o_cnt, "width": width,
+            "f_ids": f_ids, "f_cnt": f_cnt, "fwidth": fwidth}
+
+
+def exchange_record_views(torch, recv, G: int, q: int, k: int, f64: bool):
+    """The five arguments of `merge_topk` as views of a received [G * q, width] int32 record buffer (exchange_record_layout),
+    [source shard, row, entry] each: (ids, float32 scores, float64 scores or None, aux, counts)."""
+    L = exchange_record_layout(k, f64)
+    g3 = recv.view(G, q, L["width"])
+    g_sc64 = recv.view(torch.float64).view(G, q, L["width"] // 2)[:, :, :k] if f64 else None
+    return (g3[:, :, L["o_ids"]:L["o_aux"]], g3[:, :, L["o_sc"]:L["o_ids"]].view(torch.float32), g_sc64,
+            g3[:, :, L["o_aux"]:L["o_cnt"]], g3[:, :, L["o_cnt"]])
+
+
 def spread_giant_rows(torch, order, lens, max_giants: int, giant_len: int):
     """The pattern-grouped work order with its giant rows spread out (SlimEngine._row_order).  A wave of the feature-row kernel
     takes CONSECUTIVE positions of that order (2, 4 or 8) and sets its users up one after the other; the few giant rows (tens of
@@ -1194,12 +1217,8 @@ class SlimEngine:
         per = max(1, int(self.gather_chunk_rows))
         n_chunks = max(1, min(MAX_GATHER_CHUNKS, (n_rows + per // 2) // per))
         per = -(-n_rows // n_chunks)
-        # The two record layouts (offsets and widths in int32 words; a record is padded to an even number of them):
-        # exchanged: [2k float64 scores]? | k scores | k ids | k aux | count | pad;  final: k scores | k ids | count | pad
-        o_sc = 2 * k if f64 else 0
-        o_ids, o_aux, o_cnt = o_sc + k, o_sc + 2 * k, o_sc + 3 * k
-        f_ids, f_cnt = k, 2 * k
-        width, fwidth = (n + 1 + ((n + 1) & 1) for n in (o_cnt, f_cnt))
+        lay = exchange_record_layout(k, f64)
+        f_ids, f_cnt, width, fwidth = lay["f_ids"], lay["f_cnt"], lay["width"], lay["fwidth"]
 
         def record(m: int, n_words: int, parts):
             """The column blocks `parts` side by side as [m, n_words] int32 records (a zero pad word where the layout has one)."""
@@ -1230,13 +1249,11 @@ class SlimEngine:
         finals = []
         for a, b, q, recv, packed, work in pending:
             work.wait()
-            g3 = recv.view(G, q, width)         # [source shard, row of my slice, record]
-            g_sc64 = recv.view(torch.float64).view(G, q, width // 2)[:, :, :k] if f64 else None
+            g_ids, g_sc, g_sc64, g_aux, g_cnt = exchange_record_views(torch, recv, G, q, k, f64)   # [source shard, row of my slice, entry]
             s_ids = be.empty((q, k), torch.int32)
             s_sc = be.empty((q, k), torch.float32)
             s_cnt = be.empty((q,), torch.int32)
-            be.merge_topk(q, G, k, g3[:, :, o_ids:o_aux], g3[:, :, o_sc:o_ids].view(torch.float32), g_sc64, g3[:, :, o_aux:o_cnt],
-                          g3[:, :, o_cnt], s_ids, s_sc, s_cnt)
+            be.merge_topk(q, G, k, g_ids, g_sc, g_sc64, g_aux, g_cnt, s_ids, s_sc, s_cnt)
             fin = record(q, fwidth, [s_sc.view(torch.int32), s_ids, s_cnt.view(q, 1)])
             out = be.empty((G * q, fwidth), torch.int32)
             work2 = dist.all_gather_into_tensor(out, fin, group=self.group, async_op=True)

@@ -151,14 +151,16 @@ class OracleBackend:
 
     def merge_topk(self, n_rows, n_lists, top_k, g_ids, g_sc, g_sc64, g_aux, g_cnt, o_ids, o_sc, o_cnt):
         gi, gs, ga, gc = g_ids.numpy(), g_sc.numpy(), g_aux.numpy().view(np.uint32), g_cnt.numpy()
+        if g_sc64 is not None:      # include/rtrec_amd.h: the doubles are compared, the returned score is their float32 rounding
+            gs = g_sc64.numpy()
         for r in range(n_rows):
             cand = [(gs[l, r, k], ga[l, r, k], gi[l, r, k]) for l in range(n_lists) for k in range(gc[l, r])]
             cand.sort(key=lambda c: (-c[0], -int(c[1]), -int(c[2])))
             cand = cand[:top_k]
             o_cnt[r] = len(cand)
-            for k in range(top_k):
-                o_ids[r, k] = int(cand[k][2]) if k < len(cand) else -1
-                o_sc[r, k] = float(cand[k][0]) if k < len(cand) else float("-inf")
+            pad = top_k - len(cand)
+            o_ids[r] = torch.tensor([int(c[2]) for c in cand] + [-1] * pad, dtype=torch.int32)
+            o_sc[r] = torch.tensor([float(c[0]) for c in cand] + [float("-inf")] * pad, dtype=torch.float64).to(torch.float32)
 
     def similar_topk(self, queries, W, top_k, ids, sc, cnt):
         n_items = W["cptr"].shape[0] - 1

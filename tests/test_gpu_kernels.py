@@ -311,6 +311,89 @@ def test_similar_items(engine, oracle):
         assert np.array_equal(bits(sc[j, :cnt[j]]), bits(ov))
 
 
+SIMILAR_LENGTHS = (2, 63, 64, 65, 127, 128, 129, 1000)       # around one and two trips of the kernel's 64-stride column scan
+SIMILAR_LEVELS = np.array([2.5, 1.0, 0.5, 0.0, -0.0, -1.25, -3.0], dtype=np.float32)
+_similar_w_cache = []
+
+
+def similar_w():
+    """A synthetic W (CSC, I = 1200, not fitted; stored zeros kept): columns of SIMILAR_LENGTHS entries with the self entry
+    first / in the middle / last / absent, a column of length 0, one holding the self entry alone and one holding one other
+    entry; values from seven levels (negatives, a stored +0.0 and -0.0), the maximum on about a third of the entries, so that equal
+    values sit in different lanes and in different trips of the scan.  Returns (W, the columns built)."""
+    if _similar_w_cache:
+        return _similar_w_cache[0]
+    rng = np.random.default_rng(77)
+    I = 1200
+    cols = {}
+    plan = [(n, where) for n in SIMILAR_LENGTHS for where in ("first", "middle", "last", "absent")]
+    plan += [(0, "absent"), (1, "first"), (1, "absent")]
+    for n, where in plan:
+        while True:
+            rows = np.sort(rng.choice(I, n, replace=False))
+            if where == "absent":
+                free = np.setdiff1d(np.arange(I), np.concatenate([rows, np.fromiter(cols, dtype=np.int64, count=len(cols))]))
+                j = int(rng.choice(free))
+            else:
+                j = int(rows[{"first": 0, "middle": n // 2, "last": n - 1}[where]])
+            if j not in cols:
+                break
+        vals = rng.choice(SIMILAR_LEVELS, n, p=[0.34, 0.11, 0.11, 0.11, 0.11, 0.11, 0.11]).astype(np.float32)
+        cols[j] = (rows.astype(np.int32), vals)
+    ptr = np.zeros(I + 1, dtype=np.int32)
+    for j, (rows, _) in cols.items():
+        ptr[j + 1] = len(rows)
+    ptr = np.cumsum(ptr).astype(np.int32)
+    order = sorted(cols)
+    W = sp.csc_matrix((np.concatenate([cols[j][1] for j in order]), np.concatenate([cols[j][0] for j in order]), ptr), shape=(I, I))
+    assert W.nnz == sum(len(r) for r, _ in cols.values()) and W.has_sorted_indices
+    assert (np.signbit(W.data) & (W.data == 0)).any() and ((W.data == 0) & ~np.signbit(W.data)).any()
+    _similar_w_cache.append((W, order))
+    return _similar_w_cache[0]
+
+
+@pytest.mark.parametrize("top_k", [1, 7, 64, 200])
+def test_similar_items_long_columns_and_stored_order_ties(engine, oracle, top_k):
+    """similar_topk_kernel on columns longer than a wave (the second and later trips of its column scan), with ties forced:
+    equal values come out in ascending stored row order (aux = 0xffffffff - position), the self entry is dropped wherever it
+    sits, stored zeros and negatives are entries like any other, and a top_k above the column length pads with -1 / -inf."""
+    import torch
+    W, built = similar_w()
+    be = engine.be
+    rng = np.random.default_rng(top_k)
+    I = W.shape[1]
+    empty = np.setdiff1d(np.arange(I), built)[:5]
+    q_all = rng.permutation(np.concatenate([built, built[::3], empty]))              # out of order, with repeats
+    longest = int(np.argmax(np.diff(W.indptr)))
+    Wd = {"cptr": be.to_dev(W.indptr.astype(np.int32)), "crow": be.to_dev(W.indices.astype(np.int32)),
+          "cval": be.to_dev(W.data.astype(np.float32))}
+    for q in (q_all, np.array([longest])):                                           # ... and a query list of length 1
+        n = len(q)
+        ids = torch.full((n, top_k), -777, dtype=torch.int32, device=be.device)
+        sc = torch.full((n, top_k), 12345.5, dtype=torch.float32, device=be.device)
+        cnt = torch.full((n,), -555, dtype=torch.int32, device=be.device)
+        be.similar_topk(be.to_dev(q.astype(np.int32)), Wd, top_k, ids, sc, cnt)
+        be.synchronize()
+        ids, sc, cnt = ids.cpu().numpy(), sc.cpu().numpy(), cnt.cpu().numpy()
+        for t, j in enumerate(q):
+            oi, ov = oracle.similar_items(W, int(j), top_k=top_k)
+            rows, vals = W.indices[W.indptr[j]:W.indptr[j + 1]], W.data[W.indptr[j]:W.indptr[j + 1]]
+            assert cnt[t] == len(oi) == min(top_k, int((rows != j).sum())), f"column {j}"
+            assert np.array_equal(ids[t, :cnt[t]], oi), f"column {j}: {ids[t, :cnt[t]]} vs {oi}"
+            assert np.array_equal(bits(sc[t, :cnt[t]]), bits(ov)), f"column {j}"
+            assert (ids[t, cnt[t]:] == -1).all() and (bits(sc[t, cnt[t]:]) == bits(np.float32(-np.inf))).all(), f"column {j}"
+            # the tie rule, from W alone: the entries that hold the column's maximum lead, in ascending stored row order
+            others = rows != j
+            if others.any():
+                top = rows[others][vals[others] == vals[others].max()]
+                assert np.all(np.diff(top) > 0)
+                lead = min(len(top), top_k)
+                assert np.array_equal(ids[t, :lead], top[:lead]), f"column {j}: ties not in stored order"
+    lens = np.diff(W.indptr)[built]
+    top_ties = [int((W.data[W.indptr[j]:W.indptr[j + 1]] == 2.5).sum()) for j in built]
+    assert lens.max() > 128 and max(top_ties) > 64            # the maximum repeats beyond one trip of the scan
+
+
 def test_merge_topk_equals_unsharded(oracle):
     """Column-sharded scoring + merge kernel == single-shard result (the multi-GPU data path,
     run here as two engines on one GPU)."""
