@@ -269,16 +269,18 @@ typedef struct {
      * to back, each a whole number of KiB starting at KiB d_fr_super_kb[s] (fr_n_super + 1 entries both), and then, at
      * float d_fr_super_kb[fr_n_super] * 256, fr_n_frags floats: per fragment 1.0001 * max |w| over its whole tile
      * (float32-rounded), the kernel's first-level tile bound.
-     * fr_buf_bytes (a multiple of 1024, >= the largest super-tile) is the size of one LDS staging buffer.  Two forms:
-     *   streaming  fr_buf_bytes >= 32 KiB and 2 * (2 * fr_buf_bytes + 7696) <= 160 KiB: two 8-wave workgroups per CU,
-     *              two buffers each (a tile may continue in the next super-tile: its sums stay in registers).  7696 =
-     *              8 * 576 (candidate buffers) + 1024 (zero row) + 16 + 2048 (early exit: a suffix bound and a vote word per
-     *              super-tile; a W of 256 or more super-tiles is scored without the early exit);
-     *   resident   fr_n_super == 1, fr_n_tiles <= 64 and everything fits next to the per-wave setup scratch
-     *              (fr_buf_bytes + 16 * ceil256(fr_n_tiles * fr_tile_cols / 8 + 768) + 10256 <= 160 KiB): one 16-wave
-     *              workgroup per CU loads W once and keeps it.
+     * fr_buf_bytes (a multiple of 1024) is an upper bound of the size of a super-tile.  One 16-wave workgroup per CU
+     * scores every W: the leading super-tiles that fit the LDS left over stay there for the life of the workgroup (the
+     * resident HEAD; the layout puts the heavy tiles first), and behind the head every wave fetches the rows it sweeps,
+     * and only those, by LDS-DMA into a ring of its own (4 KiB per wave, which is its setup scratch before):
+     *   LDS = head + 16 * 4096 (scratch / ring) + 16 * 576 (candidate buffers) + 1024 (zero row) + 16 +
+     *         4 * min(fr_n_frags, 256) (early exit: a suffix bound per fragment; a W of more than 256 fragments is
+     *         scored without the early exit) <= 160 KiB, i.e. a head of up to 85 KiB (86 for a W of few fragments).
+     * When fr_n_super == 1, fr_n_tiles <= 64 and all of W fits next to the setup scratch its masks need
+     * (16 * ceil256(fr_n_tiles * fr_tile_cols / 8 + 768) instead of 16 * 4096; the early-exit table not counted, and
+     * dropped with the early exit where only it does not fit) all of W is the head and nothing is gathered.
      * d_fr_scratch: rtrec_slim_score_fr_scratch_bytes() bytes of device scratch.  Scores and ids are identical to
-     * the tiled-CSR path; accumulators live in registers and the matrix is streamed through LDS
+     * the tiled-CSR path; accumulators live in registers and the matrix is read from LDS
      * (csrc/score.hip, score_frows_kernel). */
     const int32_t *d_fr_map;
     const int32_t *d_fr_col_ids;
@@ -301,8 +303,9 @@ typedef struct {
                                      (-DRTREC_DIAGNOSTICS) only, ignored by the release library.  bits 8-11: users per wave
                                      of the feature-row kernel (8, 4 or 2; 0 = chosen from the batch size); bits 12-23: v > 0
                                      = the segment path gives users of more than v - 1 items (at most 512) a workgroup of
-                                     their own instead of a wave (0 = chosen from the batch size) -- test / tuning knobs,
-                                     results do not depend on them */
+                                     their own instead of a wave (0 = chosen from the batch size); bits 24-30: v > 0 = the
+                                     feature-row kernel keeps at most v - 1 KiB of W resident in LDS (0 = what the LDS
+                                     leaves) -- test / tuning knobs, results do not depend on them */
     int32_t       *d_rescored;    /* optional int32[1] on the device: receives the number of rows the exact-tie pass
                                      re-scored (SPARSE mode; rows whose fast-pass list held an exact tie reaching its
                                      (k+1)-th entry -- ties inside the leading k are ordered in place and not counted) */
@@ -364,6 +367,12 @@ typedef struct {
 } rtrec_score_opts;
 
 size_t rtrec_slim_score_fr_scratch_bytes(int32_t fr_n_tiles, int32_t fr_tile_cols);
+/* How a launch of the feature-row kernel divides a CU's LDS for this layout (a pure host function; see d_fr_map above):
+ * returns the dynamic LDS bytes of the launch, *head_kib = KiB kept for the resident head (the kernel keeps the leading
+ * super-tiles that fit it), *wave_scratch = bytes of setup scratch / row ring per wave.  head_kib_cap >= 0 caps the head
+ * (the diagnostics knob of rtrec_score_opts), -1 leaves it to the LDS.  0 for a layout the kernel does not take. */
+size_t rtrec_slim_score_fr_lds_bytes(int32_t fr_n_super, int32_t fr_n_tiles, int32_t fr_tile_cols, int32_t fr_n_frags,
+                                     int32_t fr_buf_bytes, int32_t head_kib_cap, int32_t *head_kib, int32_t *wave_scratch);
 size_t rtrec_slim_score_sg_scratch_bytes(int32_t n_items, int32_t sg_n_tiles, int32_t sg_tile_cols);
 
 /* Bytes of scratch for rtrec_slim_score_topk. */

@@ -22,7 +22,7 @@ _STATUS = {0: "ok", -1: "invalid argument", -2: "unsupported parameter", -3: "wo
 
 EXPORTS = [
     "rtrec_amd_version", "rtrec_amd_last_error", "rtrec_timer_create", "rtrec_timer_read", "rtrec_timer_destroy",
-    "rtrec_slim_score_fr_scratch_bytes", "rtrec_slim_score_sg_scratch_bytes", "rtrec_slim_score_topk_opt", "rtrec_slim_column_sqnorms", "rtrec_slim_fit_workspace_bytes",
+    "rtrec_slim_score_fr_scratch_bytes", "rtrec_slim_score_fr_lds_bytes", "rtrec_slim_score_sg_scratch_bytes", "rtrec_slim_score_topk_opt", "rtrec_slim_column_sqnorms", "rtrec_slim_fit_workspace_bytes",
     "rtrec_slim_fit_workspace_init", "rtrec_slim_fit_columns", "rtrec_slim_fit_columns_opt", "rtrec_slim_gram_workspace_bytes", "rtrec_slim_xty_workspace_bytes", "rtrec_slim_gram_matrix", "rtrec_slim_score_workspace_bytes",
     "rtrec_slim_score_topk", "rtrec_slim_score_rows", "rtrec_slim_merge_topk", "rtrec_slim_merge_topk_strided", "rtrec_slim_similar_topk",
     "rtrec_store_merge_sorted", "rtrec_store_find_sorted", "rtrec_lru_replay", "rtrec_store_apply_round", "rtrec_store_decay",
@@ -113,6 +113,8 @@ def load() -> C.CDLL:
     L.rtrec_timer_destroy.argtypes = [vp]
     L.rtrec_slim_score_fr_scratch_bytes.restype = u64
     L.rtrec_slim_score_fr_scratch_bytes.argtypes = [i32, i32]
+    L.rtrec_slim_score_fr_lds_bytes.restype = u64
+    L.rtrec_slim_score_fr_lds_bytes.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.rtrec_slim_score_sg_scratch_bytes.restype = u64
     L.rtrec_slim_score_sg_scratch_bytes.argtypes = [i32, i32, i32]
     L.rtrec_slim_column_sqnorms.restype = C.c_int

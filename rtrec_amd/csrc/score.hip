@@ -77,9 +77,9 @@ struct ScoreArgs {
 // summed over all waves in g_score_prof (read with rtrec_amd_score_profile; not part of the release ABI).
 #ifdef SCORE_PROFILE
 enum { PF_JOBS, PF_ROWPTR, PF_HDR, PF_GROUP, PF_DENSE, PF_SPARSE, PF_SELECT, PF_EMIT, PF_RESET, PF_QUEUE,
-       PF_N_DENSE, PF_N_SPARSE_ROWS, PF_N_SPARSE_CHUNKS, PF_N_OVERFLOW, PF_TOTAL, PF_COUNT };
+       PF_N_DENSE, PF_N_SPARSE_ROWS, PF_N_SPARSE_CHUNKS, PF_N_OVERFLOW, PF_TOTAL, PF_N_GATHER, PF_COUNT };
 __device__ unsigned long long g_score_prof[16];
-__device__ unsigned int g_fr_exit_depth[257];     // score_frows_kernel: histogram of the depth at which a job ended
+__device__ unsigned int g_fr_exit_depth[257];     // score_frows_kernel: histogram of the fragment at which a wave left its job
 #define PF_DECL unsigned long long pf_[16] = {0}; unsigned long long pf_t_ = __builtin_amdgcn_s_memtime();
 #define PF_MARK(slot) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); pf_[slot] += n_ - pf_t_; pf_t_ = n_; }
 #define PF_ADD(slot, v) { pf_[slot] += (v); }
@@ -1041,9 +1041,10 @@ struct FrArgs {
     const int *st_kb;       // [n_super + 1]: KiB offset of super-tile s in wd (one LDS-DMA wave-instruction moves 1 KiB)
     const int *st_tile;     // [n_super + 1]: first FRAGMENT of super-tile s (at most 64 fragments each)
     int n_super;
-    int resident;           // one super-tile that stays in LDS for the life of the workgroup
+    int head_kib;           // LDS KiB for the resident head: the leading super-tiles of W that fit stay there for the life of the workgroup
+    int wave_scratch;       // LDS bytes per wave: setup scratch, then the row ring (>= kFrRingBytes unless all of W is in the head)
+    int exit_frags;         // fragments the LDS table of suffix bounds holds (0: no table, no early exit)
     int consecutive;        // a wave takes 8 consecutive positions of the work order (pattern-sorted) instead of a strided deal
-    int buf_bytes;          // bytes of one LDS buffer (>= the largest super-tile, >= the setup scratch)
     unsigned long long *mscratch;   // [gridDim.x][waves][users][n_tiles * REGS] interacted-column lane masks
     int kk, top_k, filter;
     int *out_id; float *out_score; uint32_t *out_aux; int *out_cnt;
@@ -1055,7 +1056,12 @@ struct FrArgs {
 
 constexpr int kFrWaves = 16;                 // one workgroup per CU, four waves per SIMD
 constexpr int kFrUsers = 8;                  // users per wave
-constexpr int kFrWaveScratch = 4096;         // LDS bytes of setup scratch per wave (inside the second slice buffer)
+// LDS-DMA wave-instructions of 1 KiB a wave's row ring holds (its most in flight): 4 rows of a 256-column tile, 8 of a
+// 128-column one.  The ring is exactly the setup scratch; a ring of 8 would take 8 KiB per wave and leave a head of 21 KiB
+// (DESIGN 3.1, round 9).
+constexpr int kFrRingDepth = 4;
+constexpr int kFrRingBytes = kFrRingDepth * 1024;
+constexpr int kFrWaveScratch = 4096;         // LDS bytes of setup scratch per wave (afterwards the wave's row ring)
 constexpr int kFrMaskWords = 416;            // 64-bit mask words per user the scratch holds (n_tiles * REGS)
 constexpr int kFrUserWords = 192;            // 32-bit words of global scratch per user: 128 ratings, 32 row words, pad
 constexpr int kFrMaxKk = 16;                 // top_k + 1 entries of a list fit one DPP row
@@ -1085,23 +1091,50 @@ constexpr int kFrTileHeaderBytes = 512;      // per tile, in front of its first 
 constexpr int kFrZeroRowBytes = 1024;        // one slice row of +0.0 (the widest tile: 256 columns)
 // per-wave LDS setup scratch actually needed: the interacted-column mask words, a pad, 128 ratings
 __host__ __device__ constexpr int fr_setup_scratch(int mask_words) { return ((mask_words * 8 + 256 + 512) + 255) / 256 * 256; }
-// Streaming layout: two slice buffers (the second doubles as setup scratch).  RESIDENT layout (all of W's slices in ONE
-// super-tile that fits next to the setup scratch): one buffer, loaded once per workgroup and kept across its jobs.
-constexpr int kFrWavesStream = 8;            // streaming layout: two 8-wave workgroups per CU
-// Early exit of a job (streaming layout): sfx[s] = max of frag_wtop over the fragments of super-tiles s, s + 1, ... (sfx[n_super]
-// = 0), a constant of W that every workgroup derives once, and one vote word per super-tile -- 8 bytes of LDS per super-tile.
-// A W of kFrExitSlots or more super-tiles runs without the early exit (as if every sfx were +inf).
+// LDS of the one 16-wave workgroup a CU holds: the resident HEAD of W (its leading super-tiles, loaded once per workgroup
+// and kept for its life; all of W when it fits), per wave `wave_scratch` bytes (setup scratch while a job is set up, then
+// the wave's ROW RING: the rows it sweeps behind the head arrive there by LDS-DMA, 1 KiB per wave-instruction), per
+// wave the candidate buffers, one row of +0.0, and the suffix bounds of the early exit.
+static_assert(kFrRingBytes == kFrWaveScratch, "the row ring overlays the wave's setup scratch");
+// Early exit of a wave from its job: sfx[g] = max of frag_wtop over the fragments g, g + 1, ..., a constant of W that every
+// workgroup derives once -- 4 bytes of LDS per fragment.  A W of more than kFrExitSlots fragments runs without the early
+// exit (as if every sfx were +inf).
 constexpr int kFrExitSlots = 256;
-constexpr int kFrExitBytes = kFrExitSlots * 8;
-__host__ __device__ constexpr size_t fr_lds_bytes(int buf_bytes, bool resident = false, int mask_words = kFrMaskWords) {
-    return resident ? static_cast<size_t>(buf_bytes) + kFrWaves * fr_setup_scratch(mask_words) + kFrWaves * fr_wave_extra_bytes() +
-                          kFrZeroRowBytes + 16
-                    : 2 * static_cast<size_t>(buf_bytes) + kFrWavesStream * fr_wave_extra_bytes() + kFrZeroRowBytes + 16 +
-                          kFrExitBytes;
+__host__ __device__ constexpr size_t fr_exit_bytes(int n_frags) {
+    return (static_cast<size_t>(n_frags < kFrExitSlots ? n_frags : kFrExitSlots) * 4 + 15) / 16 * 16;
+}
+// everything but the head
+__host__ __device__ constexpr size_t fr_lds_fixed_bytes(int wave_scratch, int n_frags) {
+    return kFrWaves * static_cast<size_t>(wave_scratch) + kFrWaves * fr_wave_extra_bytes() + kFrZeroRowBytes + 16 + fr_exit_bytes(n_frags);
+}
+__host__ __device__ constexpr size_t fr_lds_bytes(int head_kib, int wave_scratch, int n_frags) {
+    return (static_cast<size_t>(head_kib) << 10) + fr_lds_fixed_bytes(wave_scratch, n_frags);
+}
+constexpr size_t kFrLdsCu = 160u * 1024u;
+// How a launch divides the CU's LDS (the one place that decides it).  All of W in one super-tile that fits beside the
+// setup scratch its masks need: W is the head, nothing is gathered, the scratch is as small as the masks allow (today's
+// resident form).  Otherwise every wave gets kFrWaveScratch (>= the ring) and the head is what is left, in KiB;
+// `head_override` >= 0 caps it (RTREC_AMD_FR_HEAD_KIB: tests and A/B; 0 = no head, every row is gathered).
+// The all-resident test charges the table of suffix bounds nothing, as the layout builder's `resident` does not (it cut
+// such a W into ONE super-tile, which no head of the other plan could hold): a W that fits only without the table
+// (a window of at most 256 bytes) stays all resident and runs without the early exit.
+struct FrLds { int head_kib, wave_scratch, exit_frags; };
+inline FrLds fr_lds_plan(int n_super, int n_tiles, int regs, int n_frags, int buf_bytes, int head_override) {
+    const int setup = fr_setup_scratch(n_tiles * regs);
+    if (n_super == 1 && n_tiles <= 64 && fr_lds_bytes(buf_bytes >> 10, setup, 0) <= kFrLdsCu &&
+        (head_override < 0 || head_override >= (buf_bytes >> 10)))
+        return FrLds{buf_bytes >> 10, setup, fr_lds_bytes(buf_bytes >> 10, setup, n_frags) <= kFrLdsCu ? n_frags : 0};
+    const long long w_kib = static_cast<long long>(n_super) * (buf_bytes >> 10);         // (an upper bound of W's size)
+    long long head = static_cast<long long>((kFrLdsCu - fr_lds_fixed_bytes(kFrWaveScratch, n_frags)) >> 10);
+    head = head < w_kib ? head : w_kib;
+    if (head_override >= 0 && head_override < head) head = head_override;
+    return FrLds{static_cast<int>(head), kFrWaveScratch, n_frags};
 }
 
 typedef __attribute__((address_space(3))) void fr_lds_void;
 typedef __attribute__((address_space(1))) const void fr_glb_void;
+typedef __attribute__((address_space(3))) const float fr_lds_f32;
+typedef __attribute__((address_space(1))) const float fr_glb_f32;
 
 template <int REGS> struct FrVec;
 template <> struct FrVec<4> { typedef float type __attribute__((ext_vector_type(4))); };
@@ -1250,21 +1283,20 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
     constexpr int NL = (UW + 3) / 4;                        // list registers: four users per 64 lanes, 16 lanes each
     // (the wave index is uniform: said so, everything derived from it -- the wave's scratch, its LDS slices -- is scalar)
     const int tid = static_cast<int>(threadIdx.x), wave = readfirst_i(tid >> 6), lane = tid & 63;
-    const int NW = static_cast<int>(blockDim.x) >> 6;       // waves of this workgroup: 16 (resident layout) or 8 (streaming)
+    constexpr int NW = kFrWaves;                            // one 16-wave workgroup per CU
+    constexpr int STEPB = kFrStep * ROWB;                   // ring bytes of one sweep step: two rows of W
+    constexpr int DPS = STEPB / 1024;                       // LDS-DMA wave-instructions per step (128-column tiles: one carries both rows)
+    constexpr int NS = kFrRingBytes / STEPB;                // steps the ring holds
+    static_assert(DPS >= 1 && NS >= 2 && (NS & (NS - 1)) == 0, "ring geometry");
     const int kk = a.kk;                                    // <= 16
-    unsigned char *buf0 = smem;
-    unsigned char *buf1 = smem + a.buf_bytes;               // second slice buffer; also (or, resident: only) setup scratch
-    const bool resident = a.resident != 0;                  // W's slices stay in buf0 for the life of the workgroup
-    const int wscratch = resident ? fr_setup_scratch(a.n_tiles * REGS) : kFrWaveScratch;
-    const size_t lds_front = resident ? static_cast<size_t>(a.buf_bytes) + NW * static_cast<size_t>(wscratch)
-                                      : 2 * static_cast<size_t>(a.buf_bytes);
+    unsigned char *head = smem;                             // the resident head of W
+    unsigned char *ring = smem + (static_cast<size_t>(a.head_kib) << 10) + static_cast<size_t>(wave) * a.wave_scratch;
+    const size_t lds_front = (static_cast<size_t>(a.head_kib) << 10) + NW * static_cast<size_t>(a.wave_scratch);
     unsigned char *extra = smem + lds_front + static_cast<size_t>(wave) * fr_wave_extra_bytes();
     float *cv = reinterpret_cast<float *>(extra);                     // [kFrCandCap] candidate scores of one user
     int *cp = reinterpret_cast<int *>(cv + kFrCandCap);               // [kFrCandCap] their layout columns
     const unsigned char *zrow = smem + lds_front + NW * fr_wave_extra_bytes();
-    int *s_job = reinterpret_cast<int *>(smem + lds_front + NW * fr_wave_extra_bytes() + kFrZeroRowBytes);
     for (int o = tid * 4; o < kFrZeroRowBytes; o += NW * 64 * 4) *reinterpret_cast<float *>(smem + (zrow - smem) + o) = 0.0f;
-    const int n_jobs = (a.n_rows + UW * NW - 1) / (UW * NW);
     const float ninf = -__builtin_huge_valf();
     const int mwords = a.n_tiles * REGS;
     // per-wave global scratch: per user 192 words (its ratings by row of W: 128; pad), then the users' mask words
@@ -1291,38 +1323,40 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
         return r;
     };
 
-    // super-tile s = fragments [st_tile[s], st_tile[s + 1]): their rows that hold a weight, tile after tile, KiB [kb0, kb1) of wd
-    auto load_super = [&](int kb0, int kb1, unsigned char *dst) {
+    // ---- the resident head: the leading super-tiles of W that fit a.head_kib KiB (the layout visits the heavy tiles first,
+    //      and every job opens tile 0).  Fragments [0, g_head) are read from LDS for the life of the workgroup; the rows of
+    //      the fragments behind them come through the wave's row ring, when a wave sweeps them. ----
+    const int kb0 = c_st_kb[0];
+    int s_head = 0;
+    while (s_head < a.n_super && c_st_kb[s_head + 1] - kb0 <= a.head_kib) ++s_head;
+    const int g_head = c_st_tile[s_head];
+    {
         const unsigned char *src = reinterpret_cast<const unsigned char *>(a.wd) + (static_cast<size_t>(kb0) << 10);
-        for (int c = wave; c < kb1 - kb0; c += NW)
+        const int head_kb = c_st_kb[s_head] - kb0;
+        for (int c = wave; c < head_kb; c += NW)
             __builtin_amdgcn_global_load_lds((fr_glb_void *)(src + (static_cast<size_t>(c) << 10) + lane * 16),
-                                             (fr_lds_void *)(dst + (c << 10)), 16, 0, 0);
-    };
+                                             (fr_lds_void *)(head + (c << 10)), 16, 0, 0);
+    }
 
-    // ---- leaving a job early.  The layout visits the heavy tiles first, so after a few super-tiles no user of a job can
-    //      open any tile that is still to come: with sfx = the largest first-level bound (frag_wtop) from some point of W
-    //      on, a user whose first-level test fails against sfx fails it against every later fragment too (__fmul_rn is
-    //      monotone in the bound, the (k+1)-th best never falls), so every later tile would be skipped for it anyway.
-    //      Streaming: sfx per super-tile in LDS; the waves vote at the hand-over and leave the job together (below).
-    //      Resident: sfx per fragment (at most 64: one super-tile) in lane g of one register; a wave leaves on its own. ----
+    // ---- leaving a job early.  The layout visits the heavy tiles first, so after a few super-tiles no user of a wave can
+    //      open any tile that is still to come: with sfx[g] = the largest first-level bound (frag_wtop) of the fragments
+    //      g, g + 1, ..., a user whose first-level test fails against sfx[g] fails it against every later fragment too
+    //      (__fmul_rn is monotone in the bound, the (k+1)-th best never falls), so every later tile would be skipped for it
+    //      anyway.  A wave leaves at the first closed tile behind which everything is closed; it asks nobody. ----
     float *s_sfx = reinterpret_cast<float *>(smem + lds_front + NW * fr_wave_extra_bytes() + kFrZeroRowBytes + 16);
-    int *s_vote = reinterpret_cast<int *>(s_sfx + kFrExitSlots);
-    const bool exit_on = resident ? n_frags <= 64 : a.n_super < kFrExitSlots;
-    float sfx_frag = 0.0f;
-    if (resident) {
-        if (exit_on) {
-            sfx_frag = lane < n_frags ? frag_wtop[lane] : 0.0f;
-            for (int d = 1; d < 64; d <<= 1) {              // suffix maximum over the lanes
-                const float o = __shfl_down(sfx_frag, d, 64);
-                sfx_frag = (lane + d < 64 && o > sfx_frag) ? o : sfx_frag;
+    const bool exit_on = a.exit_frags > 0 && n_frags <= kFrExitSlots;
+    if (exit_on && wave == 0) {                             // suffix maximum, 64 fragments at a time from the end of W
+        float carry = 0.0f;
+        for (int c0 = (n_frags - 1) & ~63; c0 >= 0; c0 -= 64) {
+            const int g = c0 + lane;
+            float m = g < n_frags ? frag_wtop[g] : 0.0f;
+            for (int d = 1; d < 64; d <<= 1) {
+                const float o = __shfl_down(m, d, 64);
+                m = (lane + d < 64 && o > m) ? o : m;
             }
-        }
-    } else if (exit_on) {
-        for (int s = wave; s <= a.n_super; s += NW) {       // (the job loop starts with a barrier)
-            float m = 0.0f;
-            for (int g = c_st_tile[s] + lane; g < n_frags; g += 64) { const float v = frag_wtop[g]; m = v > m ? v : m; }
-            for (int d = 1; d < 64; d <<= 1) { const float o = shfl_xor_t(m, d); m = o > m ? o : m; }
-            if (lane == 0) s_sfx[s] = m;
+            m = carry > m ? carry : m;
+            if (g < n_frags) s_sfx[g] = m;
+            carry = readlane_f(m, 0);
         }
     }
 
@@ -1330,45 +1364,31 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
 #ifdef SCORE_PROFILE
     const unsigned long long pf_start_ = pf_t_;
 #endif
-    if (resident) {                                         // all of W's slices: once per workgroup
-        load_super(c_st_kb[0], c_st_kb[1], buf0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    // Streaming layout: a job = 128 users of the whole workgroup (the waves share the staged slices and meet at its
-    // barriers).  Resident layout: W is read-only in LDS, so every WAVE claims its own 8 users and no barrier is left
-    // inside the loop -- a wave never waits for a slower neighbour.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();                                        // the head has landed, the zero row and the suffix bounds are written
+    // W's head is read-only in LDS and every wave fetches the other rows for itself, so every WAVE claims its own UW users
+    // and no barrier is left inside the loop: a wave never waits for a slower neighbour.
     const int n_wave_jobs = (a.n_rows + UW - 1) / UW;
-    if (resident) __syncthreads();                          // W has landed
     for (;;) {
-        int base, pstride;
-        if (resident) {
-            PF_MARK(PF_GROUP)
-            int j = 0;
-            if (lane == 0) j = atomicAdd(a.queue, 1);
-            j = readfirst_i(j);
-            PF_MARK(PF_QUEUE)
-            if (j >= n_wave_jobs) break;
-            // positions j, j + n_wave_jobs, ...: with rows handed over longest-first every wave job is the same mix
-            base = a.consecutive ? j * UW : j; pstride = a.consecutive ? 1 : n_wave_jobs;
-        } else {
-            __syncthreads();                                // the previous job has left both buffers
-            PF_MARK(PF_QUEUE)
-            if (tid == 0) *s_job = atomicAdd(a.queue, 1);
-            if (exit_on) for (int s = tid; s < a.n_super; s += NW * 64) s_vote[s] = 0;   // (every wave has read the last job's)
-            __syncthreads();
-            const int job = *s_job;
-            if (job >= n_jobs) break;
-            load_super(c_st_kb[0], c_st_kb[1], buf0);
-            // position p of the job's users goes to wave p % NW, so that with rows handed over longest-first (a.order)
-            // every wave of the workgroup gets the same mix of long and short rows and the barriers find the waves level
-            base = job * NW * UW + (a.consecutive ? wave * UW : wave); pstride = a.consecutive ? 1 : NW;
-        }
+        PF_MARK(PF_GROUP)
+        int j = 0;
+        if (lane == 0) j = atomicAdd(a.queue, 1);
+        j = readfirst_i(j);
+        PF_MARK(PF_QUEUE)
+        if (j >= n_wave_jobs) break;
+        // positions j, j + n_wave_jobs, ...: with rows handed over longest-first every wave job is the same mix
+        const int base = a.consecutive ? j * UW : j, pstride = a.consecutive ? 1 : n_wave_jobs;
+        // (the lane index as a value of this job: what the job derives from it -- store addresses, masks -- is computed where
+        // it is used instead of being carried in registers, or spilled, across the whole job loop)
+        int lane_job = tid & 63;
+        asm volatile("" : "+v"(lane_job));
+        const int lane = lane_job;
 
         // ---- setup: per user its ratings of the R feature items (dense, lane = row of W) and the interacted-column
-        //      masks, built in LDS (the second buffer is free until super-tile 0 starts) and parked in the wave's
+        //      masks, built in LDS (the wave's scratch: no row is in flight between two jobs) and parked in the wave's
         //      global scratch; the ratings come back into registers below ----
-        unsigned long long *Ml = reinterpret_cast<unsigned long long *>(buf1 + wave * wscratch);
-        float *xl = reinterpret_cast<float *>(Ml + (resident ? mwords : kFrMaskWords)) + 64;   // [128] floats
+        unsigned long long *Ml = reinterpret_cast<unsigned long long *>(ring);
+        float *xl = reinterpret_cast<float *>(Ml + mwords) + 64;                           // [128] floats
         // the eight users' row extents: lane u follows user u's chain of dependent loads (work order -> row id -> row
         // pointers), all eight chains in parallel; then the first 64 entries of every row and what they map to
         // (feature row, layout column), again all eight users' loads in flight together -- three memory round trips
@@ -1475,11 +1495,6 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
         fr_static_for<NL>([&](auto G4) { ls4[G4()] = ninf; lc4[G4()] = -1; });
 
         PF_MARK(PF_HDR) PF_ADD(PF_JOBS, 1)
-        if (!resident) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // super-tile 0 has landed
-            __syncthreads();
-        }
-        PF_MARK(PF_GROUP)
 
         // rows of W that at least one of the wave's users rates: the sweep below visits only those
         unsigned long long own_or[XR];
@@ -1510,91 +1525,101 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
             const float tot = readlane_f(b, 63);
             l1v = lane == u ? tot : l1v;
         });
-        // what the loop below holds one step ahead: the KiB extent of super-tile sidx + 1 (kb_a, kb_b), the fragments of
-        // super-tile sidx ([t_lo, t_hi)), fragment g's constants (fr); fragment numbers run on across super-tiles
-        int kb_a = c_st_kb[min(1, a.n_super)], kb_b = c_st_kb[min(2, a.n_super)];
-        int t_lo = c_st_tile[0], t_hi = c_st_tile[min(1, a.n_super)];
-        FrFrag fr = load_frag(min(t_lo, max(n_frags - 1, 0))), fr_next = fr;
-        bool wave_done = false;    // streaming: none of this wave's users can open anything from the next super-tile on
-        bool stage_next = true;    // streaming: some wave may still need the super-tile after the next one
-        int ft_last = 1 << 25;     // flags of the last fragment this wave has passed
+        // what the loop below holds one step ahead: fragment g's constants (fr), and the extent of the super-tile behind
+        // the current one (its KiB offset in wd, its last fragment); fragment numbers run on across super-tiles
+        int sup = 0, kb_cur = kb0, t_hi = c_st_tile[min(1, a.n_super)];
+        int kb_next = c_st_kb[min(1, a.n_super)], t_hi_next = c_st_tile[min(2, a.n_super)];
+        FrFrag fr = load_frag(0), fr_next = fr;
+        const unsigned char *wzero = zrow + lane16;               // a row of +0.0: what a step reads past the last row
 #ifdef SCORE_PROFILE
-        int pf_depth_ = resident ? -1 : a.n_super;
+        int pf_depth_ = n_frags;
 #endif
-        for (int sidx = 0; sidx < a.n_super; ++sidx) {
-            const unsigned char *wb = (sidx & 1) ? buf1 : buf0;
-            // (stage_next false: the vote at the end of this super-tile ends the job -- nobody will read the next one)
-            if (sidx + 1 < a.n_super && stage_next) load_super(kb_a, kb_b, (sidx & 1) ? buf0 : buf1);
-            // the next super-tile's extents: requested now, needed at the hand-over
-            const int kb_c = c_st_kb[min(sidx + 3, a.n_super)], t_hi_next = c_st_tile[min(sidx + 2, a.n_super)];
-            const unsigned char *wlane = wb + lane16;             // this lane's columns in a slice row
-            const unsigned char *wzero = zrow + lane16;           // a row of +0.0: what a step reads past the last row
-
-            // (a wave that is done only helps to stage and meets the others at the barriers: its fragments' constants are
-            // no longer loaded, nothing reads them)
-            if (!wave_done) for (int g = t_lo; g < t_hi; ++g, fr = fr_next) {
-                fr_next = load_frag(min(g + 1, n_frags - 1));     // in flight while fragment g is worked on
-                const int ft = fr.ft;
-                ft_last = ft;
-                const int t = ft & 0xffffff;                     // the tile this fragment belongs to
-                // ---- tile-major sweep: every row of W that holds a weight in this tile (and that one of the wave's
-                //      users rates) is read from LDS ONCE and applied to all eight users: acc_u += x_u * w, one
-                //      rounded product and one rounded add per column (two v_pk_mul_f32 + two v_pk_add_f32 per user
-                //      and 256 columns), rows ascending = scipy's order.  A user that does not rate the row has
-                //      x_u = 0: x * w = +-0 changes no sum (a sum that starts at +0 never becomes -0), and the same
-                //      holds for rows and blocks that are skipped altogether. ----
-                const int toff = fr.toff;
-                if (ft & (1 << 24)) {                            // first fragment of a tile
-                    // ---- can this tile matter at all?  Its header holds max |w| of every row of W over the tile's
-                    //      columns (lane f = row 64 h + f), so  B_u = sum_f |x_uf| max|w_f|  bounds every score user u
-                    //      can have in it, rounding of the float32 sums included in the 1e-4 margin.  A column enters a
-                    //      list only by BEATING the user's (k+1)-th best: when B_u <= that for all eight users the
-                    //      sweep, the selection and the tile's further fragments are skipped -- after the heavy first
-                    //      tiles that is the fate of nine tiles in ten (ML-20M shape). ----
-                    // first level, all eight users in one compare: (sum_f |x_uf|) * max_f max|w_f| -- decides 86 % of
-                    // the (wave, tile) pairs on the ML-20M shape; only the others read the header and pay the per-user
-                    // reductions below.  max_f max|w_f| (times the margin) is a constant of W: the layout stores it
-                    // per fragment (frag_wtop) instead of every wave reducing the header again for every job
-                    const float wtop = fr.wtop;
-                    // (a user with NO rating on a row of W -- an empty row, a position past the end of the batch in the last job --
-                    // has bound 0: every sum is +0, no candidate; it must not hold the tile open while its list is empty.  Such a
-                    // slot used to keep its wave sweeping EVERY tile: a batch whose size is no multiple of the job size paid one
-                    // unpruned wave at its end, 0.06-0.09 ms whatever its size -- tools/row_slice_probe.py, round 4)
-                    const unsigned long long open1 = __ballot(lane < UW && l1v > 0.0f && !(thrv >= 0.0f && __fmul_rn(l1v, wtop) <= thrv));
-                    bool all_skip = true;
-                    float wm[XR];
-                    if (open1) fr_static_for<XR>([&](auto H) {
-                        wm[H()] = *reinterpret_cast<const float *>(wb + toff - kFrTileHeaderBytes + (H() * 64 + lane) * 4);
-                    });
-                    if (open1) fr_static_for<UW>([&](auto Uc) {
-                        constexpr int u = decltype(Uc)::value;
-                        float b = __fmul_rn(fabsf(xr[u][0]), wm[0]);
-                        if constexpr (XR == 2) b = __fadd_rn(b, __fmul_rn(fabsf(xr[u][1]), wm[1]));
-                        b = __fadd_rn(b, fr_dpp_f<0x111>(b, 0.0f));
-                        b = __fadd_rn(b, fr_dpp_f<0x112>(b, 0.0f));
-                        b = __fadd_rn(b, fr_dpp_f<0x114>(b, 0.0f));
-                        b = __fadd_rn(b, fr_dpp_f<0x118>(b, 0.0f));
-                        b = __fadd_rn(b, fr_dpp_f<0x142>(b, 0.0f));      // row_bcast:15
-                        b = __fadd_rn(b, fr_dpp_f<0x143>(b, 0.0f));      // row_bcast:31: lane 63 holds the wave's sum
-                        const float bound = __fmul_rn(readlane_f(b, 63), 1.0001f);
-                        const float thr_u = readlane_f(ls4[u >> 2], (u & 3) * 16 + kk - 1);
-                        if (bound > 0.0f && !(thr_u >= 0.0f && bound <= thr_u)) all_skip = false;
-                    });
-                    // resident layout: a tile that is closed at the first level for all of the wave's users -- when every
-                    // fragment from here on is, too (sfx_frag), the wave's lists are final
-                    if (!open1 && resident && exit_on) {
-                        const float sfx = readlane_f(sfx_frag, g);
-                        if (!__ballot(lane < UW && l1v > 0.0f && !(thrv >= 0.0f && __fmul_rn(l1v, sfx) <= thrv))) {
+        for (int g = 0; g < n_frags; ++g, fr = fr_next) {
+            fr_next = load_frag(min(g + 1, n_frags - 1));         // in flight while fragment g is worked on
+            while (g >= t_hi) {                                   // fragment g opens the next super-tile
+                ++sup; kb_cur = kb_next; t_hi = t_hi_next;
+                kb_next = c_st_kb[min(sup + 1, a.n_super)]; t_hi_next = c_st_tile[min(sup + 2, a.n_super)];
+            }
+            const bool in_head = g < g_head;
+            // fragment g's rows: in the head's LDS image, or in wd (the address a gathered row is fetched from)
+            const unsigned char *wlane = head + (static_cast<size_t>(kb_cur - kb0) << 10) + lane16;
+            const unsigned char *gsrc = reinterpret_cast<const unsigned char *>(a.wd) + (static_cast<size_t>(kb_cur) << 10);
+            const int ft = fr.ft;
+            const int t = ft & 0xffffff;                         // the tile this fragment belongs to
+            // ---- tile-major sweep: every row of W that holds a weight in this tile (and that one of the wave's
+            //      users rates) is read from LDS ONCE and applied to all eight users: acc_u += x_u * w, one
+            //      rounded product and one rounded add per column (two v_pk_mul_f32 + two v_pk_add_f32 per user
+            //      and 256 columns), rows ascending = scipy's order.  A user that does not rate the row has
+            //      x_u = 0: x * w = +-0 changes no sum (a sum that starts at +0 never becomes -0), and the same
+            //      holds for rows and blocks that are skipped altogether. ----
+            const int toff = fr.toff;
+            if (ft & (1 << 24)) {                                // first fragment of a tile
+                // ---- can this tile matter at all?  Its header holds max |w| of every row of W over the tile's
+                //      columns (lane f = row 64 h + f), so  B_u = sum_f |x_uf| max|w_f|  bounds every score user u
+                //      can have in it, rounding of the float32 sums included in the 1e-4 margin.  A column enters a
+                //      list only by BEATING the user's (k+1)-th best: when B_u <= that for all eight users the
+                //      sweep, the selection and the tile's further fragments are skipped -- after the heavy first
+                //      tiles that is the fate of nine tiles in ten (ML-20M shape). ----
+                // first level, all eight users in one compare: (sum_f |x_uf|) * max_f max|w_f| -- decides 86 % of
+                // the (wave, tile) pairs on the ML-20M shape; only the others read the header and pay the per-user
+                // reductions below.  max_f max|w_f| (times the margin) is a constant of W: the layout stores it
+                // per fragment (frag_wtop) instead of every wave reducing the header again for every job
+                const float wtop = fr.wtop;
+                // (a user with NO rating on a row of W -- an empty row, a position past the end of the batch in the last job --
+                // has bound 0: every sum is +0, no candidate; it must not hold the tile open while its list is empty.  Such a
+                // slot used to keep its wave sweeping EVERY tile: a batch whose size is no multiple of the job size paid one
+                // unpruned wave at its end, 0.06-0.09 ms whatever its size -- tools/row_slice_probe.py, round 4)
+                const unsigned long long open1 = __ballot(lane < UW && l1v > 0.0f && !(thrv >= 0.0f && __fmul_rn(l1v, wtop) <= thrv));
+                bool all_skip = true;
+                float wm[XR];
+                // (behind the head the header is an ordinary load: no row of the ring is in flight between two tiles, so
+                // the wait for it waits for nothing else)
+                if (open1) fr_static_for<XR>([&](auto H) {
+                    const int o = toff - kFrTileHeaderBytes + (H() * 64 + lane) * 4;
+                    if (in_head) wm[H()] = *(fr_lds_f32 *)(wlane - lane16 + o);
+                    else wm[H()] = *(fr_glb_f32 *)(gsrc + o);
+                });
+                if (open1) fr_static_for<UW>([&](auto Uc) {
+                    constexpr int u = decltype(Uc)::value;
+                    float b = __fmul_rn(fabsf(xr[u][0]), wm[0]);
+                    if constexpr (XR == 2) b = __fadd_rn(b, __fmul_rn(fabsf(xr[u][1]), wm[1]));
+                    b = __fadd_rn(b, fr_dpp_f<0x111>(b, 0.0f));
+                    b = __fadd_rn(b, fr_dpp_f<0x112>(b, 0.0f));
+                    b = __fadd_rn(b, fr_dpp_f<0x114>(b, 0.0f));
+                    b = __fadd_rn(b, fr_dpp_f<0x118>(b, 0.0f));
+                    b = __fadd_rn(b, fr_dpp_f<0x142>(b, 0.0f));      // row_bcast:15
+                    b = __fadd_rn(b, fr_dpp_f<0x143>(b, 0.0f));      // row_bcast:31: lane 63 holds the wave's sum
+                    const float bound = __fmul_rn(readlane_f(b, 63), 1.0001f);
+                    const float thr_u = readlane_f(ls4[u >> 2], (u & 3) * 16 + kk - 1);
+                    if (bound > 0.0f && !(thr_u >= 0.0f && bound <= thr_u)) all_skip = false;
+                });
+                // a tile that is closed at the first level for all of the wave's users -- when every fragment from here
+                // on is, too (sfx), the wave's lists are final
+                if (!open1 && exit_on) {
+                    const float sfx = __int_as_float(readfirst_i(__float_as_int(s_sfx[g])));
+                    if (!__ballot(lane < UW && l1v > 0.0f && !(thrv >= 0.0f && __fmul_rn(l1v, sfx) <= thrv))) {
 #ifdef SCORE_PROFILE
-                            pf_depth_ = g;
+                        pf_depth_ = g;
 #endif
-                            break;
-                        }
+                        break;
                     }
-                    tile_skip = all_skip;
-                    if (!tile_skip) fr_static_for<UW>([&](auto Uc) { acc[decltype(Uc)::value] = vec(0.0f); });
                 }
-                if (tile_skip) continue;
+                tile_skip = all_skip;
+                if (!tile_skip) fr_static_for<UW>([&](auto Uc) { acc[decltype(Uc)::value] = vec(0.0f); });
+            }
+            if (tile_skip) continue;
+            // one sweep step: rows f[0] < f[1] of half h (w[1] = +0.0 when the half has no second row left) applied to every user
+            auto apply = [&](auto H, const int (&f)[kFrStep], const vec (&w)[kFrStep]) {
+                constexpr int h = decltype(H)::value;
+#pragma unroll
+                for (int q = 0; q < kFrStep; ++q) {
+                    fr_static_for<UW>([&](auto Uc) {
+                        constexpr int u = decltype(Uc)::value;
+                        acc[u] = acc[u] + w[q] * readlane_f(xr[u][h], f[q]);
+                    });
+                }
+            };
+            if (in_head) {
                 int below = 0;                                   // rows of this tile's slice before half h
                 fr_static_for<XR>([&](auto H) {
                     constexpr int h = decltype(H)::value;
@@ -1616,170 +1641,198 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                             w[q] = *reinterpret_cast<const vec *>(src);
                         }
                         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int q = 0; q < kFrStep; ++q) {
-                            fr_static_for<UW>([&](auto Uc) {
-                                constexpr int u = decltype(Uc)::value;
-                                acc[u] = acc[u] + w[q] * readlane_f(xr[u][h], f[q]);
-                            });
-                        }
+                        apply(H, f, w);
                         PF_ADD(PF_N_DENSE, kFrStep)
                     }
                     below += static_cast<int>(__builtin_popcountll(nz));
                 });
-
-                if (!(ft & (1 << 25))) continue;                 // the tile's slice continues in the next super-tile
-                // ---- candidates, user after user: columns that beat the user's kk-th score and are not interacted ----
-                fr_static_for<UW>([&](auto Uc) {
-                    constexpr int u = decltype(Uc)::value;
-                    constexpr int g = u >> 2, lb = (u & 3) * 16;
-                    float best = acc[u][0];
-                    fr_static_for<REGS>([&](auto Rc) { best = acc[u][Rc()] > best ? acc[u][Rc()] : best; });
-                    float thr = readlane_f(ls4[g], lb + kk - 1);      // the user's current kk-th best score
-                    float tcut = thr;
-                    if (thr >= 0.0f) {
-                        if (!__ballot(best > thr)) return;        // the common case after the first tiles: nothing enters
+            } else {
+                // ---- behind the head: the wave fetches the rows it sweeps, and only those, into its own ring.  A step is
+                //      two rows of one half, as above; its DPS LDS-DMA wave-instructions (1 KiB each: one row of a 256-column
+                //      tile, or both rows of a 128-column one -- lanes 0-31 the first, lanes 32-63 the second) fill slot
+                //      `step % NS`.  Up to NS steps are in flight; the reader is the issuing wave, so its own counted vmcnt
+                //      orders a slot's ds_read behind the DMA that filled it (RAW), and the lgkmcnt wait behind the reads of
+                //      a slot comes before the DMA that refills it (WAR).  No other vector load is issued in this span (W's
+                //      tables and the parked masks come by scalar loads), so the counts are exact.  A half with an odd
+                //      number of rows fetches its last row twice: every step is DPS instructions. ----
+                unsigned long long ir0 = fr.nz[0] & own_or[0], ir1 = 0ull;
+                if constexpr (XR == 2) ir1 = fr.nz[1] & own_or[1];
+                const int below1 = static_cast<int>(__builtin_popcountll(fr.nz[0]));
+                int n_issued = 0, n_read = 0;                    // steps
+                auto issue = [&]() {
+                    const bool second = XR == 2 && !ir0;
+                    unsigned long long r = second ? ir1 : ir0;
+                    if (!r) return;
+                    const unsigned long long nzh = second ? fr.nz[XR - 1] : fr.nz[0];
+                    const int pbase = second ? below1 : 0;
+                    const int f0 = __builtin_ctzll(r);
+                    r &= r - 1;
+                    const int p0 = pbase + static_cast<int>(__builtin_popcountll(nzh & ((1ull << f0) - 1ull)));
+                    int p1 = p0;
+                    if (r) {
+                        const int f1 = __builtin_ctzll(r);
+                        r &= r - 1;
+                        p1 = pbase + static_cast<int>(__builtin_popcountll(nzh & ((1ull << f1) - 1ull)));
                     }
-                    // the user's interacted columns in this tile, one 64-lane mask per register of the tile (see the setup)
-                    unsigned long long ex[REGS];
-                    fr_static_for<REGS>([&](auto Rc) { ex[Rc()] = 0ull; });
-                    if (a.filter) {
-                        const int n_a_u = readlane_i(na_l, u);
-                        if (!kFrOnDemand || n_a_u > kFrHeadEntries + kFrTailMax) {
-                            fr_const_u64 *mc = (fr_const_u64 *)(ms_wave + static_cast<size_t>(u) * mwords);
-                            fr_static_for<REGS>([&](auto Rc) { ex[Rc()] = mc[t * REGS + Rc()]; });
-                        } else {
-                            unsigned long long *mx = reinterpret_cast<unsigned long long *>(cp + kFrCandCap);
-                            if (lane < REGS) mx[lane] = 0ull;
-                            auto put = [&](int c) {
-                                if (c >= 0 && c / TC == t) {
-                                    const int cl = c & (TC - 1);
-                                    atomicOr(&mx[cl & (REGS - 1)], 1ull << (cl / REGS));
-                                }
-                            };
-                            put(cm0[u]);
-                            put(cm1[u]);
-                            const uint32_t *tail_u = xs_wave + u * kFrUserWords;
-                            for (int b = kFrHeadEntries; b < n_a_u; b += 64) {
-                                int c = -1;
-                                if (b + lane < n_a_u)
-                                    c = static_cast<int>(__hip_atomic_load(&tail_u[b + lane - kFrHeadEntries], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                                put(c);
-                            }
-                            fr_static_for<REGS>([&](auto Rc) {
-                                const unsigned long long v = mx[Rc()];       // LDS operations of one wave execute in order
-                                ex[Rc()] = (static_cast<unsigned long long>(readfirst_i(static_cast<int>(v >> 32))) << 32) |
-                                           static_cast<unsigned int>(readfirst_i(static_cast<int>(v & 0xffffffffull)));
-                            });
-                        }
+                    if (second) ir1 = r; else ir0 = r;
+                    unsigned char *slot = ring + (n_issued & (NS - 1)) * STEPB;
+                    const unsigned char *rows0 = gsrc + toff;
+                    // (the lane's 16 bytes of a 1 KiB instruction, as an unsigned 32-bit offset from the row's uniform address)
+                    if constexpr (REGS == 4) {
+                        __builtin_amdgcn_global_load_lds((fr_glb_void *)(rows0 + p0 * ROWB + static_cast<size_t>(lane16)), (fr_lds_void *)slot, 16, 0, 0);
+                        __builtin_amdgcn_global_load_lds((fr_glb_void *)(rows0 + p1 * ROWB + static_cast<size_t>(lane16)), (fr_lds_void *)(slot + ROWB), 16, 0, 0);
+                    } else {
+                        const int p = lane < 32 ? p0 : p1;
+                        __builtin_amdgcn_global_load_lds((fr_glb_void *)(rows0 + p * ROWB + static_cast<size_t>((lane & 31u) * 16u)), (fr_lds_void *)slot, 16, 0, 0);
                     }
-                    if (thr == ninf) {
-                        // The list is not full yet (first tile, or a user with few scored columns): everything
-                        // non-zero would pass.  Take the tile's own kk-th best admissible score (a bound from the
-                        // lane maxima) as the cut instead.
-                        PF_ADD(PF_N_OVERFLOW, 1)
-                        float bm = ninf;
-                        fr_static_for<REGS>([&](auto Rc) {
-                            constexpr int r = decltype(Rc)::value;
-                            const float v = acc[u][r];
-                            const float vm = (v != 0.0f && !((ex[r] >> lane) & 1ull)) ? v : ninf;
-                            bm = vm > bm ? vm : bm;
+                    ++n_issued;
+                };
+#pragma unroll
+                for (int i = 0; i < NS; ++i) issue();
+                fr_static_for<XR>([&](auto H) {
+                    constexpr int h = decltype(H)::value;
+                    unsigned long long rows = fr.nz[h] & own_or[h];
+                    while (rows) {
+                        int f[kFrStep];
+                        vec w[kFrStep];
+                        f[0] = __builtin_ctzll(rows);
+                        rows &= rows - 1;
+                        const bool live1 = rows != 0ull;
+                        f[1] = live1 ? __builtin_ctzll(rows) : 0;
+                        rows &= rows - 1;              // 0 stays 0
+                        // RAW: this step has landed once only the DMAs of the steps issued behind it are outstanding
+                        const int ahead = n_issued - n_read - 1;
+                        fr_static_for<NS>([&](auto Ac) {
+                            if (ahead == decltype(Ac)::value) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(decltype(Ac)::value * DPS) : "memory");
                         });
-                        // kk-th largest of the 64 lane maxima (the 16 quad maxima would do as a bound, but a loose one:
-                        // half the tile can lie above it); -inf: fewer than kk lanes hold a score, and everything
-                        // they hold (< kk * REGS <= kFrCandCap) fits the buffer
-                        const float t0 = fr_kth_lane_best(bm, 64 + kk);
-                        if (t0 != ninf) tcut = float_prev(t0);      // candidates are the values >= t0
+                        const unsigned char *slot = ring + (n_read & (NS - 1)) * STEPB + lane16;
+                        w[0] = *reinterpret_cast<const vec *>(slot);
+                        w[1] = *reinterpret_cast<const vec *>(live1 ? slot + ROWB : wzero);
+                        ++n_read;
+                        // WAR: the slot's reads are back before the DMA that refills it is issued
+                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                        issue();
+                        __builtin_amdgcn_sched_barrier(0);
+                        apply(H, f, w);
+                        PF_ADD(PF_N_DENSE, kFrStep) PF_ADD(PF_N_GATHER, kFrStep)
                     }
-                    int nc = 0;
-                    const int rel = lane - lb;
-                    const bool in = rel >= 0 && rel < kk;
-                    // merge the buffered candidates into the user's list (lane lb + j = rank j)
-                    auto merge = [&]() {
-                        const float myv = lane < nc ? cv[lane] : ninf;
-                        const int mycol = lane < nc ? cp[lane] : 0;
-                        for (int i = 0; i < nc; ++i) {
-                            const float v = readlane_f(myv, i);
-                            const int col = readlane_i(mycol, i);
-                            const float s = ls4[g];
-                            const int c = lc4[g];
-                            PF_ADD(PF_N_SPARSE_CHUNKS, 1)
-                            if (!(v > readlane_f(s, lb + kk - 1))) continue;            // the threshold has risen meanwhile
-                            // ties inside the fast pass order by higher column; exact ties are re-scored anyway
-                            const bool better = in && ((s > v) || (s == v && c > col));
-                            const int pos = static_cast<int>(__builtin_popcountll(__ballot(better)));
-                            PF_ADD(PF_N_SPARSE_ROWS, 1)
-                            const float s_up = fr_row_shift_up(s, ninf);
-                            const int c_up = fr_row_shift_up(c, -1);
-                            ls4[g] = !in || rel < pos ? s : (rel == pos ? v : s_up);
-                            lc4[g] = !in || rel < pos ? c : (rel == pos ? col : c_up);
+                });
+            }
+
+            if (!(ft & (1 << 25))) continue;                 // the tile's slice continues in the next super-tile
+            // ---- candidates, user after user: columns that beat the user's kk-th score and are not interacted ----
+            fr_static_for<UW>([&](auto Uc) {
+                constexpr int u = decltype(Uc)::value;
+                constexpr int g = u >> 2, lb = (u & 3) * 16;
+                float best = acc[u][0];
+                fr_static_for<REGS>([&](auto Rc) { best = acc[u][Rc()] > best ? acc[u][Rc()] : best; });
+                float thr = readlane_f(ls4[g], lb + kk - 1);      // the user's current kk-th best score
+                float tcut = thr;
+                if (thr >= 0.0f) {
+                    if (!__ballot(best > thr)) return;        // the common case after the first tiles: nothing enters
+                }
+                // the user's interacted columns in this tile, one 64-lane mask per register of the tile (see the setup)
+                unsigned long long ex[REGS];
+                fr_static_for<REGS>([&](auto Rc) { ex[Rc()] = 0ull; });
+                if (a.filter) {
+                    const int n_a_u = readlane_i(na_l, u);
+                    if (!kFrOnDemand || n_a_u > kFrHeadEntries + kFrTailMax) {
+                        fr_const_u64 *mc = (fr_const_u64 *)(ms_wave + static_cast<size_t>(u) * mwords);
+                        fr_static_for<REGS>([&](auto Rc) { ex[Rc()] = mc[t * REGS + Rc()]; });
+                    } else {
+                        unsigned long long *mx = reinterpret_cast<unsigned long long *>(cp + kFrCandCap);
+                        if (lane < REGS) mx[lane] = 0ull;
+                        auto put = [&](int c) {
+                            if (c >= 0 && c / TC == t) {
+                                const int cl = c & (TC - 1);
+                                atomicOr(&mx[cl & (REGS - 1)], 1ull << (cl / REGS));
+                            }
+                        };
+                        put(cm0[u]);
+                        put(cm1[u]);
+                        const uint32_t *tail_u = xs_wave + u * kFrUserWords;
+                        for (int b = kFrHeadEntries; b < n_a_u; b += 64) {
+                            int c = -1;
+                            if (b + lane < n_a_u)
+                                c = static_cast<int>(__hip_atomic_load(&tail_u[b + lane - kFrHeadEntries], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                            put(c);
                         }
-                        nc = 0;
-                        const float thr_new = readlane_f(ls4[g], lb + kk - 1);
-                        thrv = lane == u ? thr_new : thrv;
-                    };
+                        fr_static_for<REGS>([&](auto Rc) {
+                            const unsigned long long v = mx[Rc()];       // LDS operations of one wave execute in order
+                            ex[Rc()] = (static_cast<unsigned long long>(readfirst_i(static_cast<int>(v >> 32))) << 32) |
+                                       static_cast<unsigned int>(readfirst_i(static_cast<int>(v & 0xffffffffull)));
+                        });
+                    }
+                }
+                if (thr == ninf) {
+                    // The list is not full yet (first tile, or a user with few scored columns): everything
+                    // non-zero would pass.  Take the tile's own kk-th best admissible score (a bound from the
+                    // lane maxima) as the cut instead.
+                    PF_ADD(PF_N_OVERFLOW, 1)
+                    float bm = ninf;
                     fr_static_for<REGS>([&](auto Rc) {
                         constexpr int r = decltype(Rc)::value;
                         const float v = acc[u][r];
-                        // only non-zero sums compete (scipy keeps `!= 0`)
-                        unsigned long long m = __ballot(v > tcut && v != 0.0f);
-                        if (!m) return;
-                        m &= ~ex[r];
-                        if (!m) return;
-                        const int cnt = static_cast<int>(__builtin_popcountll(m));
-                        if (nc + cnt > kFrCandCap) merge();      // the buffer holds one ballot's worth (64): make room first
-                        if ((m >> lane) & 1ull) {
-                            const int pos = nc + lane_prefix(m);
-                            cv[pos] = v;
-                            cp[pos] = t * TC + lane * REGS + r;
-                        }
-                        nc += cnt;
+                        const float vm = (v != 0.0f && !((ex[r] >> lane) & 1ull)) ? v : ninf;
+                        bm = vm > bm ? vm : bm;
                     });
-                    if (nc > 0) merge();
+                    // kk-th largest of the 64 lane maxima (the 16 quad maxima would do as a bound, but a loose one:
+                    // half the tile can lie above it); -inf: fewer than kk lanes hold a score, and everything
+                    // they hold (< kk * REGS <= kFrCandCap) fits the buffer
+                    const float t0 = fr_kth_lane_best(bm, 64 + kk);
+                    if (t0 != ninf) tcut = float_prev(t0);      // candidates are the values >= t0
+                }
+                int nc = 0;
+                const int rel = lane - lb;
+                const bool in = rel >= 0 && rel < kk;
+                // merge the buffered candidates into the user's list (lane lb + j = rank j)
+                auto merge = [&]() {
+                    const float myv = lane < nc ? cv[lane] : ninf;
+                    const int mycol = lane < nc ? cp[lane] : 0;
+                    for (int i = 0; i < nc; ++i) {
+                        const float v = readlane_f(myv, i);
+                        const int col = readlane_i(mycol, i);
+                        const float s = ls4[g];
+                        const int c = lc4[g];
+                        PF_ADD(PF_N_SPARSE_CHUNKS, 1)
+                        if (!(v > readlane_f(s, lb + kk - 1))) continue;            // the threshold has risen meanwhile
+                        // ties inside the fast pass order by higher column; exact ties are re-scored anyway
+                        const bool better = in && ((s > v) || (s == v && c > col));
+                        const int pos = static_cast<int>(__builtin_popcountll(__ballot(better)));
+                        PF_ADD(PF_N_SPARSE_ROWS, 1)
+                        const float s_up = fr_row_shift_up(s, ninf);
+                        const int c_up = fr_row_shift_up(c, -1);
+                        ls4[g] = !in || rel < pos ? s : (rel == pos ? v : s_up);
+                        lc4[g] = !in || rel < pos ? c : (rel == pos ? col : c_up);
+                    }
+                    nc = 0;
+                    const float thr_new = readlane_f(ls4[g], lb + kk - 1);
+                    thrv = lane == u ? thr_new : thrv;
+                };
+                fr_static_for<REGS>([&](auto Rc) {
+                    constexpr int r = decltype(Rc)::value;
+                    const float v = acc[u][r];
+                    // only non-zero sums compete (scipy keeps `!= 0`)
+                    unsigned long long m = __ballot(v > tcut && v != 0.0f);
+                    if (!m) return;
+                    m &= ~ex[r];
+                    if (!m) return;
+                    const int cnt = static_cast<int>(__builtin_popcountll(m));
+                    if (nc + cnt > kFrCandCap) merge();      // the buffer holds one ballot's worth (64): make room first
+                    if ((m >> lane) & 1ull) {
+                        const int pos = nc + lane_prefix(m);
+                        cv[pos] = v;
+                        cp[pos] = t * TC + lane * REGS + r;
+                    }
+                    nc += cnt;
                 });
-            }
-            PF_MARK(PF_DENSE)
-            if (!resident) {
-                // ---- the vote: does this wave need super-tile s+1 (bit 0), s+2 (bit 1) or anything behind them?  The first-level
-                //      test of the tile loop with the suffix bound in place of a tile's own; a wave whose open tile continues
-                //      in s+1 needs both.  A list that never fills (thrv = -inf) keeps the job running to the end of W, a slot
-                //      without ratings (l1v = 0) never does.  One word per super-tile, OR-ed before the barrier that is here
-                //      anyway and read by every wave after it: all of them take the same decision.  Bit 1 decides whether
-                //      s+2 is staged at all: when no wave sets it, none can set bit 0 at the end of s+1 (sfx[s+2] covers the
-                //      continuation of every tile that starts in s+1, thresholds only rise), so the job ends there with no
-                //      LDS-DMA in flight.  When only the thresholds of s itself close the job, s+1 has been staged for
-                //      nothing; the wait below covers it. ----
-                if (exit_on && !wave_done) {
-                    const bool cont = !tile_skip && !(ft_last & (1 << 25));
-                    const float sfx1 = s_sfx[sidx + 1], sfx2 = s_sfx[min(sidx + 2, a.n_super)];
-                    const bool live = lane < UW && l1v > 0.0f;
-                    const bool need1 = cont || __ballot(live && !(thrv >= 0.0f && __fmul_rn(l1v, sfx1) <= thrv)) != 0ull;
-                    const bool need2 = cont || __ballot(live && !(thrv >= 0.0f && __fmul_rn(l1v, sfx2) <= thrv)) != 0ull;
-                    if (need1 && lane == 0) atomicOr(&s_vote[sidx], need2 ? 3 : 1);
-                    wave_done = !need1;
-                }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // super-tile s+1 has landed ...
-                __syncthreads();                                    // ... and every wave has left super-tile s
-            }
-            PF_MARK(PF_GROUP)
-            if (!resident && exit_on) {
-                const int vote = readfirst_i(s_vote[sidx]);
-                if (!(vote & 1)) {
-#ifdef SCORE_PROFILE
-                    pf_depth_ = sidx + 1;
-#endif
-                    break;
-                }
-                stage_next = (vote & 2) != 0;
-            }
-            kb_a = kb_b; kb_b = kb_c; t_lo = t_hi; t_hi = t_hi_next;
+                if (nc > 0) merge();
+            });
         }
+        PF_MARK(PF_DENSE)
 #ifdef SCORE_PROFILE
-        // super-tiles a streaming job worked on / fragment at which a resident wave left (n_frags: it went to the end)
-        if (lane == 0 && (resident || wave == 0)) {
-            if (pf_depth_ < 0) pf_depth_ = n_frags;
-            atomicAdd(&g_fr_exit_depth[min(pf_depth_, kFrExitSlots)], 1u);
-        }
+        // fragment at which the wave left its job (n_frags: it went to the end of W)
+        if (lane == 0) atomicAdd(&g_fr_exit_depth[min(pf_depth_, kFrExitSlots)], 1u);
 #endif
 
         // ---- the lists are the rows' answers: lane lb + j of list register g = rank j of user 4 g + lb / 16 ----
@@ -2003,6 +2056,7 @@ struct FrLayout {
     unsigned long long *scratch = nullptr; size_t scratch_bytes = 0;
     int consecutive = 0;
     int users_per_wave = 0;      // 8 / 4 / 2 forces the kernel form; 0: by batch size
+    int head_kib = -1;           // >= 0 caps the resident head (KiB; 0: every row is gathered); -1: what the LDS leaves
 };
 size_t fr_scratch_bytes(int n_tiles, int tile_cols) {
     const int regs = tile_cols / 64;
@@ -2016,10 +2070,7 @@ bool fr_usable(const FrLayout &F, int kk) {
     if (F.rows <= 0 || F.rows > kFrMaxRows || F.n_tiles <= 0 || F.n_tiles * regs > kFrMaskWords) return false;
     if (F.n_frags < F.n_tiles || F.n_super <= 0 || F.n_super > F.n_frags) return false;
     if (F.buf_bytes <= 0 || (F.buf_bytes & 1023)) return false;
-    const int regs_ = F.tile_cols / 64;
-    const bool resident = F.n_super == 1 && F.n_tiles <= 64 && fr_lds_bytes(F.buf_bytes, true, F.n_tiles * regs_) <= 160u * 1024u;
-    // streaming: two 8-wave workgroups per CU, each with two slice buffers (the second doubles as 4 KiB of setup scratch per wave)
-    if (!resident && (F.buf_bytes < kFrWavesStream * kFrWaveScratch || 2 * fr_lds_bytes(F.buf_bytes) > 160u * 1024u)) return false;
+    // (any W whose tables are sound can run: what does not fit the head is gathered row by row)
     if (F.scratch_bytes < fr_scratch_bytes(F.n_tiles, F.tile_cols)) return false;
     return kk >= 1 && kk <= kFrMaxKk;
 }
@@ -2087,7 +2138,7 @@ int score_impl(const ScoreArgs &base, int top_k, int acc_bytes, int32_t *d_out_i
         f.xb_ptr = a.xb_ptr; f.xb_col = a.xb_col; f.xb_val = a.xb_val; f.n_items = a.n_items;
         f.fmap = FR.fmap; f.col_map = FR.col_map; f.col_ids = FR.col_ids; f.tile_rows = FR.tile_rows;
         f.n_cols = a.n_cols; f.R = FR.rows; f.n_tiles = FR.n_tiles; f.wd = FR.wd;
-        f.tile_off = FR.tile_off; f.st_kb = FR.st_kb; f.st_tile = FR.st_tile; f.n_super = FR.n_super; f.buf_bytes = FR.buf_bytes;
+        f.tile_off = FR.tile_off; f.st_kb = FR.st_kb; f.st_tile = FR.st_tile; f.n_super = FR.n_super;
         f.frag_tile = FR.frag_tile;
         f.consecutive = FR.consecutive;
         f.mscratch = FR.scratch;
@@ -2095,25 +2146,24 @@ int score_impl(const ScoreArgs &base, int top_k, int acc_bytes, int32_t *d_out_i
         f.out_id = d_out_ids; f.out_score = d_out_scores; f.out_aux = d_out_aux; f.out_cnt = d_out_count;
         f.flag_list = flag_list; f.flag_len = flag_len; f.queue = queue;
         f.tie_list = reinterpret_cast<int *>(ws + L.tie_list); f.tie_len = reinterpret_cast<int *>(ws + L.flag_len) + 1;
-        // all slices in one super-tile that fits next to the setup scratch: W stays in LDS for the life of a 16-wave
-        // workgroup; otherwise two 8-wave workgroups per CU stream the super-tiles (one computes while the other sets a
-        // job up or waits at a super-tile barrier)
-        f.resident = (FR.n_super == 1 && FR.n_tiles <= 64 &&
-                      fr_lds_bytes(FR.buf_bytes, true, FR.n_tiles * (FR.tile_cols / 64)) <= 160u * 1024u) ? 1 : 0;
-        const int nw = f.resident ? kFrWaves : kFrWavesStream;
-        const int max_grid = f.resident ? 256 : 512;
+        // one 16-wave workgroup per CU; fr_lds_plan divides its LDS between the resident head of W and the waves' rings
+        const FrLds plan = fr_lds_plan(FR.n_super, FR.n_tiles, FR.tile_cols / 64, FR.n_frags, FR.buf_bytes, FR.head_kib);
+        f.head_kib = plan.head_kib; f.wave_scratch = plan.wave_scratch; f.exit_frags = plan.exit_frags;
+        const bool all_resident = plan.wave_scratch != kFrWaveScratch || FR.n_super * (FR.buf_bytes >> 10) <= plan.head_kib;
+        const int nw = kFrWaves;
+        const int max_grid = 256;
         // users per wave: 8 when that still gives every workgroup slot a few jobs, else 4, else 2 (FR.users_per_wave forces one)
         const long long slots_rows = static_cast<long long>(max_grid) * nw;            // rows per round at one user per wave
-        // (round 4: the STREAMING layout takes 8 users per wave only from ~393k rows on -- a launch cannot be shorter than a few
-        // jobs, and a 64-user job sweeps every super-tile of W: 1M x 500k shape, 125k rows (one of 8 row shards): 0.91 -> 0.62 ms
-        // with 4 per wave, 250k rows 1.22 -> 1.02 ms; ML-20M shape, all 138k rows 1.42 -> 1.39 ms; tools/fr_uw_sweep.py,
-        // profiles/r04_fr_uw_sweep_*.json.  The resident layout's waves claim jobs on their own and keep 8 from 98k rows.)
-        const long long uw8_min = f.resident ? 24 : 96;
+        // (round 4: a W that is not all resident takes 8 users per wave only from ~393k rows on -- a launch cannot be shorter than
+        // a few jobs, and the more users a wave holds the more tiles it opens: 1M x 500k shape, 125k rows (one of 8 row shards):
+        // 0.91 -> 0.62 ms with 4 per wave, 250k rows 1.22 -> 1.02 ms; ML-20M shape, all 138k rows 1.42 -> 1.39 ms;
+        // tools/fr_uw_sweep.py, profiles/r04_fr_uw_sweep_*.json.  An all-resident W keeps 8 from 98k rows.)
+        const long long uw8_min = all_resident ? 24 : 96;
         int uw = a.n_rows >= uw8_min * slots_rows ? 8 : (a.n_rows >= 6 * slots_rows ? 4 : 2);
         if (FR.users_per_wave == 8 || FR.users_per_wave == 4 || FR.users_per_wave == 2) uw = FR.users_per_wave;
         const int n_jobs = (a.n_rows + uw * nw - 1) / (uw * nw);
         const unsigned grid = static_cast<unsigned>(n_jobs < max_grid ? n_jobs : max_grid);
-        const size_t lds = f.resident ? fr_lds_bytes(FR.buf_bytes, true, FR.n_tiles * (FR.tile_cols / 64)) : fr_lds_bytes(FR.buf_bytes);
+        const size_t lds = fr_lds_bytes(plan.head_kib, plan.wave_scratch, plan.exit_frags);
         const bool two = FR.rows > 64;
 #define RTREC_FR_LAUNCH(REGS_, XR_)                                                                                            \
         do {                                                                                                                   \
@@ -2312,6 +2362,16 @@ extern "C" size_t rtrec_slim_score_fr_scratch_bytes(int32_t fr_n_tiles, int32_t 
     return fr_scratch_bytes(fr_n_tiles, fr_tile_cols);
 }
 
+extern "C" size_t rtrec_slim_score_fr_lds_bytes(int32_t fr_n_super, int32_t fr_n_tiles, int32_t fr_tile_cols, int32_t fr_n_frags,
+                                                int32_t fr_buf_bytes, int32_t head_kib_cap, int32_t *head_kib, int32_t *wave_scratch) {
+    if (fr_n_super <= 0 || fr_n_tiles <= 0 || fr_n_frags < fr_n_tiles || (fr_tile_cols != 256 && fr_tile_cols != 128) ||
+        fr_buf_bytes <= 0 || (fr_buf_bytes & 1023) || fr_n_tiles * (fr_tile_cols / 64) > kFrMaskWords) return 0;
+    const FrLds plan = fr_lds_plan(fr_n_super, fr_n_tiles, fr_tile_cols / 64, fr_n_frags, fr_buf_bytes, head_kib_cap);
+    if (head_kib) *head_kib = plan.head_kib;
+    if (wave_scratch) *wave_scratch = plan.wave_scratch;
+    return fr_lds_bytes(plan.head_kib, plan.wave_scratch, plan.exit_frags);
+}
+
 extern "C" size_t rtrec_slim_score_sg_scratch_bytes(int32_t n_items, int32_t sg_n_tiles, int32_t sg_tile_cols) {
     if (n_items <= 0 || sg_n_tiles <= 0 || sg_tile_cols <= 0) return 0;
     return sg_heavy_scratch_bytes(n_items, sg_n_tiles, sg_tile_cols);
@@ -2385,6 +2445,7 @@ extern "C" int rtrec_slim_score_topk_opt(int32_t n_rows, const int32_t *d_row_id
         FR.scratch = static_cast<unsigned long long *>(opts->d_fr_scratch); FR.scratch_bytes = opts->fr_scratch_bytes;
         FR.order = opts->d_row_order; FR.consecutive = (opts->d_row_order && opts->row_order_grouped) ? 1 : 0;
         FR.users_per_wave = (opts->diagnostics >> 8) & 0xf;
+        FR.head_kib = ((opts->diagnostics >> 24) & 0x7f) - 1;       // bits 24-30: head cap in KiB + 1 (0: none)
         FR.col_ids = opts->d_fr_col_ids; FR.col_map = opts->d_fr_col_map;
         FR.tile_rows = reinterpret_cast<const unsigned long long *>(opts->d_fr_tile_rows);
         if (FR.n_tiles != (n_cols + FR.tile_cols - 1) / (FR.tile_cols > 0 ? FR.tile_cols : 1)) return RTREC_ERR_INVALID_ARG;

@@ -157,6 +157,7 @@ class SlimEngine:
         # ablation switches of tools/score_ablate.sh: only a diagnostic build of the library looks at them
         self.diagnostics = int(settings.raw("RTREC_AMD_ABLATE", "0")) & 0xff
         self.fr_users_per_wave = int(settings.raw("RTREC_AMD_FR_USERS", "0"))      # 8 / 4 / 2: force the feature-row kernel's form
+        self.fr_head_kib = int(settings.raw("RTREC_AMD_FR_HEAD_KIB", "-1"))        # 0 .. 126: cap of the feature-row kernel's resident head
         self.native_seg_builder = settings.raw("RTREC_AMD_NATIVE_SEG_BUILD", "1") != "0"   # csrc/seg_build.hip (else tensor ops)
         self.FR_SMALL_BATCH = int(settings.raw("RTREC_AMD_FR_SMALL_BATCH", self.FR_SMALL_BATCH))     # A/B: segments for larger passes
         self.f64_refine = settings.raw("RTREC_AMD_F64_REFINE", "1") != "0"      # float64 W: float32 fast pass + float64 refine
@@ -978,7 +979,8 @@ class SlimEngine:
         timer = diagnostics = 0
         if dominant:
             timer = self.score_timer
-            diagnostics = self.diagnostics | ((self.fr_users_per_wave & 0xf) << 8) | ((self.sg_heavy_min & 0xfff) << 12)
+            diagnostics = (self.diagnostics | ((self.fr_users_per_wave & 0xf) << 8) | ((self.sg_heavy_min & 0xfff) << 12)
+                           | ((min(self.fr_head_kib, 126) + 1 if self.fr_head_kib >= 0 else 0) << 24))
             self.last_score_path = ("feature_rows" if use_fr else ("segments" if use_sg else "tiled")) + path_suffix
         be.score_topk(*args, timer=timer, diagnostics=diagnostics, use_fr=use_fr, row_order=order, rescored=rescored,
                       row_order_grouped=(order is not None and use_fr and self._order_grouped), use_sg=use_sg,
@@ -1071,8 +1073,8 @@ class SlimEngine:
     rescored = None             # optional int32[1] device tensor: rows the exact-tie pass re-scored in the last call
 
     def _grouped_order(self, lay, n_rows: Optional[int] = None) -> bool:
-        """Pattern-sorted work order with eight consecutive rows per wave: for the STREAMING feature-row layout (C3:
-        2.37 -> 2.26 ms).  The resident layout keeps the longest-first order dealt out in strides: its waves claim jobs
+        """Pattern-sorted work order with eight consecutive rows per wave: for a feature-row layout of SEVERAL super-tiles,
+        whose rows behind the LDS head every wave gathers for itself (C3: 2.37 -> 2.26 ms).  The resident layout (all of W in LDS) keeps the longest-first order dealt out in strides: its waves claim jobs
         on their own, and evenly mixed jobs matter more there than small unions (C2: 0.41 ms against 0.57 ms grouped)."""
         host = (lay or {}).get("fr_host") or {}
         return bool(self.pattern_order and host and not host.get("fr_resident")
@@ -1083,7 +1085,7 @@ class SlimEngine:
 
     def _row_order(self, d_row_ids, n_rows: int, xb, lay=None, allow_grouped: bool = True):
         """Work order for the feature-row kernel (rtrec_score_opts.d_row_order).  Default: the batch's rows by descending
-        length.  Streaming layout (_grouped_order): a wave sweeps, per tile, the UNION of the rows of W its eight users
+        length.  Layout of several super-tiles (_grouped_order): a wave sweeps -- and, behind the LDS head, fetches --, per tile, the UNION of the rows of W its eight users
         rate, so users with the same rated feature items should share a wave -- the rows are sorted by their feature-row
         pattern as one big integer, the row of W that holds a weight in the most tiles most significant, descending
         (heavy patterns first: the tail of the launch is light): 13 % fewer swept rows on C3.  A function of X, the row set and

@@ -23,8 +23,9 @@ TABLE: Dict[str, tuple] = {
     "RTREC_AMD_FORCE_EXCHANGE": (None, "run the multi-GPU exchange with one rank (test aid)"),
     "RTREC_AMD_FEATURE_ROWS": ("1", "0: no feature-row kernel"),
     "RTREC_AMD_FR_USERS": ("0", "8 / 4 / 2: force the users-per-wave form of the feature-row kernel (0: from the batch size)"),
+    "RTREC_AMD_FR_HEAD_KIB": ("-1", "cap, in KiB, of the part of W the feature-row kernel keeps resident in LDS (0: every row is gathered; -1: what the LDS leaves); tests and A/B"),
     "RTREC_AMD_FR_SMALL_BATCH": ("513", "batches below this many rows are scored from the segment form even when W has a feature-row form"),
-    "RTREC_AMD_PATTERN_ORDER": ("1", "0: no pattern-grouped work order for the streaming feature-row layout"),
+    "RTREC_AMD_PATTERN_ORDER": ("1", "0: no pattern-grouped work order for a feature-row layout of several super-tiles"),
     "RTREC_AMD_SEG_LAYOUT": ("1", "0: no segment kernel for a general W (tiled-CSR kernel instead)"),
     "RTREC_AMD_SEG_CLUSTER": ("1", "0: segment layout in item-id column order instead of the clustered one"),
     "RTREC_AMD_SEG_HEAVY": ("1", "0: no workgroup-per-long-user pass"),

@@ -1,8 +1,12 @@
-"""Histogram of the depth at which the jobs of score_frows_kernel end: super-tiles worked on (streaming form) or the
-fragment at which a wave left (resident form; n_frags = it went to the end of W).
+"""Where the waves of score_frows_kernel leave their jobs, and what they swept on the way.
+
+Depth = the fragment at which a wave left its job (n_frags = it went to the end of W).  Beside the histogram the raw
+phase counters of the -DSCORE_PROFILE build are printed: wave ticks per phase, `n_dense` = (wave, row) pairs swept and
+`n_gather` = those of them that were fetched through the wave's row ring (the rows behind the resident head).
 
 usage: RTREC_AMD_LIB=<a -DSCORE_PROFILE build> python tools/fr_exit_depth.py [bench.py arguments]
-Runs bench.py in this process, then reads the library's counters (rtrec_amd_fr_exit_depth) and prints one JSON line."""
+Runs bench.py in this process, then reads the library's counters (rtrec_amd_fr_exit_depth, rtrec_amd_score_profile) and
+prints one JSON line."""
 import ctypes
 import json
 import os
@@ -10,6 +14,8 @@ import runpy
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PHASES = ["jobs", "rowptr", "hdr", "group", "dense", "sparse", "select", "emit", "reset", "queue",
+          "n_dense", "n_sparse_rows", "n_sparse_chunks", "n_overflow", "total", "n_gather"]
 
 
 def main():
@@ -32,8 +38,13 @@ def main():
         sys.exit("reading the counters failed")
     hist = {i: int(v) for i, v in enumerate(buf) if v}
     total = max(sum(hist.values()), 1)
-    print(json.dumps({"fr_exit_depth": {"jobs": total, "hist": hist,
-                                        "share": {i: round(v / total, 4) for i, v in hist.items()}}}), flush=True)
+    out = {"fr_exit_depth": {"jobs": total, "hist": hist, "share": {i: round(v / total, 4) for i, v in hist.items()}}}
+    prof = getattr(lib, "rtrec_amd_score_profile", None)
+    if prof is not None:                     # the timed steps' totals: bench.py reset them after its warm-up
+        raw = (ctypes.c_uint64 * 16)()
+        if prof(raw, 0) == 0:
+            out["score_profile_raw"] = dict(zip(PHASES, [int(x) for x in raw]))
+    print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":

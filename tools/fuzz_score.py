@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Randomised parity run of the score path (feature-row kernel: resident and streaming layouts, fragments, tile test,
+"""Randomised parity run of the score path (feature-row kernel: W all in the LDS head and W gathered behind it, fragments, tile test,
 exact-tie pass; segment kernels: wave per user and workgroup per user; SPARSE and DENSE mode; request-sized and full
 batches) against the C oracle: random numbers of rows of W, columns, densities, users, top_k, filter, integer / float /
 negative values, 256- and 128-column tiles.   python tools/fuzz_score.py --iters 60 --seed 1
