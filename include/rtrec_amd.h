@@ -539,6 +539,9 @@ int rtrec_store_decay_device(const double *d_val, const double *d_ts, int64_t n,
  * or float64 accumulation when acc_f64: then d_out_scores64 is required) and emits the best top_k:
  * d_out_ids / d_out_scores [n_rows][top_k] (-1 / -inf beyond min(top_k, n_cands)), d_out_count[n_rows].  Meant for
  * n_rows x n_cands of a request; rtrec_slim_score_topk in RTREC_TOPK_CANDIDATES mode serves bulk calls.
+ * A candidate whose score is NaN (an infinite rating against weights of both signs) is never listed: the row's count is then
+ * the number of candidates with a non-NaN score, at most top_k, and the slots behind it are padding.  A candidate id outside
+ * [0, n_items) scores 0 and competes with the id as given (the engine rejects such ids before the call).
  * ------------------------------------------------------------------------------------- */
 int rtrec_slim_score_candidates(int32_t n_rows, const int32_t *d_row_ids, const int32_t *d_xb_ptr, const int32_t *d_xb_col,
                                 const float *d_xb_val, int32_t n_x_rows, int32_t n_items, const int32_t *d_wc_ptr,

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void score_cands_kernel(
         __syncthreads();
         if (tid >= 64) { __syncthreads(); continue; }      // selection: wave 0 (the others wait at the row's last barrier)
         // ---- the best top_k, one by one: (score descending, position descending)
-        const int n_fin = min(top_k, n_cands);
+        int n_fin = min(top_k, n_cands);
         for (int r = 0; r < n_fin; ++r) {
             ACC best = static_cast<ACC>(0);
             int bp = -1;
@@ -97,6 +97,7 @@ __global__ __launch_bounds__(256) void score_cands_kernel(
                 const int op = shfl_xor_t(bp, m);
                 if (op >= 0 && (bp < 0 || ob > best || (ob == best && op > bp))) { best = ob; bp = op; }
             }
+            if (bp < 0) { n_fin = r; break; }              // only NaN scores are left (wave-uniform): the rest of the row is padding
             if (lane == 0) {
                 const long long o = static_cast<long long>(row) * top_k + r;
                 out_ids[o] = cands[bp];
