@@ -118,6 +118,18 @@ def cd(X_csc, y: np.ndarray, alpha=0.1, l1_ratio=0.1, tol=1e-4, max_iter=100,
     return w[:n_features], float(gap.value), int(n_iter)
 
 
+def feature_scores(X_csc, y: np.ndarray, skip_col: int) -> np.ndarray:
+    """X^T y of FeatureSelectionWrapper (slim_elastic.py:139-146) per item column, left to right in float32, with
+    `skip_col` (the target's own column) left at +0: scores[n_items]."""
+    n_users, n_items = X_csc.shape
+    d, i, p = _csc(X_csc)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    assert y.shape == (n_users,)
+    scores = np.empty(max(n_items, 1), dtype=np.float32)
+    lib().slim_oracle_feature_scores(n_items, d, i, p, y, int(skip_col), scores)
+    return scores[:n_items]
+
+
 def fit_columns_sgd(X_csc, cols, alpha=0.1, l1_ratio=0.1, eta0=0.001, tol=1e-4, max_iter=100, random_state=43,
                     nn_feature_selection=None):
     """optim="sgd" behind FeatureSelectionWrapper (slim_elastic.py:139-154, 209-222): per target column the K selected items
