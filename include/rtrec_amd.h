@@ -773,6 +773,51 @@ int rtrec_slim_audience_topk(int32_t n_q, const int32_t *d_items, int32_t n_user
                              int32_t *d_out_users, float *d_out_scores, int32_t *d_out_count, int32_t *d_out_eligible,
                              void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * RERANK PER-USER CANDIDATE LISTS  (an extension: the reference ranks one candidate list shared by all users,
+ * recommend_batch(candidate_item_ids); a two-stage recommender brings a list of its own per user -- from a retrieval stage, a
+ * learned ranker's feature request, a log of what was shown, "1 positive + 99 sampled negatives".)
+ * Job r scores the list d_ids[r * ids_stride + 0 .. list_k) (item ids; valid up to d_counts[r], clamped to [0, list_k]) for CSR
+ * row d_row_ids[r] of d_xb_* (row r when d_row_ids is NULL; float32 values, columns ascending; xb_nnz = length of d_xb_col /
+ * d_xb_val) against W in CSC form d_wc_* (d_wc_ptr[n_items + 1], rows ascending per column, float32 values; wc_nnz = length of
+ * d_wc_row / d_wc_val) -- the operands of rtrec_slim_explain_topk.
+ *   score(u, i)     the float32 sum of fl32(x_uj * w_ji) over the j stored in both row u of X and column i of W: each term is one
+ *                   rounded multiply (fused with nothing), each addition one rounded add, in ascending j, starting from +0.0f.
+ *                   This is the invariant of rtrec_slim_explain_topk, scipy's csr_matmat order for one output entry, hence the
+ *                   score rtrec_slim_score_topk / rtrec_slim_score_candidates report for the pair with a float32 W.  A pair
+ *                   with no common j scores +0.0f; so does a pair whose only term is -0.0f (0 + -0 = +0)
+ *   support         the number of common j
+ *   empty position  one at or beyond d_counts[r], or whose item id is outside [0, n_items) (-1 included): score 0.0f, support
+ *                   -1; it never competes
+ *   empty row       a row id outside [0, n_x_rows) (a user without a row): its valid items get score 0.0f and support 0
+ *   ranking         the competing positions of a row are its non-empty positions, minus those whose score is NaN (the rule of
+ *                   rtrec_slim_score_candidates) and, with filter_interacted != 0, those whose item is STORED in row u of X
+ *                   (whatever its value).  Position p beats q if score[p] > score[q], or the scores are == and p > q: the LATER
+ *                   position first among equal scores -- the canonical form of np.argsort(scores)[-top_k:][::-1], the rule
+ *                   CANDIDATES mode follows.  Duplicated items are separate positions and all compete; +-inf scores compete
+ *                   normally; the order is strict, so every competing position has a unique rank
+ * Out: d_out_scores / d_out_support [n_rows][list_k] for EVERY position (filtered and NaN ones included, empty ones as above);
+ * d_out_order[n_rows][top_k]: the POSITION (not the item id: the caller gathers ids and scores, and duplicates stay
+ * distinguishable) with rank t for t < d_out_count[r] = min(top_k, number of competing positions), -1 behind it.  Every output
+ * slot is written.  With a float32 W, filter_interacted == 0 and every row carrying the same list c of known items,
+ * ids[order[t]] and the score bits equal what rtrec_slim_score_candidates returns for d_cands = c.
+ * CSR / CSC offsets are clamped to [0, xb_nnz] / [0, wc_nnz], so a malformed matrix gives wrong answers, never an out-of-range
+ * read.  A column of W of any length works (K = None fits).
+ * list_k in 1..1024 and top_k in 0..list_k (RTREC_ERR_UNSUPPORTED otherwise); top_k == 0: scores and supports only, d_out_order /
+ * d_out_count may be NULL.  waves_per_row: 1 or 4 waves of 64 threads per row, 0 = chosen by the library (others:
+ * RTREC_ERR_UNSUPPORTED); the results never depend on it.  Negative sizes, NULL arrays and ids_stride < list_k:
+ * RTREC_ERR_INVALID_ARG; n_rows == 0: RTREC_OK before any pointer check.  No global state, no environment variable, no allocation.
+ * csrc/score_pairs.hip, score_pairs_kernel: threads take list positions, walk the item's column of W and binary-search the row
+ * (staged in LDS up to 128 / 2,048 entries with 1 / 4 waves per row); ranks by counting over the LDS score array.
+ * ------------------------------------------------------------------------------------- */
+int rtrec_slim_score_pairs(int32_t n_rows, const int32_t *d_row_ids, const int32_t *d_xb_ptr, const int32_t *d_xb_col,
+                           const float *d_xb_val, int32_t n_x_rows, int64_t xb_nnz, int32_t n_items,
+                           const int32_t *d_wc_ptr, const int32_t *d_wc_row, const float *d_wc_val, int64_t wc_nnz,
+                           const int32_t *d_ids, int64_t ids_stride, int32_t list_k, const int32_t *d_counts,
+                           int32_t top_k, int32_t filter_interacted, int32_t waves_per_row,
+                           float *d_out_scores, int32_t *d_out_support, int32_t *d_out_order, int32_t *d_out_count,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,7 @@ EXPORTS = [
     "rtrec_slim_explain_topk",
     "rtrec_slim_audience_workspace_bytes",
     "rtrec_slim_audience_topk",
+    "rtrec_slim_score_pairs",
 ]
 
 
@@ -199,6 +200,9 @@ def load() -> C.CDLL:
     L.rtrec_slim_audience_topk.restype = C.c_int
     L.rtrec_slim_audience_topk.argtypes = [i32, vp, i32, i32, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp, vp, vp,
                                            vp, C.c_size_t, vp]
+    L.rtrec_slim_score_pairs.restype = C.c_int
+    L.rtrec_slim_score_pairs.argtypes = [i32, vp, vp, vp, vp, i32, C.c_int64, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, i32, vp,
+                                         i32, i32, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

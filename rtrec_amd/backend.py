@@ -274,6 +274,13 @@ class HipBackend:
         self.ops.explain_topk(row_ids, xb[0], xb[1], xb[2], n_items, W["cptr"], W["crow"], W["cval"], ids, counts, list_k, top_m,
                               items, contrib, support)
 
+    def score_pairs(self, row_ids, xb, n_items, W, ids, counts, list_k, top_k, filter_interacted, scores, support, order, count,
+                    waves_per_row=0):
+        """Per (row, list item): the score and its support, and per row the list positions by rank (csrc/score_pairs.hip); W as
+        the CSC view of DeviceWeights.csc_arrays, ids [n_rows, >= list_k]; top_k == 0: order / count are empty tensors."""
+        self.ops.score_pairs(row_ids, xb[0], xb[1], xb[2], n_items, W["cptr"], W["crow"], W["cval"], ids, counts, list_k, top_k,
+                             bool(filter_interacted), int(waves_per_row), scores, support, order, count)
+
     def audience_workspace_bytes(self, n_users, n_q, top_n):
         return int(self.lib.rtrec_slim_audience_workspace_bytes(n_users, n_q, top_n))
 

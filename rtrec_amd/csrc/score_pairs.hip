@@ -1,0 +1,178 @@
+// rtrec_amd/csrc/score_pairs.hip -- rerank per-user candidate lists: score(u, i) for every (user row, list item) pair, and the
+// order of each row's list.
+//
+// The reference ranks ONE list shared by all users (recommend_batch with candidate_item_ids; csrc/score_cands.hip); a
+// two-stage recommender brings a list of its own per user.  The contract is the comment of rtrec_slim_score_pairs in
+// include/rtrec_amd.h; in short:
+//   score(u, i)  the float32 sum of fl32(x_uj * w_ji) over the j stored in both row u of X (CSR, ascending j) and column i of W
+//                (CSC, ascending j): one rounded multiply per term (-ffp-contract=off: never fused), one rounded add per term, in
+//                ascending j from +0.0f -- the explanations' invariant, scipy's csr_matmat order for one output entry
+//   support      the number of common j; -1 for an empty list position (at or beyond counts[r], or an id outside [0, n_items))
+//   ranking      position p beats q if score[p] > score[q], or the scores are == and p > q (the LATER position first: DESIGN D1,
+//                the rule of CANDIDATES mode); NaN scores and, with filter_interacted, items stored in the row do not compete
+//
+// Mapping.  One row per workgroup of 1 or 4 waves; threads take list positions, strided by the workgroup's thread count.  A
+// thread walks its item's column of W in entry order and looks each j up in the user's row by binary search -- the row is
+// staged in LDS up to kPairsRow1 / kPairsRow4 entries and searched in global memory beyond that -- and adds the hits into its
+// accumulator, so the order of the sum is the column's and a column of any length works.  The same search answers "is item i
+// stored in the row" for the filter.  The scores go to LDS (NaN for what does not compete) and the ranking is by counting: a
+// competing position's rank is the number of positions that beat it, found with wave-uniform (broadcast) reads of the LDS
+// score array; the order is strict, so ranks are unique -- no sort, no race, nothing that depends on scheduling.
+// LDS: 4 KiB of scores + 8 bytes per staged row entry = 5 KiB (one wave, 128 entries) / 20 KiB (four waves, 2,048 entries):
+// 32 waves per CU fit the CU's 160 KiB in either form, so LDS never limits the occupancy.
+// Malformed input cannot read out of range: CSR / CSC offsets are clamped to the arrays' lengths, counts to [0, list_k], a row
+// id outside [0, n_x_rows) is an empty row and an item id outside [0, n_items) an empty position.
+#include "common.hip.h"
+#include "../../include/rtrec_amd.h"
+
+namespace rtrec {
+namespace {
+
+constexpr int kPairsMaxList = 1024;     // list_k limit: the LDS score array
+constexpr int kPairsRow1 = 128;         // row entries staged in LDS, one wave per row
+constexpr int kPairsRow4 = 2048;        // ... four waves per row
+
+template <int WAVES, int ROW>
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) void score_pairs_kernel(
+        int n_rows, const int32_t *__restrict__ row_ids, const int32_t *__restrict__ xb_ptr, const int32_t *__restrict__ xb_col,
+        const float *__restrict__ xb_val, int n_x_rows, long long xb_nnz, int n_items, const int32_t *__restrict__ wc_ptr,
+        const int32_t *__restrict__ wc_row, const float *__restrict__ wc_val, long long wc_nnz, const int32_t *__restrict__ ids,
+        long long ids_stride, int list_k, const int32_t *__restrict__ counts, int top_k, int filter_interacted,
+        float *__restrict__ out_scores, int32_t *__restrict__ out_support, int32_t *__restrict__ out_order,
+        int32_t *__restrict__ out_count) {
+    constexpr int NT = WAVES * 64;
+    __shared__ __attribute__((aligned(16))) float sc[kPairsMaxList];
+    __shared__ int32_t lcol[ROW];
+    __shared__ float lval[ROW];
+    const int tid = static_cast<int>(threadIdx.x);
+    const float nan = __builtin_nanf("");
+    const int k4 = (list_k + 3) & ~3;                                     // the ranking reads the scores four at a time
+    for (long long r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const long long u = row_ids ? static_cast<long long>(row_ids[r]) : r;
+        const int32_t *rcol = xb_col;
+        const float *rval = xb_val;
+        int len = 0;
+        if (u >= 0 && u < n_x_rows) {
+            long long b = xb_ptr[u], e = xb_ptr[u + 1];
+            b = b < 0 ? 0 : (b > xb_nnz ? xb_nnz : b);
+            e = e < b ? b : (e > xb_nnz ? xb_nnz : e);
+            rcol = xb_col + b; rval = xb_val + b; len = static_cast<int>(e - b);
+        }
+        const bool staged = len <= ROW;
+        if (staged) for (int q = tid; q < len; q += NT) { lcol[q] = rcol[q]; lval[q] = rval[q]; }
+        int cnt = counts[r];
+        cnt = cnt < 0 ? 0 : (cnt > list_k ? list_k : cnt);
+        __syncthreads();                                                  // the staged row is visible to every wave
+        // x = the row's value at item j, if the row stores j
+        auto lookup = [&](int j, float &x) -> bool {
+            int lo = 0, hi = len;
+            if (staged) {
+                while (lo < hi) { const int mid = (lo + hi) >> 1; if (lcol[mid] < j) lo = mid + 1; else hi = mid; }
+                if (lo < len && lcol[lo] == j) { x = lval[lo]; return true; }
+            } else {
+                while (lo < hi) { const int mid = (lo + hi) >> 1; if (rcol[mid] < j) lo = mid + 1; else hi = mid; }
+                if (lo < len && rcol[lo] == j) { x = rval[lo]; return true; }
+            }
+            return false;
+        };
+        // ---- scores and supports: thread t takes positions t, t + NT, ... (the trip count is the same for every thread)
+        int competing = 0;
+        for (int base = 0; base < k4; base += NT) {
+            const int p = base + tid;
+            bool competes = false;
+            float acc = 0.0f;
+            if (p < list_k) {
+                const int item = p < cnt ? ids[r * ids_stride + p] : -1;
+                int support = -1;
+                if (item >= 0 && item < n_items) {
+                    support = 0;
+                    if (len > 0) {
+                        long long s = wc_ptr[item], e = wc_ptr[item + 1];
+                        s = s < 0 ? 0 : (s > wc_nnz ? wc_nnz : s);
+                        e = e < s ? s : (e > wc_nnz ? wc_nnz : e);
+                        for (long long q = s; q < e; ++q) {
+                            float x;
+                            if (lookup(wc_row[q], x)) { acc = __fadd_rn(acc, __fmul_rn(x, wc_val[q])); ++support; }
+                        }
+                    }
+                    competes = acc == acc;                                // a NaN score is written, never listed
+                    float x;
+                    if (competes && filter_interacted && lookup(item, x)) competes = false;
+                }
+                out_scores[r * list_k + p] = acc;
+                out_support[r * list_k + p] = support;
+            }
+            if (p < k4) sc[p] = competes ? acc : nan;
+            competing += __popcll(__ballot(competes));
+        }
+        if (top_k > 0) {
+            __syncthreads();                                              // all scores are in LDS; the staged row is not needed any more
+            int n_out = competing;                                        // (one wave: the ballots have counted the whole list)
+            if constexpr (WAVES > 1) {                                    // the waves' numbers of competitors meet in the row's slots
+                if ((tid & 63) == 0) lcol[tid >> 6] = competing;
+                __syncthreads();
+                n_out = 0;
+#pragma unroll
+                for (int w = 0; w < WAVES; ++w) n_out += lcol[w];
+            }
+            n_out = n_out < top_k ? n_out : top_k;
+            // ---- rank by counting: the scores are read at wave-uniform addresses (LDS broadcasts)
+            for (int p = tid; p < list_k; p += NT) {
+                const float v = sc[p];
+                if (v != v) continue;
+                int rank = 0;
+                for (int q = 0; q < k4; q += 4) {
+                    const float4 o = *reinterpret_cast<const float4 *>(&sc[q]);
+                    rank += (o.x > v || (o.x == v && q > p)) ? 1 : 0;
+                    rank += (o.y > v || (o.y == v && q + 1 > p)) ? 1 : 0;
+                    rank += (o.z > v || (o.z == v && q + 2 > p)) ? 1 : 0;
+                    rank += (o.w > v || (o.w == v && q + 3 > p)) ? 1 : 0;
+                }
+                if (rank < top_k) out_order[r * top_k + rank] = p;
+            }
+            for (int t = n_out + tid; t < top_k; t += NT) out_order[r * top_k + t] = -1;
+            if (tid == 0) out_count[r] = n_out;
+        } else if (out_count && tid == 0) {
+            out_count[r] = 0;
+        }
+        __syncthreads();                                                  // the row is done: LDS may be overwritten
+    }
+}
+
+}  // namespace
+}  // namespace rtrec
+
+extern "C" int rtrec_slim_score_pairs(int32_t n_rows, const int32_t *d_row_ids, const int32_t *d_xb_ptr, const int32_t *d_xb_col,
+                                      const float *d_xb_val, int32_t n_x_rows, int64_t xb_nnz, int32_t n_items,
+                                      const int32_t *d_wc_ptr, const int32_t *d_wc_row, const float *d_wc_val, int64_t wc_nnz,
+                                      const int32_t *d_ids, int64_t ids_stride, int32_t list_k, const int32_t *d_counts,
+                                      int32_t top_k, int32_t filter_interacted, int32_t waves_per_row, float *d_out_scores,
+                                      int32_t *d_out_support, int32_t *d_out_order, int32_t *d_out_count, void *stream) {
+    using namespace rtrec;
+    if (n_rows < 0 || n_x_rows < 0 || xb_nnz < 0 || n_items < 0 || wc_nnz < 0) return RTREC_ERR_INVALID_ARG;
+    if (list_k < 1 || list_k > kPairsMaxList || top_k < 0 || top_k > list_k) return RTREC_ERR_UNSUPPORTED;
+    if (waves_per_row != 0 && waves_per_row != 1 && waves_per_row != 4) return RTREC_ERR_UNSUPPORTED;
+    if (ids_stride < list_k) return RTREC_ERR_INVALID_ARG;
+    if (n_rows == 0) return RTREC_OK;
+    if (!d_ids || !d_counts || !d_out_scores || !d_out_support || (top_k > 0 && (!d_out_order || !d_out_count))) return RTREC_ERR_INVALID_ARG;
+    if ((n_x_rows > 0 && !d_xb_ptr) || (xb_nnz > 0 && (!d_xb_col || !d_xb_val))) return RTREC_ERR_INVALID_ARG;
+    if ((n_items > 0 && !d_wc_ptr) || (wc_nnz > 0 && (!d_wc_row || !d_wc_val))) return RTREC_ERR_INVALID_ARG;
+    (void)hipGetLastError();
+    // waves_per_row == 0 (profiles/rerank_c3s.json): all users x 100 candidates run 2.41 ms with one wave per row and 2.81 ms
+    // with four, one row x 500 candidates 0.31 ms and 0.09 ms.  Four waves only pay while a row's block has a CU to itself
+    // (256 CUs) and the list has work for more than one wave; the answer never depends on the choice.
+    const int waves = waves_per_row != 0 ? waves_per_row : (n_rows <= 256 && list_k > 64) ? 4 : 1;
+    const int grid = n_rows < 65536 ? n_rows : 65536;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (waves == 4)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(score_pairs_kernel<4, kPairsRow4>), dim3(grid), dim3(256), 0, st, n_rows, d_row_ids, d_xb_ptr,
+                           d_xb_col, d_xb_val, n_x_rows, static_cast<long long>(xb_nnz), n_items, d_wc_ptr, d_wc_row, d_wc_val,
+                           static_cast<long long>(wc_nnz), d_ids, static_cast<long long>(ids_stride), list_k, d_counts, top_k,
+                           filter_interacted, d_out_scores, d_out_support, d_out_order, d_out_count);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(score_pairs_kernel<1, kPairsRow1>), dim3(grid), dim3(64), 0, st, n_rows, d_row_ids, d_xb_ptr,
+                           d_xb_col, d_xb_val, n_x_rows, static_cast<long long>(xb_nnz), n_items, d_wc_ptr, d_wc_row, d_wc_val,
+                           static_cast<long long>(wc_nnz), d_ids, static_cast<long long>(ids_stride), list_k, d_counts, top_k,
+                           filter_interacted, d_out_scores, d_out_support, d_out_order, d_out_count);
+    return launch_status();
+}

@@ -49,6 +49,7 @@ struct Abi {
     decltype(&rtrec_rank_metrics) rank_metrics = nullptr;
     decltype(&rtrec_slim_explain_topk) explain_topk = nullptr;
     decltype(&rtrec_slim_audience_topk) audience_topk = nullptr;
+    decltype(&rtrec_slim_score_pairs) score_pairs = nullptr;
 };
 Abi g_abi;
 
@@ -463,6 +464,44 @@ void audience_topk(const at::Tensor &items, int64_t n_users, const at::Tensor &x
           "rtrec_slim_audience_topk");
 }
 
+// ids [n_rows, >= list_k] / counts [n_rows]: one list of item ids per row; the outputs are scores / support [n_rows, list_k] for
+// every position and, with top_k > 0, order [n_rows, top_k] (list positions by rank) / count [n_rows]; with top_k == 0 order and
+// count are empty tensors (include/rtrec_amd.h, "RERANK PER-USER CANDIDATE LISTS").
+void score_pairs(const OT &row_ids, const at::Tensor &xb_ptr, const at::Tensor &xb_col, const at::Tensor &xb_val, int64_t n_items,
+                 const at::Tensor &wc_ptr, const at::Tensor &wc_row, const at::Tensor &wc_val, const at::Tensor &ids,
+                 const at::Tensor &counts, int64_t list_k, int64_t top_k, bool filter_interacted, int64_t waves_per_row,
+                 at::Tensor scores, at::Tensor support, at::Tensor order, at::Tensor count) {
+    TORCH_CHECK(list_k >= 1 && list_k <= 1024, "score_pairs: list_k must lie in 1..1024, got ", list_k);
+    TORCH_CHECK(top_k >= 0 && top_k <= list_k, "score_pairs: top_k must lie in 0..list_k, got ", top_k);
+    TORCH_CHECK(waves_per_row == 0 || waves_per_row == 1 || waves_per_row == 4, "score_pairs: waves_per_row must be 0, 1 or 4, got ", waves_per_row);
+    TORCH_CHECK(ids.dim() == 2 && ids.size(1) >= list_k, "score_pairs: ids must be [n_rows, >= list_k]");
+    const int64_t n = ids.size(0);
+    TORCH_CHECK(n <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, "score_pairs: too many rows or items");
+    TORCH_CHECK(counts.numel() == n, "score_pairs: counts must hold one entry per row");
+    TORCH_CHECK(!(row_ids.has_value() && row_ids->defined()) || row_ids->numel() == n, "score_pairs: row_ids must hold one entry per row");
+    TORCH_CHECK(xb_ptr.numel() >= 1 && xb_val.numel() == xb_col.numel(), "score_pairs: xb_ptr / xb_col / xb_val are not one CSR matrix");
+    TORCH_CHECK(wc_ptr.numel() == n_items + 1 && wc_val.numel() == wc_row.numel(), "score_pairs: wc_ptr must hold n_items + 1 entries, wc_row and wc_val one length");
+    TORCH_CHECK(scores.numel() == n * list_k && support.numel() == n * list_k, "score_pairs: scores and support must be [n_rows, list_k]");
+    TORCH_CHECK(order.numel() == n * top_k && count.numel() == (top_k > 0 ? n : count.numel()) && (count.numel() == n || count.numel() == 0),
+                "score_pairs: outputs must be order[n_rows, top_k] and count[n_rows] (count may be empty when top_k == 0)");
+    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
+    if (row_ids.has_value() && row_ids->defined()) check_tensor<const int32_t>(*row_ids);
+    check_tensor<const int32_t>(xb_ptr); check_tensor<const int32_t>(xb_col); check_tensor<const float>(xb_val);
+    check_tensor<const int32_t>(wc_ptr); check_tensor<const int32_t>(wc_row); check_tensor<const float>(wc_val);
+    check_tensor<const int32_t>(ids); check_tensor<const int32_t>(counts);
+    check_tensor<float>(scores); check_tensor<int32_t>(support); check_tensor<int32_t>(order); check_tensor<int32_t>(count);
+    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&xb_ptr, &xb_col, &xb_val, &wc_ptr, &wc_row, &wc_val, &counts, &scores, &support, &order, &count})
+        TORCH_CHECK(t->device() == ids.device(), "score_pairs: all tensors must live on one device");
+    TORCH_CHECK(!(row_ids.has_value() && row_ids->defined()) || row_ids->device() == ids.device(), "score_pairs: all tensors must live on one device");
+    check(abi().score_pairs(static_cast<int32_t>(n), ptr<const int32_t>(row_ids), ptr<const int32_t>(xb_ptr), ptr<const int32_t>(xb_col),
+                            ptr<const float>(xb_val), static_cast<int32_t>(xb_ptr.numel() - 1), xb_col.numel(), static_cast<int32_t>(n_items),
+                            ptr<const int32_t>(wc_ptr), ptr<const int32_t>(wc_row), ptr<const float>(wc_val), wc_row.numel(),
+                            ptr<const int32_t>(ids), ids.size(1), static_cast<int32_t>(list_k), ptr<const int32_t>(counts),
+                            static_cast<int32_t>(top_k), filter_interacted ? 1 : 0, static_cast<int32_t>(waves_per_row), ptr<float>(scores),
+                            ptr<int32_t>(support), ptr<int32_t>(order), ptr<int32_t>(count), stream_of(scores)),
+          "rtrec_slim_score_pairs");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -494,6 +533,7 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.rank_metrics, "rtrec_rank_metrics");
         bind_one(h, a.explain_topk, "rtrec_slim_explain_topk");
         bind_one(h, a.audience_topk, "rtrec_slim_audience_topk");
+        bind_one(h, a.score_pairs, "rtrec_slim_score_pairs");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -555,6 +595,9 @@ TORCH_LIBRARY(rtrec_amd, m) {
     m.def("audience_topk(Tensor items, int n_users, Tensor xc_ptr, Tensor xc_row, Tensor xc_val, Tensor wc_ptr, Tensor wc_row, "
           "Tensor wc_val, int top_n, bool filter_interacted, Tensor? user_mask, Tensor(a!) users, Tensor(b!) scores, "
           "Tensor(c!) count, Tensor(d!) eligible, Tensor(e!) ws) -> ()");
+    m.def("score_pairs(Tensor? row_ids, Tensor xb_ptr, Tensor xb_col, Tensor xb_val, int n_items, Tensor wc_ptr, Tensor wc_row, "
+          "Tensor wc_val, Tensor ids, Tensor counts, int list_k, int top_k, bool filter_interacted, int waves_per_row, "
+          "Tensor(a!) scores, Tensor(b!) support, Tensor(c!) order, Tensor(d!) count) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -579,4 +622,5 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("rank_metrics", &rank_metrics);
     m.impl("explain_topk", &explain_topk);
     m.impl("audience_topk", &audience_topk);
+    m.impl("score_pairs", &score_pairs);
 }

@@ -1553,16 +1553,17 @@ class SlimEngine:
     EXPLAIN_MAX_LIST = 64       # list_k / top_m limits of rtrec_slim_explain_topk
     EXPLAIN_MAX_TOP_M = 32
 
-    def _explain_weights(self) -> DeviceWeights:
-        """The W an explanation reads: all of it, with the float32 values the scores were computed from."""
+    def _explain_weights(self, what: str = "explanations", verb: str = "explain") -> DeviceWeights:
+        """The W an explanation (or a pair score: the same sum) reads: all of it, with the float32 values the scores were
+        computed from."""
         if not self._W:
-            raise RuntimeError("Model must be fitted before calling explain.")
+            raise RuntimeError(f"Model must be fitted before calling {verb}.")
         dw: DeviceWeights = self._W["dw"]
         if getattr(dw, "shard", None) is not None and self.world_size > 1:
-            raise ValueError("explanations need the whole of W on this rank, and W is column-sharded (shard_w): "
-                             "gather it with gather_item_similarity() and explain from the gathered model")
+            raise ValueError(f"{what} need the whole of W on this rank, and W is column-sharded (shard_w): "
+                             f"gather it with gather_item_similarity() and {verb} from the gathered model")
         if dw.lossy:
-            raise ValueError("explanations are exact float32 products; this W was uploaded from a float64 matrix whose values "
+            raise ValueError(f"{what} are exact float32 products; this W was uploaded from a float64 matrix whose values "
                              "are not float32 numbers (DeviceWeights.lossy)")
         return dw
 
@@ -1611,6 +1612,74 @@ class SlimEngine:
             return (np.empty((0, k, top_m), np.int32), np.empty((0, k, top_m), np.float32), np.empty((0, k), np.int32))
         up = getattr(be, "to_dev_small", be.to_dev)
         out = self.explain_device(up(rows32), B, xb, up(item_ids), up(counts), top_m)
+        return tuple(t.cpu().numpy() for t in out)
+
+    # ------------------------------------------------------------------------------ rerank: per-user candidate lists
+    PAIRS_MAX_LIST = 1024       # list_k limit of rtrec_slim_score_pairs
+
+    def _pairs_weights(self) -> DeviceWeights:
+        """The W a pair score reads: the policy (and the checks) of the explanations, whose terms it adds."""
+        return self._explain_weights("pair scores", "score_pairs")
+
+    def score_pairs_device(self, d_rows, n_rows: int, xb, ids, counts, top_k: int = 0, filter_interacted: bool = False,
+                           waves_per_row: int = 0):
+        """Device tensors (scores[n_rows, k] float32, support[n_rows, k] int32, order[n_rows, top_k] int32, count[n_rows] int32)
+        for the lists `ids` [n_rows, k] / `counts` [n_rows] (int32 device tensors: lists other kernels produced never leave HBM)
+        of the rows `d_rows` (int32 device tensor, or None = rows 0 .. n_rows-1) of `xb` = (ptr, col, val) device tensors (None:
+        the resident X).  score = the float32 sum of x_uj * w_ji over the common j in ascending j, support = their number (-1:
+        an empty position), order = the list POSITIONS by rank (score descending, the later position first among equal
+        scores; NaN scores and, with `filter_interacted`, items stored in the row do not compete), -1 behind count.  The
+        contract is the comment of rtrec_slim_score_pairs in include/rtrec_amd.h.  `top_k == 0`: scores and supports only, and
+        lists longer than 1024 are worked through in column chunks; ranking serves lists of up to 1024.  The results stay in
+        HBM.  Every rank that holds the whole W answers locally: there is no collective."""
+        be, torch = self.be, self.be.torch
+        dw = self._pairs_weights()
+        k, top_k, n_rows = int(ids.shape[-1]), int(top_k), int(n_rows)
+        if top_k > 0 and k > self.PAIRS_MAX_LIST:
+            raise ValueError(f"score_pairs ranks lists of up to {self.PAIRS_MAX_LIST} items, got {k}: longer lists are scored "
+                             "with top_k=0 only")
+        if not 0 <= top_k <= max(k, 0):
+            raise ValueError(f"score_pairs: top_k must lie in 0..{k} (the list length), got {top_k}")
+        scores = be.empty((n_rows, k), torch.float32)
+        support = be.empty((n_rows, k), torch.int32)
+        order = be.empty((n_rows, top_k), torch.int32)
+        count = be.zeros((n_rows,), torch.int32)
+        if n_rows == 0 or k == 0:
+            return scores, support, order, count
+        if xb is None:
+            xb = (self._X["rptr"], self._X["rcol"], self._X["rval"])
+        cptr, crow, cval = dw.csc_arrays(torch)
+        W = {"cptr": cptr, "crow": crow, "cval": cval}
+        if k <= self.PAIRS_MAX_LIST:
+            be.score_pairs(d_rows, xb, dw.n_items, W, ids.contiguous(), counts.contiguous(), k, top_k, bool(filter_interacted),
+                           scores, support, order, count, waves_per_row=waves_per_row)
+            return scores, support, order, count
+        for c0 in range(0, k, self.PAIRS_MAX_LIST):                      # top_k == 0: column chunks of the kernel's list length
+            c1 = min(k, c0 + self.PAIRS_MAX_LIST)
+            sc, su = be.empty((n_rows, c1 - c0), torch.float32), be.empty((n_rows, c1 - c0), torch.int32)
+            be.score_pairs(d_rows, xb, dw.n_items, W, ids[:, c0:c1].contiguous(), (counts - c0).clamp(0, c1 - c0).to(torch.int32),
+                           c1 - c0, 0, False, sc, su, order, count, waves_per_row=waves_per_row)
+            scores[:, c0:c1], support[:, c0:c1] = sc, su
+        return scores, support, order, count
+
+    def score_pairs_rows(self, row_ids: Sequence[int], item_ids: np.ndarray, counts: Optional[np.ndarray] = None, top_k: int = 0,
+                         filter_interacted: bool = False, xb=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """score_pairs_device for lists the caller brings: numpy (scores[B, k], support[B, k], order[B, top_k], count[B]) for
+        `item_ids` [B, k] (-1 = no item) of the rows `row_ids` of the resident X -- or of the device CSR batch `xb`.  A row id
+        outside the matrix is a user without a row: score 0 and support 0 for every valid item."""
+        be = self.be
+        row_ids = np.asarray(row_ids, dtype=np.int64)
+        item_ids = np.ascontiguousarray(item_ids, dtype=np.int32)
+        if item_ids.ndim != 2 or item_ids.shape[0] != len(row_ids):
+            raise ValueError("item_ids must be [len(row_ids), k]")
+        B, k = item_ids.shape
+        counts = np.full(B, k, dtype=np.int32) if counts is None else np.asarray(counts, dtype=np.int32)
+        if counts.shape != (B,):
+            raise ValueError("counts must hold one entry per row")
+        n_x = self.n_users if xb is None else int(xb[0].shape[0]) - 1
+        rows32 = np.where((row_ids >= 0) & (row_ids < n_x), row_ids, -1).astype(np.int32)
+        up = getattr(be, "to_dev_small", be.to_dev)
+        out = self.score_pairs_device(up(rows32), B, xb, up(item_ids), up(counts), top_k, filter_interacted)
         return tuple(t.cpu().numpy() for t in out)
 
     # ------------------------------------------------------------------------------ audience of an item

@@ -402,6 +402,34 @@ class SLIMElastic:
             Xb.resize((Xb.shape[0], n_items))
         return self.engine.explain_rows(np.arange(len(rows)), ids, counts, top_m, xb=self.engine._upload_csr(Xb))
 
+    def score_pairs_batch(self, user_ids: List[int], interaction_matrix: sp.csr_matrix, item_ids: Sequence[Sequence[int]],
+                          top_k: int = 0, filter_interacted: bool = False) -> Tuple[ndarray, ndarray, ndarray, ndarray]:
+        """An extension (the reference ranks one candidate list shared by all users): for every (user, item) of `item_ids` --
+        one list of item ids per user, -1 or an id outside W = no item -- the score X[u, :] @ W[:, i] as the float32 sum of
+        its terms in ascending item order, and the number of terms; with `top_k` > 0 (lists of at most 1024) also each list's
+        order (csrc/score_pairs.hip; the contract is the comment of rtrec_slim_score_pairs in include/rtrec_amd.h).  Returns
+        (scores[B, k], support[B, k], order[B, top_k], counts[B]), k = the longest list: support -1 marks an empty position,
+        order holds list POSITIONS by rank (score descending, the later position first among equal scores; with
+        `filter_interacted` the items stored in the user's row do not compete), -1 behind counts[b]."""
+        if not self.is_fitted:
+            raise RuntimeError("Model must be fitted before calling score_pairs_batch.")
+        rows = [list(r) for r in item_ids]
+        if len(rows) != len(user_ids):
+            raise ValueError("item_ids must hold one list per user")
+        k = max([len(r) for r in rows] + [1])
+        ids = np.full((len(rows), k), -1, dtype=np.int32)
+        for b, r in enumerate(rows):
+            ids[b, :len(r)] = r
+        counts = np.array([len(r) for r in rows], dtype=np.int32)
+        self._sync_weights()
+        n_items = self.n_items_fitted
+        Xb = interaction_matrix[user_ids, :].tocsr() if len(rows) else sp.csr_matrix((0, n_items), dtype=np.float32)
+        if Xb.shape[1] != n_items:
+            Xb = Xb.copy()
+            Xb.resize((Xb.shape[0], n_items))
+        return self.engine.score_pairs_rows(np.arange(len(rows)), ids, counts, top_k, filter_interacted,
+                                            xb=self.engine._upload_csr(Xb))
+
     def recommend_users_batch(self, item_ids: Sequence[int], top_n: int = 100, filter_interacted: bool = True,
                               candidate_rows: Optional[Sequence[int]] = None) -> Tuple[ndarray, ndarray, ndarray, ndarray]:
         """An extension (the reference has none): the audience of every item of `item_ids` (internal ids; an id outside W

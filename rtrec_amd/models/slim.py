@@ -486,6 +486,174 @@ class SLIM(BaseModel):
         return self.explain_batch([user], None if items is None else [list(items)], top_k=top_k, top_m=top_m,
                                   filter_interacted=filter_interacted)[0]
 
+    # ------------------------------------------------------------ rerank per-user candidate lists (an extension)
+    RERANK_MAX_LIST = 1024      # list length rtrec_slim_score_pairs ranks
+
+    def _user_rows(self, users: Any) -> Tuple[np.ndarray, np.ndarray]:
+        """(internal user id per user, cold mask): the hot / cold split of recommend_batch -- one compare for integer
+        pass-through ids, `_known_user_id` per user otherwise (with its "mixed types" error)."""
+        arr = self._int_user_array(users)
+        if arr is not None:
+            return arr, arr > self.interactions.max_user_id
+        known = [self._known_user_id(u) for u in users]
+        cold = np.fromiter((u is None for u in known), dtype=bool, count=len(known))
+        return np.fromiter((0 if u is None else u for u in known), dtype=np.int64, count=len(known)), cold
+
+    def rerank_batch(self, users: List[Any], candidates: List[List[Any]], top_k: Optional[int] = None,
+                     filter_interacted: bool = False, ret_scores: bool = False, as_arrays: bool = False) -> Any:
+        """The second stage of a two-stage recommender: `candidates` holds one list of raw item ids PER USER (from a retrieval
+        stage, a rule, what was shown, 1 positive + 99 sampled negatives), and every list is scored and ordered by
+        score(u, i) = sum_j X[u, j] * W[j, i] in one device pass over the resident X (csrc/score_pairs.hip) -- where
+        `recommend_batch(candidate_items=...)` takes one list shared by all users.
+
+        For a float32 W, `rerank_batch(users, candidates, top_k)[b] == recommend(users[b], candidate_items=candidates[b],
+        top_k=top_k)` for every user: raw candidates the model does not know are dropped from that user's list (unmapped ids,
+        integer ids above `max_item_id`), duplicated candidates are separate entries, the later entry comes first among equal
+        scores, NaN scores are never listed, and a cold-start user gets what `recommend` gives them -- the hot items that are
+        in their list, as `recommend` returns them.  The one exception: a list that is empty after mapping yields [] (the
+        reference turns it into "no candidates" and `recommend` then ranks the whole catalogue, which is not what a rerank
+        call wants).  With a float64 W (serial fit) `recommend` accumulates in double while this call adds the float32
+        products in float32, so last bits and the order of near-ties may differ.  Candidates beyond the fitted W (ingested,
+        never fitted) and users without a row in X (negative ids, ids known only through register_user_feature) are served
+        as an item without a column / a user without interactions instead of `recommend`'s wrap-around and IndexError.
+
+        `top_k=None` ranks the whole list; `filter_interacted` (default off, as `recommend` ignores it for candidate lists)
+        leaves out the candidates stored in the user's row of X.  A list longer than 1024 raises ValueError.  With integer
+        item ids `candidates` may be one [B, k] integer array instead of B lists: it is mapped without a Python loop.
+
+        Returns one list of raw item ids per user in rank order -- of (item, score) tuples with `ret_scores` -- or with
+        `as_arrays=True` (ids[B, top_k], scores[B, top_k], counts[B]): row b is valid up to counts[b], unused slots hold
+        -1 / -inf, and the ids are INTERNAL item ids (for integer ids the raw ids; map string ids with `model.item_ids.get`)."""
+        if not self.model.is_fitted:
+            raise RuntimeError("Model must be fitted before calling rerank_batch.")
+        arr = self._int_user_array(users)
+        users = arr if arr is not None else list(users)
+        B = len(users)
+        lim = 2 ** 31 - 1
+        if (isinstance(candidates, np.ndarray) and candidates.ndim == 2 and candidates.dtype.kind in "iu"
+                and self.item_ids.pass_through is True and not self.item_ids.force_identify):
+            # integer ids that pass through unmapped, as one [B, k] array: `_candidate_ids` for all lists at once -- an id above
+            # max_item_id is dropped and the rest of its list moves up
+            if candidates.shape[0] != B:
+                raise ValueError(f"candidates must hold one list per user: {candidates.shape[0]} lists for {B} users")
+            known = candidates <= self.interactions.max_item_id
+            ids = np.take_along_axis(candidates, np.argsort(~known, axis=1, kind="stable"), axis=1)
+            counts = known.sum(axis=1).astype(np.int32)
+            ids = np.where((np.arange(ids.shape[1])[None, :] < counts[:, None]) & (ids >= 0) & (ids < lim), ids, -1).astype(np.int32)
+        else:
+            lists = [self._candidate_ids(list(c)) or [] for c in candidates]
+            if len(lists) != B:
+                raise ValueError(f"candidates must hold one list per user: {len(lists)} lists for {B} users")
+            counts = np.fromiter((len(c) for c in lists), dtype=np.int32, count=B)
+            ids = np.full((B, int(counts.max()) if B else 0), -1, dtype=np.int32)
+            for b, row in enumerate(lists):
+                ids[b, :len(row)] = [i if 0 <= i < lim else -1 for i in row]
+        K = int(counts.max()) if B else 0
+        ids = ids[:, :K]
+        if K > self.RERANK_MAX_LIST:
+            raise ValueError(f"rerank_batch ranks lists of up to {self.RERANK_MAX_LIST} candidates, got one of {K}: split it, or "
+                             "score it with score_pairs and sort on the host")
+        k = K if top_k is None else max(0, min(int(top_k), K))
+        out_ids = np.full((B, k), -1, dtype=np.int64)
+        out_sc = np.full((B, k), -np.inf, dtype=np.float32)
+        out_cnt = np.zeros(B, dtype=np.int32)
+        uid, cold = self._user_rows(users)
+        if B:
+            self.model._sync_weights()
+            self.model.engine._pairs_weights()    # a W that cannot be served is refused whatever the batch holds
+        hot = np.flatnonzero(~cold)
+        if len(hot) and k > 0:
+            all_hot = len(hot) == B
+            h_ids, h_uid = (ids, uid) if all_hot else (np.ascontiguousarray(ids[hot]), uid[hot])
+            n_users = self.interactions.shape[0]
+            rows = np.where((h_uid >= 0) & (h_uid < n_users), h_uid, -1)
+            self._sync_interactions()
+            scores, _, order, cnt = self.model.engine.score_pairs_rows(rows, h_ids, counts if all_hot else counts[hot], k,
+                                                                       filter_interacted)
+            live = order >= 0
+            pos = np.where(live, order, 0)
+            out_ids[hot] = np.where(live, np.take_along_axis(h_ids, pos, axis=1), -1)
+            out_sc[hot] = np.where(live, np.take_along_axis(scores, pos, axis=1), -np.inf)
+            out_cnt[hot] = cnt
+        for b in np.flatnonzero(cold).tolist():       # BaseModel.recommend's cold-start branch, on this user's own list
+            mine = ids[b, :counts[b]].tolist()
+            if not mine or k == 0:
+                continue
+            hot_items = self.interactions.get_hot_items(None if top_k is None else int(top_k), filter_interacted=False)
+            row = [i for i in hot_items if i in mine][:k]
+            out_ids[b, :len(row)], out_sc[b, :len(row)], out_cnt[b] = row, 0.0, len(row)
+        if as_arrays:
+            return out_ids, out_sc, out_cnt
+        raw_of = (lambda i: i) if self.item_ids.pass_through else self.item_ids.get
+        id_rows, sc_rows, cnts, is_cold = out_ids.tolist(), out_sc.tolist(), out_cnt.tolist(), cold.tolist()
+        out: List[Any] = []
+        for b in range(B):
+            items = id_rows[b][:cnts[b]] if is_cold[b] else [raw_of(i) for i in id_rows[b][:cnts[b]]]
+            out.append(list(zip(items, sc_rows[b][:cnts[b]])) if ret_scores else items)
+        return out
+
+    def rerank(self, user: Any, candidates: List[Any], top_k: Optional[int] = None, filter_interacted: bool = False,
+               ret_scores: bool = False) -> List[Any]:
+        """rerank_batch for one user: the user's candidates in rank order, or (item, score) tuples."""
+        return self.rerank_batch([user], [list(candidates)], top_k=top_k, filter_interacted=filter_interacted,
+                                 ret_scores=ret_scores)[0]
+
+    def score_pairs(self, users: Any, items: Any, as_arrays: bool = False) -> Any:
+        """score(u, i) = sum_j X[u, j] * W[j, i] for the pairs (users[p], items[p]) of two equal-length sequences of raw ids:
+        the score `recommend` ranks the pair by (for a float32 W, bit for bit), as a feature for a learned ranker or for
+        logging what was shown.  Returns `scores` (float32, one per pair), or `(scores, support)` with `as_arrays=True`:
+        support = the number of items j the sum runs over.  A pair with an unknown user or an unknown item has score 0.0 and
+        support -1; a known pair without common evidence has score 0.0 and support 0.  The pairs are grouped by user on the
+        host (one stable argsort), go through the kernel as per-user lists of at most 1024 (csrc/score_pairs.hip, no ranking)
+        over the resident X, and come back in the caller's order."""
+        if not self.model.is_fitted:
+            raise RuntimeError("Model must be fitted before calling score_pairs.")
+        users = users if isinstance(users, np.ndarray) else list(users)
+        items = items if isinstance(items, np.ndarray) else list(items)
+        n = len(users)
+        if len(items) != n:
+            raise ValueError(f"users and items must have one length: {n} users and {len(items)} items")
+        scores = np.zeros(n, dtype=np.float32)
+        support = np.full(n, -1, dtype=np.int32)
+        n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
+
+        def ids_of(values: Any, known) -> np.ndarray:
+            out = np.full(n, -1, dtype=np.int64)
+            for p_, raw in enumerate(values.tolist() if isinstance(values, np.ndarray) else values):
+                try:
+                    i = known(raw)
+                except (ValueError, TypeError):       # an id of the other kind: nobody / nothing the model knows
+                    i = None
+                if i is not None:
+                    out[p_] = i
+            return out
+
+        uid, iid = ids_of(users, self._known_user_id), ids_of(items, self.item_ids.get_id)
+        if n:
+            self.model._sync_weights()
+            self.model.engine._pairs_weights()
+        valid = np.flatnonzero((uid >= 0) & (uid < n_users) & (iid >= 0) & (iid < n_items))
+        if len(valid):
+            L = self.RERANK_MAX_LIST
+            by_user = valid[np.argsort(uid[valid], kind="stable")]
+            u_sorted = uid[by_user]
+            first = np.flatnonzero(np.r_[True, u_sorted[1:] != u_sorted[:-1]])       # where each user's run starts
+            run = np.diff(np.r_[first, len(by_user)])
+            in_run = np.arange(len(by_user)) - np.repeat(first, run)
+            row_base = np.r_[0, np.cumsum((run + L - 1) // L)]                       # a user with more than L pairs takes several rows
+            row = np.repeat(row_base[:-1], run) + in_run // L
+            col = in_run % L
+            n_rows, width = int(row_base[-1]), int(min(L, run.max()))
+            ids = np.full((n_rows, width), -1, dtype=np.int32)
+            ids[row, col] = iid[by_user]
+            counts = np.bincount(row, minlength=n_rows).astype(np.int32)
+            rows = np.zeros(n_rows, dtype=np.int64)
+            rows[row] = u_sorted
+            self._sync_interactions()
+            sc, su, _, _ = self.model.engine.score_pairs_rows(rows, ids, counts, 0, False)
+            scores[by_user], support[by_user] = sc[row, col], su[row, col]
+        return (scores, support) if as_arrays else scores
+
     # ------------------------------------------------------------ audience of an item (an extension: the reference has none)
     def _sync_interactions_csc(self) -> None:
         """_sync_interactions, and the CSC orientation of the GPU copy too: the device mirror's, or -- on the branch that

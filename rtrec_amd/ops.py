@@ -22,6 +22,7 @@ is written on top of them; they are also the interface for callers that already 
     torch.ops.rtrec_amd.rank_metrics        the nine ranking figures of Recommender.evaluate per user, from lists on the device
     torch.ops.rtrec_amd.explain_topk        per (user, item) of a top-k list: the top-m terms x_uj * w_ji of the score, and their number
     torch.ops.rtrec_amd.audience_topk       per query item: the top-n users by score (the scoring product read by W's column), and its reach
+    torch.ops.rtrec_amd.score_pairs         per (user, item) of per-user candidate lists: the score and its support, and each list's order
 
 The registration lives in csrc/torch_ops.cpp (TORCH_LIBRARY / TORCH_LIBRARY_IMPL: librtrec_amd_ops.so, built by
 rtrec_amd/build.py with the host compiler); importing this module loads it and binds it to the C-ABI library
@@ -41,7 +42,8 @@ from . import build as _build
 
 OPS = ["column_sqnorms", "fit_workspace_init", "gram_matrix", "fit_columns", "score_topk", "score_rows", "merge_topk",
        "similar_topk", "store_decay_device", "store_fold_device", "fit_sgd_epochs", "first_touch_aux", "dense_fill",
-       "refine_topk_f64", "score_candidates", "seg_plan", "seg_fill", "ordered_sums", "rank_metrics", "explain_topk", "audience_topk"]
+       "refine_topk_f64", "score_candidates", "seg_plan", "seg_fill", "ordered_sums", "rank_metrics", "explain_topk", "audience_topk",
+       "score_pairs"]
 
 # C-ABI export each op launches (tests: every kernel-launching export of include/rtrec_amd.h is behind an op)
 EXPORT_OF = {"column_sqnorms": "rtrec_slim_column_sqnorms", "fit_workspace_init": "rtrec_slim_fit_workspace_init",
@@ -53,7 +55,8 @@ EXPORT_OF = {"column_sqnorms": "rtrec_slim_column_sqnorms", "fit_workspace_init"
              "dense_fill": "rtrec_slim_dense_fill", "refine_topk_f64": "rtrec_slim_refine_topk_f64",
              "score_candidates": "rtrec_slim_score_candidates", "seg_plan": "rtrec_slim_seg_plan", "seg_fill": "rtrec_slim_seg_fill",
              "ordered_sums": "rtrec_slim_ordered_sums", "rank_metrics": "rtrec_rank_metrics",
-             "explain_topk": "rtrec_slim_explain_topk", "audience_topk": "rtrec_slim_audience_topk"}
+             "explain_topk": "rtrec_slim_explain_topk", "audience_topk": "rtrec_slim_audience_topk",
+             "score_pairs": "rtrec_slim_score_pairs"}
 
 
 def _load() -> None:

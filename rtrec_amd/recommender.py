@@ -125,6 +125,21 @@ class Recommender:
         return self.model.recommend_users_batch(items, top_n=top_n, filter_interacted=filter_interacted,
                                                 candidate_users=candidate_users, ret_scores=ret_scores, as_arrays=as_arrays)
 
+    def rerank(self, user: Any, candidates: List[Any], top_k: Optional[int] = None, filter_interacted: bool = False,
+               ret_scores: bool = False) -> Any:
+        """An extension (the reference ranks one list for all users): the user's own candidates in rank order -- SLIM.rerank."""
+        return self.model.rerank(user, candidates, top_k=top_k, filter_interacted=filter_interacted, ret_scores=ret_scores)
+
+    def rerank_batch(self, users: List[Any], candidates: List[List[Any]], top_k: Optional[int] = None,
+                     filter_interacted: bool = False, ret_scores: bool = False, as_arrays: bool = False) -> Any:
+        """SLIM.rerank_batch: one candidate list per user, scored and ordered in one device pass."""
+        return self.model.rerank_batch(users, candidates, top_k=top_k, filter_interacted=filter_interacted,
+                                       ret_scores=ret_scores, as_arrays=as_arrays)
+
+    def score_pairs(self, users: Any, items: Any, as_arrays: bool = False) -> Any:
+        """SLIM.score_pairs: the model's score of every (users[p], items[p]) pair, and with `as_arrays` its support."""
+        return self.model.score_pairs(users, items, as_arrays=as_arrays)
+
     def similar_items(self, query_items: List[Any], query_item_tags: Optional[List[str]] = None, top_k: int = 10,
                       ret_scores: bool = False):
         batch = getattr(self.model, "similar_items_batch", None)

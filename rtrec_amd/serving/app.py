@@ -16,6 +16,9 @@ the GPU), POST /recommend (one user's top-k).  Differences, all forced by the de
   * POST /recommend_users is an addition (the other direction: which users for this item): {"item": ..., "top_n",
     "filter_interacted", "candidate_users": [...] or absent} -> {"item": ..., "users": [{"user": ..., "score": ...}, ...]}
     (SLIM.recommend_users); same token check as /recommend, not coalesced;
+  * POST /rerank is an addition (the second stage of a two-stage recommender: the caller brings the user's own candidates):
+    {"user": ..., "items": [...], "top_k" or absent = the whole list, "filter_interacted"} -> {"user": ..., "items": [{"item": ...,
+    "score": ...}, ...]} (SLIM.rerank); same token check as /recommend, answered under the model lock, not coalesced;
   * concurrent POST /recommend calls are coalesced (`RecommendCoalescer`): requests that arrive within a bounded
     wait (RTREC_AMD_COALESCE_MS, default 1 ms; 0 = only what queued up behind the model lock) share ONE
     recommend_batch launch per (top_k, filter_interacted) group; each caller gets exactly what its own
@@ -69,6 +72,13 @@ class AudienceRequest(BaseModel):
     top_n: int = 100
     filter_interacted: bool = True
     candidate_users: Optional[List[Any]] = None
+
+
+class RerankRequest(BaseModel):
+    user: Any
+    items: List[Any]
+    top_k: Optional[int] = None
+    filter_interacted: bool = False
 
 
 class RecommendationResponse(BaseModel):
@@ -273,6 +283,13 @@ def build_router(gate: ModelGate) -> APIRouter:
                                                                   filter_interacted=request.filter_interacted,
                                                                   candidate_users=request.candidate_users, ret_scores=True))
         return {"item": request.item, "users": [{"user": u, "score": s} for u, s in pairs]}
+
+    @api.post("/rerank")
+    def rerank(request: RerankRequest, x_token: str = Header()):
+        _authorise(x_token)
+        pairs = gate.call("Rerank", lambda m: m.rerank(request.user, request.items, top_k=request.top_k,
+                                                       filter_interacted=request.filter_interacted, ret_scores=True))
+        return {"user": request.user, "items": [{"item": i, "score": s} for i, s in pairs]}
 
     return api
 
