@@ -29,7 +29,7 @@
 //
 // Malformed input cannot read out of range: CSC offsets are clamped to the arrays' lengths, an item id outside [0, n_items) has
 // no column, a row outside the wave's range (an unsorted column) is skipped.
-#include "common.hip.h"
+#include "row_lookup.hip.h"
 #include "../../include/rtrec_amd.h"
 
 namespace rtrec {
@@ -132,12 +132,6 @@ __device__ int select_sorted(KeyFn key, int n, int n_valid, int top_n, unsigned 
     return cnt;
 }
 
-// [lo, hi) clamped into [0, nnz], never reversed
-__device__ __forceinline__ void clamp_range(long long &lo, long long &hi, long long nnz) {
-    lo = lo < 0 ? 0 : (lo > nnz ? nnz : lo);
-    hi = hi < lo ? lo : (hi > nnz ? nnz : hi);
-}
-
 // first p in [lo, hi) with row[p] >= R
 __device__ __forceinline__ long long lower_bound_row(const int32_t *__restrict__ row, long long lo, long long hi, long long R) {
     while (lo < hi) {
@@ -165,7 +159,7 @@ __global__ __launch_bounds__(kAudThreads) void audience_tile_kernel(
     const long long slot = static_cast<long long>(q) * n_tiles + tile;
     const int item = items[q];
     long long ws = 0, we = 0;
-    if (item >= 0 && item < n_items) { ws = wc_ptr[item]; we = wc_ptr[item + 1]; clamp_range(ws, we, wc_nnz); }
+    if (item >= 0 && item < n_items) { ws = wc_ptr[item]; we = wc_ptr[item + 1]; clamp_span(ws, we, wc_nnz); }
     if (we == ws) {                                                       // no column: nobody has support
         if (tid == 0) { ws_cnt[2 * slot] = 0; ws_cnt[2 * slot + 1] = 0; }
         return;
@@ -190,7 +184,7 @@ __global__ __launch_bounds__(kAudThreads) void audience_tile_kernel(
             const int c = t % nc, b = t / nc;
             const int j = wc_row[base + c];
             long long lo = 0, hi = 0;
-            if (j >= 0 && j < n_items) { lo = xc_ptr[j]; hi = xc_ptr[j + 1]; clamp_range(lo, hi, xc_nnz); }
+            if (j >= 0 && j < n_items) { lo = xc_ptr[j]; hi = xc_ptr[j + 1]; clamp_span(lo, hi, xc_nnz); }
             bounds[b][c] = static_cast<int>(lower_bound_row(xc_row, lo, hi, tile_lo + static_cast<long long>(b) * kAudSub));
             if (b == 0) wv[c] = wc_val[base + c];
         }
@@ -217,7 +211,7 @@ __global__ __launch_bounds__(kAudThreads) void audience_tile_kernel(
     if (filter_interacted) {                                              // the users stored in column `item` of X
         if (tid < 2) {
             long long lo = xc_ptr[item], hi = xc_ptr[item + 1];
-            clamp_range(lo, hi, xc_nnz);
+            clamp_span(lo, hi, xc_nnz);
             misc[tid] = static_cast<int>(lower_bound_row(xc_row, lo, hi, tile_lo + static_cast<long long>(tid) * kAudTile));
         }
         __syncthreads();

@@ -14,7 +14,7 @@
 //   at most 64 entries is probed once and kept in registers; a longer one is probed again every round.
 // Malformed input cannot read out of range: CSR / CSC offsets are clamped to the arrays' lengths, a row id outside
 // [0, n_x_rows) is an empty row and an item id outside [0, n_items) has no column.
-#include "common.hip.h"
+#include "row_lookup.hip.h"
 #include "../../include/rtrec_amd.h"
 
 namespace rtrec {
@@ -71,8 +71,7 @@ __global__ __launch_bounds__(64) void explain_topk_kernel(
         row.col = xb_col; row.val = xb_val; row.len = 0;
         if (u >= 0 && u < n_x_rows) {
             long long b = xb_ptr[u], e = xb_ptr[u + 1];
-            b = b < 0 ? 0 : (b > xb_nnz ? xb_nnz : b);
-            e = e < b ? b : (e > xb_nnz ? xb_nnz : e);
+            clamp_span(b, e, xb_nnz);
             row.col = xb_col + b; row.val = xb_val + b; row.len = static_cast<int>(e - b);
         }
         row.in_regs = row.len <= 64;
@@ -85,8 +84,7 @@ __global__ __launch_bounds__(64) void explain_topk_kernel(
             long long s = 0, e = 0;
             if (item >= 0 && item < n_items && row.len > 0) {
                 s = wc_ptr[item]; e = wc_ptr[item + 1];
-                s = s < 0 ? 0 : (s > wc_nnz ? wc_nnz : s);
-                e = e < s ? s : (e > wc_nnz ? wc_nnz : e);
+                clamp_span(s, e, wc_nnz);
             }
             const bool one = e - s <= 64;                                 // the whole column in one probe: keep it in registers
             Cand<float> mine; mine.id = -1; mine.score = ninf; mine.aux = 0u;

@@ -38,7 +38,8 @@ __global__ __launch_bounds__(256) void score_cands_kernel(
         if (staged) for (int q = tid; q < n_a; q += nthreads) { lcol[q] = xb_col[a0 + q]; lval[q] = xb_val[a0 + q]; }
         // ---- scores of the candidates (thread t: candidates t, t + threads, ...).  A column's entries are requested four at a
         //      time (rows and weights of the next four entries in flight together), looked up in the row's items, and added in
-        //      entry order
+        //      entry order.  (The search is spelled out here, not taken from row_lookup.hip.h like its copies in score_pairs and
+        //      score_refine: with the shared find the compiler shaped this loop differently and the kernel measured 1 - 2 % slower.)
         auto lookup = [&](int i, float &x) -> bool {
             int lo = 0, hi = n_a;
             if (staged) {

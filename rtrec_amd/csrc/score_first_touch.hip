@@ -11,7 +11,7 @@
 // integer ratings and weights.)  A rank that holds only part of W's columns therefore completes the key for every entry of
 // its lists before the exchange: one lane per entry walks the column's stored rows (ascending item id, CSC) and looks each
 // up in the user's row (ascending item id: binary search); the first hit is the lowest item, i.e. the lowest position.
-#include "common.hip.h"
+#include "row_lookup.hip.h"
 #include "../../include/rtrec_amd.h"
 
 namespace rtrec {
@@ -37,13 +37,8 @@ __global__ __launch_bounds__(256) void first_touch_aux_kernel(FirstTouchArgs a) 
                 const int *items = a.xb_col + a0;
                 const int j1 = a.wc_ptr[c + 1];
                 for (int j = a.wc_ptr[c]; j < j1; ++j) {
-                    const int r = a.wc_row[j];
-                    int lo = 0, hi = n_a;
-                    while (lo < hi) {
-                        const int mid = (lo + hi) >> 1;
-                        if (items[mid] < r) lo = mid + 1; else hi = mid;
-                    }
-                    if (lo < n_a && items[lo] == r) { key = static_cast<uint32_t>(lo); break; }
+                    int pos;
+                    if (find_sorted(items, n_a, a.wc_row[j], pos)) { key = static_cast<uint32_t>(pos); break; }
                 }
             }
         }

@@ -22,7 +22,7 @@
 // 32 waves per CU fit the CU's 160 KiB in either form, so LDS never limits the occupancy.
 // Malformed input cannot read out of range: CSR / CSC offsets are clamped to the arrays' lengths, counts to [0, list_k], a row
 // id outside [0, n_x_rows) is an empty row and an item id outside [0, n_items) an empty position.
-#include "common.hip.h"
+#include "row_lookup.hip.h"
 #include "../../include/rtrec_amd.h"
 
 namespace rtrec {
@@ -54,8 +54,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) vo
         int len = 0;
         if (u >= 0 && u < n_x_rows) {
             long long b = xb_ptr[u], e = xb_ptr[u + 1];
-            b = b < 0 ? 0 : (b > xb_nnz ? xb_nnz : b);
-            e = e < b ? b : (e > xb_nnz ? xb_nnz : e);
+            clamp_span(b, e, xb_nnz);
             rcol = xb_col + b; rval = xb_val + b; len = static_cast<int>(e - b);
         }
         const bool staged = len <= ROW;
@@ -65,15 +64,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) vo
         __syncthreads();                                                  // the staged row is visible to every wave
         // x = the row's value at item j, if the row stores j
         auto lookup = [&](int j, float &x) -> bool {
-            int lo = 0, hi = len;
-            if (staged) {
-                while (lo < hi) { const int mid = (lo + hi) >> 1; if (lcol[mid] < j) lo = mid + 1; else hi = mid; }
-                if (lo < len && lcol[lo] == j) { x = lval[lo]; return true; }
-            } else {
-                while (lo < hi) { const int mid = (lo + hi) >> 1; if (rcol[mid] < j) lo = mid + 1; else hi = mid; }
-                if (lo < len && rcol[lo] == j) { x = rval[lo]; return true; }
-            }
-            return false;
+            return staged ? find_sorted(lcol, lval, len, j, x) : find_sorted(rcol, rval, len, j, x);
         };
         // ---- scores and supports: thread t takes positions t, t + NT, ... (the trip count is the same for every thread)
         int competing = 0;
@@ -88,8 +79,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) vo
                     support = 0;
                     if (len > 0) {
                         long long s = wc_ptr[item], e = wc_ptr[item + 1];
-                        s = s < 0 ? 0 : (s > wc_nnz ? wc_nnz : s);
-                        e = e < s ? s : (e > wc_nnz ? wc_nnz : e);
+                        clamp_span(s, e, wc_nnz);
                         for (long long q = s; q < e; ++q) {
                             float x;
                             if (lookup(wc_row[q], x)) { acc = __fadd_rn(acc, __fmul_rn(x, wc_val[q])); ++support; }

@@ -27,7 +27,7 @@
 // the candidates is above that, the sorted candidates are the answer.  Flagged for the float64 tiled kernel: rows that fail
 // the test, rows whose list is not full (a cancelled float32 sum may hide a column), a candidate whose float64 sum is
 // exactly 0 (no stored product in the reference), exact ties.
-#include "common.hip.h"
+#include "row_lookup.hip.h"
 #include "../../include/rtrec_amd.h"
 
 namespace rtrec {
@@ -92,22 +92,9 @@ __global__ __launch_bounds__(kRfWaves * 64) void refine_f64_kernel(
             if (c >= 0 && c < n_items) {
                 for (int q = wc_ptr[c]; q < wc_ptr[c + 1]; ++q) {
                     const int i = wc_row[q];
-                    int lo = 0, hi = n_a;                                   // first position with item >= i
-                    if (staged) {
-                        while (lo < hi) {
-                            const int mid = (lo + hi) >> 1;
-                            if (lcol[mid] < i) lo = mid + 1; else hi = mid;
-                        }
-                        if (lo < n_a && lcol[lo] == i)
-                            acc = __dadd_rn(acc, __dmul_rn(static_cast<double>(lval[lo]), static_cast<double>(wc_val[q])));
-                    } else {
-                        while (lo < hi) {
-                            const int mid = (lo + hi) >> 1;
-                            if (xb_col[a0 + mid] < i) lo = mid + 1; else hi = mid;
-                        }
-                        if (lo < n_a && xb_col[a0 + lo] == i)
-                            acc = __dadd_rn(acc, __dmul_rn(static_cast<double>(xb_val[a0 + lo]), static_cast<double>(wc_val[q])));
-                    }
+                    float x;
+                    if (staged ? find_sorted(lcol, lval, n_a, i, x) : find_sorted(xb_col + a0, xb_val + a0, n_a, i, x))
+                        acc = __dadd_rn(acc, __dmul_rn(static_cast<double>(x), static_cast<double>(wc_val[q])));
                 }
             }
             e = acc;

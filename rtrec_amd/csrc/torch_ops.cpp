@@ -398,6 +398,36 @@ void rank_metrics(const at::Tensor &ids, const at::Tensor &counts, const at::Ten
           "rtrec_rank_metrics");
 }
 
+// One CSC matrix of n_items columns: ptr [n_items + 1], row and val of one length, int32 / float32 (checked even when empty).
+void check_csc(const char *op, const char *name, const at::Tensor &cptr, const at::Tensor &crow, const at::Tensor &cval, int64_t n_items) {
+    TORCH_CHECK(cptr.numel() == n_items + 1 && cval.numel() == crow.numel(), op, ": ", name, "_ptr must hold n_items + 1 entries, ", name,
+                "_row and ", name, "_val one length");
+    check_tensor<const int32_t>(cptr); check_tensor<const int32_t>(crow); check_tensor<const float>(cval);
+}
+
+// The inputs explain_topk and score_pairs share: ids [n_rows, >= list_k] / counts [n_rows], optional row_ids [n_rows], X as a CSR
+// triple, W as a CSC triple of n_items columns, all on ids' device.  Every tensor is checked even when it is empty (ptr<> skips
+// those): an empty call is still a typed call.  Returns n_rows.
+int64_t check_lists_x_w(const char *op, const OT &row_ids, const at::Tensor &xb_ptr, const at::Tensor &xb_col, const at::Tensor &xb_val,
+                        int64_t n_items, const at::Tensor &wc_ptr, const at::Tensor &wc_row, const at::Tensor &wc_val,
+                        const at::Tensor &ids, const at::Tensor &counts, int64_t list_k) {
+    TORCH_CHECK(ids.dim() == 2 && ids.size(1) >= list_k, op, ": ids must be [n_rows, >= list_k]");
+    const int64_t n = ids.size(0);
+    const bool has_rows = row_ids.has_value() && row_ids->defined();
+    TORCH_CHECK(n <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, op, ": too many rows or items");
+    TORCH_CHECK(counts.numel() == n, op, ": counts must hold one entry per row");
+    TORCH_CHECK(!has_rows || row_ids->numel() == n, op, ": row_ids must hold one entry per row");
+    TORCH_CHECK(xb_ptr.numel() >= 1 && xb_val.numel() == xb_col.numel(), op, ": xb_ptr / xb_col / xb_val are not one CSR matrix");
+    check_tensor<const int32_t>(xb_ptr); check_tensor<const int32_t>(xb_col); check_tensor<const float>(xb_val);
+    check_csc(op, "wc", wc_ptr, wc_row, wc_val, n_items);
+    check_tensor<const int32_t>(ids); check_tensor<const int32_t>(counts);
+    if (has_rows) check_tensor<const int32_t>(*row_ids);
+    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&xb_ptr, &xb_col, &xb_val, &wc_ptr, &wc_row, &wc_val, &counts})
+        TORCH_CHECK(t->device() == ids.device(), op, ": all tensors must live on one device");
+    TORCH_CHECK(!has_rows || row_ids->device() == ids.device(), op, ": all tensors must live on one device");
+    return n;
+}
+
 // ids [n_rows, >= list_k] / counts [n_rows]: lists of item ids (score_topk's, or any the caller brings); the outputs are
 // items / contrib [n_rows, list_k, top_m] and support [n_rows, list_k] (include/rtrec_amd.h, "EXPLANATIONS").
 void explain_topk(const OT &row_ids, const at::Tensor &xb_ptr, const at::Tensor &xb_col, const at::Tensor &xb_val, int64_t n_items,
@@ -405,20 +435,9 @@ void explain_topk(const OT &row_ids, const at::Tensor &xb_ptr, const at::Tensor 
                   const at::Tensor &counts, int64_t list_k, int64_t top_m, at::Tensor items, at::Tensor contrib, at::Tensor support) {
     TORCH_CHECK(list_k >= 1 && list_k <= 64, "explain_topk: list_k must lie in 1..64, got ", list_k);
     TORCH_CHECK(top_m >= 1 && top_m <= 32, "explain_topk: top_m must lie in 1..32, got ", top_m);
-    TORCH_CHECK(ids.dim() == 2 && ids.size(1) >= list_k, "explain_topk: ids must be [n_rows, >= list_k]");
-    const int64_t n = ids.size(0);
-    TORCH_CHECK(n <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, "explain_topk: too many rows or items");
-    TORCH_CHECK(counts.numel() == n, "explain_topk: counts must hold one entry per row");
-    TORCH_CHECK(!(row_ids.has_value() && row_ids->defined()) || row_ids->numel() == n, "explain_topk: row_ids must hold one entry per row");
-    TORCH_CHECK(xb_ptr.numel() >= 1 && xb_val.numel() == xb_col.numel(), "explain_topk: xb_ptr / xb_col / xb_val are not one CSR matrix");
-    TORCH_CHECK(wc_ptr.numel() == n_items + 1 && wc_val.numel() == wc_row.numel(), "explain_topk: wc_ptr must hold n_items + 1 entries, wc_row and wc_val one length");
+    const int64_t n = check_lists_x_w("explain_topk", row_ids, xb_ptr, xb_col, xb_val, n_items, wc_ptr, wc_row, wc_val, ids, counts, list_k);
     TORCH_CHECK(items.numel() == n * list_k * top_m && contrib.numel() == n * list_k * top_m && support.numel() == n * list_k,
                 "explain_topk: outputs must be items[n_rows, list_k, top_m], contrib[same], support[n_rows, list_k]");
-    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
-    if (row_ids.has_value() && row_ids->defined()) check_tensor<const int32_t>(*row_ids);
-    check_tensor<const int32_t>(xb_ptr); check_tensor<const int32_t>(xb_col); check_tensor<const float>(xb_val);
-    check_tensor<const int32_t>(wc_ptr); check_tensor<const int32_t>(wc_row); check_tensor<const float>(wc_val);
-    check_tensor<const int32_t>(ids); check_tensor<const int32_t>(counts);
     check_tensor<int32_t>(items); check_tensor<float>(contrib); check_tensor<int32_t>(support);
     check(abi().explain_topk(static_cast<int32_t>(n), ptr<const int32_t>(row_ids), ptr<const int32_t>(xb_ptr), ptr<const int32_t>(xb_col),
                              ptr<const float>(xb_val), static_cast<int32_t>(xb_ptr.numel() - 1), xb_col.numel(), static_cast<int32_t>(n_items),
@@ -438,17 +457,15 @@ void audience_topk(const at::Tensor &items, int64_t n_users, const at::Tensor &x
     const int64_t n = items.numel(), n_items = wc_ptr.numel() - 1;
     TORCH_CHECK(items.dim() == 1 && n <= INT32_MAX, "audience_topk: items must be one list of query item ids");
     TORCH_CHECK(n_users >= 0 && n_users < INT32_MAX && n_items >= 0, "audience_topk: n_users out of range or wc_ptr empty");
-    TORCH_CHECK(xc_ptr.numel() == n_items + 1 && xc_val.numel() == xc_row.numel() && xc_row.numel() <= INT32_MAX,
-                "audience_topk: xc_ptr must hold n_items + 1 entries like wc_ptr, xc_row and xc_val one length below 2^31");
-    TORCH_CHECK(wc_val.numel() == wc_row.numel() && wc_row.numel() <= INT32_MAX, "audience_topk: wc_row and wc_val must have one length below 2^31");
+    check_csc("audience_topk", "xc", xc_ptr, xc_row, xc_val, n_items);             // (n_items is wc_ptr's: X must have W's columns)
+    check_csc("audience_topk", "wc", wc_ptr, wc_row, wc_val, n_items);
+    TORCH_CHECK(xc_row.numel() <= INT32_MAX && wc_row.numel() <= INT32_MAX, "audience_topk: xc_row and wc_row must be shorter than 2^31");
     const bool masked = user_mask.has_value() && user_mask->defined();
     TORCH_CHECK(!masked || user_mask->numel() == (n_users + 31) / 32, "audience_topk: user_mask must hold (n_users + 31) / 32 words");
     TORCH_CHECK(users.numel() == n * top_n && scores.numel() == n * top_n && count.numel() == n && eligible.numel() == n,
                 "audience_topk: outputs must be users[n_q, top_n], scores[same], count[n_q], eligible[n_q]");
     // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
     check_tensor<const int32_t>(items);
-    check_tensor<const int32_t>(xc_ptr); check_tensor<const int32_t>(xc_row); check_tensor<const float>(xc_val);
-    check_tensor<const int32_t>(wc_ptr); check_tensor<const int32_t>(wc_row); check_tensor<const float>(wc_val);
     if (masked) check_tensor<const int32_t>(*user_mask);
     check_tensor<int32_t>(users); check_tensor<float>(scores); check_tensor<int32_t>(count); check_tensor<int32_t>(eligible);
     check_tensor<void>(ws);
@@ -474,25 +491,13 @@ void score_pairs(const OT &row_ids, const at::Tensor &xb_ptr, const at::Tensor &
     TORCH_CHECK(list_k >= 1 && list_k <= 1024, "score_pairs: list_k must lie in 1..1024, got ", list_k);
     TORCH_CHECK(top_k >= 0 && top_k <= list_k, "score_pairs: top_k must lie in 0..list_k, got ", top_k);
     TORCH_CHECK(waves_per_row == 0 || waves_per_row == 1 || waves_per_row == 4, "score_pairs: waves_per_row must be 0, 1 or 4, got ", waves_per_row);
-    TORCH_CHECK(ids.dim() == 2 && ids.size(1) >= list_k, "score_pairs: ids must be [n_rows, >= list_k]");
-    const int64_t n = ids.size(0);
-    TORCH_CHECK(n <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, "score_pairs: too many rows or items");
-    TORCH_CHECK(counts.numel() == n, "score_pairs: counts must hold one entry per row");
-    TORCH_CHECK(!(row_ids.has_value() && row_ids->defined()) || row_ids->numel() == n, "score_pairs: row_ids must hold one entry per row");
-    TORCH_CHECK(xb_ptr.numel() >= 1 && xb_val.numel() == xb_col.numel(), "score_pairs: xb_ptr / xb_col / xb_val are not one CSR matrix");
-    TORCH_CHECK(wc_ptr.numel() == n_items + 1 && wc_val.numel() == wc_row.numel(), "score_pairs: wc_ptr must hold n_items + 1 entries, wc_row and wc_val one length");
+    const int64_t n = check_lists_x_w("score_pairs", row_ids, xb_ptr, xb_col, xb_val, n_items, wc_ptr, wc_row, wc_val, ids, counts, list_k);
     TORCH_CHECK(scores.numel() == n * list_k && support.numel() == n * list_k, "score_pairs: scores and support must be [n_rows, list_k]");
     TORCH_CHECK(order.numel() == n * top_k && count.numel() == (top_k > 0 ? n : count.numel()) && (count.numel() == n || count.numel() == 0),
                 "score_pairs: outputs must be order[n_rows, top_k] and count[n_rows] (count may be empty when top_k == 0)");
-    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
-    if (row_ids.has_value() && row_ids->defined()) check_tensor<const int32_t>(*row_ids);
-    check_tensor<const int32_t>(xb_ptr); check_tensor<const int32_t>(xb_col); check_tensor<const float>(xb_val);
-    check_tensor<const int32_t>(wc_ptr); check_tensor<const int32_t>(wc_row); check_tensor<const float>(wc_val);
-    check_tensor<const int32_t>(ids); check_tensor<const int32_t>(counts);
     check_tensor<float>(scores); check_tensor<int32_t>(support); check_tensor<int32_t>(order); check_tensor<int32_t>(count);
-    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&xb_ptr, &xb_col, &xb_val, &wc_ptr, &wc_row, &wc_val, &counts, &scores, &support, &order, &count})
+    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&scores, &support, &order, &count})
         TORCH_CHECK(t->device() == ids.device(), "score_pairs: all tensors must live on one device");
-    TORCH_CHECK(!(row_ids.has_value() && row_ids->defined()) || row_ids->device() == ids.device(), "score_pairs: all tensors must live on one device");
     check(abi().score_pairs(static_cast<int32_t>(n), ptr<const int32_t>(row_ids), ptr<const int32_t>(xb_ptr), ptr<const int32_t>(xb_col),
                             ptr<const float>(xb_val), static_cast<int32_t>(xb_ptr.numel() - 1), xb_col.numel(), static_cast<int32_t>(n_items),
                             ptr<const int32_t>(wc_ptr), ptr<const int32_t>(wc_row), ptr<const float>(wc_val), wc_row.numel(),

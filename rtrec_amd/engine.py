@@ -143,6 +143,7 @@ class SlimEngine:
         self.force_exchange = settings.raw("RTREC_AMD_FORCE_EXCHANGE") == "1"
         self.tile_cols = int(tile_cols or DEFAULT_TILE_COLS)
         self.be = backend if backend is not None else HipBackend(device)
+        self._up = getattr(self.be, "to_dev_small", self.be.to_dev)      # host -> device for request-sized arrays
         self.n_users = 0
         self.n_items = 0
         self._X: Dict[str, Any] = {}
@@ -1179,8 +1180,8 @@ class SlimEngine:
         if not self._W:
             raise RuntimeError("Model must be fitted before calling batch_recommend.")
         if xb is None:
-            xb = (self._X["rptr"], self._X["rcol"], self._X["rval"])
-        up = getattr(be, "to_dev_small", be.to_dev)
+            xb = self._x_csr()
+        up = self._up
         if d_rows is None and row_ids is not None:
             d_rows = up(np.asarray(row_ids, dtype=np.int32))
         if mode == _native.TOPK_CANDIDATES and candidates is not None:
@@ -1533,8 +1534,7 @@ class SlimEngine:
         ids = be.empty((n, top_k), torch.int32)
         sc = be.empty((n, top_k), torch.float32)
         cnt = be.empty((n,), torch.int32)
-        cptr, crow, cval = W["dw"].csc_arrays(torch)
-        be.similar_topk(d_q, {"cptr": cptr, "crow": crow, "cval": cval}, top_k, ids, sc, cnt)
+        be.similar_topk(d_q, self._w_csc(), top_k, ids, sc, cnt)
         if getattr(W["dw"], "shard", None) is not None and self.world_size > 1:
             # W is column-sharded: column j is held by its owner alone ("similar_items(j) is served by the owner of
             # column j"); every rank answers its own queries and one all-gather of [n, 2k + 1] words brings them together
@@ -1553,50 +1553,41 @@ class SlimEngine:
     EXPLAIN_MAX_LIST = 64       # list_k / top_m limits of rtrec_slim_explain_topk
     EXPLAIN_MAX_TOP_M = 32
 
-    def _explain_weights(self, what: str = "explanations", verb: str = "explain") -> DeviceWeights:
-        """The W an explanation (or a pair score: the same sum) reads: all of it, with the float32 values the scores were
-        computed from."""
+    # The request calls below read the whole of W on this rank, with the float32 values the scores were computed from (a
+    # float64 W whose values are float32 numbers is served with those numbers).  Per call: who needs it, what to do with the
+    # gathered model, what would not be exact.
+    _WHOLE_W = {
+        "explain": ("explanations need", "explain", "explanations are exact float32 products"),
+        "score_pairs": ("pair scores need", "score_pairs", "pair scores are exact float32 products"),
+        "recommend_users": ("an audience needs", "serve audiences", "audience scores are exact float32 sums"),
+    }
+
+    def _whole_w(self, call: str) -> DeviceWeights:
+        """The W that `call` (a key of _WHOLE_W) reads, or the reason why this engine cannot serve it."""
+        needs, verb, exact = self._WHOLE_W[call]
         if not self._W:
-            raise RuntimeError(f"Model must be fitted before calling {verb}.")
+            raise RuntimeError(f"Model must be fitted before calling {call}.")
         dw: DeviceWeights = self._W["dw"]
         if getattr(dw, "shard", None) is not None and self.world_size > 1:
-            raise ValueError(f"{what} need the whole of W on this rank, and W is column-sharded (shard_w): "
+            raise ValueError(f"{needs} the whole of W on this rank, and W is column-sharded (shard_w): "
                              f"gather it with gather_item_similarity() and {verb} from the gathered model")
         if dw.lossy:
-            raise ValueError(f"{what} are exact float32 products; this W was uploaded from a float64 matrix whose values "
+            raise ValueError(f"{exact}; this W was uploaded from a float64 matrix whose values "
                              "are not float32 numbers (DeviceWeights.lossy)")
         return dw
 
-    def explain_device(self, d_rows, n_rows: int, xb, ids, counts, top_m: int):
-        """Device tensors (reason_items[n_rows, k, top_m], contributions[same], support[n_rows, k]) for the lists `ids`
-        [n_rows, k] / `counts` [n_rows] (int32 device tensors, e.g. what score_topk_device returned: they never leave HBM) of
-        the rows `d_rows` (int32 device tensor, or None = rows 0 .. n_rows-1) of `xb` = (ptr, col, val) device tensors (None:
-        the resident X).  The contract is the comment of rtrec_slim_explain_topk in include/rtrec_amd.h.  Every rank that
-        holds the whole W answers locally: there is no collective."""
-        be, torch = self.be, self.be.torch
-        dw = self._explain_weights()
-        k = int(ids.shape[-1])
-        if not 1 <= k <= self.EXPLAIN_MAX_LIST or not 1 <= int(top_m) <= self.EXPLAIN_MAX_TOP_M:
-            raise ValueError(f"explain: lists of 1..{self.EXPLAIN_MAX_LIST} items and top_m in 1..{self.EXPLAIN_MAX_TOP_M} "
-                             f"are supported, got {k} and {top_m}")
-        if xb is None:
-            xb = (self._X["rptr"], self._X["rcol"], self._X["rval"])
-        items = be.empty((n_rows, k, int(top_m)), torch.int32)
-        contrib = be.empty((n_rows, k, int(top_m)), torch.float32)
-        support = be.empty((n_rows, k), torch.int32)
-        if n_rows == 0:
-            return items, contrib, support
-        cptr, crow, cval = dw.csc_arrays(torch)
-        be.explain_topk(d_rows, xb, dw.n_items, {"cptr": cptr, "crow": crow, "cval": cval}, ids.contiguous(), counts.contiguous(),
-                        k, int(top_m), items, contrib, support)
-        return items, contrib, support
+    def _w_csc(self) -> Dict[str, Any]:
+        """W's CSC view as the dict the backend's request methods take."""
+        cptr, crow, cval = self._W["dw"].csc_arrays(self.be.torch)
+        return {"cptr": cptr, "crow": crow, "cval": cval}
 
-    def explain_rows(self, row_ids: Sequence[int], item_ids: np.ndarray, counts: Optional[np.ndarray] = None, top_m: int = 3,
-                     xb=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """explain_device for lists the caller brings: numpy (reason_items[B, k, top_m], contributions, support[B, k]) for
-        `item_ids` [B, k] (-1 = no item) of the rows `row_ids` of the resident X -- or of the device CSR batch `xb`.  A row id
-        outside the matrix is a user without a row: support 0 everywhere."""
-        be = self.be
+    def _x_csr(self):
+        """The resident X as the (ptr, col, val) device tensors an `xb` argument stands for."""
+        return self._X["rptr"], self._X["rcol"], self._X["rval"]
+
+    def _upload_lists(self, row_ids, item_ids, counts, xb):
+        """The host side of explain_rows / score_pairs_rows: (B, k, device rows, device ids, device counts) for the lists
+        `item_ids` [B, k] of the rows `row_ids`; counts default to k, a row outside the matrix becomes -1 (no row)."""
         row_ids = np.asarray(row_ids, dtype=np.int64)
         item_ids = np.ascontiguousarray(item_ids, dtype=np.int32)
         if item_ids.ndim != 2 or item_ids.shape[0] != len(row_ids):
@@ -1607,19 +1598,45 @@ class SlimEngine:
             raise ValueError("counts must hold one entry per row")
         n_x = self.n_users if xb is None else int(xb[0].shape[0]) - 1
         rows32 = np.where((row_ids >= 0) & (row_ids < n_x), row_ids, -1).astype(np.int32)
+        return B, k, self._up(rows32), self._up(item_ids), self._up(counts)
+
+    def explain_device(self, d_rows, n_rows: int, xb, ids, counts, top_m: int):
+        """Device tensors (reason_items[n_rows, k, top_m], contributions[same], support[n_rows, k]) for the lists `ids`
+        [n_rows, k] / `counts` [n_rows] (int32 device tensors, e.g. what score_topk_device returned: they never leave HBM) of
+        the rows `d_rows` (int32 device tensor, or None = rows 0 .. n_rows-1) of `xb` = (ptr, col, val) device tensors (None:
+        the resident X).  The contract is the comment of rtrec_slim_explain_topk in include/rtrec_amd.h.  Every rank that
+        holds the whole W answers locally: there is no collective."""
+        be, torch = self.be, self.be.torch
+        dw = self._whole_w("explain")
+        k = int(ids.shape[-1])
+        if not 1 <= k <= self.EXPLAIN_MAX_LIST or not 1 <= int(top_m) <= self.EXPLAIN_MAX_TOP_M:
+            raise ValueError(f"explain: lists of 1..{self.EXPLAIN_MAX_LIST} items and top_m in 1..{self.EXPLAIN_MAX_TOP_M} "
+                             f"are supported, got {k} and {top_m}")
+        if xb is None:
+            xb = self._x_csr()
+        items = be.empty((n_rows, k, int(top_m)), torch.int32)
+        contrib = be.empty((n_rows, k, int(top_m)), torch.float32)
+        support = be.empty((n_rows, k), torch.int32)
+        if n_rows == 0:
+            return items, contrib, support
+        be.explain_topk(d_rows, xb, dw.n_items, self._w_csc(), ids.contiguous(), counts.contiguous(), k, int(top_m), items, contrib,
+                        support)
+        return items, contrib, support
+
+    def explain_rows(self, row_ids: Sequence[int], item_ids: np.ndarray, counts: Optional[np.ndarray] = None, top_m: int = 3,
+                     xb=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """explain_device for lists the caller brings: numpy (reason_items[B, k, top_m], contributions, support[B, k]) for
+        `item_ids` [B, k] (-1 = no item) of the rows `row_ids` of the resident X -- or of the device CSR batch `xb`.  A row id
+        outside the matrix is a user without a row: support 0 everywhere."""
+        B, k, d_rows, d_ids, d_counts = self._upload_lists(row_ids, item_ids, counts, xb)
         if B == 0:
-            self._explain_weights()
+            self._whole_w("explain")
             return (np.empty((0, k, top_m), np.int32), np.empty((0, k, top_m), np.float32), np.empty((0, k), np.int32))
-        up = getattr(be, "to_dev_small", be.to_dev)
-        out = self.explain_device(up(rows32), B, xb, up(item_ids), up(counts), top_m)
+        out = self.explain_device(d_rows, B, xb, d_ids, d_counts, top_m)
         return tuple(t.cpu().numpy() for t in out)
 
     # ------------------------------------------------------------------------------ rerank: per-user candidate lists
     PAIRS_MAX_LIST = 1024       # list_k limit of rtrec_slim_score_pairs
-
-    def _pairs_weights(self) -> DeviceWeights:
-        """The W a pair score reads: the policy (and the checks) of the explanations, whose terms it adds."""
-        return self._explain_weights("pair scores", "score_pairs")
 
     def score_pairs_device(self, d_rows, n_rows: int, xb, ids, counts, top_k: int = 0, filter_interacted: bool = False,
                            waves_per_row: int = 0):
@@ -1633,7 +1650,7 @@ class SlimEngine:
         lists longer than 1024 are worked through in column chunks; ranking serves lists of up to 1024.  The results stay in
         HBM.  Every rank that holds the whole W answers locally: there is no collective."""
         be, torch = self.be, self.be.torch
-        dw = self._pairs_weights()
+        dw = self._whole_w("score_pairs")
         k, top_k, n_rows = int(ids.shape[-1]), int(top_k), int(n_rows)
         if top_k > 0 and k > self.PAIRS_MAX_LIST:
             raise ValueError(f"score_pairs ranks lists of up to {self.PAIRS_MAX_LIST} items, got {k}: longer lists are scored "
@@ -1647,9 +1664,8 @@ class SlimEngine:
         if n_rows == 0 or k == 0:
             return scores, support, order, count
         if xb is None:
-            xb = (self._X["rptr"], self._X["rcol"], self._X["rval"])
-        cptr, crow, cval = dw.csc_arrays(torch)
-        W = {"cptr": cptr, "crow": crow, "cval": cval}
+            xb = self._x_csr()
+        W = self._w_csc()
         if k <= self.PAIRS_MAX_LIST:
             be.score_pairs(d_rows, xb, dw.n_items, W, ids.contiguous(), counts.contiguous(), k, top_k, bool(filter_interacted),
                            scores, support, order, count, waves_per_row=waves_per_row)
@@ -1667,37 +1683,16 @@ class SlimEngine:
         """score_pairs_device for lists the caller brings: numpy (scores[B, k], support[B, k], order[B, top_k], count[B]) for
         `item_ids` [B, k] (-1 = no item) of the rows `row_ids` of the resident X -- or of the device CSR batch `xb`.  A row id
         outside the matrix is a user without a row: score 0 and support 0 for every valid item."""
-        be = self.be
-        row_ids = np.asarray(row_ids, dtype=np.int64)
-        item_ids = np.ascontiguousarray(item_ids, dtype=np.int32)
-        if item_ids.ndim != 2 or item_ids.shape[0] != len(row_ids):
-            raise ValueError("item_ids must be [len(row_ids), k]")
-        B, k = item_ids.shape
-        counts = np.full(B, k, dtype=np.int32) if counts is None else np.asarray(counts, dtype=np.int32)
-        if counts.shape != (B,):
-            raise ValueError("counts must hold one entry per row")
-        n_x = self.n_users if xb is None else int(xb[0].shape[0]) - 1
-        rows32 = np.where((row_ids >= 0) & (row_ids < n_x), row_ids, -1).astype(np.int32)
-        up = getattr(be, "to_dev_small", be.to_dev)
-        out = self.score_pairs_device(up(rows32), B, xb, up(item_ids), up(counts), top_k, filter_interacted)
+        B, _, d_rows, d_ids, d_counts = self._upload_lists(row_ids, item_ids, counts, xb)
+        out = self.score_pairs_device(d_rows, B, xb, d_ids, d_counts, top_k, filter_interacted)
         return tuple(t.cpu().numpy() for t in out)
 
     # ------------------------------------------------------------------------------ audience of an item
     AUDIENCE_MAX_TOP_N = 1024   # top_n limit of rtrec_slim_audience_topk
 
     def _audience_check(self, top_n: int) -> DeviceWeights:
-        """The one argument check of the audience calls: the W an audience is scored from -- all of it, with the float32 values
-        the scores are computed from (a float64 W whose values are float32 numbers is served with those numbers: the float32
-        model's scores) -- and top_n within the kernel's range."""
-        if not self._W:
-            raise RuntimeError("Model must be fitted before calling recommend_users.")
-        dw: DeviceWeights = self._W["dw"]
-        if getattr(dw, "shard", None) is not None and self.world_size > 1:
-            raise ValueError("an audience needs the whole of W on this rank, and W is column-sharded (shard_w): "
-                             "gather it with gather_item_similarity() and serve audiences from the gathered model")
-        if dw.lossy:
-            raise ValueError("audience scores are exact float32 sums; this W was uploaded from a float64 matrix whose values "
-                             "are not float32 numbers (DeviceWeights.lossy)")
+        """The one argument check of the audience calls: a W they can be scored from, and top_n within the kernel's range."""
+        dw = self._whole_w("recommend_users")
         if not 1 <= int(top_n) <= self.AUDIENCE_MAX_TOP_N:
             raise ValueError(f"recommend_users: top_n in 1..{self.AUDIENCE_MAX_TOP_N} is supported, got {top_n}")
         return dw
@@ -1739,15 +1734,13 @@ class SlimEngine:
         eligible = be.empty((n_q,), torch.int32)
         if n_q == 0:
             return users, scores, count, eligible
-        cptr, crow, cval = dw.csc_arrays(torch)
         X = self._X
         xptr, n_w = X["cptr"], dw.n_items          # the kernel reads the columns of X that W knows: X may have grown since the fit
         if xptr.numel() > n_w + 1:
             xptr = xptr[:n_w + 1]
         elif xptr.numel() < n_w + 1:
             xptr = torch.cat([xptr, xptr[-1:].expand(n_w + 1 - xptr.numel())])
-        be.audience_topk(d_items, self.n_users, (xptr, X["crow"], X["cval"]), {"cptr": cptr, "crow": crow, "cval": cval}, top_n,
-                         bool(filter_interacted), d_user_mask, users, scores, count, eligible)
+        be.audience_topk(d_items, self.n_users, (xptr, X["crow"], X["cval"]), self._w_csc(), top_n, bool(filter_interacted), d_user_mask, users, scores, count, eligible)
         return users, scores, count, eligible
 
     def audience_items(self, item_ids: Sequence[int], top_n: int = 100, filter_interacted: bool = True,
@@ -1769,8 +1762,7 @@ class SlimEngine:
             bits = np.zeros(((self.n_users + 31) // 32) * 32, dtype=np.uint8)
             bits[rows] = 1
             d_mask = be.to_dev(np.packbits(bits, bitorder="little").view(np.int32))
-        up = getattr(be, "to_dev_small", be.to_dev)
-        out = self.audience_device(up(q32), len(q32), top_n, filter_interacted, d_mask)
+        out = self.audience_device(self._up(q32), len(q32), top_n, filter_interacted, d_mask)
         return tuple(t.cpu().numpy() for t in out)
 
 

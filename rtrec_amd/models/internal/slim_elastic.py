@@ -378,14 +378,9 @@ class SLIMElastic:
         ids, scores, counts = self._topk(Xb, candidate_item_ids, top_k, filter_interacted, dense_output)
         return self._format(ids, scores, counts, ret_scores)
 
-    def explain_batch(self, user_ids: List[int], interaction_matrix: sp.csr_matrix, item_ids: Sequence[Sequence[int]],
-                      top_m: int = 3) -> Tuple[ndarray, ndarray, ndarray]:
-        """An extension (the reference has none): for every (user, item) of `item_ids` -- one list of item ids per user, at
-        most 64 each, -1 or an id outside W = no item -- the `top_m` largest terms X[u, j] * W[j, i] of the score
-        (csrc/explain.hip; the contract is the comment of rtrec_slim_explain_topk in include/rtrec_amd.h).  Returns
-        (reason_items[B, k, top_m], contributions[B, k, top_m], support[B, k]), k = the longest list, -1 / -inf padded."""
-        if not self.is_fitted:
-            raise RuntimeError("Model must be fitted before calling explain_batch.")
+    def _lists_on_rows(self, user_ids: List[int], interaction_matrix: sp.csr_matrix, item_ids: Sequence[Sequence[int]]):
+        """What explain_batch and score_pairs_batch hand the engine: (rows 0..B-1, ids[B, k] padded with -1, counts[B], the
+        uploaded CSR batch interaction_matrix[user_ids] cut or widened to the fitted W's columns), k = the longest list."""
         rows = [list(r) for r in item_ids]
         if len(rows) != len(user_ids):
             raise ValueError("item_ids must hold one list per user")
@@ -400,7 +395,18 @@ class SLIMElastic:
         if Xb.shape[1] != n_items:
             Xb = Xb.copy()
             Xb.resize((Xb.shape[0], n_items))
-        return self.engine.explain_rows(np.arange(len(rows)), ids, counts, top_m, xb=self.engine._upload_csr(Xb))
+        return np.arange(len(rows)), ids, counts, self.engine._upload_csr(Xb)
+
+    def explain_batch(self, user_ids: List[int], interaction_matrix: sp.csr_matrix, item_ids: Sequence[Sequence[int]],
+                      top_m: int = 3) -> Tuple[ndarray, ndarray, ndarray]:
+        """An extension (the reference has none): for every (user, item) of `item_ids` -- one list of item ids per user, at
+        most 64 each, -1 or an id outside W = no item -- the `top_m` largest terms X[u, j] * W[j, i] of the score
+        (csrc/explain.hip; the contract is the comment of rtrec_slim_explain_topk in include/rtrec_amd.h).  Returns
+        (reason_items[B, k, top_m], contributions[B, k, top_m], support[B, k]), k = the longest list, -1 / -inf padded."""
+        if not self.is_fitted:
+            raise RuntimeError("Model must be fitted before calling explain_batch.")
+        rows, ids, counts, xb = self._lists_on_rows(user_ids, interaction_matrix, item_ids)
+        return self.engine.explain_rows(rows, ids, counts, top_m, xb=xb)
 
     def score_pairs_batch(self, user_ids: List[int], interaction_matrix: sp.csr_matrix, item_ids: Sequence[Sequence[int]],
                           top_k: int = 0, filter_interacted: bool = False) -> Tuple[ndarray, ndarray, ndarray, ndarray]:
@@ -413,22 +419,8 @@ class SLIMElastic:
         `filter_interacted` the items stored in the user's row do not compete), -1 behind counts[b]."""
         if not self.is_fitted:
             raise RuntimeError("Model must be fitted before calling score_pairs_batch.")
-        rows = [list(r) for r in item_ids]
-        if len(rows) != len(user_ids):
-            raise ValueError("item_ids must hold one list per user")
-        k = max([len(r) for r in rows] + [1])
-        ids = np.full((len(rows), k), -1, dtype=np.int32)
-        for b, r in enumerate(rows):
-            ids[b, :len(r)] = r
-        counts = np.array([len(r) for r in rows], dtype=np.int32)
-        self._sync_weights()
-        n_items = self.n_items_fitted
-        Xb = interaction_matrix[user_ids, :].tocsr() if len(rows) else sp.csr_matrix((0, n_items), dtype=np.float32)
-        if Xb.shape[1] != n_items:
-            Xb = Xb.copy()
-            Xb.resize((Xb.shape[0], n_items))
-        return self.engine.score_pairs_rows(np.arange(len(rows)), ids, counts, top_k, filter_interacted,
-                                            xb=self.engine._upload_csr(Xb))
+        rows, ids, counts, xb = self._lists_on_rows(user_ids, interaction_matrix, item_ids)
+        return self.engine.score_pairs_rows(rows, ids, counts, top_k, filter_interacted, xb=xb)
 
     def recommend_users_batch(self, item_ids: Sequence[int], top_n: int = 100, filter_interacted: bool = True,
                               candidate_rows: Optional[Sequence[int]] = None) -> Tuple[ndarray, ndarray, ndarray, ndarray]:

@@ -394,9 +394,8 @@ class SLIM(BaseModel):
         from .._native import TOPK_DENSE, TOPK_SPARSE
         if not self.model.is_fitted:
             raise RuntimeError("Model must be fitted before calling explain_batch.")
-        arr = self._int_user_array(users)          # integer pass-through ids: the hot / cold split is one compare
-        if arr is None:
-            users = list(users)
+        arr = self._int_user_array(users)
+        users = arr if arr is not None else list(users)
         B, m = len(users), int(top_m)
         if items is not None:
             items = [list(row) for row in items]
@@ -414,25 +413,15 @@ class SLIM(BaseModel):
         support = np.zeros((B, K), dtype=np.int32)
         eng = self.model.engine
         n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
-        if arr is not None:
-            uid, cold = arr, arr > self.interactions.max_user_id
-        else:
-            known = [self._known_user_id(u) for u in users]
-            cold = np.fromiter((u is None for u in known), dtype=bool, count=B)
-            uid = np.fromiter((0 if u is None else u for u in known), dtype=np.int64, count=B)
+        uid, cold = self._user_rows(users)
         regular = ~cold & (uid >= 0) & (uid < n_users)
         if B:
             self.model._sync_weights()
-            eng._explain_weights()               # a W that cannot be explained is refused whatever the batch holds
+            eng._whole_w("explain")                # a W that cannot be explained is refused whatever the batch holds
         if items is not None:
             for b, row in enumerate(items):
                 counts[b] = len(row)
-                for p_, raw in enumerate(row):
-                    try:
-                        i = self.item_ids.get_id(raw)
-                    except (ValueError, TypeError):       # an id of the other kind: no such item
-                        i = None
-                    ids[b, p_] = i if (i is not None and 0 <= i < n_items) else -1
+                ids[b, :len(row)] = self._ids_or_minus_one(row, self.item_ids.get_id, n_items)
             if regular.any():
                 self._sync_interactions()
                 r_ids[:], contrib[:], support[:] = eng.explain_rows(np.where(regular, uid, -1), ids, counts, m)
@@ -454,8 +443,7 @@ class SLIM(BaseModel):
                 rows = uid[regular].astype(np.int32)
                 mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
                 if eng.topk_supported(k, mode):
-                    be = eng.be
-                    d_rows = getattr(be, "to_dev_small", be.to_dev)(rows)
+                    d_rows = eng._up(rows)
                     d_ids, _, d_cnt = eng.score_topk_device(None, len(rows), k, filter_interacted, mode, d_rows=d_rows)
                     out = eng.explain_device(d_rows, len(rows), None, d_ids, d_cnt, m)
                     h_ids, h_cnt = d_ids.cpu().numpy(), d_cnt.cpu().numpy()
@@ -468,7 +456,7 @@ class SLIM(BaseModel):
                 r_ids[pos, :k], contrib[pos, :k], support[pos, :k] = h_r, h_c, h_s
         if as_arrays:
             return ids, counts, r_ids, contrib, support
-        raw_of = (lambda i: i) if self.item_ids.pass_through else self.item_ids.get
+        raw_of = self._raw_of(self.item_ids)
         id_rows, cnts, reason_rows, contrib_rows = ids.tolist(), counts.tolist(), r_ids.tolist(), contrib.tolist()
         n_reasons = np.minimum(support, m).tolist()
         out_rows: List[List[Tuple[Any, List[Tuple[Any, float]]]]] = []
@@ -488,6 +476,26 @@ class SLIM(BaseModel):
 
     # ------------------------------------------------------------ rerank per-user candidate lists (an extension)
     RERANK_MAX_LIST = 1024      # list length rtrec_slim_score_pairs ranks
+
+    @staticmethod
+    def _ids_or_minus_one(values: Any, known, bound: Optional[int] = None) -> np.ndarray:
+        """Raw ids to an int64 array of internal ids through `known` (item_ids.get_id, _known_user_id): -1 for an id the model
+        does not know, an id of the other kind, and an internal id outside [0, bound)."""
+        values = values.tolist() if isinstance(values, np.ndarray) else list(values)
+        out = np.full(len(values), -1, dtype=np.int64)
+        for p_, raw in enumerate(values):
+            try:
+                i = known(raw)
+            except (ValueError, TypeError):       # an id of the other kind: nobody / nothing the model knows
+                i = None
+            if i is not None and 0 <= i and (bound is None or i < bound):
+                out[p_] = i
+        return out
+
+    @staticmethod
+    def _raw_of(id_map: Any):
+        """Internal id -> raw id: the identity for ids that pass through unmapped."""
+        return (lambda i: i) if id_map.pass_through else id_map.get
 
     def _user_rows(self, users: Any) -> Tuple[np.ndarray, np.ndarray]:
         """(internal user id per user, cold mask): the hot / cold split of recommend_batch -- one compare for integer
@@ -560,7 +568,7 @@ class SLIM(BaseModel):
         uid, cold = self._user_rows(users)
         if B:
             self.model._sync_weights()
-            self.model.engine._pairs_weights()    # a W that cannot be served is refused whatever the batch holds
+            self.model.engine._whole_w("score_pairs")    # a W that cannot be served is refused whatever the batch holds
         hot = np.flatnonzero(~cold)
         if len(hot) and k > 0:
             all_hot = len(hot) == B
@@ -584,7 +592,7 @@ class SLIM(BaseModel):
             out_ids[b, :len(row)], out_sc[b, :len(row)], out_cnt[b] = row, 0.0, len(row)
         if as_arrays:
             return out_ids, out_sc, out_cnt
-        raw_of = (lambda i: i) if self.item_ids.pass_through else self.item_ids.get
+        raw_of = self._raw_of(self.item_ids)
         id_rows, sc_rows, cnts, is_cold = out_ids.tolist(), out_sc.tolist(), out_cnt.tolist(), cold.tolist()
         out: List[Any] = []
         for b in range(B):
@@ -616,23 +624,12 @@ class SLIM(BaseModel):
         scores = np.zeros(n, dtype=np.float32)
         support = np.full(n, -1, dtype=np.int32)
         n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
-
-        def ids_of(values: Any, known) -> np.ndarray:
-            out = np.full(n, -1, dtype=np.int64)
-            for p_, raw in enumerate(values.tolist() if isinstance(values, np.ndarray) else values):
-                try:
-                    i = known(raw)
-                except (ValueError, TypeError):       # an id of the other kind: nobody / nothing the model knows
-                    i = None
-                if i is not None:
-                    out[p_] = i
-            return out
-
-        uid, iid = ids_of(users, self._known_user_id), ids_of(items, self.item_ids.get_id)
+        uid = self._ids_or_minus_one(users, self._known_user_id, n_users)
+        iid = self._ids_or_minus_one(items, self.item_ids.get_id, n_items)
         if n:
             self.model._sync_weights()
-            self.model.engine._pairs_weights()
-        valid = np.flatnonzero((uid >= 0) & (uid < n_users) & (iid >= 0) & (iid < n_items))
+            self.model.engine._whole_w("score_pairs")
+        valid = np.flatnonzero((uid >= 0) & (iid >= 0))
         if len(valid):
             L = self.RERANK_MAX_LIST
             by_user = valid[np.argsort(uid[valid], kind="stable")]
@@ -683,26 +680,11 @@ class SLIM(BaseModel):
         if not self.model.is_fitted:
             raise RuntimeError("Model must be fitted before calling recommend_users_batch.")
         items = list(items)
-        n_items = self.model.n_items_fitted
-        q = np.full(len(items), -1, dtype=np.int64)
-        for p_, raw in enumerate(items):
-            try:
-                i = self.item_ids.get_id(raw)
-            except (ValueError, TypeError):       # an id of the other kind: no such item
-                i = None
-            if i is not None and 0 <= i < n_items:
-                q[p_] = i
+        q = self._ids_or_minus_one(items, self.item_ids.get_id, self.model.n_items_fitted)
         rows = None
         if candidate_users is not None:
-            known = []
-            for raw in candidate_users:
-                try:
-                    u = self._known_user_id(raw)
-                except (ValueError, TypeError):
-                    u = None
-                if u is not None and u >= 0:
-                    known.append(u)
-            rows = np.asarray(known, dtype=np.int64)
+            rows = self._ids_or_minus_one(candidate_users, self._known_user_id)
+            rows = rows[rows >= 0]
         self.model._sync_weights()
         self.model.engine._audience_check(top_n)  # a W or a top_n that cannot be served is refused before X is touched
         if len(items):
@@ -710,7 +692,7 @@ class SLIM(BaseModel):
         users, scores, counts, eligible = self.model.recommend_users_batch(q, top_n, filter_interacted, rows)
         if as_arrays:
             return users, scores, counts, eligible
-        raw_of = (lambda u: u) if self.user_ids.pass_through else self.user_ids.get
+        raw_of = self._raw_of(self.user_ids)
         user_rows, score_rows, cnts = users.tolist(), scores.tolist(), counts.tolist()
         if ret_scores:
             return [[(raw_of(u), s) for u, s in zip(user_rows[b][:cnts[b]], score_rows[b][:cnts[b]])] for b in range(len(items))]

@@ -1,10 +1,11 @@
-"""Four small kernels called directly through the C ABI (be.lib) and compared with plain numpy / Python models written from
-their contracts in include/rtrec_amd.h:
+"""Five small kernels called directly -- through the C ABI (be.lib), the last one through its custom op -- and compared with
+plain numpy / Python models written from their contracts in include/rtrec_amd.h:
 
   1. rtrec_slim_score_candidates  (csrc/score_cands.hip)      ranking of a given candidate list
   2. rtrec_slim_dense_fill        (csrc/score_dense_fill.hip) zero-score columns behind a short DENSE list
   3. rtrec_slim_score_rows        (csrc/score.hip)            score-vector export (predict*)
   4. rtrec_store_fold_device      (csrc/store_device.hip)     per-pair fold of a bulk ingest
+  5. rtrec_slim_refine_topk_f64   (csrc/score_refine.hip)     float64 scores and order of a fast pass's lists
 
 Bar: exact equality -- ids, counts, float32 / float64 bit patterns, and the bytes of memory outside the contract (every
 output buffer starts as sentinels and carries a guard region behind its last row).  tests/test_request_kernels_host.py checks
@@ -875,3 +876,111 @@ def test_ingest_fold_without_pairs(engine):
     rc, val, ts, v32 = run_fold(engine.be, order, start, delta, tstamp, old, -3.0, 10.0, False, True, n_groups=0)
     assert rc == RTREC_OK
     assert (val == SENTINEL_SCORE).all() and (ts == SENTINEL_SCORE).all() and (v32 == np.float32(SENTINEL_SCORE)).all()
+
+
+# ======================================================================================================================
+# 5. float64 refine: rows on both sides of the staging limit (kRfItems / rows per wave), searched in LDS or in global memory
+# ======================================================================================================================
+RF_ITEMS = 700
+RF_COL_MAX = 30                # stored weights per column of W, at most
+RF_STAGED = {10: 256, 3: 64}   # top_k -> staged items per row: 1,024 slots per wave over 64 / P rows, P = 16 and 4 lanes per row
+RF_ROW_LENS = [0, 1, 63, 64, 65, 255, 256, 257, 600, 5, 17, 30]
+RF_ROWS = 70                   # list rows per call: five workgroups at top_k 10 (16 rows each), two at top_k 3 (64 rows each)
+RF_FOREIGN = 23                # the list row whose row id is no row of X
+
+
+@functools.lru_cache(maxsize=None)
+def refine_data():
+    """(X [12, 700] CSR, W [700, 700] CSC), float32, continuous positive values: no two float64 sums tie unless both are 0."""
+    rng = np.random.default_rng(41)
+    cols = [np.sort(rng.choice(RF_ITEMS, n, replace=False)) for n in RF_ROW_LENS]
+    ptr = np.concatenate([[0], np.cumsum(RF_ROW_LENS)])
+    X = sp.csr_matrix((rng.uniform(0.5, 5.0, ptr[-1]).astype(np.float32), np.concatenate(cols).astype(np.int32), ptr.astype(np.int32)),
+                      shape=(len(RF_ROW_LENS), RF_ITEMS))
+    col_len = rng.integers(0, RF_COL_MAX + 1, RF_ITEMS)
+    wrows = [np.sort(rng.choice(RF_ITEMS, n, replace=False)) for n in col_len]
+    wptr = np.concatenate([[0], np.cumsum(col_len)])
+    W = sp.csc_matrix((rng.uniform(0.01, 1.0, wptr[-1]).astype(np.float32), np.concatenate(wrows).astype(np.int32), wptr.astype(np.int32)),
+                      shape=(RF_ITEMS, RF_ITEMS))
+    frozen(X.data, X.indices, X.indptr, W.data, W.indices, W.indptr)
+    return X, W
+
+
+@functools.lru_cache(maxsize=None)
+def refine_case(top_k):
+    """(row_ids [70], in_ids [70, top_k + 1], in_count [70]): every row of X several times, neighbours of a wave on different
+    sides of the staging limit, one row id outside the matrix; top_k + 1 distinct columns per list in no order, and lists that
+    are empty, hold one entry, top_k - 1 or top_k entries instead of all top_k + 1."""
+    rng = np.random.default_rng([43, top_k])
+    n_x, kin = len(RF_ROW_LENS), top_k + 1
+    row_ids = np.concatenate([rng.permutation(n_x) for _ in range(RF_ROWS // n_x + 1)])[:RF_ROWS].astype(np.int32)
+    row_ids[RF_FOREIGN] = n_x
+    in_ids = np.stack([rng.choice(RF_ITEMS, kin, replace=False) for _ in range(RF_ROWS)]).astype(np.int32)
+    in_count = np.full(RF_ROWS, kin, dtype=np.int32)
+    in_count[[3, 18, 37, 52, 66]] = [0, 1, top_k - 1, top_k, 2]
+    return frozen(row_ids, in_ids, in_count)
+
+
+def refine_model(top_k, cap=None, **mut):
+    """The lists rtrec_slim_refine_topk_f64 writes: (ids [R, top_k], float32 scores, float64 scores, counts).  Per list entry the
+    float64 sum of double(x) * double(w) over the column's entries in ascending order (fold_column), the entries by (score
+    descending, list position ascending), slots behind the count -1 / -inf.  Mutations of the host file: cap (only the first
+    `cap` items of a longer row are seen), **mut (fold_column)."""
+    X, W = refine_data()
+    row_ids, in_ids, in_count = refine_case(top_k)
+    R = len(row_ids)
+    o_ids = np.full((R, top_k), -1, dtype=np.int32)
+    o_sc = np.full((R, top_k), -np.inf, dtype=np.float32)
+    o_sc64 = np.full((R, top_k), -np.inf, dtype=np.float64)
+    o_cnt = np.zeros(R, dtype=np.int32)
+    for r, xr in enumerate(row_ids.tolist()):
+        a, b = (X.indptr[xr], X.indptr[xr + 1]) if 0 <= xr < X.shape[0] else (0, 0)
+        if cap is not None and b - a > cap:
+            b = a + cap
+        n = min(int(in_count[r]), top_k + 1)
+        sc = [fold_column(X.indices[a:b], X.data[a:b], W.indices[W.indptr[c]:W.indptr[c + 1]], W.data[W.indptr[c]:W.indptr[c + 1]], True,
+                          **mut) for c in in_ids[r, :n].tolist()]
+        best = sorted(range(n), key=lambda p: (-sc[p], p))[:top_k]
+        o_cnt[r] = len(best)
+        for j, p in enumerate(best):
+            o_ids[r, j], o_sc[r, j], o_sc64[r, j] = in_ids[r, p], np.float32(sc[p]), sc[p]
+    return o_ids, o_sc, o_sc64, o_cnt
+
+
+def run_refine(be, top_k):
+    """(ids, float32 scores, float64 scores, counts) of one call of the op; the outputs have GUARD_ROWS rows more than the call
+    may write and start as sentinels."""
+    import torch
+    X, W = refine_data()
+    row_ids, in_ids, in_count = refine_case(top_k)
+    R = len(row_ids)
+    d = [dev(be, a) for a in (row_ids, X.indptr, X.indices, X.data, W.indptr, W.indices, W.data, in_ids, in_count)]
+    in_sc = torch.zeros((R, top_k + 1), dtype=torch.float32, device=be.device)      # read by the margin test only (not asserted)
+    o_ids = torch.full((R + GUARD_ROWS, top_k), SENTINEL_ID, dtype=torch.int32, device=be.device)
+    o_sc = torch.full((R + GUARD_ROWS, top_k), SENTINEL_SCORE, dtype=torch.float32, device=be.device)
+    o_sc64 = torch.full((R + GUARD_ROWS, top_k), SENTINEL_SCORE, dtype=torch.float64, device=be.device)
+    o_cnt = torch.full((R + GUARD_ROWS,), SENTINEL_CNT, dtype=torch.int32, device=be.device)
+    flagged = torch.zeros((R + 1,), dtype=torch.int32, device=be.device)            # [0]: the counter; a slot for every row
+    be.ops.refine_topk_f64(d[0], d[1], d[2], d[3], R, RF_ITEMS, d[4], d[5], d[6], top_k, d[7], in_sc, d[8], 2.0 ** -20, None,
+                           o_ids, o_sc, o_sc64, o_cnt, flagged)
+    be.synchronize()
+    return tuple(t.cpu().numpy() for t in (o_ids, o_sc, o_sc64, o_cnt))
+
+
+@pytest.mark.parametrize("top_k", sorted(RF_STAGED, reverse=True))
+def test_refine_equals_model_on_both_sides_of_the_staging_limit(engine, top_k):
+    """Rows of 0 .. 600 items with 64 (top_k 3) or 256 (top_k 10) staged items per row: the longer ones are searched in global
+    memory, the others in LDS, side by side in one wave.  ids, float32 and float64 score bits and counts equal the model; what
+    the call flags is the margin test's business (tests/test_gpu_seg.py) and not looked at."""
+    g_ids, g_sc, g_sc64, g_cnt = run_refine(engine.be, top_k)
+    w_ids, w_sc, w_sc64, w_cnt = refine_model(top_k)
+    R = len(w_cnt)
+    assert all_sentinels(g_ids[R:], g_sc[R:], g_sc64[R:], g_cnt[R:]), "written behind the last row"
+    assert np.array_equal(g_cnt[:R], w_cnt), f"counts {g_cnt[:R]} vs {w_cnt}"
+    bad = np.flatnonzero((g_ids[:R] != w_ids).any(axis=1))
+    assert bad.size == 0, f"ids differ on rows {bad[:8]}, first: {g_ids[bad[0]]} vs {w_ids[bad[0]]}"
+    bad = np.flatnonzero((bits64(g_sc64[:R]) != bits64(w_sc64)).any(axis=1))
+    assert bad.size == 0, f"float64 bits differ on rows {bad[:8]}, first: {g_sc64[bad[0]]} vs {w_sc64[bad[0]]}"
+    bad = np.flatnonzero((bits(g_sc[:R]) != bits(w_sc)).any(axis=1))
+    assert bad.size == 0, f"float32 bits differ on rows {bad[:8]}, first: {g_sc[bad[0]]} vs {w_sc[bad[0]]}"
+

@@ -368,3 +368,62 @@ def test_fold_inputs_detect(name):
         if any(not same_or_both_nan(x, y) for x, y in zip(a, b)):
             return
     pytest.fail(f"no case of the GPU test tells the mutant '{name}' from the model")
+
+
+# ---- 5. float64 refine ------------------------------------------------------------------------------------------------
+def test_refine_inputs_reach_both_searches():
+    X, W = rk.refine_data()
+    lens = np.diff(X.indptr)
+    assert lens.tolist() == rk.RF_ROW_LENS and 0 < np.diff(W.indptr).max() <= rk.RF_COL_MAX and (np.diff(W.indptr) == 0).any()
+    assert (X.data > 0).all() and (W.data > 0).all()
+    for top_k, staged in rk.RF_STAGED.items():
+        P = 2
+        while P < top_k + 1:
+            P *= 2
+        assert staged == 1024 // (64 // P)                          # kRfItems over the rows of a wave
+        assert {0, 1, staged - 1, staged, staged + 1, 600} <= set(lens.tolist())
+        row_ids, in_ids, in_count = rk.refine_case(top_k)
+        assert len(row_ids) > 4 * (64 // P)                         # more than one workgroup of four waves
+        assert set(range(X.shape[0])) <= set(row_ids.tolist()) and row_ids[rk.RF_FOREIGN] == X.shape[0]
+        assert ((row_ids < 0) | (row_ids >= X.shape[0])).sum() == 1
+        assert {0, 1, top_k - 1, top_k, top_k + 1} <= set(in_count.tolist())
+        assert all(len(set(r)) == top_k + 1 for r in in_ids.tolist()) and in_ids.min() >= 0 and in_ids.max() < rk.RF_ITEMS
+        # in every wave a row searched in global memory works next to rows searched in LDS
+        long_row = lens[np.clip(row_ids, 0, X.shape[0] - 1)] > staged
+        long_row[rk.RF_FOREIGN] = False
+        waves = [long_row[i:i + 64 // P] for i in range(0, len(row_ids) - 64 // P + 1, 64 // P)]
+        assert any(w.any() and not w.all() for w in waves)
+
+
+@pytest.mark.parametrize("top_k", sorted(rk.RF_STAGED))
+def test_refine_model_equals_the_scipy_product_and_a_stable_sort(top_k):
+    """float64 X @ W by scipy (csr_matmat adds a column's terms in ascending item order), bit for bit, ranked by a stable
+    argsort of the negated scores: score descending, list position ascending."""
+    X, W = rk.refine_data()
+    row_ids, in_ids, in_count = rk.refine_case(top_k)
+    ids, sc, sc64, cnt = rk.refine_model(top_k)
+    S = (X.astype(np.float64) @ W.tocsr().astype(np.float64)).toarray()
+    S = np.vstack([S, np.zeros((1, rk.RF_ITEMS))])                  # the foreign row id: an empty row
+    n_tied = 0
+    for r in range(len(row_ids)):
+        n = min(int(in_count[r]), top_k + 1)
+        s = S[row_ids[r], in_ids[r, :n]]
+        o = np.argsort(-s, kind="stable")[:top_k]
+        assert cnt[r] == len(o) and ids[r, :len(o)].tolist() == in_ids[r, o].tolist()
+        assert same_or_both_nan(sc64[r, :len(o)], s[o]) and same_or_both_nan(sc[r, :len(o)], s[o].astype(np.float32))
+        assert (ids[r, len(o):] == -1).all() and np.isneginf(sc[r, len(o):]).all() and np.isneginf(sc64[r, len(o):]).all()
+        n_tied += len(set(s.tolist())) < n
+    assert n_tied >= 2                                              # zero scores tie (the empty row at least): position decides
+
+
+@pytest.mark.parametrize("top_k", sorted(rk.RF_STAGED))
+def test_refine_inputs_tell_wrong_searches_from_the_right_one(top_k):
+    want = rk.refine_model(top_k)
+    staged = rk.RF_STAGED[top_k]
+    differs = lambda got: any(not same_or_both_nan(g, w) for g, w in zip(got, want))
+    assert differs(rk.refine_model(top_k, cap=staged))              # longer rows staged anyway: their tail is lost
+    assert not differs(rk.refine_model(top_k, cap=600))
+    assert differs(rk.refine_model(top_k, descending=True))         # the sum's order shows in the float64 bits
+    # a row of exactly `staged` items searched in global memory or in LDS gives one answer; one too few slots does not
+    assert differs(rk.refine_model(top_k, cap=staged - 1))
+
