@@ -1,0 +1,63 @@
+/*
+ * include/rtrec_amd_ext.h -- the EXTENSION surface of librtrec_amd.so: entry points without a counterpart in the reference.
+ *
+ * include/rtrec_amd.h stands in for the method set of the reference's SLIMElastic and stays exactly that.  Calls the
+ * reference has no form of at all live here, under the same discipline: the comment is the contract, every pointer named
+ * d_* is a device pointer, nothing allocates, frees or synchronises, `stream` is a hipStream_t passed as void*, the return
+ * value is 0 or a negative rtrec_status, and the library keeps no state and reads no environment variable.  The symbols are
+ * compiled into the same librtrec_amd.so; rtrec_amd/_native.py lists them in EXT_EXPORTS, rtrec_amd/ops.py in EXT_OPS.
+ */
+#ifndef RTREC_AMD_EXT_H
+#define RTREC_AMD_EXT_H
+
+#include "rtrec_amd.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---------------------------------------------------------------------------------------
+ * DIVERSIFIED LISTS  (greedy maximal-marginal-relevance re-rank; W is the item-item similarity.)
+ * Every list served so far is ranked by score alone, so a SLIM top-10 tends to be ten neighbours of the two or three items
+ * the user rated.  This call re-ranks a list by trading the score against the similarity to what already stands above.
+ * Row r brings list_k positions (1..1024): item ids d_ids[r * ids_stride + p] and float32 base scores
+ * d_scores[r * scores_stride + p] (both strides >= list_k), valid up to d_counts[r] (clamped to [0, list_k]).  W is given in
+ * CSC form d_wc_* (d_wc_ptr[n_items + 1], rows ascending and distinct per column, float32 values; wc_nnz = length of
+ * d_wc_row / d_wc_val) -- the operand of rtrec_slim_similar_topk, rtrec_slim_explain_topk and rtrec_slim_score_pairs.
+ * Offsets are clamped to [0, wc_nnz], so a malformed matrix gives wrong answers, never an out-of-range read.
+ *   competing   a position competes when p < counts[r], 0 <= id < n_items, its score is finite, and no earlier-chosen
+ *               position holds the same item id (a diversified list never shows an item twice; duplicates only occur in
+ *               lists a caller brings)
+ *   similarity  for a != b: sim(a, b) = fmaxf(|W[a,b]|, |W[b,a]|), where W[j,i] is the value stored at row j of column i, or 0
+ *               if none is stored; a NaN weight is ignored (fmaxf's rule).  Symmetric, non-negative, exact; a negative weight
+ *               counts by its magnitude
+ *   selection   pen[p] = +0.0f for every position, oml = fl(1.0f - lambda).  For t = 0 .. keep-1: every competing, unchosen
+ *               position has the value v[p] = fl(fl(lambda * score[p]) - fl(oml * pen[p])): three separately rounded
+ *               operations, never fused.  p beats q if v[p] > v[q], or v[p] == v[q] and p < q (lists arrive best first, so the
+ *               EARLIER position wins; -0.0 == +0.0 is a tie).  A position whose v is NaN is skipped in that step; if no
+ *               position has a v that is a number, the list ends.  The winner c is recorded, and every other competing
+ *               position gets pen[p] = fmaxf(pen[p], sim(id[p], id[c]))
+ * Out: d_out_order[n_rows][keep] holds list POSITIONS (not item ids: the caller gathers, as with rtrec_slim_score_pairs),
+ * d_out_value[n_rows][keep] v at the moment of choice, d_out_penalty[n_rows][keep] pen at the moment of choice (how similar the
+ * entry is to what stands above it), d_out_count[r] the number chosen; behind it -1 / -inf / -inf.  Every slot is written.
+ * Consequences: with lambda == 1, v == score exactly, so a list sorted by score descending comes back as positions
+ * 0 .. count-1; step 0 always has pen == 0.
+ * list_k in 1..1024, keep in 1..list_k and waves_per_row in {0, 1, 4} (1 or 4 waves of 64 threads per row, 0 = chosen by the
+ * library): RTREC_ERR_UNSUPPORTED otherwise.  lambda outside [0, 1] or NaN, NULL arrays, negative sizes and a stride below
+ * list_k: RTREC_ERR_INVALID_ARG.  n_rows == 0: RTREC_OK before any pointer check.  No global state, no environment variable, no
+ * allocation.  The results never depend on waves_per_row, on the grid size or on scheduling.
+ * csrc/diversify.hip, diversify_lists_kernel: one row per workgroup; ids, lambda * score and penalties in LDS; per step an
+ * arg-max under the strict order above, then two binary searches per position (the winner's column is staged in LDS up to
+ * 128 entries and searched in global memory beyond that, so a column of any length works).
+ * ------------------------------------------------------------------------------------- */
+int rtrec_slim_diversify_lists(int32_t n_rows, int32_t n_items, const int32_t *d_wc_ptr, const int32_t *d_wc_row,
+                               const float *d_wc_val, int64_t wc_nnz, const int32_t *d_ids, int64_t ids_stride,
+                               const float *d_scores, int64_t scores_stride, int32_t list_k, const int32_t *d_counts,
+                               int32_t keep, float lambda, int32_t waves_per_row, int32_t *d_out_order, float *d_out_value,
+                               float *d_out_penalty, int32_t *d_out_count, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RTREC_AMD_EXT_H */

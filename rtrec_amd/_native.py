@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/rtrec_amd.h (librtrec_amd.so).
+"""ctypes binding of the C-ABI in include/rtrec_amd.h and include/rtrec_amd_ext.h (librtrec_amd.so).
 
 There is no CPU fallback: if the HIP library is missing or does not load, every product
 entry point raises.  Device buffers are torch tensors (plumbing only); the functions take
@@ -44,6 +44,11 @@ EXPORTS = [
     "rtrec_slim_audience_workspace_bytes",
     "rtrec_slim_audience_topk",
     "rtrec_slim_score_pairs",
+]
+
+# The extension surface (include/rtrec_amd_ext.h): calls without a counterpart in the reference, in the same library.
+EXT_EXPORTS = [
+    "rtrec_slim_diversify_lists",
 ]
 
 
@@ -203,6 +208,12 @@ def load() -> C.CDLL:
     L.rtrec_slim_score_pairs.restype = C.c_int
     L.rtrec_slim_score_pairs.argtypes = [i32, vp, vp, vp, vp, i32, C.c_int64, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, i32, vp,
                                          i32, i32, i32, vp, vp, vp, vp, vp]
+    missing = [name for name in EXT_EXPORTS if not hasattr(L, name)]
+    if missing:
+        raise NativeLibraryError(f"{path} does not export {missing} (include/rtrec_amd_ext.h): rebuild it with `python -m rtrec_amd.build`")
+    L.rtrec_slim_diversify_lists.restype = C.c_int
+    L.rtrec_slim_diversify_lists.argtypes = [i32, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, i32, vp, i32, C.c_float, i32,
+                                             vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -281,6 +281,12 @@ class HipBackend:
         self.ops.score_pairs(row_ids, xb[0], xb[1], xb[2], n_items, W["cptr"], W["crow"], W["cval"], ids, counts, list_k, top_k,
                              bool(filter_interacted), int(waves_per_row), scores, support, order, count)
 
+    def diversify_lists(self, n_items, W, ids, scores, counts, list_k, keep, lam, order, value, penalty, count, waves_per_row=0):
+        """Per list: the greedy MMR order over W's similarities (csrc/diversify.hip; include/rtrec_amd_ext.h); W as the CSC view of
+        DeviceWeights.csc_arrays, ids / scores [n_rows, >= list_k], the outputs [n_rows, keep] and [n_rows]."""
+        self.ops.diversify_lists(W["cptr"], W["crow"], W["cval"], n_items, ids, scores, counts, list_k, keep, float(lam),
+                                 int(waves_per_row), order, value, penalty, count)
+
     def audience_workspace_bytes(self, n_users, n_q, top_n):
         return int(self.lib.rtrec_slim_audience_workspace_bytes(n_users, n_q, top_n))
 

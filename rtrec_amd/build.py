@@ -14,8 +14,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "librtrec_amd.so")
-SOURCES = ["score.hip", "fit.hip", "store_host.hip", "store_device.hip", "seg_build.hip", "score_refine.hip", "score_cands.hip", "fit_sgd.hip", "score_dense_fill.hip", "score_first_touch.hip", "ordered_fold.hip", "rank_metrics.hip", "explain.hip", "audience.hip", "score_pairs.hip"]
-HEADERS = ["common.hip.h", "row_lookup.hip.h", "score_seg.hip.h", "fold_spec.hip.h", os.path.join("..", "..", "include", "rtrec_amd.h")]
+SOURCES = ["score.hip", "fit.hip", "store_host.hip", "store_device.hip", "seg_build.hip", "score_refine.hip", "score_cands.hip", "fit_sgd.hip", "score_dense_fill.hip", "score_first_touch.hip", "ordered_fold.hip", "rank_metrics.hip", "explain.hip", "audience.hip", "score_pairs.hip", "diversify.hip"]
+# (the core header stays last: ops_stale reads HEADERS[-1]; the extension surface's header stands in front of it)
+HEADERS = ["common.hip.h", "row_lookup.hip.h", "score_seg.hip.h", "fold_spec.hip.h", os.path.join("..", "..", "include", "rtrec_amd_ext.h"),
+           os.path.join("..", "..", "include", "rtrec_amd.h")]
+EXT_HEADER = HEADERS[-2]
 # -ffp-contract=off: the kernels reproduce the reference's float32 rounding sequence, so a
 # multiply must never be fused into the following add.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
@@ -41,7 +44,7 @@ def _sha256(path: str) -> str:
 
 
 def source_sha256() -> str:
-    """sha256 over the kernel sources the library is compiled from (csrc/*.hip, their headers, include/rtrec_amd.h) and the
+    """sha256 over the kernel sources the library is compiled from (csrc/*.hip, their headers, include/rtrec_amd.h and rtrec_amd_ext.h) and the
     compiler flags: the same for every rebuild of the same tree, whatever the binary's bytes."""
     import hashlib
     h = hashlib.sha256(" ".join(HIPCC_FLAGS).encode())
@@ -144,7 +147,8 @@ def ops_stale() -> bool:
     if not os.path.exists(OPS_PATH):
         return True
     t = os.path.getmtime(OPS_PATH)
-    if any(os.path.getmtime(d) > t for d in (OPS_SOURCE, os.path.normpath(os.path.join(CSRC, HEADERS[-1])))):
+    if any(os.path.getmtime(d) > t for d in (OPS_SOURCE, os.path.normpath(os.path.join(CSRC, HEADERS[-1])),
+                                             os.path.normpath(os.path.join(CSRC, EXT_HEADER)))):
         return True
     try:
         return open(OPS_STAMP).read().strip() != _torch_stamp()

@@ -1,6 +1,6 @@
 // rtrec_amd/csrc/torch_ops.cpp -- the PyTorch-ROCm custom ops `torch.ops.rtrec_amd.*`, registered from C++.
 //
-// One op per entry point of include/rtrec_amd.h, in out-variant style: every buffer is a ROCm tensor owned by the
+// One op per entry point of include/rtrec_amd.h (and of the extension surface, include/rtrec_amd_ext.h), in out-variant style: every buffer is a ROCm tensor owned by the
 // caller, outputs and scratch are marked mutable in the schema, scalars are plain ints / floats / bools, and the work is
 // enqueued on the current HIP stream of the tensors' device.  The ops only marshal pointers -- all computation is in
 // librtrec_amd.so, which this library binds at run time (rtrec_ops_bind: dlopen + dlsym of the C-ABI, so an A/B build
@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "../../include/rtrec_amd.h"
+#include "../../include/rtrec_amd_ext.h"
 
 namespace {
 
@@ -50,6 +51,7 @@ struct Abi {
     decltype(&rtrec_slim_explain_topk) explain_topk = nullptr;
     decltype(&rtrec_slim_audience_topk) audience_topk = nullptr;
     decltype(&rtrec_slim_score_pairs) score_pairs = nullptr;
+    decltype(&rtrec_slim_diversify_lists) diversify_lists = nullptr;          // include/rtrec_amd_ext.h
 };
 Abi g_abi;
 
@@ -507,6 +509,36 @@ void score_pairs(const OT &row_ids, const at::Tensor &xb_ptr, const at::Tensor &
           "rtrec_slim_score_pairs");
 }
 
+// ids / scores [n_rows, >= list_k] / counts [n_rows]: one list of item ids and base scores per row; W as a CSC triple of n_items
+// columns; the outputs are order / value / penalty [n_rows, keep] and count [n_rows] (include/rtrec_amd_ext.h, "DIVERSIFIED LISTS").
+void diversify_lists(const at::Tensor &wc_ptr, const at::Tensor &wc_row, const at::Tensor &wc_val, int64_t n_items, const at::Tensor &ids,
+                     const at::Tensor &scores, const at::Tensor &counts, int64_t list_k, int64_t keep, double lam, int64_t waves_per_row,
+                     at::Tensor order, at::Tensor value, at::Tensor penalty, at::Tensor count) {
+    TORCH_CHECK(list_k >= 1 && list_k <= 1024, "diversify_lists: list_k must lie in 1..1024, got ", list_k);
+    TORCH_CHECK(keep >= 1 && keep <= list_k, "diversify_lists: keep must lie in 1..list_k, got ", keep);
+    TORCH_CHECK(lam >= 0.0 && lam <= 1.0, "diversify_lists: lam must lie in [0, 1], got ", lam);
+    TORCH_CHECK(waves_per_row == 0 || waves_per_row == 1 || waves_per_row == 4, "diversify_lists: waves_per_row must be 0, 1 or 4, got ", waves_per_row);
+    TORCH_CHECK(ids.dim() == 2 && ids.size(1) >= list_k, "diversify_lists: ids must be [n_rows, >= list_k]");
+    const int64_t n = ids.size(0);
+    TORCH_CHECK(scores.dim() == 2 && scores.size(0) == n && scores.size(1) >= list_k, "diversify_lists: scores must be [n_rows, >= list_k]");
+    TORCH_CHECK(n <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, "diversify_lists: too many rows or items");
+    TORCH_CHECK(counts.numel() == n, "diversify_lists: counts must hold one entry per row");
+    TORCH_CHECK(order.numel() == n * keep && value.numel() == n * keep && penalty.numel() == n * keep && count.numel() == n,
+                "diversify_lists: outputs must be order[n_rows, keep], value[same], penalty[same], count[n_rows]");
+    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
+    check_csc("diversify_lists", "wc", wc_ptr, wc_row, wc_val, n_items);
+    check_tensor<const int32_t>(ids); check_tensor<const float>(scores); check_tensor<const int32_t>(counts);
+    check_tensor<int32_t>(order); check_tensor<float>(value); check_tensor<float>(penalty); check_tensor<int32_t>(count);
+    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&wc_ptr, &wc_row, &wc_val, &scores, &counts, &order, &value, &penalty, &count})
+        TORCH_CHECK(t->device() == ids.device(), "diversify_lists: all tensors must live on one device");
+    check(abi().diversify_lists(static_cast<int32_t>(n), static_cast<int32_t>(n_items), ptr<const int32_t>(wc_ptr), ptr<const int32_t>(wc_row),
+                                ptr<const float>(wc_val), wc_row.numel(), ptr<const int32_t>(ids), ids.size(1), ptr<const float>(scores),
+                                scores.size(1), static_cast<int32_t>(list_k), ptr<const int32_t>(counts), static_cast<int32_t>(keep),
+                                static_cast<float>(lam), static_cast<int32_t>(waves_per_row), ptr<int32_t>(order), ptr<float>(value),
+                                ptr<float>(penalty), ptr<int32_t>(count), stream_of(order)),
+          "rtrec_slim_diversify_lists");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -539,6 +571,7 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.explain_topk, "rtrec_slim_explain_topk");
         bind_one(h, a.audience_topk, "rtrec_slim_audience_topk");
         bind_one(h, a.score_pairs, "rtrec_slim_score_pairs");
+        bind_one(h, a.diversify_lists, "rtrec_slim_diversify_lists");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -603,6 +636,9 @@ TORCH_LIBRARY(rtrec_amd, m) {
     m.def("score_pairs(Tensor? row_ids, Tensor xb_ptr, Tensor xb_col, Tensor xb_val, int n_items, Tensor wc_ptr, Tensor wc_row, "
           "Tensor wc_val, Tensor ids, Tensor counts, int list_k, int top_k, bool filter_interacted, int waves_per_row, "
           "Tensor(a!) scores, Tensor(b!) support, Tensor(c!) order, Tensor(d!) count) -> ()");
+    // the extension surface (include/rtrec_amd_ext.h)
+    m.def("diversify_lists(Tensor wc_ptr, Tensor wc_row, Tensor wc_val, int n_items, Tensor ids, Tensor scores, Tensor counts, int list_k, "
+          "int keep, float lam, int waves_per_row, Tensor(a!) order, Tensor(b!) value, Tensor(c!) penalty, Tensor(d!) count) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -628,4 +664,5 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("explain_topk", &explain_topk);
     m.impl("audience_topk", &audience_topk);
     m.impl("score_pairs", &score_pairs);
+    m.impl("diversify_lists", &diversify_lists);
 }

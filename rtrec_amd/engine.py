@@ -1560,6 +1560,7 @@ class SlimEngine:
         "explain": ("explanations need", "explain", "explanations are exact float32 products"),
         "score_pairs": ("pair scores need", "score_pairs", "pair scores are exact float32 products"),
         "recommend_users": ("an audience needs", "serve audiences", "audience scores are exact float32 sums"),
+        "diversify": ("diversified lists need", "diversify", "similarities are W's float32 values"),
     }
 
     def _whole_w(self, call: str) -> DeviceWeights:
@@ -1685,6 +1686,52 @@ class SlimEngine:
         outside the matrix is a user without a row: score 0 and support 0 for every valid item."""
         B, _, d_rows, d_ids, d_counts = self._upload_lists(row_ids, item_ids, counts, xb)
         out = self.score_pairs_device(d_rows, B, xb, d_ids, d_counts, top_k, filter_interacted)
+        return tuple(t.cpu().numpy() for t in out)
+
+    # ------------------------------------------------------------------------------ diversified lists (greedy MMR over W)
+    DIVERSE_MAX_LIST = 1024     # list_k limit of rtrec_slim_diversify_lists
+
+    def diversify_device(self, ids, scores, counts, keep: int, lam: float, waves_per_row: int = 0):
+        """Device tensors (order[n_rows, keep] int32, value[n_rows, keep] float32, penalty[n_rows, keep] float32, count[n_rows]
+        int32) for the lists `ids` [n_rows, k] int32 / `scores` [n_rows, k] float32 / `counts` [n_rows] int32 (device tensors,
+        e.g. what score_topk_device returned: they never leave HBM): the greedy selection that trades lam * score against
+        (1 - lam) * the largest similarity to what is already chosen, similarity = max(|W[a, b]|, |W[b, a]|).  order holds list
+        POSITIONS, value / penalty the step's value and penalty of the chosen entry, -1 / -inf / -inf behind count.  The
+        contract is the comment of rtrec_slim_diversify_lists in include/rtrec_amd_ext.h.  Every rank that holds the whole W
+        answers locally: there is no collective."""
+        be, torch = self.be, self.be.torch
+        dw = self._whole_w("diversify")
+        n_rows, k, keep, lam = int(ids.shape[0]), int(ids.shape[-1]), int(keep), float(lam)
+        if not 1 <= k <= self.DIVERSE_MAX_LIST or not 1 <= keep <= k:
+            raise ValueError(f"diversify: lists of 1..{self.DIVERSE_MAX_LIST} items and keep in 1..the list length are "
+                             f"supported, got {k} and {keep}")
+        if not 0.0 <= lam <= 1.0:                                         # (a NaN fails both compares)
+            raise ValueError(f"diversify: lam must lie in [0, 1], got {lam}")
+        if tuple(scores.shape) != (n_rows, k) or int(counts.numel()) != n_rows:
+            raise ValueError("diversify: scores must have the shape of ids, counts one entry per row")
+        order = be.empty((n_rows, keep), torch.int32)
+        value = be.empty((n_rows, keep), torch.float32)
+        penalty = be.empty((n_rows, keep), torch.float32)
+        count = be.zeros((n_rows,), torch.int32)
+        if n_rows == 0:
+            return order, value, penalty, count
+        be.diversify_lists(dw.n_items, self._w_csc(), ids.contiguous(), scores.contiguous(), counts.contiguous(), k, keep, lam,
+                           order, value, penalty, count, waves_per_row=waves_per_row)
+        return order, value, penalty, count
+
+    def diversify_lists(self, item_ids: np.ndarray, scores: np.ndarray, counts: Optional[np.ndarray] = None, keep: int = 10,
+                        lam: float = 0.7) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """diversify_device for lists the caller brings: numpy (order[B, keep], value, penalty, count[B]) for `item_ids` [B, k]
+        (-1 or an id outside W = an empty position) with the base scores `scores` [B, k]; counts default to k."""
+        item_ids = np.ascontiguousarray(item_ids, dtype=np.int32)
+        scores = np.ascontiguousarray(scores, dtype=np.float32)
+        if item_ids.ndim != 2 or scores.shape != item_ids.shape:
+            raise ValueError("item_ids and scores must be two [B, k] arrays of one shape")
+        B, k = item_ids.shape
+        counts = np.full(B, k, dtype=np.int32) if counts is None else np.asarray(counts, dtype=np.int32)
+        if counts.shape != (B,):
+            raise ValueError("counts must hold one entry per row")
+        out = self.diversify_device(self._up(item_ids), self._up(scores), self._up(counts), keep, lam)
         return tuple(t.cpu().numpy() for t in out)
 
     # ------------------------------------------------------------------------------ audience of an item

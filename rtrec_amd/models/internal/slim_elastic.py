@@ -422,6 +422,27 @@ class SLIMElastic:
         rows, ids, counts, xb = self._lists_on_rows(user_ids, interaction_matrix, item_ids)
         return self.engine.score_pairs_rows(rows, ids, counts, top_k, filter_interacted, xb=xb)
 
+    def diversify_batch(self, item_ids: Sequence[Sequence[int]], scores: Sequence[Sequence[float]], top_k: int = 10,
+                        lam: float = 0.7) -> Tuple[ndarray, ndarray, ndarray, ndarray]:
+        """An extension (the reference has none): the greedy MMR order of every list of `item_ids` (one list of item ids per
+        row, best first; -1 or an id outside W = an empty position) with the base scores `scores` (one per item), W being the
+        item-item similarity (csrc/diversify.hip; the contract is the comment of rtrec_slim_diversify_lists in
+        include/rtrec_amd_ext.h).  Returns (order[B, keep], value[B, keep], penalty[B, keep], counts[B]), keep = min(top_k, the
+        longest list): order holds list POSITIONS, -1 / -inf / -inf behind counts[b]."""
+        if not self.is_fitted:
+            raise RuntimeError("Model must be fitted before calling diversify_batch.")
+        rows, sc = [list(r) for r in item_ids], [list(r) for r in scores]
+        if len(rows) != len(sc) or any(len(a) != len(b) for a, b in zip(rows, sc)):
+            raise ValueError("scores must hold one score per item of item_ids")
+        k = max([len(r) for r in rows] + [1])
+        ids = np.full((len(rows), k), -1, dtype=np.int32)
+        val = np.zeros((len(rows), k), dtype=np.float32)
+        for b, (r, v) in enumerate(zip(rows, sc)):
+            ids[b, :len(r)], val[b, :len(r)] = r, v
+        counts = np.array([len(r) for r in rows], dtype=np.int32)
+        self._sync_weights()
+        return self.engine.diversify_lists(ids, val, counts, max(1, min(int(top_k), k)), lam)
+
     def recommend_users_batch(self, item_ids: Sequence[int], top_n: int = 100, filter_interacted: bool = True,
                               candidate_rows: Optional[Sequence[int]] = None) -> Tuple[ndarray, ndarray, ndarray, ndarray]:
         """An extension (the reference has none): the audience of every item of `item_ids` (internal ids; an id outside W

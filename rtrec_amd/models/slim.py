@@ -651,6 +651,147 @@ class SLIM(BaseModel):
             scores[by_user], support[by_user] = sc[row, col], su[row, col]
         return (scores, support) if as_arrays else scores
 
+    # ------------------------------------------------------------ diversified lists (an extension: the reference has none)
+    DIVERSE_MAX_POOL = 1024     # list length rtrec_slim_diversify_lists re-ranks
+
+    @staticmethod
+    def _mmr_lambda(diversity: float, what: str) -> np.float32:
+        """lambda = float32(1 - diversity) of the greedy selection; a diversity outside [0, 1] (or NaN) is refused."""
+        if not 0.0 <= float(diversity) <= 1.0:
+            raise ValueError(f"{what}: diversity must lie in [0, 1], got {diversity}")
+        return np.float32(1.0 - float(diversity))
+
+    def recommend_diverse_batch(self, users: List[Any], top_k: int = 10, pool: int = 50, diversity: float = 0.3,
+                                filter_interacted: bool = True, ret_scores: bool = False, as_arrays: bool = False) -> Any:
+        """Recommendations that trade score against similarity to what is already on the page: a list ranked by score alone
+        tends to be the neighbours of the two or three items the user rated.  Per user the `pool` best items are scored as
+        `recommend_batch` scores them, and `top_k` of them are chosen greedily (maximal marginal relevance): every step takes
+        the item with the largest lambda * score - (1 - lambda) * penalty, lambda = float32(1 - diversity), penalty = the
+        largest similarity to an item already chosen, similarity(a, b) = max(|W[a, b]|, |W[b, a]|) -- W is the item-item
+        similarity SLIM learned.  The first item is always the best-scored one; among equal values the better-scored item
+        wins.  `diversity=0` returns `recommend_batch`'s lists; 1 ignores the scores after the first item.  Scores and
+        similarities are NOT normalised against each other: W's scale is what the fit made it, so choose `diversity` for the
+        model at hand.
+
+        For known users this is one device pass: the scoring kernels' lists of `pool` go straight into the selection kernel
+        (csrc/diversify.hip; the contract is the comment of rtrec_slim_diversify_lists in include/rtrec_amd_ext.h), the
+        chosen entries are gathered on the device and only `top_k` per user are downloaded.  Unknown users get the first
+        `top_k` of their cold-start list unchanged (it carries no scores); users outside the matrix follow
+        `recommend_batch`'s rules.  With several ranks the scoring pass is the usual collective and every rank computes the
+        same lists.
+
+        Raises ValueError unless 1 <= top_k <= pool <= 1024 and 0 <= diversity <= 1; for a pool the fused top-k kernels do not
+        serve for this model -- they rank at most 1023 items, so 1024 is served only by a catalogue of fewer items, and a wide
+        catalogue lowers the limit further (its per-tile lists must fit the merge); for a W whose values are not float32 numbers (a float64 W holding float32 numbers is served
+        with them); and for a column-sharded W (gather it with gather_item_similarity()).
+
+        Returns one list of raw item ids per user -- of (item, base score) tuples with `ret_scores` -- or with
+        `as_arrays=True` (ids[B, top_k], scores[B, top_k], counts[B], value[B, top_k], penalty[B, top_k]): what
+        `rerank_batch(as_arrays=True)` returns (INTERNAL item ids, base scores, -1 / -inf behind counts[b]) plus the value the
+        entry was chosen with and its penalty, i.e. how similar it is to what stands above it (-inf for the unchanged lists
+        of unknown users)."""
+        from .._native import TOPK_DENSE, TOPK_SPARSE
+        top_k, pool = int(top_k), int(pool)
+        if not 1 <= top_k <= pool <= self.DIVERSE_MAX_POOL:
+            raise ValueError(f"recommend_diverse_batch needs 1 <= top_k <= pool <= {self.DIVERSE_MAX_POOL}, got top_k={top_k} and "
+                             f"pool={pool}")
+        lam = self._mmr_lambda(diversity, "recommend_diverse_batch")
+        if not self.model.is_fitted:
+            raise RuntimeError("Model must be fitted before calling recommend_diverse_batch.")
+        arr = self._int_user_array(users)
+        users = arr if arr is not None else list(users)
+        B = len(users)
+        out_ids = np.full((B, top_k), -1, dtype=np.int64)
+        out_sc = np.full((B, top_k), -np.inf, dtype=np.float32)
+        out_val = np.full((B, top_k), -np.inf, dtype=np.float32)
+        out_pen = np.full((B, top_k), -np.inf, dtype=np.float32)
+        out_cnt = np.zeros(B, dtype=np.int32)
+        if B:
+            eng = self.model.engine
+            n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
+            uid, cold = self._user_rows(users)
+            regular = ~cold & (uid >= 0) & (uid < n_users)
+            self.model._sync_weights()
+            eng._whole_w("diversify")              # a W that cannot be served is refused whatever the batch holds
+            mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+            k_pool = min(pool, n_items)
+            if k_pool < 1 or not eng.topk_supported(k_pool, mode):
+                why = (f"they rank lists of at most {eng.MAX_TOP_K} items" if k_pool > eng.MAX_TOP_K else
+                       f"the per-tile lists of one user, (pool + 1) per tile of W's columns, exceed the {eng.MAX_MERGE_CANDIDATES} "
+                       "entries the merge takes") if k_pool >= 1 else "the model has no item"
+                raise ValueError(f"recommend_diverse_batch: the fused score + top-k kernels do not serve lists of pool={pool} for "
+                                 f"this model ({why}): choose a smaller pool")
+            if cold.any():
+                cold_list = self._recommend_cold_batch([None], top_k=top_k)[0][:top_k]
+                out_ids[cold, :len(cold_list)] = np.asarray(cold_list, dtype=np.int64)[None, :]
+                out_sc[cold, :len(cold_list)] = 0.0
+                out_cnt[cold] = len(cold_list)
+            odd = ~cold & ~regular
+            if odd.any():
+                lists = self._recommend_odd_ids(uid[~cold], n_users, None, top_k, filter_interacted)
+                for b, row in zip(np.flatnonzero(~cold).tolist(), lists):
+                    if odd[b]:
+                        out_ids[b, :len(row)], out_sc[b, :len(row)], out_cnt[b] = row, 0.0, len(row)
+            if regular.any():
+                self._sync_interactions()
+                torch = eng.be.torch
+                rows = uid[regular].astype(np.int32)
+                keep = min(top_k, k_pool)
+                d_ids, d_sc, d_cnt = eng.score_topk_device(None, len(rows), k_pool, filter_interacted, mode, d_rows=eng._up(rows))
+                d_sc = d_sc.to(torch.float32)
+                order, value, pen, cnt = eng.diversify_device(d_ids, d_sc, d_cnt, keep, lam)
+                gone = order < 0                     # the chosen entries are gathered where the lists are: top_k per user travel
+                at = order.clamp(min=0).to(torch.int64)
+                g_ids = torch.gather(d_ids, 1, at).masked_fill(gone, -1)
+                g_sc = torch.gather(d_sc, 1, at).masked_fill(gone, float("-inf"))
+                pos = np.flatnonzero(regular)
+                out_ids[pos, :keep], out_sc[pos, :keep] = g_ids.cpu().numpy(), g_sc.cpu().numpy()
+                out_val[pos, :keep], out_pen[pos, :keep], out_cnt[pos] = value.cpu().numpy(), pen.cpu().numpy(), cnt.cpu().numpy()
+        if as_arrays:
+            return out_ids, out_sc, out_cnt, out_val, out_pen
+        raw_of = self._raw_of(self.item_ids)
+        id_rows, sc_rows, cnts = out_ids.tolist(), out_sc.tolist(), out_cnt.tolist()
+        out: List[Any] = []
+        for b in range(B):
+            items = [raw_of(i) for i in id_rows[b][:cnts[b]]]
+            out.append(list(zip(items, sc_rows[b][:cnts[b]])) if ret_scores else items)
+        return out
+
+    def recommend_diverse(self, user: Any, top_k: int = 10, pool: int = 50, diversity: float = 0.3, filter_interacted: bool = True,
+                          ret_scores: bool = False) -> List[Any]:
+        """recommend_diverse_batch for one user: the diversified list, or (item, base score) tuples."""
+        return self.recommend_diverse_batch([user], top_k=top_k, pool=pool, diversity=diversity, filter_interacted=filter_interacted,
+                                            ret_scores=ret_scores)[0]
+
+    def diversify_batch(self, items: List[List[Any]], scores: List[List[float]], top_k: int = 10, diversity: float = 0.3,
+                        as_arrays: bool = False) -> Any:
+        """The selection of recommend_diverse_batch for lists the caller brings -- from another ranker, a rule, a cache; no
+        user is needed: `items` holds one list of raw item ids per row, best first, `scores` their base scores (one per item,
+        finite; an entry with a non-finite score does not compete).  An item the model does not know is an empty position, an
+        item listed twice is shown once (at its first chosen entry).  Lists longer than 1024 raise ValueError, as do
+        `top_k < 1` and a `diversity` outside [0, 1].
+
+        Returns per row the `top_k` chosen (item, base score) tuples in their new order -- or with `as_arrays=True`
+        (order[B, keep], value[B, keep], penalty[B, keep], counts[B]), keep = min(top_k, the longest list): order holds list
+        POSITIONS, value / penalty the step's value and the entry's similarity to what stands above it, -1 / -inf / -inf
+        behind counts[b]."""
+        lam = self._mmr_lambda(diversity, "diversify_batch")
+        if not self.model.is_fitted:
+            raise RuntimeError("Model must be fitted before calling diversify_batch.")
+        items, scores = [list(r) for r in items], [list(r) for r in scores]
+        if len(items) != len(scores) or any(len(a) != len(b) for a, b in zip(items, scores)):
+            raise ValueError("scores must hold one list per list of items, and one score per item")
+        K = max([len(r) for r in items] + [1])
+        if int(top_k) < 1 or K > self.DIVERSE_MAX_POOL:
+            raise ValueError(f"diversify_batch serves top_k >= 1 and lists of up to {self.DIVERSE_MAX_POOL} items, got top_k={top_k} "
+                             f"and a list of {K}")
+        n_items = self.model.n_items_fitted
+        ids = [self._ids_or_minus_one(r, self.item_ids.get_id, min(n_items, 2 ** 31 - 1)).tolist() for r in items]
+        order, value, pen, cnt = self.model.diversify_batch(ids, scores, top_k=int(top_k), lam=lam)
+        if as_arrays:
+            return order, value, pen, cnt
+        return [[(items[b][p_], float(scores[b][p_])) for p_ in order[b, :cnt[b]].tolist()] for b in range(len(items))]
+
     # ------------------------------------------------------------ audience of an item (an extension: the reference has none)
     def _sync_interactions_csc(self) -> None:
         """_sync_interactions, and the CSC orientation of the GPU copy too: the device mirror's, or -- on the branch that

@@ -140,6 +140,23 @@ class Recommender:
         """SLIM.score_pairs: the model's score of every (users[p], items[p]) pair, and with `as_arrays` its support."""
         return self.model.score_pairs(users, items, as_arrays=as_arrays)
 
+    def recommend_diverse(self, user: Any, top_k: int = 10, pool: int = 50, diversity: float = 0.3, filter_interacted: bool = True,
+                          ret_scores: bool = False) -> Any:
+        """An extension (the reference has none): the user's list re-ranked against W's similarities -- SLIM.recommend_diverse."""
+        return self.model.recommend_diverse(user, top_k=top_k, pool=pool, diversity=diversity, filter_interacted=filter_interacted,
+                                            ret_scores=ret_scores)
+
+    def recommend_diverse_batch(self, users: List[Any], top_k: int = 10, pool: int = 50, diversity: float = 0.3,
+                                filter_interacted: bool = True, ret_scores: bool = False, as_arrays: bool = False) -> Any:
+        """SLIM.recommend_diverse_batch: score a pool per user and choose top_k of it greedily, in one device pass."""
+        return self.model.recommend_diverse_batch(users, top_k=top_k, pool=pool, diversity=diversity,
+                                                  filter_interacted=filter_interacted, ret_scores=ret_scores, as_arrays=as_arrays)
+
+    def diversify_batch(self, items: List[List[Any]], scores: List[List[float]], top_k: int = 10, diversity: float = 0.3,
+                        as_arrays: bool = False) -> Any:
+        """SLIM.diversify_batch: the same selection for lists (and base scores) the caller brings."""
+        return self.model.diversify_batch(items, scores, top_k=top_k, diversity=diversity, as_arrays=as_arrays)
+
     def similar_items(self, query_items: List[Any], query_item_tags: Optional[List[str]] = None, top_k: int = 10,
                       ret_scores: bool = False):
         batch = getattr(self.model, "similar_items_batch", None)

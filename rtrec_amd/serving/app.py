@@ -19,6 +19,9 @@ the GPU), POST /recommend (one user's top-k).  Differences, all forced by the de
   * POST /rerank is an addition (the second stage of a two-stage recommender: the caller brings the user's own candidates):
     {"user": ..., "items": [...], "top_k" or absent = the whole list, "filter_interacted"} -> {"user": ..., "items": [{"item": ...,
     "score": ...}, ...]} (SLIM.rerank); same token check as /recommend, answered under the model lock, not coalesced;
+  * POST /recommend_diverse is an addition (a list that trades score against similarity to what is already on the page):
+    {"user": ..., "top_k", "pool", "diversity", "filter_interacted"} -> {"user": ..., "items": [{"item": ..., "score": ...}, ...]}
+    with the BASE scores (SLIM.recommend_diverse); same token check as /rerank, answered under the model lock, not coalesced;
   * concurrent POST /recommend calls are coalesced (`RecommendCoalescer`): requests that arrive within a bounded
     wait (RTREC_AMD_COALESCE_MS, default 1 ms; 0 = only what queued up behind the model lock) share ONE
     recommend_batch launch per (top_k, filter_interacted) group; each caller gets exactly what its own
@@ -79,6 +82,14 @@ class RerankRequest(BaseModel):
     items: List[Any]
     top_k: Optional[int] = None
     filter_interacted: bool = False
+
+
+class DiverseRequest(BaseModel):
+    user: Any
+    top_k: int = 10
+    pool: int = 50
+    diversity: float = 0.3
+    filter_interacted: bool = True
 
 
 class RecommendationResponse(BaseModel):
@@ -289,6 +300,15 @@ def build_router(gate: ModelGate) -> APIRouter:
         _authorise(x_token)
         pairs = gate.call("Rerank", lambda m: m.rerank(request.user, request.items, top_k=request.top_k,
                                                        filter_interacted=request.filter_interacted, ret_scores=True))
+        return {"user": request.user, "items": [{"item": i, "score": s} for i, s in pairs]}
+
+    @api.post("/recommend_diverse")
+    def recommend_diverse(request: DiverseRequest, x_token: str = Header()):
+        _authorise(x_token)
+        pairs = gate.call("Recommend diverse", lambda m: m.recommend_diverse(request.user, top_k=request.top_k, pool=request.pool,
+                                                                             diversity=request.diversity,
+                                                                             filter_interacted=request.filter_interacted,
+                                                                             ret_scores=True))
         return {"user": request.user, "items": [{"item": i, "score": s} for i, s in pairs]}
 
     return api
