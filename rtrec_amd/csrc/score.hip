@@ -1369,12 +1369,13 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
     // W's head is read-only in LDS and every wave fetches the other rows for itself, so every WAVE claims its own UW users
     // and no barrier is left inside the loop: a wave never waits for a slower neighbour.
     const int n_wave_jobs = (a.n_rows + UW - 1) / UW;
-    for (;;) {
+    // A wave's FIRST job is its own number in the grid; the queue hands out the jobs behind those (its count starts at 0:
+    // the index is the count plus the number of waves), claimed at the end of the job before.  No launch begins with 4,096
+    // atomic adds to one address.  Measured end to end: c3 0.977 -> 0.930 ms, `small` 0.198 -> 0.153 ms;
+    // the phase split does not show the claim's wait shrinking, so WHY this is faster is not established.
+    const int n_waves = static_cast<int>(gridDim.x) * NW;
+    for (int j = static_cast<int>(blockIdx.x) * NW + wave;;) {
         PF_MARK(PF_GROUP)
-        int j = 0;
-        if (lane == 0) j = atomicAdd(a.queue, 1);
-        j = readfirst_i(j);
-        PF_MARK(PF_QUEUE)
         if (j >= n_wave_jobs) break;
         // positions j, j + n_wave_jobs, ...: with rows handed over longest-first every wave job is the same mix
         const int base = a.consecutive ? j * UW : j, pstride = a.consecutive ? 1 : n_wave_jobs;
@@ -1393,11 +1394,12 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
         // pointers), all eight chains in parallel; then the first 64 entries of every row and what they map to
         // (feature row, layout column), again all eight users' loads in flight together -- three memory round trips
         // per job instead of four per user
-        int a0_l = 0, na_l = 0;
+        int a0_l = 0, na_l = 0, orow = -1;      // orow: lane u = the row of the output user u's list goes to (-1: none), kept for the emit
         if (lane < UW) {
             const int p = base + lane * pstride;
             if (p < a.n_rows) {
                 const int r = a.order ? a.order[p] : p;
+                orow = r;
                 const int xrow = a.row_ids ? a.row_ids[r] : r;
                 if (xrow >= 0 && xrow < a.n_x_rows) { a0_l = a.xb_ptr[xrow]; na_l = a.xb_ptr[xrow + 1] - a0_l; }
             }
@@ -1836,12 +1838,8 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
 #endif
 
         // ---- the lists are the rows' answers: lane lb + j of list register g = rank j of user 4 g + lb / 16 ----
-        int gid[NL], orow = 0;
+        int gid[NL];
         fr_static_for<NL>([&](auto G4) { gid[G4()] = lc4[G4()] >= 0 ? a.col_ids[lc4[G4()]] : -1; });    // all gathers in flight together
-        if (lane < UW) {
-            const int p = base + lane * pstride;
-            orow = p < a.n_rows ? (a.order ? a.order[p] : p) : -1;
-        }
         fr_static_for<UW>([&](auto Uc) {
             constexpr int u = decltype(Uc)::value;
             const int r = readlane_i(orow, u);
@@ -1880,6 +1878,10 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
             }
         });
         PF_MARK(PF_EMIT)
+        j = 0;
+        if (lane == 0) j = atomicAdd(a.queue, 1);
+        j = readfirst_i(j) + n_waves;
+        PF_MARK(PF_QUEUE)
     }
 #ifdef SCORE_PROFILE
     if (lane == 0) {
