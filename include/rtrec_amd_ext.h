@@ -56,6 +56,45 @@ int rtrec_slim_diversify_lists(int32_t n_rows, int32_t n_items, const int32_t *d
                                int32_t keep, float lambda, int32_t waves_per_row, int32_t *d_out_order, float *d_out_value,
                                float *d_out_penalty, int32_t *d_out_count, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * LIST QUALITY  (per list: intra-list similarity, linked pairs, a weight sum; over all lists: the catalogue exposure.)
+ * The stage above ships a knob; this call measures what a value of it buys, on the lists where the scoring kernels and
+ * rtrec_slim_diversify_lists leave them.  Row r brings list_k positions (1..1024): item ids d_ids[r * ids_stride + p]
+ * (ids_stride >= list_k), valid up to d_counts[r] (clamped to [0, list_k]).  W is given in CSC form d_wc_* exactly as for
+ * rtrec_slim_diversify_lists (d_wc_ptr[n_items + 1], rows ascending and distinct per column, float32 values; wc_nnz = length
+ * of d_wc_row / d_wc_val).  Offsets are clamped to [0, wc_nnz], so a malformed matrix gives wrong answers, never an
+ * out-of-range read.  d_item_weight[n_items] (float32) and d_exposure[n_items] (int32) may each be NULL.
+ *   counted     position p is counted when p < counts[r], 0 <= id < n_items, and no earlier counted position of the row holds
+ *               the same id: an item shown twice is judged once, at its first place.  m = the number of counted positions
+ *   similarity  rtrec_slim_diversify_lists's: for a != b, sim(a, b) = fmaxf(|W[a,b]|, |W[b,a]|), 0 where nothing is stored; a
+ *               NaN weight is ignored, so sim is never NaN and never negative; a stored inf gives inf
+ *   sim_sum     a two-level float32 sum, never fused.  For each counted p in ascending order, s_p = the sum from +0.0f of
+ *               sim(id_p, id_q) over the counted q < p in ascending q, one rounded add each; sim_sum = the sum from +0.0f of the
+ *               s_p in ascending p, one rounded add each.  (Each s_p is a chain of at most p adds and the chains are independent
+ *               of each other; one chain over all pairs would be about 500,000 dependent adds for a list of 1,024.)
+ *   linked      the number of counted pairs q < p with sim > 0 (int32); a pair whose only stored weights are explicit zeros is
+ *               not linked
+ *   weight_sum  the sum from +0.0f of d_item_weight[id_p] over the counted p in ascending order, one rounded add each; +0.0f
+ *               when d_item_weight is NULL.  The kernel knows nothing about what the weight means
+ *   exposure    every counted position adds 1 to d_exposure[id] with an integer atomic when d_exposure is not NULL.  The array
+ *               is never zeroed here, so a caller accumulates over several calls; integer adds commute, so the result does not
+ *               depend on scheduling
+ * Out, every slot written for every row (rows with m = 0 included): d_out_n[r] = m (int32), d_out_sim_sum[r] (float32),
+ * d_out_linked[r] (int32), d_out_weight_sum[r] (float32).
+ * list_k in 1..1024 and waves_per_row in {0, 1, 4} (1 or 4 waves of 64 threads per row, 0 = chosen by the library):
+ * RTREC_ERR_UNSUPPORTED otherwise.  NULL required arrays, negative sizes and ids_stride < list_k: RTREC_ERR_INVALID_ARG.
+ * n_rows == 0: RTREC_OK before any pointer check.  No global state, no environment variable, no allocation, no
+ * synchronisation.  The results never depend on waves_per_row, on the grid size or on scheduling.
+ * csrc/list_quality.hip, list_quality_kernel: one row per workgroup; ids and the spans of their columns in LDS; every position
+ * looks for its id at a lower position, then its owner walks the counted positions below it with two binary searches each,
+ * and one thread adds the per-position figures in order.
+ * ------------------------------------------------------------------------------------- */
+int rtrec_slim_list_quality(int32_t n_rows, int32_t n_items, const int32_t *d_wc_ptr, const int32_t *d_wc_row,
+                            const float *d_wc_val, int64_t wc_nnz, const int32_t *d_ids, int64_t ids_stride, int32_t list_k,
+                            const int32_t *d_counts, const float *d_item_weight, int32_t *d_exposure, int32_t waves_per_row,
+                            int32_t *d_out_n, float *d_out_sim_sum, int32_t *d_out_linked, float *d_out_weight_sum,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif

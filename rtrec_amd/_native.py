@@ -49,6 +49,7 @@ EXPORTS = [
 # The extension surface (include/rtrec_amd_ext.h): calls without a counterpart in the reference, in the same library.
 EXT_EXPORTS = [
     "rtrec_slim_diversify_lists",
+    "rtrec_slim_list_quality",
 ]
 
 
@@ -214,6 +215,8 @@ def load() -> C.CDLL:
     L.rtrec_slim_diversify_lists.restype = C.c_int
     L.rtrec_slim_diversify_lists.argtypes = [i32, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, i32, vp, i32, C.c_float, i32,
                                              vp, vp, vp, vp, vp]
+    L.rtrec_slim_list_quality.restype = C.c_int
+    L.rtrec_slim_list_quality.argtypes = [i32, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

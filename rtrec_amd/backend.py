@@ -287,6 +287,13 @@ class HipBackend:
         self.ops.diversify_lists(W["cptr"], W["crow"], W["cval"], n_items, ids, scores, counts, list_k, keep, float(lam),
                                  int(waves_per_row), order, value, penalty, count)
 
+    def list_quality(self, n_items, W, ids, counts, list_k, item_weight, exposure, n, sim_sum, linked, weight_sum, waves_per_row=0):
+        """Per list: the counted positions, the intra-list similarity sum over W, its linked pairs and the sum of item_weight
+        (csrc/list_quality.hip; include/rtrec_amd_ext.h); every counted position adds 1 to exposure.  W as the CSC view of
+        DeviceWeights.csc_arrays, ids [n_rows, >= list_k], item_weight / exposure [n_items] or None, the outputs [n_rows]."""
+        self.ops.list_quality(W["cptr"], W["crow"], W["cval"], n_items, ids, counts, list_k, item_weight, int(waves_per_row),
+                              n, sim_sum, linked, weight_sum, exposure)
+
     def audience_workspace_bytes(self, n_users, n_q, top_n):
         return int(self.lib.rtrec_slim_audience_workspace_bytes(n_users, n_q, top_n))
 

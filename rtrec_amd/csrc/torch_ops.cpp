@@ -52,6 +52,7 @@ struct Abi {
     decltype(&rtrec_slim_audience_topk) audience_topk = nullptr;
     decltype(&rtrec_slim_score_pairs) score_pairs = nullptr;
     decltype(&rtrec_slim_diversify_lists) diversify_lists = nullptr;          // include/rtrec_amd_ext.h
+    decltype(&rtrec_slim_list_quality) list_quality = nullptr;
 };
 Abi g_abi;
 
@@ -539,6 +540,41 @@ void diversify_lists(const at::Tensor &wc_ptr, const at::Tensor &wc_row, const a
           "rtrec_slim_diversify_lists");
 }
 
+// ids [n_rows, >= list_k] / counts [n_rows]: one list of item ids per row; W as a CSC triple of n_items columns; item_weight
+// (float32) and exposure (int32, ADDED to, never zeroed) hold n_items entries each and may be absent; the outputs are n / sim_sum /
+// linked / weight_sum [n_rows] (include/rtrec_amd_ext.h, "LIST QUALITY").
+void list_quality(const at::Tensor &wc_ptr, const at::Tensor &wc_row, const at::Tensor &wc_val, int64_t n_items, const at::Tensor &ids,
+                  const at::Tensor &counts, int64_t list_k, const OT &item_weight, int64_t waves_per_row, at::Tensor n, at::Tensor sim_sum,
+                  at::Tensor linked, at::Tensor weight_sum, const OT &exposure) {
+    TORCH_CHECK(list_k >= 1 && list_k <= 1024, "list_quality: list_k must lie in 1..1024, got ", list_k);
+    TORCH_CHECK(waves_per_row == 0 || waves_per_row == 1 || waves_per_row == 4, "list_quality: waves_per_row must be 0, 1 or 4, got ", waves_per_row);
+    TORCH_CHECK(ids.dim() == 2 && ids.size(1) >= list_k, "list_quality: ids must be [n_rows, >= list_k]");
+    const int64_t rows = ids.size(0);
+    TORCH_CHECK(rows <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, "list_quality: too many rows or items");
+    TORCH_CHECK(counts.numel() == rows, "list_quality: counts must hold one entry per row");
+    TORCH_CHECK(n.numel() == rows && sim_sum.numel() == rows && linked.numel() == rows && weight_sum.numel() == rows,
+                "list_quality: outputs must be n[n_rows], sim_sum[n_rows], linked[n_rows], weight_sum[n_rows]");
+    const bool weighted = item_weight.has_value() && item_weight->defined(), exposed = exposure.has_value() && exposure->defined();
+    TORCH_CHECK(!weighted || item_weight->numel() == n_items, "list_quality: item_weight must hold n_items entries");
+    TORCH_CHECK(!exposed || exposure->numel() == n_items, "list_quality: exposure must hold n_items entries");
+    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
+    check_csc("list_quality", "wc", wc_ptr, wc_row, wc_val, n_items);
+    check_tensor<const int32_t>(ids); check_tensor<const int32_t>(counts);
+    check_tensor<int32_t>(n); check_tensor<float>(sim_sum); check_tensor<int32_t>(linked); check_tensor<float>(weight_sum);
+    if (weighted) check_tensor<const float>(*item_weight);
+    if (exposed) check_tensor<int32_t>(*exposure);
+    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&wc_ptr, &wc_row, &wc_val, &counts, &n, &sim_sum, &linked, &weight_sum})
+        TORCH_CHECK(t->device() == ids.device(), "list_quality: all tensors must live on one device");
+    TORCH_CHECK((!weighted || item_weight->device() == ids.device()) && (!exposed || exposure->device() == ids.device()),
+                "list_quality: all tensors must live on one device");
+    check(abi().list_quality(static_cast<int32_t>(rows), static_cast<int32_t>(n_items), ptr<const int32_t>(wc_ptr), ptr<const int32_t>(wc_row),
+                             ptr<const float>(wc_val), wc_row.numel(), ptr<const int32_t>(ids), ids.size(1), static_cast<int32_t>(list_k),
+                             ptr<const int32_t>(counts), ptr<const float>(item_weight), ptr<int32_t>(exposure),
+                             static_cast<int32_t>(waves_per_row), ptr<int32_t>(n), ptr<float>(sim_sum), ptr<int32_t>(linked),
+                             ptr<float>(weight_sum), stream_of(n)),
+          "rtrec_slim_list_quality");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -572,6 +608,7 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.audience_topk, "rtrec_slim_audience_topk");
         bind_one(h, a.score_pairs, "rtrec_slim_score_pairs");
         bind_one(h, a.diversify_lists, "rtrec_slim_diversify_lists");
+        bind_one(h, a.list_quality, "rtrec_slim_list_quality");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -639,6 +676,8 @@ TORCH_LIBRARY(rtrec_amd, m) {
     // the extension surface (include/rtrec_amd_ext.h)
     m.def("diversify_lists(Tensor wc_ptr, Tensor wc_row, Tensor wc_val, int n_items, Tensor ids, Tensor scores, Tensor counts, int list_k, "
           "int keep, float lam, int waves_per_row, Tensor(a!) order, Tensor(b!) value, Tensor(c!) penalty, Tensor(d!) count) -> ()");
+    m.def("list_quality(Tensor wc_ptr, Tensor wc_row, Tensor wc_val, int n_items, Tensor ids, Tensor counts, int list_k, Tensor? item_weight, "
+          "int waves_per_row, Tensor(a!) n, Tensor(b!) sim_sum, Tensor(c!) linked, Tensor(d!) weight_sum, Tensor(e!)? exposure) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -665,4 +704,5 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("audience_topk", &audience_topk);
     m.impl("score_pairs", &score_pairs);
     m.impl("diversify_lists", &diversify_lists);
+    m.impl("list_quality", &list_quality);
 }

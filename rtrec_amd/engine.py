@@ -1561,6 +1561,7 @@ class SlimEngine:
         "score_pairs": ("pair scores need", "score_pairs", "pair scores are exact float32 products"),
         "recommend_users": ("an audience needs", "serve audiences", "audience scores are exact float32 sums"),
         "diversify": ("diversified lists need", "diversify", "similarities are W's float32 values"),
+        "list_quality": ("list quality needs", "measure the lists", "similarities are W's float32 values"),
     }
 
     def _whole_w(self, call: str) -> DeviceWeights:
@@ -1733,6 +1734,78 @@ class SlimEngine:
             raise ValueError("counts must hold one entry per row")
         out = self.diversify_device(self._up(item_ids), self._up(scores), self._up(counts), keep, lam)
         return tuple(t.cpu().numpy() for t in out)
+
+    # ------------------------------------------------------------------------------ list quality (what a list looks like, over W)
+    QUALITY_MAX_LIST = 1024     # list_k limit of rtrec_slim_list_quality
+
+    def item_novelty_device(self):
+        """The novelty table of the resident X for W's items, a float32 device tensor [W's n_items]: self-information
+        log2(n_users) - log2(max(pop_i, 1)), pop_i = the stored entries of column i of X (utils.metrics.novelty_weights: numpy
+        in float64, rounded once).  Columns X has beyond W are cut, columns W has beyond X count as never seen -- the way
+        audience_device treats cptr.  Built once per (X, W's width): it is cached on the X dict like the other tensors derived
+        from X, so the next set_interactions drops it."""
+        from .utils.metrics import novelty_weights
+        dw = self._whole_w("list_quality")
+        if not self._X:
+            raise RuntimeError("set_interactions() must be called before item_novelty_device()")
+        cache = self._X.setdefault("item_novelty", {})
+        if dw.n_items not in cache:
+            if "col_nnz" in self._X:
+                pop = np.asarray(self._X["col_nnz"], dtype=np.int64)
+            else:                       # only the CSR orientation is resident: one count of its column ids on the device
+                rcol = self._X["rcol"]
+                pop = self.be.torch.bincount(rcol.to(self.be.torch.int64), minlength=self.n_items).cpu().numpy().astype(np.int64)
+            cache[dw.n_items] = self._up(novelty_weights(pop, self.n_users, dw.n_items))
+        return cache[dw.n_items]
+
+    def list_quality_device(self, ids, counts, item_weight=None, exposure=None, waves_per_row: int = 0):
+        """Device tensors (n[n_rows] int32, sim_sum[n_rows] float32, linked[n_rows] int32, weight_sum[n_rows] float32) for the
+        lists `ids` [n_rows, k] int32 / `counts` [n_rows] int32 (device tensors, e.g. what score_topk_device or the gather
+        behind diversify_device left: they never leave HBM): the counted positions of each list (inside W, below counts, every
+        item once), the two-level float32 sum of similarity = max(|W[a, b]|, |W[b, a]|) over its pairs, the pairs with a
+        similarity above 0, and the sum of `item_weight` [W's n_items] float32 (None: +0).  `exposure` [W's n_items] int32
+        (None: not kept) gets 1 added per counted position and is never zeroed, so it accumulates over calls.  The contract is
+        the comment of rtrec_slim_list_quality in include/rtrec_amd_ext.h.  Every rank that holds the whole W answers locally:
+        there is no collective."""
+        be, torch = self.be, self.be.torch
+        dw = self._whole_w("list_quality")
+        n_rows, k = int(ids.shape[0]), int(ids.shape[-1])
+        if ids.dim() != 2 or not 1 <= k <= self.QUALITY_MAX_LIST:
+            raise ValueError(f"list_quality: lists of 1..{self.QUALITY_MAX_LIST} items are supported, got {k}")
+        if int(counts.numel()) != n_rows:
+            raise ValueError("list_quality: counts must hold one entry per row")
+        for name, t in (("item_weight", item_weight), ("exposure", exposure)):
+            if t is not None and int(t.numel()) != dw.n_items:
+                raise ValueError(f"list_quality: {name} must hold one entry per item of W ({dw.n_items}), got {int(t.numel())}")
+        n = be.zeros((n_rows,), torch.int32)
+        sim_sum = be.zeros((n_rows,), torch.float32)
+        linked = be.zeros((n_rows,), torch.int32)
+        weight_sum = be.zeros((n_rows,), torch.float32)
+        if n_rows == 0:
+            return n, sim_sum, linked, weight_sum
+        be.list_quality(dw.n_items, self._w_csc(), ids.contiguous(), counts.contiguous(), k, item_weight, exposure, n, sim_sum, linked,
+                        weight_sum, waves_per_row=waves_per_row)
+        return n, sim_sum, linked, weight_sum
+
+    def list_quality_lists(self, item_ids: np.ndarray, counts: Optional[np.ndarray] = None, item_weight: Optional[np.ndarray] = None,
+                           novelty: bool = False, with_exposure: bool = True, waves_per_row: int = 0):
+        """list_quality_device for lists the caller brings: numpy (n[B], sim_sum[B], linked[B], weight_sum[B], exposure[W's
+        n_items] or None) for `item_ids` [B, k] (-1 or an id outside W = an empty position); counts default to k,
+        `item_weight` [W's n_items] float32 or None; `novelty=True` weighs with item_novelty_device() instead."""
+        item_ids = np.ascontiguousarray(item_ids, dtype=np.int32)
+        if item_ids.ndim != 2:
+            raise ValueError("item_ids must be a [B, k] array")
+        B, k = item_ids.shape
+        counts = np.full(B, k, dtype=np.int32) if counts is None else np.asarray(counts, dtype=np.int32)
+        if counts.shape != (B,):
+            raise ValueError("counts must hold one entry per row")
+        dw = self._whole_w("list_quality")
+        if novelty and item_weight is not None:
+            raise ValueError("list_quality: pass item_weight or novelty=True, not both")
+        d_w = self.item_novelty_device() if novelty else None if item_weight is None else self._up(np.ascontiguousarray(item_weight, dtype=np.float32))
+        d_exp = self.be.zeros((dw.n_items,), self.be.torch.int32) if with_exposure else None
+        out = self.list_quality_device(self._up(item_ids), self._up(counts), d_w, d_exp, waves_per_row)
+        return tuple(t.cpu().numpy() for t in out) + (d_exp.cpu().numpy() if with_exposure else None,)
 
     # ------------------------------------------------------------------------------ audience of an item
     AUDIENCE_MAX_TOP_N = 1024   # top_n limit of rtrec_slim_audience_topk

@@ -286,13 +286,16 @@ class SLIM(BaseModel):
         return np.fromiter((-1 if (i := get(v)) is None else i for v in values.tolist()), dtype=np.int64, count=len(values))
 
     def _evaluate_device(self, users: np.ndarray, items: np.ndarray, size: int, filter_interacted: bool,
-                         want_rel: bool = False):
+                         want_rel: bool = False, diversity: float = 0.0, pool: int = 50, list_quality: bool = False):
         """Recommender.evaluate without leaving the device: every user of the frame scored in ONE pass whose lists stay in
         HBM, rank_metrics_kernel (csrc/rank_metrics.hip) on (lists, ground truth), and only the per-user figures come back.
         Returns (users in evaluation order, metrics[n, 8] float64 in utils.metrics.METRIC_COLUMNS order, tp[n] int32,
         rel[n] uint64 or None).  Known users get recommend_batch's hot lists, unknown ones its cold-start list.  What this
         path does not serve is refused with ValueError -- the caller evaluates on the host instead.  With several ranks the
-        scoring pass is the usual collective and every rank computes the same figures."""
+        scoring pass is the usual collective and every rank computes the same figures.
+        `diversity > 0`: known users are judged on recommend_diverse_batch(top_k=size, pool, diversity)'s lists instead, with
+        its refusals.  `list_quality=True`: the same lists also go through list_quality_kernel (csrc/list_quality.hip) in the
+        same pass, and a fifth element is returned: numpy (n, sim_sum, linked, weight_sum, exposure[W's n_items])."""
         from .._native import TOPK_DENSE, TOPK_SPARSE
         from ..backend import HipBackend
         from ..utils.metrics import discount_tables, ground_truth_csr
@@ -308,6 +311,9 @@ class SLIM(BaseModel):
         for name, col in (("user", users), ("item", items)):
             if col.dtype.kind not in "iuO":
                 raise ValueError(f"on_device evaluation takes integer or object id columns; the {name} column is {col.dtype}")
+        lam = None
+        if float(diversity) != 0.0:                                         # (a NaN is not 0: _mmr_lambda refuses it)
+            _, pool, lam = self._diverse_args("on_device evaluation with diversity", size, pool, diversity)
         if not self.model.is_fitted:
             raise RuntimeError("Model must be fitted before calling batch_recommend.")
         n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
@@ -327,7 +333,9 @@ class SLIM(BaseModel):
         eval_users, rows, truth_ptr, truth_items, truth_len = ground_truth_csr(users, items, user_index, item_index)
         n = len(eval_users)
         if n == 0:
-            return eval_users, np.empty((0, 8), np.float64), np.empty(0, np.int32), (np.empty(0, np.uint64) if want_rel else None)
+            none = (eval_users, np.empty((0, 8), np.float64), np.empty(0, np.int32), (np.empty(0, np.uint64) if want_rel else None))
+            return none if not list_quality else none + ((np.empty(0, np.int32), np.empty(0, np.float32), np.empty(0, np.int32),
+                                                          np.empty(0, np.float32), np.zeros(n_items, np.int32)),)
         hot = rows >= 0
         hot_rows = rows[hot]
         if len(hot_rows) and int(hot_rows.max()) >= n_users:
@@ -337,12 +345,17 @@ class SLIM(BaseModel):
         self.model._sync_weights()
         if top_k < 1 or not eng.topk_supported(top_k, mode):
             raise ValueError(f"on_device evaluation: the fused top-k kernels do not serve recommend_size {size} for this model")
+        k_pool = 0
+        if lam is not None:
+            eng._whole_w("diversify")
+            k_pool = self._pool_width("on_device evaluation with diversity", pool, mode)
+        if list_quality:
+            eng._whole_w("list_quality")
         torch = be.torch
         ids = cnt = None
         if len(hot_rows):
             self._sync_interactions()
-            ids, _, cnt = eng.score_topk_device(hot_rows.astype(np.int32), len(hot_rows), top_k, filter_interacted, mode,
-                                                with_scores=False)
+            ids, cnt = self._hot_lists_device(hot_rows, top_k, lam, k_pool, filter_interacted, mode)
         if len(hot_rows) < n or top_k < size or not ids.is_contiguous():
             # the rows of unknown users (recommend_batch gives them all the hot-items list) and lists narrower than `size`
             # are placed on the device
@@ -366,7 +379,13 @@ class SLIM(BaseModel):
         be.ops.rank_metrics(ids, cnt.contiguous(), be.to_dev(truth_ptr), be.to_dev(truth_items), be.to_dev(truth_len),
                             be.to_dev(discount), be.to_dev(ideal), size, d_metrics, d_tp, d_rel)
         rel = d_rel.cpu().numpy().view(np.uint64) if want_rel else None
-        return eval_users, d_metrics.cpu().numpy(), d_tp.cpu().numpy(), rel
+        if not list_quality:
+            return eval_users, d_metrics.cpu().numpy(), d_tp.cpu().numpy(), rel
+        self._sync_interactions()                                           # (the novelty table is X's, whoever is in the frame)
+        exposure = be.zeros((eng._whole_w("list_quality").n_items,), torch.int32)
+        quality = eng.list_quality_device(ids, cnt.contiguous(), eng.item_novelty_device(), exposure)
+        return (eval_users, d_metrics.cpu().numpy(), d_tp.cpu().numpy(), rel,
+                tuple(t.cpu().numpy() for t in quality) + (exposure.cpu().numpy(),))
 
     # ------------------------------------------------------------ explanations (an extension: the reference has none)
     def explain_batch(self, users: List[Any], items: Optional[List[List[Any]]] = None, top_k: int = 10, top_m: int = 3,
@@ -661,6 +680,46 @@ class SLIM(BaseModel):
             raise ValueError(f"{what}: diversity must lie in [0, 1], got {diversity}")
         return np.float32(1.0 - float(diversity))
 
+    def _diverse_args(self, what: str, top_k: int, pool: int, diversity: float) -> Tuple[int, int, np.float32]:
+        """(top_k, pool, lambda) of a diversified call named `what`, or its refusal."""
+        top_k, pool = int(top_k), int(pool)
+        if not 1 <= top_k <= pool <= self.DIVERSE_MAX_POOL:
+            raise ValueError(f"{what} needs 1 <= top_k <= pool <= {self.DIVERSE_MAX_POOL}, got top_k={top_k} and "
+                             f"pool={pool}")
+        lam = self._mmr_lambda(diversity, what)
+        if not self.model.is_fitted:
+            raise RuntimeError(f"Model must be fitted before calling {what}.")
+        return top_k, pool, lam
+
+    def _pool_width(self, what: str, pool: int, mode: int) -> int:
+        """min(pool, the catalogue): the width of the lists the scoring pass of `what` hands to the selection, refused where the
+        fused top-k kernels do not serve it for this model (the weights are synced by the caller)."""
+        eng = self.model.engine
+        k_pool = min(pool, self.model.n_items_fitted)
+        if k_pool < 1 or not eng.topk_supported(k_pool, mode):
+            why = (f"they rank lists of at most {eng.MAX_TOP_K} items" if k_pool > eng.MAX_TOP_K else
+                   f"the per-tile lists of one user, (pool + 1) per tile of W's columns, exceed the {eng.MAX_MERGE_CANDIDATES} "
+                   "entries the merge takes") if k_pool >= 1 else "the model has no item"
+            raise ValueError(f"{what}: the fused score + top-k kernels do not serve lists of pool={pool} for "
+                             f"this model ({why}): choose a smaller pool")
+        return k_pool
+
+    def _diverse_device(self, rows: np.ndarray, top_k: int, k_pool: int, lam: float, filter_interacted: bool, mode: int):
+        """The device section of the diversified calls for the user rows `rows` (int32, inside the matrix): device tensors
+        (ids[n, keep] int32, base scores[n, keep] float32, counts[n] int32, value[n, keep], penalty[n, keep]), keep =
+        min(top_k, k_pool); -1 / -inf behind counts.  The scoring kernels' lists of k_pool go straight into the selection
+        kernel and the chosen entries are gathered where the lists are, so nothing has left HBM yet."""
+        eng = self.model.engine
+        torch = eng.be.torch
+        d_ids, d_sc, d_cnt = eng.score_topk_device(None, len(rows), k_pool, filter_interacted, mode, d_rows=eng._up(rows))
+        d_sc = d_sc.to(torch.float32)
+        order, value, pen, cnt = eng.diversify_device(d_ids, d_sc, d_cnt, min(top_k, k_pool), lam)
+        gone = order < 0
+        at = order.clamp(min=0).to(torch.int64)
+        g_ids = torch.gather(d_ids, 1, at).masked_fill(gone, -1)
+        g_sc = torch.gather(d_sc, 1, at).masked_fill(gone, float("-inf"))
+        return g_ids, g_sc, cnt, value, pen
+
     def recommend_diverse_batch(self, users: List[Any], top_k: int = 10, pool: int = 50, diversity: float = 0.3,
                                 filter_interacted: bool = True, ret_scores: bool = False, as_arrays: bool = False) -> Any:
         """Recommendations that trade score against similarity to what is already on the page: a list ranked by score alone
@@ -691,13 +750,7 @@ class SLIM(BaseModel):
         entry was chosen with and its penalty, i.e. how similar it is to what stands above it (-inf for the unchanged lists
         of unknown users)."""
         from .._native import TOPK_DENSE, TOPK_SPARSE
-        top_k, pool = int(top_k), int(pool)
-        if not 1 <= top_k <= pool <= self.DIVERSE_MAX_POOL:
-            raise ValueError(f"recommend_diverse_batch needs 1 <= top_k <= pool <= {self.DIVERSE_MAX_POOL}, got top_k={top_k} and "
-                             f"pool={pool}")
-        lam = self._mmr_lambda(diversity, "recommend_diverse_batch")
-        if not self.model.is_fitted:
-            raise RuntimeError("Model must be fitted before calling recommend_diverse_batch.")
+        top_k, pool, lam = self._diverse_args("recommend_diverse_batch", top_k, pool, diversity)
         arr = self._int_user_array(users)
         users = arr if arr is not None else list(users)
         B = len(users)
@@ -714,13 +767,7 @@ class SLIM(BaseModel):
             self.model._sync_weights()
             eng._whole_w("diversify")              # a W that cannot be served is refused whatever the batch holds
             mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
-            k_pool = min(pool, n_items)
-            if k_pool < 1 or not eng.topk_supported(k_pool, mode):
-                why = (f"they rank lists of at most {eng.MAX_TOP_K} items" if k_pool > eng.MAX_TOP_K else
-                       f"the per-tile lists of one user, (pool + 1) per tile of W's columns, exceed the {eng.MAX_MERGE_CANDIDATES} "
-                       "entries the merge takes") if k_pool >= 1 else "the model has no item"
-                raise ValueError(f"recommend_diverse_batch: the fused score + top-k kernels do not serve lists of pool={pool} for "
-                                 f"this model ({why}): choose a smaller pool")
+            k_pool = self._pool_width("recommend_diverse_batch", pool, mode)
             if cold.any():
                 cold_list = self._recommend_cold_batch([None], top_k=top_k)[0][:top_k]
                 out_ids[cold, :len(cold_list)] = np.asarray(cold_list, dtype=np.int64)[None, :]
@@ -734,16 +781,8 @@ class SLIM(BaseModel):
                         out_ids[b, :len(row)], out_sc[b, :len(row)], out_cnt[b] = row, 0.0, len(row)
             if regular.any():
                 self._sync_interactions()
-                torch = eng.be.torch
-                rows = uid[regular].astype(np.int32)
                 keep = min(top_k, k_pool)
-                d_ids, d_sc, d_cnt = eng.score_topk_device(None, len(rows), k_pool, filter_interacted, mode, d_rows=eng._up(rows))
-                d_sc = d_sc.to(torch.float32)
-                order, value, pen, cnt = eng.diversify_device(d_ids, d_sc, d_cnt, keep, lam)
-                gone = order < 0                     # the chosen entries are gathered where the lists are: top_k per user travel
-                at = order.clamp(min=0).to(torch.int64)
-                g_ids = torch.gather(d_ids, 1, at).masked_fill(gone, -1)
-                g_sc = torch.gather(d_sc, 1, at).masked_fill(gone, float("-inf"))
+                g_ids, g_sc, cnt, value, pen = self._diverse_device(uid[regular].astype(np.int32), top_k, k_pool, lam, filter_interacted, mode)
                 pos = np.flatnonzero(regular)
                 out_ids[pos, :keep], out_sc[pos, :keep] = g_ids.cpu().numpy(), g_sc.cpu().numpy()
                 out_val[pos, :keep], out_pen[pos, :keep], out_cnt[pos] = value.cpu().numpy(), pen.cpu().numpy(), cnt.cpu().numpy()
@@ -791,6 +830,131 @@ class SLIM(BaseModel):
         if as_arrays:
             return order, value, pen, cnt
         return [[(items[b][p_], float(scores[b][p_])) for p_ in order[b, :cnt[b]].tolist()] for b in range(len(items))]
+
+    # ------------------------------------------------------------ list quality (an extension: the reference has none)
+    QUALITY_MAX_LIST = 1024     # list length rtrec_slim_list_quality measures
+
+    def list_quality_batch(self, items: List[List[Any]], as_arrays: bool = False) -> Any:
+        """What each list of `items` (raw item ids; from this model, another ranker, a rule, a cache -- no user is needed)
+        looks like apart from its accuracy.  An item the model does not know is not counted, an item listed twice is judged
+        once, at its first place.  Per list a dict: `n` the counted items, `intra_list_similarity` the mean of
+        similarity(a, b) = max(|W[a, b]|, |W[b, a]|) over its pairs (NaN below two items), `linked_pairs` the pairs with a
+        similarity above 0, `novelty` the mean self-information log2(n_users / the item's users) of its items (NaN for no
+        item).  The figures come from one kernel over the lists (csrc/list_quality.hip; the contract is the comment of
+        rtrec_slim_list_quality in include/rtrec_amd_ext.h) and utils.metrics.list_quality_figures.  With `as_arrays=True`:
+        the kernel's raw arrays (n[B], sim_sum[B], linked[B], weight_sum[B]) plus exposure[n_items], how often each INTERNAL
+        item id was counted over all lists.  Lists longer than 1024 raise ValueError; W must be whole and hold float32
+        numbers, as for recommend_diverse_batch."""
+        from ..utils.metrics import quality_frame_columns
+        if not self.model.is_fitted:
+            raise RuntimeError("Model must be fitted before calling list_quality_batch.")
+        items = [list(r) for r in items]
+        K = max([len(r) for r in items] + [1])
+        if K > self.QUALITY_MAX_LIST:
+            raise ValueError(f"list_quality_batch serves lists of up to {self.QUALITY_MAX_LIST} items, got a list of {K}")
+        n_items = self.model.n_items_fitted
+        ids = np.full((len(items), K), -1, dtype=np.int32)
+        for b, row in enumerate(items):
+            ids[b, :len(row)] = self._ids_or_minus_one(row, self.item_ids.get_id, min(n_items, 2 ** 31 - 1))
+        counts = np.array([len(r) for r in items], dtype=np.int32)
+        self.model._sync_weights()
+        self.model.engine._whole_w("list_quality")
+        self._sync_interactions()
+        n, sim_sum, linked, weight_sum, exposure = self.model.engine.list_quality_lists(ids, counts, novelty=True)
+        if as_arrays:
+            return n, sim_sum, linked, weight_sum, exposure
+        cols = {key: col.tolist() for key, col in quality_frame_columns(n, sim_sum, linked, weight_sum).items()}
+        return [{key: cols[key][b] for key in cols} for b in range(len(items))]
+
+    def list_quality(self, items: List[Any]) -> Dict[str, Any]:
+        """list_quality_batch for one list: {n, intra_list_similarity, linked_pairs, novelty}."""
+        return self.list_quality_batch([items])[0]
+
+    def _hot_lists_device(self, rows: np.ndarray, top_k: int, lam: Optional[float], k_pool: int, filter_interacted: bool, mode: int):
+        """Device (ids[n, <= top_k] int32, counts[n] int32) of the lists the user rows `rows` are served: recommend_batch's
+        (lam None) or recommend_diverse_batch's."""
+        if lam is None:
+            ids, _, cnt = self.model.engine.score_topk_device(rows.astype(np.int32), len(rows), top_k, filter_interacted, mode,
+                                                              with_scores=False)
+            return ids, cnt
+        ids, _, cnt, _, _ = self._diverse_device(rows.astype(np.int32), top_k, k_pool, lam, filter_interacted, mode)
+        return ids, cnt
+
+    def recommend_quality(self, users: List[Any], top_k: int = 10, diversity: float = 0.0, pool: int = 50,
+                          filter_interacted: bool = True, per_user: bool = False) -> Any:
+        """What the lists these users would be served look like, and what all of them together show of the catalogue: with
+        `diversity == 0` the lists of `recommend_batch(users, top_k=top_k)`, otherwise those of
+        `recommend_diverse_batch(users, top_k, pool, diversity)` -- so one call per value of `diversity` gives the curve the knob
+        is set by.  Known users' lists go from the scoring kernels (through the selection kernel and its gather where asked)
+        into the measuring kernel (csrc/list_quality.hip) without leaving HBM; unknown users contribute their cold-start list,
+        uploaded once; users outside the matrix follow `recommend_batch`'s rules.  Four numbers per user and one count per
+        item are downloaded.
+
+        Returns utils.metrics.quality_summary's dict: n_lists, n_lists_nonempty, n_lists_pairs, mean_length, the means (exactly
+        rounded sums, so they do not depend on the order of the users) of intra_list_similarity and linked_share over the
+        lists of two items or more and of novelty over the lists of one or more, and distinct_items, coverage (of the
+        fitted catalogue) and gini of the exposure.  `per_user=True` returns (dict, frame): n, intra_list_similarity,
+        linked_pairs and novelty per user, in the order of `users`.
+
+        Raises what recommend_diverse_batch raises when `diversity > 0`; with `diversity == 0`, `pool` is not read and top_k must
+        be one the fused top-k kernels serve for this model."""
+        from .._native import TOPK_DENSE, TOPK_SPARSE
+        from ..utils.metrics import quality_frame_columns, quality_summary
+        what = "recommend_quality"
+        lam: Optional[float] = None
+        if float(diversity) != 0.0:                                        # (a NaN is not 0: _mmr_lambda refuses it)
+            top_k, pool, lam = self._diverse_args(what, top_k, pool, diversity)
+        else:
+            top_k = int(top_k)
+            if not 1 <= top_k <= self.QUALITY_MAX_LIST:
+                raise ValueError(f"{what} needs 1 <= top_k <= {self.QUALITY_MAX_LIST}, got top_k={top_k}")
+            if not self.model.is_fitted:
+                raise RuntimeError(f"Model must be fitted before calling {what}.")
+        arr = self._int_user_array(users)
+        users = arr if arr is not None else list(users)
+        B = len(users)
+        eng = self.model.engine
+        n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
+        self.model._sync_weights()
+        dw = eng._whole_w("diversify" if lam is not None else "list_quality")
+        mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+        k_pool = self._pool_width(what, pool, mode) if lam is not None else 0
+        k = min(top_k, n_items)
+        if lam is None and (k < 1 or not eng.topk_supported(k, mode)):
+            raise ValueError(f"{what}: the fused score + top-k kernels do not serve lists of top_k={top_k} for this model")
+        self._sync_interactions()
+        be, torch = eng.be, eng.be.torch
+        d_ids = torch.full((B, top_k), -1, dtype=torch.int32, device=be.device)
+        d_cnt = be.zeros((B,), torch.int32)
+        if B:
+            uid, cold = self._user_rows(users)
+            regular = ~cold & (uid >= 0) & (uid < n_users)
+            if regular.any():
+                ids, cnt = self._hot_lists_device(uid[regular], k, lam, k_pool, filter_interacted, mode)
+                pos = be.to_dev(np.flatnonzero(regular))
+                d_ids[pos, :int(ids.shape[1])] = ids
+                d_cnt[pos] = cnt
+            if cold.any():                                                 # one upload, broadcast on the device
+                cold_list = self._recommend_cold_batch([None], top_k=top_k)[0][:top_k]
+                if cold_list:
+                    pos = be.to_dev(np.flatnonzero(cold))
+                    d_ids[pos, :len(cold_list)] = be.to_dev(np.asarray(cold_list, dtype=np.int32))[None, :]
+                    d_cnt[pos] = len(cold_list)
+            odd = ~cold & ~regular
+            if odd.any():
+                lists = self._recommend_odd_ids(uid[~cold], n_users, None, top_k, filter_interacted)
+                for b, row in zip(np.flatnonzero(~cold).tolist(), lists):
+                    if odd[b] and len(row):
+                        d_ids[b, :len(row)] = be.to_dev(np.asarray(row, dtype=np.int32))
+                        d_cnt[b] = len(row)
+        exposure = be.zeros((dw.n_items,), torch.int32)
+        out = eng.list_quality_device(d_ids, d_cnt, eng.item_novelty_device(), exposure)
+        n, sim_sum, linked, weight_sum = (t.cpu().numpy() for t in out)
+        summary = quality_summary(n, sim_sum, linked, weight_sum, exposure.cpu().numpy())
+        if not per_user:
+            return summary
+        import pandas as pd
+        return summary, pd.DataFrame(quality_frame_columns(n, sim_sum, linked, weight_sum), index=pd.Index(users, name="user"))
 
     # ------------------------------------------------------------ audience of an item (an extension: the reference has none)
     def _sync_interactions_csc(self) -> None:

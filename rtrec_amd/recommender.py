@@ -16,7 +16,8 @@ import numpy as np
 import pandas as pd
 
 from .models.base import BaseModel
-from .utils.metrics import METRIC_COLUMNS, RESULT_KEYS, _query_metrics, compute_scores, scores_from_columns
+from .utils.metrics import (METRIC_COLUMNS, RESULT_KEYS, _query_metrics, compute_scores, quality_frame_columns, quality_summary,
+                            scores_from_columns)
 
 _COLUMNS = ["user", "item", "tstamp", "rating"]
 _COLUMNAR_CHUNK = 1 << 22
@@ -157,6 +158,20 @@ class Recommender:
         """SLIM.diversify_batch: the same selection for lists (and base scores) the caller brings."""
         return self.model.diversify_batch(items, scores, top_k=top_k, diversity=diversity, as_arrays=as_arrays)
 
+    def list_quality(self, items: List[Any]) -> Dict[str, Any]:
+        """An extension (the reference has none): {n, intra_list_similarity, linked_pairs, novelty} of one list -- SLIM.list_quality."""
+        return self.model.list_quality(items)
+
+    def list_quality_batch(self, items: List[List[Any]], as_arrays: bool = False) -> Any:
+        """SLIM.list_quality_batch: the same for many lists the caller brings, in one device pass."""
+        return self.model.list_quality_batch(items, as_arrays=as_arrays)
+
+    def recommend_quality(self, users: List[Any], top_k: int = 10, diversity: float = 0.0, pool: int = 50,
+                          filter_interacted: bool = True, per_user: bool = False) -> Any:
+        """SLIM.recommend_quality: intra-list similarity, novelty and catalogue exposure of the lists these users would be served."""
+        return self.model.recommend_quality(users, top_k=top_k, diversity=diversity, pool=pool, filter_interacted=filter_interacted,
+                                            per_user=per_user)
+
     def similar_items(self, query_items: List[Any], query_item_tags: Optional[List[str]] = None, top_k: int = 10,
                       ret_scores: bool = False):
         batch = getattr(self.model, "similar_items_batch", None)
@@ -166,7 +181,8 @@ class Recommender:
 
     def evaluate(self, test_data: pd.DataFrame, user_tags: Optional[Dict[Any, List[str]]] = None,
                  recommend_size: int = 10, batch_size=100, filter_interacted: bool = True,
-                 on_device: bool = False, per_user: bool = False) -> Any:
+                 on_device: bool = False, per_user: bool = False, diversity: float = 0.0, pool: int = 50,
+                 list_quality: bool = False) -> Any:
         """Average ranking metrics over the users of test_data (columns user, item).
 
         `on_device=True` (extension) evaluates without leaving the GPU: the held-out items go up once, all users are scored
@@ -176,9 +192,16 @@ class Recommender:
         columns that are neither integer nor object dtype, users that only the host path can place -- raises ValueError
         naming the reason: drop `on_device` then.
         `per_user=True` (extension, either path) returns `(dict, frame)`: the frame holds the nine figures per user, indexed
-        by user in evaluation order (the order the means are summed in)."""
+        by user in evaluation order (the order the means are summed in).
+        `diversity > 0` (extension, `on_device=True` only) judges the lists of `recommend_diverse_batch(top_k=recommend_size,
+        pool=pool, diversity=diversity)` instead, so the nine figures price the knob; `list_quality=True` (`on_device=True`
+        only) adds the keys of `SLIM.recommend_quality` (utils.metrics.QUALITY_KEYS) for the same lists, computed in the same
+        pass, and its four per-user columns to the frame.  With the defaults nothing changes."""
+        if (diversity != 0.0 or list_quality) and not on_device:
+            raise ValueError("evaluate: diversity and list_quality are served by the device path only: pass on_device=True")
         if on_device:
-            return self._evaluate_on_device(test_data, user_tags, recommend_size, filter_interacted, per_user)
+            return self._evaluate_on_device(test_data, user_tags, recommend_size, filter_interacted, per_user, diversity, pool,
+                                            list_quality)
         truth = test_data.groupby("user")["item"].apply(list).to_dict()
         users = list(truth.keys())
 
@@ -204,7 +227,7 @@ class Recommender:
         return scores_from_columns(metrics, tp), frame
 
     def _evaluate_on_device(self, test_data: pd.DataFrame, user_tags, recommend_size, filter_interacted: bool,
-                            per_user: bool) -> Any:
+                            per_user: bool, diversity: float = 0.0, pool: int = 50, list_quality: bool = False) -> Any:
         if user_tags:
             raise ValueError("on_device evaluation does not take user_tags")
         if isinstance(recommend_size, bool) or not isinstance(recommend_size, (int, np.integer)) or not 1 <= recommend_size <= 64:
@@ -212,11 +235,23 @@ class Recommender:
         hook = getattr(self.model, "_evaluate_device", None)
         if hook is None:
             raise ValueError(f"on_device evaluation: {type(self.model).__name__} has no device evaluation hook")
-        users, metrics, tp, _ = hook(test_data["user"].to_numpy(), test_data["item"].to_numpy(), int(recommend_size),
-                                     bool(filter_interacted))
-        if per_user:
-            return self._scores_and_frame(metrics, tp, pd.Index(users, name="user"))
-        return scores_from_columns(metrics, tp)
+        if diversity == 0.0 and not list_quality:
+            users, metrics, tp, _ = hook(test_data["user"].to_numpy(), test_data["item"].to_numpy(), int(recommend_size),
+                                         bool(filter_interacted))
+            if per_user:
+                return self._scores_and_frame(metrics, tp, pd.Index(users, name="user"))
+            return scores_from_columns(metrics, tp)
+        out = hook(test_data["user"].to_numpy(), test_data["item"].to_numpy(), int(recommend_size), bool(filter_interacted),
+                   diversity=diversity, pool=pool, list_quality=bool(list_quality))
+        users, metrics, tp = out[:3]
+        scores, frame = self._scores_and_frame(metrics, tp, pd.Index(users, name="user"))
+        scores = dict(scores)                       # (no user at all: compute_scores' empty defaultdict)
+        if list_quality:
+            n, sim_sum, linked, weight_sum, exposure = out[4]
+            scores.update(quality_summary(n, sim_sum, linked, weight_sum, exposure))
+            for name, col in quality_frame_columns(n, sim_sum, linked, weight_sum).items():
+                frame[name] = col
+        return (scores, frame) if per_user else scores
 
     @staticmethod
     def generate_batches(df: pd.DataFrame, batch_size: int = 1_000, as_generator: bool = False

@@ -184,3 +184,93 @@ def scores_from_columns(metrics: np.ndarray, tp: np.ndarray) -> Dict[str, float]
     col = {name: sequential_sum(metrics[:, j]) / n for j, name in enumerate(METRIC_COLUMNS)}
     col["tp"] = int(np.asarray(tp, dtype=np.int64).sum())
     return {name: col[name] for name in RESULT_KEYS}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# List quality (csrc/list_quality.hip): what a served list looks like apart from its accuracy.  The kernel returns four raw
+# figures per list and one exposure count per item; everything below is pure host arithmetic over them.
+
+QUALITY_COLUMNS = ("n", "intra_list_similarity", "linked_pairs", "novelty")            # the per-list figures, as the frames carry them
+QUALITY_KEYS = ("n_lists", "n_lists_nonempty", "n_lists_pairs", "mean_length", "intra_list_similarity", "linked_share", "novelty",
+                "distinct_items", "coverage", "gini")
+
+
+def novelty_weights(pop: np.ndarray, n_users: int, n_items: int) -> np.ndarray:
+    """float32[n_items]: the self-information log2(n_users) - log2(max(pop_i, 1)) of every item, computed in float64 and rounded
+    once; `pop` (the stored entries per column of X) is cut or zero-padded to n_items, so an item X has never seen weighs like
+    one seen once.  (No user at all counts as one: the table is then all zeros rather than -inf.)"""
+    pop = np.asarray(pop, dtype=np.int64)[:n_items]
+    if len(pop) < n_items:
+        pop = np.concatenate([pop, np.zeros(n_items - len(pop), dtype=np.int64)])
+    return (np.log2(np.float64(max(int(n_users), 1))) - np.log2(np.maximum(pop, 1).astype(np.float64))).astype(np.float32)
+
+
+def list_quality_figures(n: np.ndarray, sim_sum: np.ndarray, linked: np.ndarray, weight_sum: np.ndarray
+                         ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Per list (float64 arrays): intra_list_similarity = sim_sum / (m (m - 1) / 2) and linked_share = linked / that number of
+    pairs for m >= 2, novelty = weight_sum / m for m >= 1; NaN where a figure is not defined."""
+    m = np.asarray(n, dtype=np.int64)
+    pairs = (m * (m - 1) // 2).astype(np.float64)
+    ils = np.full(len(m), np.nan)
+    share = np.full(len(m), np.nan)
+    nov = np.full(len(m), np.nan)
+    two, one = m >= 2, m >= 1
+    with np.errstate(invalid="ignore", over="ignore"):
+        ils[two] = np.asarray(sim_sum, dtype=np.float32)[two].astype(np.float64) / pairs[two]
+        share[two] = np.asarray(linked, dtype=np.int64)[two].astype(np.float64) / pairs[two]
+        nov[one] = np.asarray(weight_sum, dtype=np.float32)[one].astype(np.float64) / m[one].astype(np.float64)
+    return ils, share, nov
+
+
+def fsum_mean(values: np.ndarray) -> float:
+    """math.fsum(values) / len(values): the exactly rounded sum, so the mean does not depend on the order; NaN for no value."""
+    from math import fsum
+    values = np.asarray(values, dtype=np.float64)
+    if len(values) == 0:
+        return float("nan")
+    with np.errstate(invalid="ignore"):
+        try:
+            return fsum(values.tolist()) / len(values)
+        except (OverflowError, ValueError):     # (inf - inf, or a sum beyond the doubles: fsum raises where + would give nan / inf)
+            return float(np.sum(values) / len(values))
+
+
+def gini(exposure: np.ndarray) -> float:
+    """The Gini coefficient of an exposure count per item, never-shown items counting as 0: with e ascending and i = 1..n,
+    sum_i (2 i - n - 1) e_i / (n sum_i e_i), numerator and denominator as exact integers and one correctly rounded division.
+    0 for a uniform exposure, (n - 1) / n for a single item; NaN when nothing was shown."""
+    e = np.sort(np.asarray(exposure).astype(np.int64).ravel())
+    n = len(e)
+    total = int(e.sum(dtype=object)) if n else 0
+    if total <= 0:
+        return float("nan")
+    coef = 2 * np.arange(1, n + 1, dtype=np.int64) - n - 1
+    if n * total < 2 ** 62:
+        num = int(np.dot(coef, e))
+    else:
+        num = int(np.dot(coef.astype(object), e.astype(object)))
+    return num / (n * total)
+
+
+def quality_summary(n: np.ndarray, sim_sum: np.ndarray, linked: np.ndarray, weight_sum: np.ndarray, exposure: np.ndarray
+                    ) -> Dict[str, Any]:
+    """The figures of a batch of lists, in QUALITY_KEYS order: n_lists (all of them, mean_length's count), n_lists_nonempty
+    (m >= 1: novelty's count), n_lists_pairs (m >= 2: the count behind intra_list_similarity and linked_share); the fsum means
+    of the per-list figures over the lists where each is defined (NaN over none); and the catalogue side of `exposure`
+    [n_items]: distinct_items shown at all, coverage = distinct_items / n_items (NaN for an empty catalogue), gini."""
+    m = np.asarray(n, dtype=np.int64)
+    ils, share, nov = list_quality_figures(m, sim_sum, linked, weight_sum)
+    exposure = np.asarray(exposure)
+    distinct = int(np.count_nonzero(exposure > 0))
+    out = {"n_lists": int(len(m)), "n_lists_nonempty": int((m >= 1).sum()), "n_lists_pairs": int((m >= 2).sum()),
+           "mean_length": fsum_mean(m), "intra_list_similarity": fsum_mean(ils[m >= 2]), "linked_share": fsum_mean(share[m >= 2]),
+           "novelty": fsum_mean(nov[m >= 1]), "distinct_items": distinct,
+           "coverage": distinct / len(exposure) if len(exposure) else float("nan"), "gini": gini(exposure)}
+    return {key: out[key] for key in QUALITY_KEYS}
+
+
+def quality_frame_columns(n: np.ndarray, sim_sum: np.ndarray, linked: np.ndarray, weight_sum: np.ndarray) -> Dict[str, np.ndarray]:
+    """The per-list columns in QUALITY_COLUMNS order: n and linked_pairs as int64, the two ratios as float64."""
+    ils, _, nov = list_quality_figures(n, sim_sum, linked, weight_sum)
+    return {"n": np.asarray(n, dtype=np.int64), "intra_list_similarity": ils, "linked_pairs": np.asarray(linked, dtype=np.int64),
+            "novelty": nov}
