@@ -95,6 +95,47 @@ int rtrec_slim_list_quality(int32_t n_rows, int32_t n_items, const int32_t *d_wc
                             int32_t *d_out_n, float *d_out_sim_sum, int32_t *d_out_linked, float *d_out_weight_sum,
                             void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * CATALOGUE RANKS  (at which position of the whole catalogue does a held-out item stand: counts, no sort.)
+ * Row r brings a dense score vector d_scores[r * scores_stride + c], c in [0, n_items), scores_stride >= n_items (what lies
+ * beyond n_items is never read): float32, or float64 when scores_f64 != 0 -- the rows rtrec_slim_score_rows writes, the bits
+ * the top-k kernels rank by.  The interaction rows used for filtering are a CSR without values: d_row_ids[r] (NULL: row r)
+ * names the row of d_xb_ptr[n_x_rows + 1] / d_xb_col[xb_nnz], columns ascending inside a row as everywhere on this surface.
+ * The targets are a CSR over the rows: d_tg_ptr[n_rows + 1] (int64, non-decreasing; every offset is clamped to [0, n_tg])
+ * into d_tg_items[n_tg] (int32).  The targets of a row may come in any order and may repeat.
+ *   own          only when filter_interacted != 0: the columns stored in X's row, whatever their value, each once (an equal
+ *                neighbour is the same column); a row id outside [0, n_x_rows) gives the empty set; offsets are clamped to
+ *                [0, xb_nnz]; columns outside [0, n_items) are ignored
+ *   competes(c)  s[c] is not NaN, c is not in own, and mode == RTREC_TOPK_DENSE or s[c] != 0 (-0.0 counts as zero): the
+ *                competition rule of the top-k kernels for the same mode and filter_interacted
+ *   target t with item i, i in [0, n_items) and competes(i):
+ *                above[t] = the number of c != i with competes(c) and s[c] > s[i]
+ *                tied[t]  = the number of c != i with competes(c) and s[c] == s[i]   (+0.0 == -0.0; +-inf compare as numbers)
+ *                otherwise above[t] = -1 and tied[t] = 0: the item can never be listed.  The other targets of the row compete
+ *                like any column; a caller subtracts them where a metric wants that
+ *   score[t]     (double) s[i] when i is in range -- also for an item that does not compete -- else -inf
+ *   competing[r] the number of c with competes(c)
+ * CONSEQUENCE: with finite scores, tied == 0 and 0 <= above < K, the list of K entries the top-k kernels produce for the same
+ * row, mode and filter_interacted holds item i at position `above`; with ties it holds i somewhere in positions
+ * above .. above + tied (as far as the list reaches).
+ * Out, every slot written: d_out_above[n_tg], d_out_tied[n_tg] (int32), d_out_score[n_tg] (float64), d_out_competing[n_rows]
+ * (int32); a slot in front of d_tg_ptr[0] or behind d_tg_ptr[n_rows] gets -1 / 0 / -inf.  A d_tg_ptr that is not
+ * non-decreasing gives wrong answers, never an out-of-range access.
+ * mode other than RTREC_TOPK_SPARSE / RTREC_TOPK_DENSE: RTREC_ERR_UNSUPPORTED.  NULL required arrays (d_xb_* are required
+ * only with filter_interacted, the per-target arrays only with n_tg > 0), negative sizes and scores_stride < n_items:
+ * RTREC_ERR_INVALID_ARG.  n_rows == 0: RTREC_OK before any pointer check.  No global state, no environment variable, no
+ * allocation, no synchronisation.  The results never depend on the grid size, on the number of targets taken per sweep or on
+ * scheduling: they are integer counts and copies.
+ * csrc/catalogue_ranks.hip, catalogue_ranks_kernel: one row per workgroup of four waves (grid-stride beyond 2,048 workgroups);
+ * the row is swept once per group of up to 8 targets with 16-byte loads and integer counters in registers; own is taken back
+ * by walking the stored row; no atomics.
+ * ------------------------------------------------------------------------------------- */
+int rtrec_slim_catalogue_ranks(int32_t n_rows, int32_t n_items, const void *d_scores, int64_t scores_stride, int32_t scores_f64,
+                               const int32_t *d_row_ids, const int32_t *d_xb_ptr, const int32_t *d_xb_col, int32_t n_x_rows,
+                               int64_t xb_nnz, int32_t filter_interacted, int32_t mode, const int64_t *d_tg_ptr,
+                               const int32_t *d_tg_items, int64_t n_tg, int32_t *d_out_above, int32_t *d_out_tied,
+                               double *d_out_score, int32_t *d_out_competing, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,7 @@ EXPORTS = [
 EXT_EXPORTS = [
     "rtrec_slim_diversify_lists",
     "rtrec_slim_list_quality",
+    "rtrec_slim_catalogue_ranks",
 ]
 
 
@@ -217,6 +218,9 @@ def load() -> C.CDLL:
                                              vp, vp, vp, vp, vp]
     L.rtrec_slim_list_quality.restype = C.c_int
     L.rtrec_slim_list_quality.argtypes = [i32, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.rtrec_slim_catalogue_ranks.restype = C.c_int
+    L.rtrec_slim_catalogue_ranks.argtypes = [i32, i32, vp, C.c_int64, i32, vp, vp, vp, i32, C.c_int64, i32, i32, vp, vp, C.c_int64,
+                                             vp, vp, vp, vp, vp]
     _lib = L
     return L
 

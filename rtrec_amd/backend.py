@@ -294,6 +294,13 @@ class HipBackend:
         self.ops.list_quality(W["cptr"], W["crow"], W["cval"], n_items, ids, counts, list_k, item_weight, int(waves_per_row),
                               n, sim_sum, linked, weight_sum, exposure)
 
+    def catalogue_ranks(self, n_items, scores, row_ids, xb, filter_interacted, mode, tg_ptr, tg_items, above, tied, score, competing):
+        """Per target (row, item) of a dense score block: the competing columns above it and tied with it, its score, and per row
+        the competing columns (csrc/catalogue_ranks.hip; include/rtrec_amd_ext.h).  scores [n_rows, >= n_items] float32 or
+        float64, xb the (ptr, col, val) triple of X (val is not read), tg_ptr [n_rows + 1] int64 into tg_items int32."""
+        self.ops.catalogue_ranks(scores, n_items, row_ids, xb[0], xb[1], bool(filter_interacted), int(mode), tg_ptr, tg_items,
+                                 above, tied, score, competing)
+
     def audience_workspace_bytes(self, n_users, n_q, top_n):
         return int(self.lib.rtrec_slim_audience_workspace_bytes(n_users, n_q, top_n))
 

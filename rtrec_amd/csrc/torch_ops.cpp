@@ -53,6 +53,7 @@ struct Abi {
     decltype(&rtrec_slim_score_pairs) score_pairs = nullptr;
     decltype(&rtrec_slim_diversify_lists) diversify_lists = nullptr;          // include/rtrec_amd_ext.h
     decltype(&rtrec_slim_list_quality) list_quality = nullptr;
+    decltype(&rtrec_slim_catalogue_ranks) catalogue_ranks = nullptr;
 };
 Abi g_abi;
 
@@ -575,6 +576,44 @@ void list_quality(const at::Tensor &wc_ptr, const at::Tensor &wc_row, const at::
           "rtrec_slim_list_quality");
 }
 
+// scores [n_rows, >= n_items] float32 or float64 (the dtype selects the kernel); the rows of X used for filtering as a CSR without
+// values (row_ids: the row of X per score row, absent = row r); the targets as a CSR over the score rows: tg_ptr [n_rows + 1] int64
+// into tg_items int32; the outputs are above / tied [n_tg] int32, score [n_tg] float64, competing [n_rows] int32
+// (include/rtrec_amd_ext.h, "CATALOGUE RANKS").
+void catalogue_ranks(const at::Tensor &scores, int64_t n_items, const OT &row_ids, const at::Tensor &xb_ptr, const at::Tensor &xb_col,
+                     bool filter_interacted, int64_t mode, const at::Tensor &tg_ptr, const at::Tensor &tg_items, at::Tensor above,
+                     at::Tensor tied, at::Tensor score, at::Tensor competing) {
+    TORCH_CHECK(mode == RTREC_TOPK_SPARSE || mode == RTREC_TOPK_DENSE, "catalogue_ranks: mode must be 0 (SPARSE) or 1 (DENSE), got ", mode);
+    TORCH_CHECK(scores.dim() == 2, "catalogue_ranks: scores must be [n_rows, >= n_items]");
+    const int64_t rows = scores.size(0), n_tg = tg_items.numel();
+    TORCH_CHECK(rows <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, "catalogue_ranks: too many rows or items");
+    TORCH_CHECK(scores.size(1) >= n_items, "catalogue_ranks: scores must be [n_rows, >= n_items]");
+    TORCH_CHECK(scores.scalar_type() == at::kFloat || scores.scalar_type() == at::kDouble, "catalogue_ranks: scores must be float32 or float64, got ",
+                scores.scalar_type());
+    TORCH_CHECK(tg_ptr.numel() == rows + 1, "catalogue_ranks: tg_ptr must hold n_rows + 1 offsets");
+    TORCH_CHECK(above.numel() == n_tg && tied.numel() == n_tg && score.numel() == n_tg && competing.numel() == rows,
+                "catalogue_ranks: outputs must be above[n_tg], tied[n_tg], score[n_tg], competing[n_rows]");
+    TORCH_CHECK(xb_ptr.numel() >= 1 && xb_ptr.numel() - 1 <= INT32_MAX, "catalogue_ranks: xb_ptr must hold n_x_rows + 1 offsets");
+    const bool with_rows = row_ids.has_value() && row_ids->defined();
+    TORCH_CHECK(!with_rows || row_ids->numel() == rows, "catalogue_ranks: row_ids must hold one entry per row");
+    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
+    const bool f64 = scores.scalar_type() == at::kDouble;
+    if (f64) check_tensor<const double>(scores); else check_tensor<const float>(scores);
+    check_tensor<const int32_t>(xb_ptr); check_tensor<const int32_t>(xb_col);
+    check_tensor<const int64_t>(tg_ptr); check_tensor<const int32_t>(tg_items);
+    check_tensor<int32_t>(above); check_tensor<int32_t>(tied); check_tensor<double>(score); check_tensor<int32_t>(competing);
+    if (with_rows) check_tensor<const int32_t>(*row_ids);
+    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&xb_ptr, &xb_col, &tg_ptr, &tg_items, &above, &tied, &score, &competing})
+        TORCH_CHECK(t->device() == scores.device(), "catalogue_ranks: all tensors must live on one device");
+    TORCH_CHECK(!with_rows || row_ids->device() == scores.device(), "catalogue_ranks: all tensors must live on one device");
+    check(abi().catalogue_ranks(static_cast<int32_t>(rows), static_cast<int32_t>(n_items), ptr<const void>(scores), scores.size(1), f64 ? 1 : 0,
+                                ptr<const int32_t>(row_ids), ptr<const int32_t>(xb_ptr), ptr<const int32_t>(xb_col),
+                                static_cast<int32_t>(xb_ptr.numel() - 1), xb_col.numel(), filter_interacted ? 1 : 0, static_cast<int32_t>(mode),
+                                ptr<const int64_t>(tg_ptr), ptr<const int32_t>(tg_items), n_tg, ptr<int32_t>(above), ptr<int32_t>(tied),
+                                ptr<double>(score), ptr<int32_t>(competing), stream_of(competing)),
+          "rtrec_slim_catalogue_ranks");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -609,6 +648,7 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.score_pairs, "rtrec_slim_score_pairs");
         bind_one(h, a.diversify_lists, "rtrec_slim_diversify_lists");
         bind_one(h, a.list_quality, "rtrec_slim_list_quality");
+        bind_one(h, a.catalogue_ranks, "rtrec_slim_catalogue_ranks");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -678,6 +718,8 @@ TORCH_LIBRARY(rtrec_amd, m) {
           "int keep, float lam, int waves_per_row, Tensor(a!) order, Tensor(b!) value, Tensor(c!) penalty, Tensor(d!) count) -> ()");
     m.def("list_quality(Tensor wc_ptr, Tensor wc_row, Tensor wc_val, int n_items, Tensor ids, Tensor counts, int list_k, Tensor? item_weight, "
           "int waves_per_row, Tensor(a!) n, Tensor(b!) sim_sum, Tensor(c!) linked, Tensor(d!) weight_sum, Tensor(e!)? exposure) -> ()");
+    m.def("catalogue_ranks(Tensor scores, int n_items, Tensor? row_ids, Tensor xb_ptr, Tensor xb_col, bool filter_interacted, int mode, "
+          "Tensor tg_ptr, Tensor tg_items, Tensor(a!) above, Tensor(b!) tied, Tensor(c!) score, Tensor(d!) competing) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -705,4 +747,5 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("score_pairs", &score_pairs);
     m.impl("diversify_lists", &diversify_lists);
     m.impl("list_quality", &list_quality);
+    m.impl("catalogue_ranks", &catalogue_ranks);
 }

@@ -1562,6 +1562,8 @@ class SlimEngine:
         "recommend_users": ("an audience needs", "serve audiences", "audience scores are exact float32 sums"),
         "diversify": ("diversified lists need", "diversify", "similarities are W's float32 values"),
         "list_quality": ("list quality needs", "measure the lists", "similarities are W's float32 values"),
+        # (no third entry: the ranks are counted over the score rows this W gives, in float64 for a float64 W, whatever was uploaded)
+        "catalogue_ranks": ("catalogue ranks need", "rank", None),
     }
 
     def _whole_w(self, call: str) -> DeviceWeights:
@@ -1573,7 +1575,7 @@ class SlimEngine:
         if getattr(dw, "shard", None) is not None and self.world_size > 1:
             raise ValueError(f"{needs} the whole of W on this rank, and W is column-sharded (shard_w): "
                              f"gather it with gather_item_similarity() and {verb} from the gathered model")
-        if dw.lossy:
+        if dw.lossy and exact is not None:
             raise ValueError(f"{exact}; this W was uploaded from a float64 matrix whose values "
                              "are not float32 numbers (DeviceWeights.lossy)")
         return dw
@@ -1806,6 +1808,100 @@ class SlimEngine:
         d_exp = self.be.zeros((dw.n_items,), self.be.torch.int32) if with_exposure else None
         out = self.list_quality_device(self._up(item_ids), self._up(counts), d_w, d_exp, waves_per_row)
         return tuple(t.cpu().numpy() for t in out) + (d_exp.cpu().numpy() if with_exposure else None,)
+
+    # ------------------------------------------------------------------------------ catalogue ranks of held-out items
+    RANKS_BLOCK_BYTES = 1 << 30     # the dense score block of one pass of catalogue_ranks_rows
+
+    def _catalogue_layout(self) -> Optional[Dict[str, Any]]:
+        """The plain tiled layout over ALL columns of W, whatever this rank's column block is.  With one rank, or with
+        score_shard == "rows", that is _layout(compact=False); with several ranks and column shards every rank still holds the
+        whole W (_whole_w has refused a column-sharded one) but its score layouts cover [col_lo, col_hi) only, so a layout over
+        [0, n_items) is built for this call and cached beside the others.  None: W stores no weight."""
+        W = self._W
+        if W["col_lo"] == 0 and W["col_hi"] == W["n_items"]:
+            return self._layout(compact=False)
+        key = ("whole", self._tile_width(False, 10))
+        if key not in W["layouts"]:
+            dw: DeviceWeights = W["dw"]
+            W["layouts"][key] = (build_tiled_w_device(self.be.torch, dw.rows, dw.cols, dw.vals, W["n_items"], 0, W["n_items"], key[1],
+                                                      compact=False, dense_fill=None) if W["n_items"] > 0 else None)
+        return W["layouts"][key]
+
+    def catalogue_ranks_device(self, scores, d_rows, tg_ptr, tg_items, filter_interacted: bool, mode: int, xb=None):
+        """Device tensors (above[n_tg] int32, tied[n_tg] int32, score[n_tg] float64, competing[n_rows] int32) for the targets
+        `tg_ptr` [n_rows + 1] int64 / `tg_items` [n_tg] int32 of the dense score block `scores` [n_rows, >= W's n_items]
+        (float32 or float64, e.g. what score_rows left: it never leaves HBM); `d_rows` names the row of `xb` = (ptr, col, val)
+        device tensors (None: the resident X) each score row belongs to (None: row r).  The contract is the comment of
+        rtrec_slim_catalogue_ranks in include/rtrec_amd_ext.h."""
+        be, torch = self.be, self.be.torch
+        dw = self._whole_w("catalogue_ranks")
+        n_rows, n_tg = int(scores.shape[0]), int(tg_items.numel())
+        above = be.empty((n_tg,), torch.int32)
+        tied = be.empty((n_tg,), torch.int32)
+        score = be.empty((n_tg,), torch.float64)
+        competing = be.empty((n_rows,), torch.int32)
+        if n_rows == 0:
+            return above, tied, score, competing
+        if xb is None:
+            xb = self._x_csr()
+        be.catalogue_ranks(dw.n_items, scores, d_rows, xb, bool(filter_interacted), int(mode), tg_ptr, tg_items, above, tied,
+                           score, competing)
+        return above, tied, score, competing
+
+    def catalogue_ranks_rows(self, row_ids: Sequence[int], targets_ptr: np.ndarray, targets: np.ndarray,
+                             filter_interacted: bool = True, mode: int = 0, block_bytes: Optional[int] = None
+                             ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """At which position of the whole catalogue do the items `targets[targets_ptr[b] : targets_ptr[b + 1]]` stand for row
+        `row_ids[b]` of the resident X: numpy (above[n_tg] int32, tied[n_tg] int32, score[n_tg] float64, competing[B] int32),
+        the counts of rtrec_slim_catalogue_ranks (include/rtrec_amd_ext.h) over the score rows `recommend` ranks by.  Every
+        rank that holds the whole W answers locally, over all columns (_catalogue_layout): there is no collective.  The
+        rows are taken in passes whose dense score block [rows, n_items] (float64 when W accumulates in float64) stays within
+        `block_bytes` (default RANKS_BLOCK_BYTES; one row at least): score_rows fills the block from the plain layout, the
+        rank kernel reads it where it lies, and only the per-target and per-row results come back.  A row id outside the
+        matrix is a user without a row: every score is 0.  `mode` is _native.TOPK_SPARSE or TOPK_DENSE."""
+        be, torch = self.be, self.be.torch
+        dw = self._whole_w("catalogue_ranks")
+        if mode not in (_native.TOPK_SPARSE, _native.TOPK_DENSE):
+            raise ValueError(f"catalogue_ranks: mode must be TOPK_SPARSE or TOPK_DENSE, got {mode}")
+        row_ids = np.asarray(row_ids, dtype=np.int64)
+        tptr = np.asarray(targets_ptr, dtype=np.int64)
+        tgt = np.asarray(targets, dtype=np.int64)
+        B, n_tg = len(row_ids), len(tgt)
+        if tptr.shape != (B + 1,) or tptr[0] != 0 or tptr[-1] != n_tg or (np.diff(tptr) < 0).any():
+            raise ValueError("catalogue_ranks: targets_ptr must hold len(row_ids) + 1 non-decreasing offsets from 0 to len(targets)")
+        tgt32 = np.where((tgt >= 0) & (tgt < dw.n_items), tgt, -1).astype(np.int32)     # (an id beyond int32 is no column either)
+        above, tied = np.full(n_tg, -1, np.int32), np.zeros(n_tg, np.int32)
+        score, competing = np.full(n_tg, -np.inf, np.float64), np.zeros(B, np.int32)
+        if B == 0:
+            return above, tied, score, competing
+        if not self._X:
+            raise RuntimeError("set_interactions() must be called before catalogue_ranks_rows()")
+        W = self._W
+        f64 = bool(W["acc_f64"])
+        dt = torch.float64 if f64 else torch.float32
+        n_items = dw.n_items
+        lay = self._catalogue_layout()
+        row_bytes = max(n_items, 1) * (8 if f64 else 4)
+        per_pass = int(max(1, min(B, (self.RANKS_BLOCK_BYTES if block_bytes is None else int(block_bytes)) // row_bytes)))
+        rows32 = np.where((row_ids >= 0) & (row_ids < self.n_users), row_ids, -1).astype(np.int32)
+        xb = self._x_csr()
+        # The block is allocated zeroed once and reused by every pass without another memset: score_rows_kernel writes
+        # out[row, c] for EVERY column c < n_cols of every row it is given (it zeroes its LDS tile, accumulates, then stores the
+        # whole tile -- it never adds to what the buffer held), so nothing of the previous pass survives in the rows a pass
+        # uses, and the rank kernel reads no other row.  The zeros only matter for a W without a layout (no stored weight at
+        # all: no launch, every score 0), where they are never overwritten.
+        block = be.zeros((per_pass, max(n_items, 1)), dt)
+        for r0 in range(0, B, per_pass):
+            r1 = min(B, r0 + per_pass)
+            t0, t1 = int(tptr[r0]), int(tptr[r1])
+            d_rows = self._up(rows32[r0:r1])
+            sub = block[:r1 - r0]
+            if lay is not None:
+                be.score_rows(r1 - r0, d_rows, xb, W["n_items"], 0, lay, f64, sub)
+            out = self.catalogue_ranks_device(sub, d_rows, self._up(tptr[r0:r1 + 1] - t0), self._up(tgt32[t0:t1]), filter_interacted,
+                                              mode, xb)
+            above[t0:t1], tied[t0:t1], score[t0:t1], competing[r0:r1] = (t.cpu().numpy() for t in out)
+        return above, tied, score, competing
 
     # ------------------------------------------------------------------------------ audience of an item
     AUDIENCE_MAX_TOP_N = 1024   # top_n limit of rtrec_slim_audience_topk

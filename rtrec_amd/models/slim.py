@@ -670,6 +670,96 @@ class SLIM(BaseModel):
             scores[by_user], support[by_user] = sc[row, col], su[row, col]
         return (scores, support) if as_arrays else scores
 
+    # ------------------------------------------------------------ catalogue ranks (an extension: the reference has none)
+    def _catalogue_ranks(self, uid: np.ndarray, tg_ptr: np.ndarray, iid: np.ndarray, filter_interacted: bool):
+        """(above, tied, score, competing) of SlimEngine.catalogue_ranks_rows for the internal user ids `uid` (a user without a
+        row in X scores 0 everywhere) and internal item ids `iid` (-1: no column), in the mode `recommend` ranks this model by."""
+        from .._native import TOPK_DENSE, TOPK_SPARSE
+        mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+        self.model._sync_weights()
+        self.model.engine._whole_w("catalogue_ranks")     # a W that cannot be served is refused whatever the batch holds
+        if len(uid) == 0:
+            return np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.float64), np.empty(0, np.int32)
+        self._sync_interactions()
+        n_users = self.interactions.shape[0]
+        rows = np.where((uid >= 0) & (uid < n_users), uid, -1)
+        return self.model.engine.catalogue_ranks_rows(rows, tg_ptr, iid, filter_interacted, mode)
+
+    def rank_items_batch(self, users: List[Any], items: List[List[Any]], filter_interacted: bool = True,
+                         as_arrays: bool = False) -> Any:
+        """At which position of the WHOLE catalogue does each of `items[b]` (raw ids) stand for `users[b]`: the exact rank a
+        held-out item has, without a sort and without the score matrix leaving the device.  The user's score row is the one
+        `recommend` ranks by (float64 for a float64 W); csrc/catalogue_ranks.hip counts, per item, the competing items that
+        score higher (`above`) and the same (`tied`), and per user the competing items (`competing`).  An item competes as in
+        `recommend(filter_interacted=...)`: its score is not NaN, the user has not interacted with it (when filtering), and
+        -- for integer item ids, where `recommend` lists stored non-zero products only -- its score is not 0.  With no tie,
+        `recommend(user, top_k=K)` holds the item at position `above` whenever above < K; with ties it stands somewhere in
+        above .. above + tied.  An item that does not compete has above = -1, tied = 0 and can never be listed; its score is
+        still returned.  An item the model does not know (no column in W) has -1 / 0 / -inf; a cold-start user (nothing
+        `recommend` could rank) has -1 / 0 / -inf for every item and competing = 0.  The other items of the same list
+        compete like any item.
+
+        Returns one dict per user: {"items": the raw ids as given, "above": [...], "tied": [...], "score": [...],
+        "competing": n} -- or with `as_arrays=True` (ptr[B + 1] int64, above int32, tied int32, score float64, competing[B]
+        int32): user b's items are the slots ptr[b] .. ptr[b + 1], in the order given."""
+        if not self.model.is_fitted:
+            raise RuntimeError("Model must be fitted before calling rank_items_batch.")
+        arr = self._int_user_array(users)
+        users = arr if arr is not None else list(users)
+        lists = [c.tolist() if isinstance(c, np.ndarray) else list(c) for c in items]
+        B = len(users)
+        if len(lists) != B:
+            raise ValueError(f"items must hold one list per user: {len(lists)} lists for {B} users")
+        ptr = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum([len(c) for c in lists], out=ptr[1:])
+        flat = [x for c in lists for x in c]
+        iid = self._ids_or_minus_one(flat, self.item_ids.get_id, self.model.n_items_fitted)
+        uid, cold = self._user_rows(users)
+        iid = np.where(np.repeat(cold, np.diff(ptr)), -1, iid)             # a cold user's items are nobody's
+        above, tied, score, competing = self._catalogue_ranks(np.where(cold, -1, uid), ptr, iid, filter_interacted)
+        competing = np.where(cold, 0, competing).astype(np.int32)
+        if as_arrays:
+            return ptr, above, tied, score, competing
+        a, t, s, c = above.tolist(), tied.tolist(), score.tolist(), competing.tolist()
+        return [{"items": lists[b], "above": a[ptr[b]:ptr[b + 1]], "tied": t[ptr[b]:ptr[b + 1]], "score": s[ptr[b]:ptr[b + 1]],
+                 "competing": c[b]} for b in range(B)]
+
+    def rank_items(self, user: Any, items: List[Any], filter_interacted: bool = True) -> Dict[str, Any]:
+        """rank_items_batch for one user: {"items", "above", "tied", "score", "competing"}."""
+        return self.rank_items_batch([user], [list(items)], filter_interacted=filter_interacted)[0]
+
+    def _evaluate_catalogue(self, users: np.ndarray, items: np.ndarray, filter_interacted: bool):
+        """The device side of Recommender.evaluate_catalogue: (users evaluated, tg_ptr, above, tied, score, competing,
+        unknown_items, skipped_users).  Per user of the frame (sorted, missing keys dropped, as evaluate orders them) the
+        targets are the distinct held-out items with a column in W; frame rows whose item has none are counted in
+        unknown_items; users without a row in X or without a target left are counted in skipped_users and left out."""
+        from ..utils.metrics import _distinct, _missing, ground_truth_csr
+        if not self.model.is_fitted:
+            raise RuntimeError("Model must be fitted before calling evaluate_catalogue.")
+        n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
+
+        def user_index(values: np.ndarray) -> np.ndarray:
+            return self._ids_or_minus_one(values, self._known_user_id, n_users)
+
+        def item_index(values: np.ndarray) -> np.ndarray:
+            return self._ids_or_minus_one(values, self.item_ids.get_id, min(n_items, 2 ** 31 - 1))
+
+        users, items = np.asarray(users), np.asarray(items)
+        eval_users, rows, tptr, titems, _ = ground_truth_csr(users, items, user_index, item_index)
+        in_frame = ~_missing(users)
+        held = items[in_frame]
+        held = held[~_missing(held)]
+        distinct, pos = _distinct(held) if len(held) else (held, np.empty(0, np.int64))
+        known_rows = int((item_index(distinct)[pos] >= 0).sum()) if len(held) else 0
+        unknown_items = int(in_frame.sum()) - known_rows
+        keep = (rows >= 0) & (np.diff(tptr) > 0)
+        skipped = int((~keep).sum())
+        sel = np.repeat(keep, np.diff(tptr))
+        kept_ptr = np.zeros(int(keep.sum()) + 1, dtype=np.int64)
+        np.cumsum(np.diff(tptr)[keep], out=kept_ptr[1:])
+        above, tied, score, competing = self._catalogue_ranks(rows[keep], kept_ptr, titems[sel].astype(np.int64), filter_interacted)
+        return eval_users[keep], kept_ptr, above, tied, score, competing, unknown_items, skipped
+
     # ------------------------------------------------------------ diversified lists (an extension: the reference has none)
     DIVERSE_MAX_POOL = 1024     # list length rtrec_slim_diversify_lists re-ranks
 

@@ -10,14 +10,14 @@ from __future__ import annotations
 
 import math
 import time
-from typing import Any, Dict, Iterable, Iterator, List, Optional, Tuple
+from typing import Any, Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
 
 from .models.base import BaseModel
-from .utils.metrics import (METRIC_COLUMNS, RESULT_KEYS, _query_metrics, compute_scores, quality_frame_columns, quality_summary,
-                            scores_from_columns)
+from .utils.metrics import (CATALOGUE_KS, METRIC_COLUMNS, RESULT_KEYS, _query_metrics, catalogue_rank_summary, compute_scores,
+                            quality_frame_columns, quality_summary, scores_from_columns)
 
 _COLUMNS = ["user", "item", "tstamp", "rating"]
 _COLUMNAR_CHUNK = 1 << 22
@@ -171,6 +171,37 @@ class Recommender:
         """SLIM.recommend_quality: intra-list similarity, novelty and catalogue exposure of the lists these users would be served."""
         return self.model.recommend_quality(users, top_k=top_k, diversity=diversity, pool=pool, filter_interacted=filter_interacted,
                                             per_user=per_user)
+
+    def rank_items(self, user: Any, items: List[Any], filter_interacted: bool = True) -> Dict[str, Any]:
+        """An extension (the reference has none): where `items` stand in the whole catalogue for `user` -- SLIM.rank_items."""
+        return self.model.rank_items(user, items, filter_interacted=filter_interacted)
+
+    def rank_items_batch(self, users: List[Any], items: List[List[Any]], filter_interacted: bool = True,
+                         as_arrays: bool = False) -> Any:
+        """SLIM.rank_items_batch: the same for many users, each with its own items, in passes over the resident X."""
+        return self.model.rank_items_batch(users, items, filter_interacted=filter_interacted, as_arrays=as_arrays)
+
+    def evaluate_catalogue(self, test_data: pd.DataFrame, ks: Sequence[int] = CATALOGUE_KS, filter_interacted: bool = True,
+                           per_user: bool = False) -> Any:
+        """An extension (the reference has none): accuracy over the WHOLE catalogue instead of the first recommend_size <= 64
+        entries.  Every held-out (user, item) of test_data (columns user, item) gets its exact position among all the items
+        `recommend(filter_interacted=...)` could list for the user (SLIM.rank_items_batch, csrc/catalogue_ranks.hip: counts on
+        the device, no sort, no score matrix on the host), and utils.metrics.catalogue_rank_summary turns the positions into
+        recall@k / hit_rate@k / ndcg@k for every k of `ks` in one pass, mrr, the exact auc and mean_percentile_rank, with the
+        counts n_users, n_targets, tied_targets, never_listed, auc_users, unknown_items and skipped_users.  Per user the
+        targets are its distinct held-out items the model has a column for; others are dropped and counted in unknown_items;
+        users the model has no row for, or with no target left, are skipped and counted.  Ties are judged pessimistically (rank
+        = above + tied).  `per_user=True` returns `(dict, frame)`: the per-user figures indexed by user in evaluation order."""
+        hook = getattr(self.model, "_evaluate_catalogue", None)
+        if hook is None:
+            raise ValueError(f"evaluate_catalogue: {type(self.model).__name__} has no catalogue-rank hook")
+        users, tg_ptr, above, tied, score, competing, unknown, skipped = hook(test_data["user"].to_numpy(), test_data["item"].to_numpy(),
+                                                                              bool(filter_interacted))
+        summary, cols = catalogue_rank_summary(tg_ptr, above, tied, score, competing, ks=ks, unknown_items=unknown,
+                                               skipped_users=skipped)
+        if per_user:
+            return summary, pd.DataFrame(cols, index=pd.Index(users, name="user"))
+        return summary
 
     def similar_items(self, query_items: List[Any], query_item_tags: Optional[List[str]] = None, top_k: int = 10,
                       ret_scores: bool = False):

@@ -19,6 +19,9 @@ the GPU), POST /recommend (one user's top-k).  Differences, all forced by the de
   * POST /rerank is an addition (the second stage of a two-stage recommender: the caller brings the user's own candidates):
     {"user": ..., "items": [...], "top_k" or absent = the whole list, "filter_interacted"} -> {"user": ..., "items": [{"item": ...,
     "score": ...}, ...]} (SLIM.rerank); same token check as /recommend, answered under the model lock, not coalesced;
+  * POST /rank_items is an addition (where do these items stand in the whole catalogue for this user): {"user": ..., "items":
+    [...], "filter_interacted"} -> {"user": ..., "competing": n, "items": [{"item": ..., "above": ..., "tied": ..., "score": ... or
+    null where it is not finite}, ...]} (SLIM.rank_items); same token check as /rerank, answered under the model lock, not coalesced;
   * POST /recommend_diverse is an addition (a list that trades score against similarity to what is already on the page):
     {"user": ..., "top_k", "pool", "diversity", "filter_interacted"} -> {"user": ..., "items": [{"item": ..., "score": ...}, ...]}
     with the BASE scores (SLIM.recommend_diverse); same token check as /rerank, answered under the model lock, not coalesced;
@@ -82,6 +85,12 @@ class RerankRequest(BaseModel):
     items: List[Any]
     top_k: Optional[int] = None
     filter_interacted: bool = False
+
+
+class RankItemsRequest(BaseModel):
+    user: Any
+    items: List[Any]
+    filter_interacted: bool = True
 
 
 class DiverseRequest(BaseModel):
@@ -301,6 +310,15 @@ def build_router(gate: ModelGate) -> APIRouter:
         pairs = gate.call("Rerank", lambda m: m.rerank(request.user, request.items, top_k=request.top_k,
                                                        filter_interacted=request.filter_interacted, ret_scores=True))
         return {"user": request.user, "items": [{"item": i, "score": s} for i, s in pairs]}
+
+    @api.post("/rank_items")
+    def rank_items(request: RankItemsRequest, x_token: str = Header()):
+        _authorise(x_token)
+        out = gate.call("Rank items", lambda m: m.rank_items(request.user, request.items, filter_interacted=request.filter_interacted))
+        finite = lambda s: s if s == s and abs(s) != float("inf") else None          # (JSON has no inf / nan)
+        return {"user": request.user, "competing": out["competing"],
+                "items": [{"item": i, "above": a, "tied": t, "score": finite(s)}
+                          for i, a, t, s in zip(out["items"], out["above"], out["tied"], out["score"])]}
 
     @api.post("/recommend_diverse")
     def recommend_diverse(request: DiverseRequest, x_token: str = Header()):

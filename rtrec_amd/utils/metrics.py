@@ -274,3 +274,102 @@ def quality_frame_columns(n: np.ndarray, sim_sum: np.ndarray, linked: np.ndarray
     ils, _, nov = list_quality_figures(n, sim_sum, linked, weight_sum)
     return {"n": np.asarray(n, dtype=np.int64), "intra_list_similarity": ils, "linked_pairs": np.asarray(linked, dtype=np.int64),
             "novelty": nov}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Catalogue ranks (csrc/catalogue_ranks.hip): where the held-out items stand in the WHOLE catalogue.  The kernel returns, per
+# target, the competing columns above it and tied with it and its score, and per user the competing columns; everything below
+# is pure host arithmetic over them, in float64.
+
+CATALOGUE_KS = (1, 5, 10, 20, 50, 100)
+
+
+def catalogue_rank_summary(tg_ptr: np.ndarray, above: np.ndarray, tied: np.ndarray, score: np.ndarray, competing: np.ndarray,
+                           ks: Sequence[int] = CATALOGUE_KS, unknown_items: int = 0, skipped_users: int = 0
+                           ) -> Tuple[Dict[str, Any], Dict[str, np.ndarray]]:
+    """(summary, per-user columns) of the ranks of user u's targets tg_ptr[u] .. tg_ptr[u + 1] (distinct items): `above` / `tied`
+    / `score` per target and `competing` per user as rtrec_slim_catalogue_ranks defines them (include/rtrec_amd_ext.h).
+
+    A target with above == -1 can never be listed: it is a miss everywhere and counts in `never_listed`.  The integer rank
+    of a listed target is the pessimistic above + tied, 0-based.  Per user, with P = its targets and k in `ks`:
+        recall@k, hit_rate@k   the targets with rank < k, over P; whether there is one
+        ndcg@k                 the sum of 1 / log2(rank + 2) over them in rank order, over the same sum for ranks
+                               0 .. min(P, k) - 1 (utils.metrics.discount_tables)
+        mrr                    1 / (best rank + 1) over the whole catalogue, 0 without a listed target
+        auc                    mid-rank Mann-Whitney of the targets against the N = competing - listed targets negatives: a
+                               listed target has neg_above = above - (the listed targets scoring higher) negatives above it and
+                               neg_tied = tied - (the other listed targets scoring the same) tied with it, by the float64
+                               scores; it contributes N - neg_above - neg_tied / 2, a never-listed one 0; the sum over P * N.
+                               A user with N == 0 has no auc (NaN in the column) and is left out of the mean
+        mean_percentile_rank   per target (neg_above + neg_tied / 2) / N, 1.0 for a never-listed one, 0.0 for a listed one
+                               with N == 0: the share of the negatives that stand above it
+    The summary holds the math.fsum means over the users in row order (auc over its `auc_users`; mean_percentile_rank over all
+    `n_targets` targets), NaN over nothing, and the counts n_users, n_targets, tied_targets (listed, tied > 0), never_listed,
+    auc_users, unknown_items and skipped_users -- the last two are the caller's, plus the rows that bring no target here."""
+    tg_ptr = np.asarray(tg_ptr, dtype=np.int64)
+    above, tied = np.asarray(above, dtype=np.int64), np.asarray(tied, dtype=np.int64)
+    score, competing = np.asarray(score, dtype=np.float64), np.asarray(competing, dtype=np.int64)
+    ks = [int(k) for k in ks]
+    if any(k < 1 for k in ks):
+        raise ValueError(f"catalogue_rank_summary: every k must be at least 1, got {ks}")
+    n_rows = len(tg_ptr) - 1
+    P_all = np.diff(tg_ptr)
+    keep = P_all > 0
+    skipped_users = int(skipped_users) + int((~keep).sum())
+    n, n_tg = int(keep.sum()), int(P_all.sum())
+    u = np.repeat(np.cumsum(keep) - 1, P_all)                      # the kept user of every target
+    P, comp = P_all[keep], competing[keep]
+    above, tied, score = above[tg_ptr[0]:tg_ptr[-1]], tied[tg_ptr[0]:tg_ptr[-1]], score[tg_ptr[0]:tg_ptr[-1]]
+    listed = above >= 0
+    rank = np.where(listed, above + tied, np.iinfo(np.int64).max)
+    n_listed = np.bincount(u[listed], minlength=n)
+    N = comp - n_listed
+    # the listed targets scoring higher than / the same as each listed target, inside its user: one sort by (user, score desc)
+    pos_above, pos_tied = np.zeros(n_tg, np.int64), np.zeros(n_tg, np.int64)
+    li = np.flatnonzero(listed)
+    if len(li):
+        order = li[np.lexsort((-score[li], u[li]))]
+        su, ss = u[order], score[order]
+        new_user = np.r_[True, su[1:] != su[:-1]]
+        new_run = new_user | np.r_[True, ss[1:] != ss[:-1]]
+        idx = np.arange(len(order))
+        run_start = np.maximum.accumulate(np.where(new_run, idx, 0))
+        user_start = np.maximum.accumulate(np.where(new_user, idx, 0))
+        run_len = np.bincount(np.cumsum(new_run) - 1)[np.cumsum(new_run) - 1]
+        pos_above[order], pos_tied[order] = run_start - user_start, run_len - 1
+    neg_above, neg_tied = above - pos_above, tied - pos_tied
+    Nt = N[u].astype(np.float64)
+    mid = neg_above + 0.5 * neg_tied
+    with np.errstate(invalid="ignore", divide="ignore"):
+        pct = np.where(listed, np.where(Nt > 0, mid / Nt, 0.0), 1.0)
+        wins = np.where(listed, Nt - mid, 0.0)
+        auc_user = np.bincount(u, weights=wins, minlength=n) / (P * N.astype(np.float64))
+    auc_user = np.where(N > 0, auc_user, np.nan)
+    best = np.full(n, np.iinfo(np.int64).max)
+    np.minimum.at(best, u, rank)
+    has = n_listed > 0
+    cols: Dict[str, np.ndarray] = {"n_targets": P, "never_listed": P - n_listed, "competing": comp,
+                                   "best_rank": np.where(has, best, -1),
+                                   "mrr": np.where(has, 1.0 / (np.where(has, best, 0) + 1.0), 0.0), "auc": auc_user,
+                                   "mean_percentile_rank": np.bincount(u, weights=pct, minlength=n) / np.maximum(P, 1)}
+    by_rank = np.lexsort((rank, u))                                 # dcg adds its terms in rank order, like _query_metrics
+    for k in ks:
+        _, ideal = discount_tables(k)
+        hit = rank < k
+        tp = np.bincount(u[hit], minlength=n)
+        sel = by_rank[hit[by_rank]]
+        dcg = np.bincount(u[sel], weights=1.0 / np.log2(rank[sel] + 2.0), minlength=n)
+        cols[f"recall@{k}"] = tp / np.maximum(P, 1)
+        cols[f"hit_rate@{k}"] = (tp > 0).astype(np.float64)
+        cols[f"ndcg@{k}"] = dcg / ideal[np.minimum(P, k)] if n else dcg
+    out: Dict[str, Any] = {}
+    for k in ks:
+        for name in (f"recall@{k}", f"hit_rate@{k}", f"ndcg@{k}"):
+            out[name] = fsum_mean(cols[name])
+    out["mrr"] = fsum_mean(cols["mrr"])
+    out["auc"] = fsum_mean(auc_user[N > 0])
+    out["mean_percentile_rank"] = fsum_mean(pct)
+    out.update({"n_users": n, "n_targets": n_tg, "tied_targets": int((listed & (tied > 0)).sum()),
+                "never_listed": int((~listed).sum()), "auc_users": int((N > 0).sum()), "unknown_items": int(unknown_items),
+                "skipped_users": skipped_users})
+    return out, cols
