@@ -136,6 +136,61 @@ int rtrec_slim_catalogue_ranks(int32_t n_rows, int32_t n_items, const void *d_sc
                                const int32_t *d_tg_items, int64_t n_tg, int32_t *d_out_above, int32_t *d_out_tied,
                                double *d_out_score, int32_t *d_out_competing, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * BLENDED LISTS  (the union of two per-row lists by item id: each min-max normalised, the second weighted per item, re-ranked.)
+ * The reference's hybrid model merges SLIM's list with a second scorer's in Python, one user at a time over dicts
+ * (HybridSlimFM._ensemble_by_scores); this call takes both lists where they lie.  List A is the other scorer's, list B SLIM's;
+ * both arrive best first.  Row r brings ka positions of A (1..1024): item ids d_a_ids[r * a_ids_stride + p] and float32 scores
+ * d_a_scores[r * a_scores_stride + p] (both strides >= ka), valid up to d_a_counts[r] (clamped to [0, ka]); and kb positions of
+ * B in the same form.  With weight_mode == RTREC_BLEND_CONTACTS the row of the interaction matrix behind list r is
+ * d_row_ids[r] (NULL: row r) of the CSR without values d_xb_ptr[n_x_rows + 1] / d_xb_col[xb_nnz], and the optional count CSR
+ * d_cn_ptr[n_x_rows + 1] / d_cn_col[cn_nnz] / d_cn_val[cn_nnz] (all int32; d_cn_ptr may be NULL) stores how often a user
+ * touched an item; columns ascend inside a row in both.  Offsets are clamped to [0, xb_nnz] / [0, cn_nnz], so a malformed CSR
+ * gives wrong answers, never an out-of-range read.  With RTREC_BLEND_CONSTANT none of d_row_ids, d_xb_*, d_cn_* is read.
+ *   length      a list is cut at its first position that lies behind its count, whose id is outside [0, n_items), or whose
+ *               score is not finite or is <= -FLT_MAX (the reference's cut for what its top-k filtered out).  na and nb are
+ *               what remains; an empty list contributes nothing
+ *   norm        per non-empty list over its effective positions: mn / mx = the least / largest score,
+ *               den = fl(fl(mx - mn) + 1e-8f), norm[p] = fl(fl(s[p] - mn) / den); the division is correctly rounded IEEE, float32
+ *               denormals are kept.  A list whose scores are all equal normalises to zeros; mx - mn may overflow (norm is then 0
+ *               or NaN by IEEE rules)
+ *   weight      of a B position with item i.  RTREC_BLEND_CONSTANT: w = weight_b.  RTREC_BLEND_CONTACTS: n = the count stored for
+ *               (row, i) in the count CSR (the first of equal columns); if the pair is not stored there -- or d_cn_ptr is NULL --
+ *               n = 1 if X's row stores i, else 0; w = (float)((2.0 * (double)n) / ((double)n + k)), float64 left to right,
+ *               rounded once to float32; n <= 0 gives +0.0f.  A row id outside [0, n_x_rows) is an empty row: every w is 0
+ *   union       the entries stand in this order: first the distinct ids of A in order of first appearance -- an id repeated
+ *               inside A stands at its first position and carries the normalised score of its LAST one (the reference's
+ *               dict(zip(ids, scores))) -- then the ids only B holds, in order of first appearance in B, each starting from +0.0f.
+ *               Then for q = 0 .. nb-1 ascending: term = fl(w * normB[q]) and the value of the entry of B's id at q becomes
+ *               fl(value + term): separately rounded, never fused; an id repeated inside B adds once per occurrence
+ *   mnz         mnz != 0: the value of an entry that stands in both lists is doubled once at the end (CombMNZ on the normalised
+ *               scores; mnz == 0 is the reference's hybrid, the plain sum)
+ *   order       an entry beats another if its value is larger, or the values are == (-0.0 == +0.0) and it stands earlier in the
+ *               union: a stable descending sort.  An entry whose value is NaN is never listed
+ * Out, every slot written: d_out_ids[n_rows][keep] item ids, d_out_value[n_rows][keep] their values (float32; the sign of a zero
+ * is not part of the contract), d_out_source[n_rows][keep] (int32: 1 = only A holds the item, 2 = only B, 3 = both),
+ * d_out_count[r] the number listed = min(keep, the entries whose value is a number); behind it -1 / -inf / 0.
+ * ka and kb in 1..1024, keep in 1..ka+kb, waves_per_row in {0, 1, 4} (1 or 4 waves of 64 threads per row, 0 = chosen by the
+ * library, by the rule of rtrec_slim_score_pairs on the longer list) and weight_mode one of the two above: RTREC_ERR_UNSUPPORTED
+ * otherwise.  NULL required arrays (d_xb_* only with RTREC_BLEND_CONTACTS; d_cn_col / d_cn_val only with a d_cn_ptr and
+ * cn_nnz > 0), negative sizes, a stride below its list length, and a weight_b or k that is negative or NaN:
+ * RTREC_ERR_INVALID_ARG.  n_rows == 0: RTREC_OK before any pointer check.  No global state, no environment variable, no
+ * allocation, no synchronisation.  The results never depend on waves_per_row, on the grid size or on scheduling.
+ * csrc/blend.hip, blend_lists_kernel: one row per workgroup; both lists, their normalised values and the union (up to 2,048
+ * entries) in LDS; lengths and extremes by a reduction; every position looks for its id at the other positions, the owner of an
+ * entry adds its B terms in ascending q (two binary searches per entry of B for the contacts); ranks by counting; no atomics.
+ * ------------------------------------------------------------------------------------- */
+#define RTREC_BLEND_CONSTANT 0
+#define RTREC_BLEND_CONTACTS 1
+int rtrec_slim_blend_lists(int32_t n_rows, int32_t n_items, const int32_t *d_a_ids, int64_t a_ids_stride, const float *d_a_scores,
+                           int64_t a_scores_stride, const int32_t *d_a_counts, int32_t ka, const int32_t *d_b_ids,
+                           int64_t b_ids_stride, const float *d_b_scores, int64_t b_scores_stride, const int32_t *d_b_counts,
+                           int32_t kb, int32_t keep, float weight_b, int32_t weight_mode, double k, int32_t mnz,
+                           const int32_t *d_row_ids, const int32_t *d_xb_ptr, const int32_t *d_xb_col, int32_t n_x_rows,
+                           int64_t xb_nnz, const int32_t *d_cn_ptr, const int32_t *d_cn_col, const int32_t *d_cn_val,
+                           int64_t cn_nnz, int32_t waves_per_row, int32_t *d_out_ids, float *d_out_value, int32_t *d_out_source,
+                           int32_t *d_out_count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ _lib: Optional[C.CDLL] = None
 
 RTREC_OK = 0
 TOPK_SPARSE, TOPK_DENSE, TOPK_CANDIDATES = 0, 1, 2
+BLEND_CONSTANT, BLEND_CONTACTS = 0, 1      # weight_mode of rtrec_slim_blend_lists (include/rtrec_amd_ext.h)
 _STATUS = {0: "ok", -1: "invalid argument", -2: "unsupported parameter", -3: "workspace too small",
            -4: "kernel launch failed"}
 
@@ -51,6 +52,7 @@ EXT_EXPORTS = [
     "rtrec_slim_diversify_lists",
     "rtrec_slim_list_quality",
     "rtrec_slim_catalogue_ranks",
+    "rtrec_slim_blend_lists",
 ]
 
 
@@ -221,6 +223,10 @@ def load() -> C.CDLL:
     L.rtrec_slim_catalogue_ranks.restype = C.c_int
     L.rtrec_slim_catalogue_ranks.argtypes = [i32, i32, vp, C.c_int64, i32, vp, vp, vp, i32, C.c_int64, i32, i32, vp, vp, C.c_int64,
                                              vp, vp, vp, vp, vp]
+    L.rtrec_slim_blend_lists.restype = C.c_int
+    L.rtrec_slim_blend_lists.argtypes = [i32, i32, vp, C.c_int64, vp, C.c_int64, vp, i32, vp, C.c_int64, vp, C.c_int64, vp, i32, i32,
+                                         C.c_float, i32, C.c_double, i32, vp, vp, vp, i32, C.c_int64, vp, vp, vp, C.c_int64, i32,
+                                         vp, vp, vp, vp, vp]
     _lib = L
     return L
 

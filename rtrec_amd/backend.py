@@ -301,6 +301,19 @@ class HipBackend:
         self.ops.catalogue_ranks(scores, n_items, row_ids, xb[0], xb[1], bool(filter_interacted), int(mode), tg_ptr, tg_items,
                                  above, tied, score, competing)
 
+    def blend_lists(self, n_items, a_ids, a_scores, a_counts, ka, b_ids, b_scores, b_counts, kb, keep, weight_b, contacts, k, mnz,
+                    row_ids, xb, cn, out_ids, value, source, count, waves_per_row=0):
+        """Per row: the union of list A and list B by item id, each min-max normalised, B weighted by `weight_b` or -- with
+        `contacts` -- by how often the row's user touched the item, ranked by the summed value (csrc/blend.hip;
+        include/rtrec_amd_ext.h).  a_* / b_* [n_rows, >= ka / kb] and [n_rows]; xb the (ptr, col, val) triple of X (val is not
+        read) and cn the (ptr, col, val) int32 triple of the count CSR, each or both None; the outputs [n_rows, keep] and
+        [n_rows]."""
+        xb = (None, None) if xb is None else xb
+        cn = (None, None, None) if cn is None else cn
+        self.ops.blend_lists(n_items, a_ids, a_scores, a_counts, ka, b_ids, b_scores, b_counts, kb, keep, float(weight_b),
+                             bool(contacts), float(k), bool(mnz), row_ids, xb[0], xb[1], cn[0], cn[1], cn[2], int(waves_per_row),
+                             out_ids, value, source, count)
+
     def audience_workspace_bytes(self, n_users, n_q, top_n):
         return int(self.lib.rtrec_slim_audience_workspace_bytes(n_users, n_q, top_n))
 

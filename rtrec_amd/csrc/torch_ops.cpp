@@ -54,6 +54,7 @@ struct Abi {
     decltype(&rtrec_slim_diversify_lists) diversify_lists = nullptr;          // include/rtrec_amd_ext.h
     decltype(&rtrec_slim_list_quality) list_quality = nullptr;
     decltype(&rtrec_slim_catalogue_ranks) catalogue_ranks = nullptr;
+    decltype(&rtrec_slim_blend_lists) blend_lists = nullptr;
 };
 Abi g_abi;
 
@@ -614,6 +615,67 @@ void catalogue_ranks(const at::Tensor &scores, int64_t n_items, const OT &row_id
           "rtrec_slim_catalogue_ranks");
 }
 
+// a_ids / a_scores [n_rows, >= ka] / a_counts [n_rows] and the same for b: two lists of item ids and scores per row; with
+// `contacts` the rows of X as a CSR without values (row_ids: the row of X per list row, absent = row r) and, optionally, the count
+// CSR cn_* (int32) over the same rows; the outputs are ids / value / source [n_rows, keep] and count [n_rows]
+// (include/rtrec_amd_ext.h, "BLENDED LISTS").
+void blend_lists(int64_t n_items, const at::Tensor &a_ids, const at::Tensor &a_scores, const at::Tensor &a_counts, int64_t ka,
+                 const at::Tensor &b_ids, const at::Tensor &b_scores, const at::Tensor &b_counts, int64_t kb, int64_t keep, double weight_b,
+                 bool contacts, double k, bool mnz, const OT &row_ids, const OT &xb_ptr, const OT &xb_col, const OT &cn_ptr, const OT &cn_col,
+                 const OT &cn_val, int64_t waves_per_row, at::Tensor ids, at::Tensor value, at::Tensor source, at::Tensor count) {
+    TORCH_CHECK(ka >= 1 && ka <= 1024 && kb >= 1 && kb <= 1024, "blend_lists: ka and kb must lie in 1..1024, got ", ka, " and ", kb);
+    TORCH_CHECK(keep >= 1 && keep <= ka + kb, "blend_lists: keep must lie in 1..ka+kb, got ", keep);
+    TORCH_CHECK(weight_b >= 0.0 && k >= 0.0, "blend_lists: weight_b and k must lie in [0, inf], got ", weight_b, " and ", k);
+    TORCH_CHECK(waves_per_row == 0 || waves_per_row == 1 || waves_per_row == 4, "blend_lists: waves_per_row must be 0, 1 or 4, got ", waves_per_row);
+    TORCH_CHECK(a_ids.dim() == 2 && a_ids.size(1) >= ka, "blend_lists: a_ids must be [n_rows, >= ka]");
+    const int64_t rows = a_ids.size(0);
+    TORCH_CHECK(a_scores.dim() == 2 && a_scores.size(0) == rows && a_scores.size(1) >= ka, "blend_lists: a_scores must be [n_rows, >= ka]");
+    TORCH_CHECK(b_ids.dim() == 2 && b_ids.size(0) == rows && b_ids.size(1) >= kb, "blend_lists: b_ids must be [n_rows, >= kb]");
+    TORCH_CHECK(b_scores.dim() == 2 && b_scores.size(0) == rows && b_scores.size(1) >= kb, "blend_lists: b_scores must be [n_rows, >= kb]");
+    TORCH_CHECK(rows <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, "blend_lists: too many rows or items");
+    TORCH_CHECK(a_counts.numel() == rows && b_counts.numel() == rows, "blend_lists: a_counts and b_counts must hold one entry per row");
+    TORCH_CHECK(ids.numel() == rows * keep && value.numel() == rows * keep && source.numel() == rows * keep && count.numel() == rows,
+                "blend_lists: outputs must be ids[n_rows, keep], value[same], source[same], count[n_rows]");
+    const auto has = [](const OT &t) { return t.has_value() && t->defined(); };
+    int64_t n_x_rows = 0, xb_nnz = 0, cn_nnz = 0;
+    if (contacts) {
+        TORCH_CHECK(has(xb_ptr) && has(xb_col), "blend_lists: contacts need xb_ptr and xb_col");
+        TORCH_CHECK(xb_ptr->numel() >= 1 && xb_ptr->numel() - 1 <= INT32_MAX, "blend_lists: xb_ptr must hold n_x_rows + 1 offsets");
+        n_x_rows = xb_ptr->numel() - 1;
+        xb_nnz = xb_col->numel();
+        TORCH_CHECK(!has(row_ids) || row_ids->numel() == rows, "blend_lists: row_ids must hold one entry per row");
+        check_tensor<const int32_t>(*xb_ptr); check_tensor<const int32_t>(*xb_col);
+        if (has(row_ids)) check_tensor<const int32_t>(*row_ids);
+        if (has(cn_ptr)) {
+            TORCH_CHECK(has(cn_col) && has(cn_val), "blend_lists: cn_ptr comes with cn_col and cn_val");
+            TORCH_CHECK(cn_ptr->numel() == n_x_rows + 1, "blend_lists: cn_ptr must hold n_x_rows + 1 offsets");
+            TORCH_CHECK(cn_col->numel() == cn_val->numel(), "blend_lists: cn_col and cn_val must have one length");
+            cn_nnz = cn_col->numel();
+            check_tensor<const int32_t>(*cn_ptr); check_tensor<const int32_t>(*cn_col); check_tensor<const int32_t>(*cn_val);
+        }
+        for (const OT *t : std::initializer_list<const OT *>{&row_ids, &xb_ptr, &xb_col, &cn_ptr, &cn_col, &cn_val})
+            TORCH_CHECK(!has(*t) || (*t)->device() == a_ids.device(), "blend_lists: all tensors must live on one device");
+    }
+    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
+    check_tensor<const int32_t>(a_ids); check_tensor<const float>(a_scores); check_tensor<const int32_t>(a_counts);
+    check_tensor<const int32_t>(b_ids); check_tensor<const float>(b_scores); check_tensor<const int32_t>(b_counts);
+    check_tensor<int32_t>(ids); check_tensor<float>(value); check_tensor<int32_t>(source); check_tensor<int32_t>(count);
+    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&a_scores, &a_counts, &b_ids, &b_scores, &b_counts, &ids, &value, &source, &count})
+        TORCH_CHECK(t->device() == a_ids.device(), "blend_lists: all tensors must live on one device");
+    const bool counted = contacts && has(cn_ptr);
+    check(abi().blend_lists(static_cast<int32_t>(rows), static_cast<int32_t>(n_items), ptr<const int32_t>(a_ids), a_ids.size(1),
+                            ptr<const float>(a_scores), a_scores.size(1), ptr<const int32_t>(a_counts), static_cast<int32_t>(ka),
+                            ptr<const int32_t>(b_ids), b_ids.size(1), ptr<const float>(b_scores), b_scores.size(1), ptr<const int32_t>(b_counts),
+                            static_cast<int32_t>(kb), static_cast<int32_t>(keep), static_cast<float>(weight_b),
+                            contacts ? RTREC_BLEND_CONTACTS : RTREC_BLEND_CONSTANT, k, mnz ? 1 : 0,
+                            contacts ? ptr<const int32_t>(row_ids) : nullptr, contacts ? ptr<const int32_t>(xb_ptr) : nullptr,
+                            contacts ? ptr<const int32_t>(xb_col) : nullptr, static_cast<int32_t>(n_x_rows), xb_nnz,
+                            counted ? ptr<const int32_t>(cn_ptr) : nullptr, counted ? ptr<const int32_t>(cn_col) : nullptr,
+                            counted ? ptr<const int32_t>(cn_val) : nullptr, cn_nnz, static_cast<int32_t>(waves_per_row), ptr<int32_t>(ids),
+                            ptr<float>(value), ptr<int32_t>(source), ptr<int32_t>(count), stream_of(count)),
+          "rtrec_slim_blend_lists");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -649,6 +711,7 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.diversify_lists, "rtrec_slim_diversify_lists");
         bind_one(h, a.list_quality, "rtrec_slim_list_quality");
         bind_one(h, a.catalogue_ranks, "rtrec_slim_catalogue_ranks");
+        bind_one(h, a.blend_lists, "rtrec_slim_blend_lists");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -720,6 +783,10 @@ TORCH_LIBRARY(rtrec_amd, m) {
           "int waves_per_row, Tensor(a!) n, Tensor(b!) sim_sum, Tensor(c!) linked, Tensor(d!) weight_sum, Tensor(e!)? exposure) -> ()");
     m.def("catalogue_ranks(Tensor scores, int n_items, Tensor? row_ids, Tensor xb_ptr, Tensor xb_col, bool filter_interacted, int mode, "
           "Tensor tg_ptr, Tensor tg_items, Tensor(a!) above, Tensor(b!) tied, Tensor(c!) score, Tensor(d!) competing) -> ()");
+    m.def("blend_lists(int n_items, Tensor a_ids, Tensor a_scores, Tensor a_counts, int ka, Tensor b_ids, Tensor b_scores, Tensor b_counts, "
+          "int kb, int keep, float weight_b, bool contacts, float k, bool mnz, Tensor? row_ids, Tensor? xb_ptr, Tensor? xb_col, "
+          "Tensor? cn_ptr, Tensor? cn_col, Tensor? cn_val, int waves_per_row, Tensor(a!) ids, Tensor(b!) value, Tensor(c!) source, "
+          "Tensor(d!) count) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -748,4 +815,5 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("diversify_lists", &diversify_lists);
     m.impl("list_quality", &list_quality);
     m.impl("catalogue_ranks", &catalogue_ranks);
+    m.impl("blend_lists", &blend_lists);
 }

@@ -1564,6 +1564,7 @@ class SlimEngine:
         "list_quality": ("list quality needs", "measure the lists", "similarities are W's float32 values"),
         # (no third entry: the ranks are counted over the score rows this W gives, in float64 for a float64 W, whatever was uploaded)
         "catalogue_ranks": ("catalogue ranks need", "rank", None),
+        "blend": ("blended lists need", "blend", "SLIM's side of a blend is its float32 scores"),
     }
 
     def _whole_w(self, call: str) -> DeviceWeights:
@@ -1808,6 +1809,94 @@ class SlimEngine:
         d_exp = self.be.zeros((dw.n_items,), self.be.torch.int32) if with_exposure else None
         out = self.list_quality_device(self._up(item_ids), self._up(counts), d_w, d_exp, waves_per_row)
         return tuple(t.cpu().numpy() for t in out) + (d_exp.cpu().numpy() if with_exposure else None,)
+
+    # ------------------------------------------------------------------------------ blended lists (two lists per row, one union)
+    BLEND_MAX_LIST = 1024       # ka / kb limit of rtrec_slim_blend_lists
+
+    def blend_device(self, a_ids, a_scores, a_counts, b_ids, b_scores, b_counts, keep: int, weight_b: float = 1.0,
+                     contacts: bool = False, k: float = 2.0, mnz: bool = False, d_rows=None, xb=None, cn=None,
+                     waves_per_row: int = 0):
+        """Device tensors (ids[n_rows, keep] int32, value[n_rows, keep] float32, source[n_rows, keep] int32, count[n_rows] int32)
+        for the union of the lists A = `a_ids` [n_rows, ka] int32 / `a_scores` [n_rows, ka] float32 / `a_counts` [n_rows] int32
+        (another scorer's) and B in the same form (SLIM's, e.g. what score_topk_device returned: it never leaves HBM): each list
+        min-max normalised in float32, B's part weighted by `weight_b` or -- with `contacts` -- by (float32)(2 n / (n + k)) with n
+        the contacts of the row's user with the item, added into the union by item id, ranked by value with the earlier entry
+        first among equal values; `mnz` doubles what stands in both lists.  source is 1 (only A), 2 (only B) or 3; -1 / -inf / 0
+        stand behind count.  With `contacts`, `d_rows` (int32 device tensor, None = rows 0 .. n_rows-1) names the row of
+        `xb` = (ptr, col, val) device tensors (None: the resident X) behind each list, and `cn` = (ptr, col, val) int32 device
+        tensors (or None) is the count CSR over the same rows: a stored count wins, otherwise n is 1 for an item the row stores
+        and 0 for any other.  The contract is the comment of rtrec_slim_blend_lists in include/rtrec_amd_ext.h.  W is not read
+        (only its width, the catalogue): every rank answers locally."""
+        be, torch = self.be, self.be.torch
+        if not self._W:
+            raise RuntimeError("Model must be fitted before calling blend.")
+        n_items = int(self._W["n_items"])
+        n_rows, ka, kb, keep = int(a_ids.shape[0]), int(a_ids.shape[-1]), int(b_ids.shape[-1]), int(keep)
+        if a_ids.dim() != 2 or b_ids.dim() != 2 or not 1 <= ka <= self.BLEND_MAX_LIST or not 1 <= kb <= self.BLEND_MAX_LIST:
+            raise ValueError(f"blend: two lists of 1..{self.BLEND_MAX_LIST} items per row are supported, got {ka} and {kb}")
+        if not 1 <= keep <= ka + kb:
+            raise ValueError(f"blend: keep must lie in 1..{ka + kb} (both list lengths together), got {keep}")
+        if not float(weight_b) >= 0.0 or not float(k) >= 0.0:                # (a NaN fails the compare)
+            raise ValueError(f"blend: the weight and k must not be negative or NaN, got {weight_b} and {k}")
+        if (tuple(a_scores.shape) != (n_rows, ka) or tuple(b_ids.shape) != (n_rows, kb) or tuple(b_scores.shape) != (n_rows, kb)
+                or int(a_counts.numel()) != n_rows or int(b_counts.numel()) != n_rows):
+            raise ValueError("blend: scores must have the shape of their ids, both lists one row per row, counts one entry per row")
+        ids = be.empty((n_rows, keep), torch.int32)
+        value = be.empty((n_rows, keep), torch.float32)
+        source = be.empty((n_rows, keep), torch.int32)
+        count = be.zeros((n_rows,), torch.int32)
+        if n_rows == 0:
+            return ids, value, source, count
+        if contacts and xb is None:
+            if not self._X:
+                raise RuntimeError("set_interactions() must be called before blend with contacts")
+            xb = self._x_csr()
+        be.blend_lists(n_items, a_ids.contiguous(), a_scores.contiguous(), a_counts.contiguous(), ka, b_ids.contiguous(),
+                       b_scores.contiguous(), b_counts.contiguous(), kb, keep, float(weight_b), bool(contacts), float(k), bool(mnz),
+                       d_rows if contacts else None, xb if contacts else None, cn if contacts else None, ids, value, source, count,
+                       waves_per_row=waves_per_row)
+        return ids, value, source, count
+
+    def blend_lists(self, a_ids: np.ndarray, a_scores: np.ndarray, b_ids: np.ndarray, b_scores: np.ndarray,
+                    a_counts: Optional[np.ndarray] = None, b_counts: Optional[np.ndarray] = None, keep: int = 10, weight_b: float = 1.0,
+                    mnz: bool = False, row_ids: Optional[Sequence[int]] = None, contact_counts: Optional[sp.csr_matrix] = None,
+                    k: float = 2.0, waves_per_row: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """blend_device for lists the caller brings: numpy (ids[B, keep], value, source, count[B]) for `a_ids` [B, ka] /
+        `a_scores` and `b_ids` [B, kb] / `b_scores` (a position with -1, an id outside the catalogue or a non-finite score ends its
+        list); counts default to the widths.  `row_ids` given: B is weighted by the contacts of those rows of the resident X
+        (a row outside the matrix has none), with the counts of `contact_counts` (a CSR of integers over X's rows, or None)
+        where it stores one; otherwise by `weight_b`."""
+        lists = []
+        for ids_, sc_, cnt_ in ((a_ids, a_scores, a_counts), (b_ids, b_scores, b_counts)):
+            ids_ = np.ascontiguousarray(ids_, dtype=np.int32)
+            sc_ = np.ascontiguousarray(sc_, dtype=np.float32)
+            if ids_.ndim != 2 or sc_.shape != ids_.shape:
+                raise ValueError("ids and scores of a list must be two [B, k] arrays of one shape")
+            cnt_ = np.full(ids_.shape[0], ids_.shape[1], dtype=np.int32) if cnt_ is None else np.asarray(cnt_, dtype=np.int32)
+            if cnt_.shape != (ids_.shape[0],):
+                raise ValueError("counts must hold one entry per row")
+            lists.append((ids_, sc_, cnt_))
+        if lists[0][0].shape[0] != lists[1][0].shape[0]:
+            raise ValueError("both lists must have one row per row")
+        contacts = row_ids is not None
+        d_rows = cn = None
+        if contacts:
+            if not self._X:
+                raise RuntimeError("set_interactions() must be called before blend with contacts")
+            rows = np.asarray(row_ids, dtype=np.int64)
+            if rows.shape != (lists[0][0].shape[0],):
+                raise ValueError("row_ids must hold one entry per row")
+            d_rows = self._up(np.where((rows >= 0) & (rows < self.n_users), rows, -1).astype(np.int32))
+            if contact_counts is not None:
+                C = sp.csr_matrix(contact_counts)
+                if C.shape[0] != self.n_users:
+                    raise ValueError(f"contact_counts must have one row per row of X ({self.n_users}), got {C.shape[0]}")
+                C.sort_indices()
+                cn = (self._up(C.indptr.astype(np.int32)), self._up(C.indices.astype(np.int32)),
+                      self._up(np.clip(C.data, -2 ** 31, 2 ** 31 - 1).astype(np.int32)))
+        dev = [tuple(self._up(a) for a in lst) for lst in lists]
+        out = self.blend_device(*dev[0], *dev[1], keep, weight_b, contacts, k, mnz, d_rows=d_rows, cn=cn, waves_per_row=waves_per_row)
+        return tuple(t.cpu().numpy() for t in out)
 
     # ------------------------------------------------------------------------------ catalogue ranks of held-out items
     RANKS_BLOCK_BYTES = 1 << 30     # the dense score block of one pass of catalogue_ranks_rows

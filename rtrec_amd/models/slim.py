@@ -921,6 +921,193 @@ class SLIM(BaseModel):
             return order, value, pen, cnt
         return [[(items[b][p_], float(scores[b][p_])) for p_ in order[b, :cnt[b]].tolist()] for b in range(len(items))]
 
+    # ------------------------------------------------------------ blended lists (the reference's hybrid merge, on the device)
+    BLEND_MAX_LIST = 1024       # list length rtrec_slim_blend_lists takes on either side
+
+    @staticmethod
+    def _blend_weight(weighting: Any, what: str) -> Tuple[bool, float]:
+        """(contacts, constant weight) of a `weighting` argument: "contacts" or a non-negative number."""
+        if isinstance(weighting, str):
+            if weighting != "contacts":
+                raise ValueError(f'{what}: weighting must be "contacts" or a non-negative number, got {weighting!r}')
+            return True, 1.0
+        w = float(weighting)
+        if not w >= 0.0:                                                  # (a NaN fails the compare)
+            raise ValueError(f'{what}: weighting must be "contacts" or a non-negative number, got {weighting!r}')
+        return False, w
+
+    def _brought_lists(self, what: str, items: List[List[Any]], scores: List[List[float]], n_rows: Optional[int] = None):
+        """(ids[B, K] int32, scores[B, K] float32, counts[B] int32) of the raw-id lists `items` with `scores`: ids the model does
+        not know are dropped (with their scores) before upload, so they never cut a list.  Lists of lists, or -- for integer
+        ids -- two [B, K] arrays."""
+        bound = min(self.model.n_items_fitted, 2 ** 31 - 1)
+        if (isinstance(items, np.ndarray) and items.ndim == 2 and items.dtype.kind in "iu" and self.item_ids.pass_through
+                and 1 <= items.shape[1] <= self.BLEND_MAX_LIST and np.shape(scores) == items.shape
+                and (n_rows is None or items.shape[0] == n_rows)):
+            # integer ids that pass through unmapped, as two [B, K] arrays: the same dropping without a Python loop per item
+            known = (items >= 0) & (items < bound)
+            if known.all():
+                return items.astype(np.int32), np.ascontiguousarray(scores, dtype=np.float32), np.full(len(items), items.shape[1], np.int32)
+            order = np.argsort(~known, axis=1, kind="stable")           # the known ids to the front, in their order
+            ids = np.take_along_axis(np.where(known, items, -1), order, axis=1).astype(np.int32)
+            val = np.take_along_axis(np.where(known, np.asarray(scores, dtype=np.float32), np.float32(0.0)), order, axis=1)
+            return ids, val, known.sum(axis=1).astype(np.int32)
+        items, scores = [list(r) for r in items], [list(r) for r in scores]
+        if len(items) != len(scores) or any(len(a) != len(b) for a, b in zip(items, scores)):
+            raise ValueError(f"{what}: scores must hold one list per list of items, and one score per item")
+        if n_rows is not None and len(items) != n_rows:
+            raise ValueError(f"{what}: one list of items is needed per user, got {len(items)} for {n_rows} users")
+        if max([len(r) for r in items] + [0]) > self.BLEND_MAX_LIST:
+            raise ValueError(f"{what} serves lists of up to {self.BLEND_MAX_LIST} items, got a list of {max(len(r) for r in items)}")
+        kept = []
+        for r, sc in zip(items, scores):
+            iid = self._ids_or_minus_one(r, self.item_ids.get_id, bound)
+            known = iid >= 0
+            kept.append((iid[known], np.asarray(sc, dtype=np.float32).reshape(-1)[known]))
+        K = max([len(i) for i, _ in kept] + [1])
+        ids = np.full((len(kept), K), -1, dtype=np.int32)
+        val = np.zeros((len(kept), K), dtype=np.float32)
+        for b, (i, v) in enumerate(kept):
+            ids[b, :len(i)], val[b, :len(i)] = i, v
+        return ids, val, np.array([len(i) for i, _ in kept], dtype=np.int32)
+
+    def _contact_csr(self, contact_counts: Optional[Iterable[Tuple[Any, Any, int]]], n_rows: int):
+        """The count CSR of rtrec_slim_blend_lists over the `n_rows` rows of X from (user, item, count) triples in raw ids:
+        (ptr, col, val) int32 arrays, or None without triples.  Unknown users and items are skipped; a pair given twice keeps
+        its last count."""
+        if contact_counts is None:
+            return None
+        n_items = self.model.n_items_fitted
+        last = {}
+        for user, item, n in contact_counts:
+            u = self._ids_or_minus_one([user], self._known_user_id, n_rows)[0]
+            i = self._ids_or_minus_one([item], self.item_ids.get_id, n_items)[0]
+            if u >= 0 and i >= 0:
+                last[(int(u), int(i))] = int(n)
+        keys = sorted(last)
+        ptr = np.zeros(n_rows + 1, dtype=np.int64)
+        for u, _ in keys:
+            ptr[u + 1] += 1
+        return (np.cumsum(ptr).astype(np.int32), np.array([i for _, i in keys], dtype=np.int32),
+                np.clip(np.array([last[key] for key in keys], dtype=np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32))
+
+    def recommend_blended_batch(self, users: List[Any], other_items: List[List[Any]], other_scores: List[List[float]], top_k: int = 10,
+                                pool: Optional[int] = None, weighting: Any = "contacts",
+                                contact_counts: Optional[Iterable[Tuple[Any, Any, int]]] = None, similarity_weight_factor: float = 2.0,
+                                mnz: bool = False, filter_interacted: bool = True, as_arrays: bool = False) -> Any:
+        """SLIM's list blended with the list of a second scorer -- a factor model, a popularity prior, an editorial ranking --
+        the way the reference's hybrid model merges its two halves (HybridSlimFM._ensemble_by_scores): both lists are min-max
+        normalised, SLIM's part is weighted per item, the union by item id is sorted by the summed value (the earlier entry
+        first among equal values: the other scorer's items in their order, then SLIM's) and cut to `top_k`.
+
+        `other_items` / `other_scores` hold one list per user in raw item ids, best first, with one score per item; ids the
+        model does not know are dropped.  SLIM's side is its own top-`pool` list (`pool` defaults to `top_k`, as in the
+        reference), scored as `recommend_batch` scores it; unknown users have an empty SLIM side, so their list is the other
+        scorer's.  `weighting="contacts"` is the reference's rule: weight = 2 n / (n + similarity_weight_factor), n = how often
+        the user touched the item: the count `contact_counts` -- an iterable of (user, item, count) in raw ids, unknown ids
+        skipped -- gives for the pair, else 1 for an item the user's row stores and 0 for any other (so with
+        `filter_interacted` and no counts SLIM's items weigh nothing, as in the reference).  A non-negative number is a constant
+        weight instead.  `mnz=True` doubles the value of an item both lists hold (CombMNZ on the normalised scores).
+
+        For known users this is one device pass: the scoring kernels' lists go straight into the blend kernel (csrc/blend.hip;
+        the contract is the comment of rtrec_slim_blend_lists in include/rtrec_amd_ext.h) and only `top_k` per user are
+        downloaded.  With several ranks the scoring pass is the usual collective and every rank computes the same lists.
+
+        Raises ValueError unless 1 <= top_k and 1 <= pool <= 1024 and no brought list is longer than 1024; for a `pool` the fused
+        top-k kernels do not serve for this model; for a W whose values are not float32 numbers (a float64 W holding float32
+        numbers is served with its float32 scores); and for a column-sharded W (gather it with gather_item_similarity()).
+
+        Returns one list of raw item ids per user, or with `as_arrays=True` (ids[B, top_k] int64 INTERNAL item ids,
+        value[B, top_k] float32, source[B, top_k] int32 -- 1: only the other scorer holds the item, 2: only SLIM, 3: both --
+        counts[B]); -1 / -inf / 0 behind counts[b]."""
+        from .._native import TOPK_DENSE, TOPK_SPARSE
+        what = "recommend_blended_batch"
+        top_k = int(top_k)
+        pool = top_k if pool is None else int(pool)
+        if top_k < 1 or not 1 <= pool <= self.BLEND_MAX_LIST:
+            raise ValueError(f"{what} needs top_k >= 1 and 1 <= pool <= {self.BLEND_MAX_LIST}, got top_k={top_k} and pool={pool}")
+        contacts, weight = self._blend_weight(weighting, what)
+        k = float(similarity_weight_factor)
+        if not k >= 0.0:
+            raise ValueError(f"{what}: similarity_weight_factor must not be negative or NaN, got {similarity_weight_factor}")
+        if not self.model.is_fitted:
+            raise RuntimeError(f"Model must be fitted before calling {what}.")
+        arr = self._int_user_array(users)
+        users = arr if arr is not None else list(users)
+        B = len(users)
+        a_ids, a_sc, a_cnt = self._brought_lists(what, other_items, other_scores, B)
+        out_ids = np.full((B, top_k), -1, dtype=np.int64)
+        out_val = np.full((B, top_k), -np.inf, dtype=np.float32)
+        out_src = np.zeros((B, top_k), dtype=np.int32)
+        out_cnt = np.zeros(B, dtype=np.int32)
+        if B:
+            eng = self.model.engine
+            torch = eng.be.torch
+            n_users = self.interactions.shape[0]
+            uid, cold = self._user_rows(users)
+            regular = ~cold & (uid >= 0) & (uid < n_users)
+            self.model._sync_weights()
+            eng._whole_w("blend")                  # a W that cannot be served is refused whatever the batch holds
+            mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+            k_pool = self._pool_width(what, pool, mode)
+            self._sync_interactions()
+            rows = np.where(regular, uid, -1).astype(np.int32)
+            pos = np.flatnonzero(regular)
+            if len(pos) == B:                      # SLIM's lists go from the scoring kernels into the blend kernel as they are
+                b_ids, b_sc, b_cnt = eng.score_topk_device(None, B, k_pool, filter_interacted, mode, d_rows=eng._up(rows))
+                b_sc = b_sc.to(torch.float32)
+            else:                                  # users without a row have an empty SLIM side
+                b_ids = eng.be.zeros((B, k_pool), torch.int32)
+                b_sc = eng.be.zeros((B, k_pool), torch.float32)
+                b_cnt = eng.be.zeros((B,), torch.int32)
+                if len(pos):
+                    i, s_, c = eng.score_topk_device(None, len(pos), k_pool, filter_interacted, mode, d_rows=eng._up(rows[pos]))
+                    at = eng._up(pos.astype(np.int64))
+                    b_ids[at], b_sc[at], b_cnt[at] = i, s_.to(torch.float32), c
+            cn = self._contact_csr(contact_counts, eng.n_users) if contacts else None      # (one row per row of the resident X)
+            keep = min(top_k, a_ids.shape[1] + k_pool)
+            ids, value, source, count = eng.blend_device(eng._up(a_ids), eng._up(a_sc), eng._up(a_cnt), b_ids, b_sc, b_cnt, keep, weight,
+                                                         contacts, k, mnz, d_rows=eng._up(rows),
+                                                         cn=None if cn is None else tuple(eng._up(a) for a in cn))
+            out_ids[:, :keep], out_val[:, :keep] = ids.cpu().numpy(), value.cpu().numpy()
+            out_src[:, :keep], out_cnt[:] = source.cpu().numpy(), count.cpu().numpy()
+        if as_arrays:
+            return out_ids, out_val, out_src, out_cnt
+        raw_of = self._raw_of(self.item_ids)
+        id_rows, cnts = out_ids.tolist(), out_cnt.tolist()
+        return [[raw_of(i) for i in id_rows[b][:cnts[b]]] for b in range(B)]
+
+    def recommend_blended(self, user: Any, other_items: List[Any], other_scores: List[float], top_k: int = 10, pool: Optional[int] = None,
+                          weighting: Any = "contacts", contact_counts: Optional[Iterable[Tuple[Any, Any, int]]] = None,
+                          similarity_weight_factor: float = 2.0, mnz: bool = False, filter_interacted: bool = True) -> List[Any]:
+        """recommend_blended_batch for one user and one brought list."""
+        return self.recommend_blended_batch([user], [other_items], [other_scores], top_k=top_k, pool=pool, weighting=weighting,
+                                            contact_counts=contact_counts, similarity_weight_factor=similarity_weight_factor, mnz=mnz,
+                                            filter_interacted=filter_interacted)[0]
+
+    def blend_batch(self, items_a: List[List[Any]], scores_a: List[List[float]], items_b: List[List[Any]], scores_b: List[List[float]],
+                    top_k: int = 10, weight: float = 1.0, mnz: bool = False) -> List[List[Tuple[Any, float]]]:
+        """The blend of recommend_blended_batch for two lists the caller brings per row -- no user is needed, so list B is
+        weighted by the constant `weight` (non-negative): both lists min-max normalised, united by item id (A's items in their
+        order, then the items only B holds), `weight` x B's normalised score added to A's, `mnz` doubling what both hold.  Ids
+        the model does not know are dropped.  Returns per row the `top_k` best (item, value) tuples.  Lists longer than 1024,
+        `top_k < 1` and a negative or NaN `weight` raise ValueError."""
+        what = "blend_batch"
+        contacts, w = self._blend_weight(weight, what)
+        if contacts or int(top_k) < 1:
+            raise ValueError(f"{what} takes a constant non-negative weight and top_k >= 1, got weight={weight!r} and top_k={top_k}")
+        if not self.model.is_fitted:
+            raise RuntimeError(f"Model must be fitted before calling {what}.")
+        A = self._brought_lists(what, items_a, scores_a)
+        Bl = self._brought_lists(what, items_b, scores_b, len(A[0]))
+        if not len(A[0]):
+            return []
+        self.model._sync_weights()
+        keep = min(int(top_k), A[0].shape[1] + Bl[0].shape[1])
+        ids, value, _, count = self.model.engine.blend_lists(A[0], A[1], Bl[0], Bl[1], A[2], Bl[2], keep=keep, weight_b=w, mnz=mnz)
+        raw_of = self._raw_of(self.item_ids)
+        return [[(raw_of(int(i)), float(v)) for i, v in zip(ids[b, :count[b]], value[b, :count[b]])] for b in range(len(ids))]
+
     # ------------------------------------------------------------ list quality (an extension: the reference has none)
     QUALITY_MAX_LIST = 1024     # list length rtrec_slim_list_quality measures
 

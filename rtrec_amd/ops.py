@@ -62,9 +62,9 @@ EXPORT_OF = {"column_sqnorms": "rtrec_slim_column_sqnorms", "fit_workspace_init"
              "score_pairs": "rtrec_slim_score_pairs"}
 
 # The extension surface (include/rtrec_amd_ext.h, _native.EXT_EXPORTS): the same rules -- one op per kernel-launching export
-EXT_OPS = ["diversify_lists", "list_quality", "catalogue_ranks"]
+EXT_OPS = ["diversify_lists", "list_quality", "catalogue_ranks", "blend_lists"]
 EXT_EXPORT_OF = {"diversify_lists": "rtrec_slim_diversify_lists", "list_quality": "rtrec_slim_list_quality",
-                 "catalogue_ranks": "rtrec_slim_catalogue_ranks"}
+                 "catalogue_ranks": "rtrec_slim_catalogue_ranks", "blend_lists": "rtrec_slim_blend_lists"}
 
 
 def _load() -> None:

@@ -158,6 +158,28 @@ class Recommender:
         """SLIM.diversify_batch: the same selection for lists (and base scores) the caller brings."""
         return self.model.diversify_batch(items, scores, top_k=top_k, diversity=diversity, as_arrays=as_arrays)
 
+    def recommend_blended(self, user: Any, other_items: List[Any], other_scores: List[float], top_k: int = 10, pool: Optional[int] = None,
+                          weighting: Any = "contacts", contact_counts: Any = None, similarity_weight_factor: float = 2.0,
+                          mnz: bool = False, filter_interacted: bool = True) -> List[Any]:
+        """The user's SLIM list merged with a second scorer's list the way the reference's hybrid merges -- SLIM.recommend_blended."""
+        return self.model.recommend_blended(user, other_items, other_scores, top_k=top_k, pool=pool, weighting=weighting,
+                                            contact_counts=contact_counts, similarity_weight_factor=similarity_weight_factor, mnz=mnz,
+                                            filter_interacted=filter_interacted)
+
+    def recommend_blended_batch(self, users: List[Any], other_items: List[List[Any]], other_scores: List[List[float]], top_k: int = 10,
+                                pool: Optional[int] = None, weighting: Any = "contacts", contact_counts: Any = None,
+                                similarity_weight_factor: float = 2.0, mnz: bool = False, filter_interacted: bool = True,
+                                as_arrays: bool = False) -> Any:
+        """SLIM.recommend_blended_batch: score SLIM's lists and blend them with the brought ones, in one device pass."""
+        return self.model.recommend_blended_batch(users, other_items, other_scores, top_k=top_k, pool=pool, weighting=weighting,
+                                                  contact_counts=contact_counts, similarity_weight_factor=similarity_weight_factor,
+                                                  mnz=mnz, filter_interacted=filter_interacted, as_arrays=as_arrays)
+
+    def blend_batch(self, items_a: List[List[Any]], scores_a: List[List[float]], items_b: List[List[Any]], scores_b: List[List[float]],
+                    top_k: int = 10, weight: float = 1.0, mnz: bool = False) -> Any:
+        """SLIM.blend_batch: the same blend for two lists per row the caller brings, with a constant weight."""
+        return self.model.blend_batch(items_a, scores_a, items_b, scores_b, top_k=top_k, weight=weight, mnz=mnz)
+
     def list_quality(self, items: List[Any]) -> Dict[str, Any]:
         """An extension (the reference has none): {n, intra_list_similarity, linked_pairs, novelty} of one list -- SLIM.list_quality."""
         return self.model.list_quality(items)

@@ -25,6 +25,10 @@ the GPU), POST /recommend (one user's top-k).  Differences, all forced by the de
   * POST /recommend_diverse is an addition (a list that trades score against similarity to what is already on the page):
     {"user": ..., "top_k", "pool", "diversity", "filter_interacted"} -> {"user": ..., "items": [{"item": ..., "score": ...}, ...]}
     with the BASE scores (SLIM.recommend_diverse); same token check as /rerank, answered under the model lock, not coalesced;
+  * POST /recommend_blended is an addition (SLIM's list merged with the list of a second scorer the caller brings, the
+    reference's hybrid merge): {"user": ..., "items": [...], "scores": [...], "top_k", "pool" or absent = top_k, "weighting":
+    "contacts" or a number, "contact_counts": [[item, count], ...] or absent, "similarity_weight_factor", "mnz", "filter_interacted"}
+    -> {"user": ..., "items": [...]} (SLIM.recommend_blended); same token check as /rerank, answered under the model lock, not coalesced;
   * concurrent POST /recommend calls are coalesced (`RecommendCoalescer`): requests that arrive within a bounded
     wait (RTREC_AMD_COALESCE_MS, default 1 ms; 0 = only what queued up behind the model lock) share ONE
     recommend_batch launch per (top_k, filter_interacted) group; each caller gets exactly what its own
@@ -98,6 +102,19 @@ class DiverseRequest(BaseModel):
     top_k: int = 10
     pool: int = 50
     diversity: float = 0.3
+    filter_interacted: bool = True
+
+
+class BlendedRequest(BaseModel):
+    user: Any
+    items: List[Any]
+    scores: List[float]
+    top_k: int = 10
+    pool: Optional[int] = None
+    weighting: Any = "contacts"
+    contact_counts: Optional[List[Tuple[Any, int]]] = None
+    similarity_weight_factor: float = 2.0
+    mnz: bool = False
     filter_interacted: bool = True
 
 
@@ -328,6 +345,16 @@ def build_router(gate: ModelGate) -> APIRouter:
                                                                              filter_interacted=request.filter_interacted,
                                                                              ret_scores=True))
         return {"user": request.user, "items": [{"item": i, "score": s} for i, s in pairs]}
+
+    @api.post("/recommend_blended")
+    def recommend_blended(request: BlendedRequest, x_token: str = Header()):
+        _authorise(x_token)
+        counts = None if request.contact_counts is None else [(request.user, i, n) for i, n in request.contact_counts]
+        items = gate.call("Recommend blended", lambda m: m.recommend_blended(
+            request.user, request.items, request.scores, top_k=request.top_k, pool=request.pool, weighting=request.weighting,
+            contact_counts=counts, similarity_weight_factor=request.similarity_weight_factor, mnz=request.mnz,
+            filter_interacted=request.filter_interacted))
+        return {"user": request.user, "items": items}
 
     return api
 
