@@ -191,6 +191,52 @@ int rtrec_slim_blend_lists(int32_t n_rows, int32_t n_items, const int32_t *d_a_i
                            int64_t cn_nnz, int32_t waves_per_row, int32_t *d_out_ids, float *d_out_value, int32_t *d_out_source,
                            int32_t *d_out_count, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * FACTOR TOP-K  (dense user vectors against dense item vectors: the best top_k items per job, scored and selected in one pass.)
+ * The reference's hybrid model takes its second list from implicit.topk(items=item_vector, query=user_vector, k,
+ * filter_query_items) (rtrec/models/hybrid.py): a float32 GEMM and a top-k per row with the interacted items filtered.  This
+ * call does that for vectors the caller brings; training a factor model is not part of this library.
+ *   vectors     job r names row x = d_row_ids[r] of X (d_row_ids == NULL: x = r).  Its vector is row d_p_index[x] of
+ *               d_p[n_p_rows][p_stride] (d_p_index == NULL: row x); d_p_index holds n_x_rows entries.  A job has no vector when x
+ *               lies outside [0, n_x_rows), when its index is -1, or when its index lies outside [0, n_p_rows): it returns an
+ *               empty list.  Item vectors are stored component-major: component c of item i is d_qt[c * qt_stride + i],
+ *               qt_stride >= n_items (32 neighbouring items are one contiguous read per component)
+ *   score       s = +0.0f, then for c = 0 .. dim-1 ascending s = fmaf(p[c], q[c], s): one correctly rounded fused multiply-add
+ *               per component, float32 denormals kept, nothing else added.  Biases are components the caller stacks
+ *               ([b_u, 1, e...] . [1, b_i, e...], as the reference does).  The sign of a zero score is not part of the contract
+ *   competing   item i competes when 0 <= i < n_items; d_item_mask == NULL or d_item_mask[i] != 0; filter_interacted == 0 or i is
+ *               not stored in row x of the CSR without values d_xb_ptr[n_x_rows + 1] / d_xb_col[xb_nnz] (columns ascend inside a
+ *               row; offsets are clamped to [0, xb_nnz], so a malformed CSR gives wrong answers, never an out-of-range read);
+ *               and its score is not NaN.  +-inf compete as numbers
+ *   order       the larger score first; among == scores (-0.0 == +0.0) the lower item id.  Strict, so a list is unique
+ * Out, every slot written: d_out_ids[n_rows][top_k] / d_out_scores[n_rows][top_k], behind the list -1 / -inf;
+ * d_out_count[r] = min(top_k, competing items).
+ * item_splits cuts the catalogue into that many chunks of whole 32-item tiles (never more chunks than tiles), each scanned by
+ * its own workgroups, and a second kernel merges the chunks' lists under the same order: it is what lets a request of one job
+ * use more than one CU.  Chunked calls keep their partial lists in d_workspace:
+ * RTREC_FACTOR_TOPK_WORKSPACE_BYTES(n_rows, top_k, item_splits) bytes for item_splits > 1, none for 1.  With item_splits == 0
+ * the library chooses (from n_rows: chunks until about four workgroups per CU exist) and lowers its choice to what the
+ * workspace it was handed holds; without a workspace it is 1.  (The size is a macro, not an entry point: every symbol of this
+ * header launches and stands behind exactly one op.)
+ * dim in 1..256, top_k in 1..128, item_splits in 0..64: RTREC_ERR_UNSUPPORTED otherwise.  NULL required arrays (d_xb_* only with
+ * filter_interacted; d_workspace only with item_splits > 1), negative sizes and strides below their widths:
+ * RTREC_ERR_INVALID_ARG.  A workspace too small for an explicit item_splits: RTREC_ERR_WORKSPACE.  n_rows == 0: RTREC_OK before
+ * any pointer check.  No global state, no environment variable, no allocation, no synchronisation.  The results never depend on
+ * item_splits, on the grid or on scheduling.
+ * csrc/factor_topk.hip, factor_topk_kernel: 32 jobs x one chunk per one-wave workgroup; a 32 x 32 tile of scores is one chain of
+ * v_mfma_f32_32x32x2_f32 over ascending components (items the A operand, read straight from d_qt; the jobs' vectors the B
+ * operand, in registers), which is that fmaf chain bit for bit; scores that cannot beat a job's threshold are dropped in
+ * registers, survivors are checked against the mask and the row of X and appended to the job's buffer in LDS, a full buffer is
+ * ranked by counting and cut to top_k; factor_merge_kernel merges the chunks.  No atomics.
+ * ------------------------------------------------------------------------------------- */
+#define RTREC_FACTOR_TOPK_WORKSPACE_BYTES(n_rows, top_k, item_splits) \
+    ((size_t)(n_rows) * (size_t)(item_splits) * ((size_t)(top_k) * 8u + 4u))
+int rtrec_factor_topk(int32_t n_rows, const int32_t *d_row_ids, const int32_t *d_p_index, int32_t n_x_rows, const float *d_p,
+                      int64_t p_stride, int32_t n_p_rows, const float *d_qt, int64_t qt_stride, int32_t n_items, int32_t dim,
+                      const uint8_t *d_item_mask, const int32_t *d_xb_ptr, const int32_t *d_xb_col, int64_t xb_nnz,
+                      int32_t filter_interacted, int32_t top_k, int32_t item_splits, int32_t *d_out_ids, float *d_out_scores,
+                      int32_t *d_out_count, void *d_workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

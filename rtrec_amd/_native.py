@@ -53,6 +53,7 @@ EXT_EXPORTS = [
     "rtrec_slim_list_quality",
     "rtrec_slim_catalogue_ranks",
     "rtrec_slim_blend_lists",
+    "rtrec_factor_topk",
 ]
 
 
@@ -227,6 +228,9 @@ def load() -> C.CDLL:
     L.rtrec_slim_blend_lists.argtypes = [i32, i32, vp, C.c_int64, vp, C.c_int64, vp, i32, vp, C.c_int64, vp, C.c_int64, vp, i32, i32,
                                          C.c_float, i32, C.c_double, i32, vp, vp, vp, i32, C.c_int64, vp, vp, vp, C.c_int64, i32,
                                          vp, vp, vp, vp, vp]
+    L.rtrec_factor_topk.restype = C.c_int
+    L.rtrec_factor_topk.argtypes = [i32, vp, vp, i32, vp, C.c_int64, i32, vp, C.c_int64, i32, i32, vp, vp, vp, C.c_int64, i32, i32, i32,
+                                    vp, vp, vp, vp, C.c_size_t, vp]
     _lib = L
     return L
 

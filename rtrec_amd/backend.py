@@ -314,6 +314,28 @@ class HipBackend:
                              bool(contacts), float(k), bool(mnz), row_ids, xb[0], xb[1], cn[0], cn[1], cn[2], int(waves_per_row),
                              out_ids, value, source, count)
 
+    FACTOR_AUTO_BLOCKS = 1024       # item_splits == 0: chunks until this many workgroups exist (the rule of csrc/factor_topk.hip)
+
+    def factor_splits(self, n_rows, n_items, item_splits=0):
+        """The number of catalogue chunks a factor_topk call of `n_rows` jobs runs with: `item_splits`, or for 0 the library's own
+        rule (chunks until FACTOR_AUTO_BLOCKS workgroups of 32 jobs exist, at most 64), never more than the 32-item tiles."""
+        blocks = max(1, (int(n_rows) + 31) // 32)
+        s = int(item_splits) if item_splits else min(64, (self.FACTOR_AUTO_BLOCKS + blocks - 1) // blocks)
+        return max(1, min(s, (int(n_items) + 31) // 32))
+
+    def factor_topk(self, row_ids, p_index, n_x_rows, p, qt, n_items, dim, item_mask, xb, filter_interacted, top_k, ids, scores,
+                    count, item_splits=0):
+        """Per job: the top_k items by the fmaf chain of its vector (row p_index[x] of `p`, x = row_ids[r]) against the
+        component-major item vectors `qt`, the mask and -- with `filter_interacted` -- the row of X = `xb` (ptr, col, val; val
+        is not read) applied (csrc/factor_topk.hip; include/rtrec_amd_ext.h).  The partial lists of a chunked call live in a
+        workspace allocated here: RTREC_FACTOR_TOPK_WORKSPACE_BYTES of the header."""
+        n_rows = int(count.numel())
+        splits = self.factor_splits(n_rows, n_items, item_splits)
+        ws = self.empty((n_rows * splits * (int(top_k) * 8 + 4),), self.torch.uint8) if splits > 1 else None
+        xb = (None, None) if xb is None else xb
+        self.ops.factor_topk(row_ids, p_index, int(n_x_rows), p, qt, int(n_items), int(dim), item_mask, xb[0], xb[1],
+                             bool(filter_interacted), int(top_k), splits, ids, scores, count, ws)
+
     def audience_workspace_bytes(self, n_users, n_q, top_n):
         return int(self.lib.rtrec_slim_audience_workspace_bytes(n_users, n_q, top_n))
 

@@ -55,6 +55,7 @@ struct Abi {
     decltype(&rtrec_slim_list_quality) list_quality = nullptr;
     decltype(&rtrec_slim_catalogue_ranks) catalogue_ranks = nullptr;
     decltype(&rtrec_slim_blend_lists) blend_lists = nullptr;
+    decltype(&rtrec_factor_topk) factor_topk = nullptr;
 };
 Abi g_abi;
 
@@ -676,6 +677,58 @@ void blend_lists(int64_t n_items, const at::Tensor &a_ids, const at::Tensor &a_s
           "rtrec_slim_blend_lists");
 }
 
+// p [n_p_rows, >= dim] float32: one vector per row; qt [>= dim, >= n_items] float32: the item vectors component-major; one job
+// per entry of count: row_ids names its row of X (absent = row r), p_index [n_x_rows] the vector of a row of X (absent = row x);
+// item_mask [>= n_items] uint8 / bool; xb_* the rows of X as a CSR without values (only with filter_interacted); the outputs are
+// ids / scores [n_rows, top_k] and count [n_rows]; workspace: bytes for the partial lists of item_splits chunks
+// (include/rtrec_amd_ext.h, "FACTOR TOP-K").
+void factor_topk(const OT &row_ids, const OT &p_index, int64_t n_x_rows, const at::Tensor &p, const at::Tensor &qt, int64_t n_items,
+                 int64_t dim, const OT &item_mask, const OT &xb_ptr, const OT &xb_col, bool filter_interacted, int64_t top_k,
+                 int64_t item_splits, at::Tensor ids, at::Tensor scores, at::Tensor count, const OT &workspace) {
+    TORCH_CHECK(dim >= 1 && dim <= 256, "factor_topk: dim must lie in 1..256, got ", dim);
+    TORCH_CHECK(top_k >= 1 && top_k <= 128, "factor_topk: top_k must lie in 1..128, got ", top_k);
+    TORCH_CHECK(item_splits >= 0 && item_splits <= 64, "factor_topk: item_splits must lie in 0..64, got ", item_splits);
+    const int64_t rows = count.numel();
+    TORCH_CHECK(rows <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX && n_x_rows >= 0 && n_x_rows < INT32_MAX,
+                "factor_topk: too many rows or items");
+    TORCH_CHECK(p.dim() == 2 && p.size(1) >= dim && p.size(0) <= INT32_MAX, "factor_topk: p must be [n_p_rows, >= dim]");
+    TORCH_CHECK(qt.dim() == 2 && qt.size(0) >= dim && qt.size(1) >= n_items, "factor_topk: qt must be [>= dim, >= n_items]");
+    TORCH_CHECK(ids.numel() == rows * top_k && scores.numel() == rows * top_k, "factor_topk: outputs must be ids[n_rows, top_k], scores[same], count[n_rows]");
+    const auto has = [](const OT &t) { return t.has_value() && t->defined(); };
+    TORCH_CHECK(!has(row_ids) || row_ids->numel() == rows, "factor_topk: row_ids must hold one entry per job");
+    TORCH_CHECK(!has(p_index) || p_index->numel() == n_x_rows, "factor_topk: p_index must hold one entry per row of X");
+    if (has(item_mask)) {
+        TORCH_CHECK(item_mask->numel() >= n_items && (item_mask->scalar_type() == at::kByte || item_mask->scalar_type() == at::kBool),
+                    "factor_topk: item_mask must hold one uint8 / bool entry per item");
+        check_tensor<void>(*item_mask);
+    }
+    int64_t xb_nnz = 0;
+    if (filter_interacted) {
+        TORCH_CHECK(has(xb_ptr) && has(xb_col), "factor_topk: filter_interacted needs xb_ptr and xb_col");
+        TORCH_CHECK(xb_ptr->numel() == n_x_rows + 1, "factor_topk: xb_ptr must hold n_x_rows + 1 offsets");
+        xb_nnz = xb_col->numel();
+        check_tensor<const int32_t>(*xb_ptr); check_tensor<const int32_t>(*xb_col);
+    }
+    check_tensor<const float>(p); check_tensor<const float>(qt);
+    check_tensor<int32_t>(ids); check_tensor<float>(scores); check_tensor<int32_t>(count);
+    if (has(row_ids)) check_tensor<const int32_t>(*row_ids);
+    if (has(p_index)) check_tensor<const int32_t>(*p_index);
+    if (has(workspace)) check_tensor<void>(*workspace);
+    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&p, &qt, &ids, &scores})
+        TORCH_CHECK(t->device() == count.device(), "factor_topk: all tensors must live on one device");
+    for (const OT *t : std::initializer_list<const OT *>{&row_ids, &p_index, &item_mask, &xb_ptr, &xb_col, &workspace})
+        TORCH_CHECK(!has(*t) || (*t)->device() == count.device(), "factor_topk: all tensors must live on one device");
+    const size_t ws_bytes = has(workspace) ? static_cast<size_t>(workspace->numel()) * workspace->element_size() : 0;
+    check(abi().factor_topk(static_cast<int32_t>(rows), ptr<const int32_t>(row_ids), ptr<const int32_t>(p_index),
+                            static_cast<int32_t>(n_x_rows), ptr<const float>(p), p.size(1), static_cast<int32_t>(p.size(0)),
+                            ptr<const float>(qt), qt.size(1), static_cast<int32_t>(n_items), static_cast<int32_t>(dim),
+                            has(item_mask) && item_mask->numel() > 0 ? static_cast<const uint8_t *>(item_mask->data_ptr()) : nullptr,
+                            filter_interacted ? ptr<const int32_t>(xb_ptr) : nullptr, filter_interacted ? ptr<const int32_t>(xb_col) : nullptr,
+                            xb_nnz, filter_interacted ? 1 : 0, static_cast<int32_t>(top_k), static_cast<int32_t>(item_splits),
+                            ptr<int32_t>(ids), ptr<float>(scores), ptr<int32_t>(count), ptr<void>(workspace), ws_bytes, stream_of(count)),
+          "rtrec_factor_topk");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -712,6 +765,7 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.list_quality, "rtrec_slim_list_quality");
         bind_one(h, a.catalogue_ranks, "rtrec_slim_catalogue_ranks");
         bind_one(h, a.blend_lists, "rtrec_slim_blend_lists");
+        bind_one(h, a.factor_topk, "rtrec_factor_topk");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -787,6 +841,9 @@ TORCH_LIBRARY(rtrec_amd, m) {
           "int kb, int keep, float weight_b, bool contacts, float k, bool mnz, Tensor? row_ids, Tensor? xb_ptr, Tensor? xb_col, "
           "Tensor? cn_ptr, Tensor? cn_col, Tensor? cn_val, int waves_per_row, Tensor(a!) ids, Tensor(b!) value, Tensor(c!) source, "
           "Tensor(d!) count) -> ()");
+    m.def("factor_topk(Tensor? row_ids, Tensor? p_index, int n_x_rows, Tensor p, Tensor qt, int n_items, int dim, Tensor? item_mask, "
+          "Tensor? xb_ptr, Tensor? xb_col, bool filter_interacted, int top_k, int item_splits, Tensor(a!) ids, Tensor(b!) scores, "
+          "Tensor(c!) count, Tensor(d!)? workspace) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -816,4 +873,5 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("list_quality", &list_quality);
     m.impl("catalogue_ranks", &catalogue_ranks);
     m.impl("blend_lists", &blend_lists);
+    m.impl("factor_topk", &factor_topk);
 }

@@ -148,6 +148,7 @@ class SlimEngine:
         self.n_items = 0
         self._X: Dict[str, Any] = {}
         self._W: Dict[str, Any] = {}
+        self._F: Dict[str, Any] = {}       # resident factor vectors (set_factors)
         self._fit_ws: Dict[Tuple[int, int, int, int], Any] = {}
         self._score_ws = None
         self.gather_chunk_rows = GATHER_CHUNK_ROWS
@@ -1896,6 +1897,110 @@ class SlimEngine:
                       self._up(np.clip(C.data, -2 ** 31, 2 ** 31 - 1).astype(np.int32)))
         dev = [tuple(self._up(a) for a in lst) for lst in lists]
         out = self.blend_device(*dev[0], *dev[1], keep, weight_b, contacts, k, mnz, d_rows=d_rows, cn=cn, waves_per_row=waves_per_row)
+        return tuple(t.cpu().numpy() for t in out)
+
+    # ------------------------------------------------------------------------------ factor scorer (dense vectors, top-k per row)
+    FACTOR_MAX_DIM = 256        # dim / top_k limits of rtrec_factor_topk
+    FACTOR_MAX_K = 128
+
+    @staticmethod
+    def _as_float32(a, what: str) -> np.ndarray:
+        """`a` as a float32 array; a value that is no float32 number is refused (scores are float32 fmaf chains of what is stored)."""
+        a = np.asarray(a)
+        a32 = np.ascontiguousarray(a, dtype=np.float32)
+        if a.dtype != np.float32 and not np.array_equal(a32.astype(a.dtype), a, equal_nan=True):
+            raise ValueError(f"{what} holds values that are not float32 numbers: factor scores are float32 sums of the stored "
+                             "vectors, convert them first (and accept what that does to the ranking)")
+        return a32
+
+    def set_factors(self, user_vectors, item_vectors, user_index: Optional[np.ndarray] = None,
+                    item_mask: Optional[np.ndarray] = None) -> None:
+        """Upload the vectors of a factor model somebody else trained: `user_vectors` [n_p, dim] and `item_vectors`
+        [n_items, dim] (stored transposed, component-major, so that neighbouring items are one contiguous read); `user_index`
+        [n_users] int names the vector of every row of X (-1: none; None: row x has vector x, rows beyond n_p none);
+        `item_mask` [n_items] marks the items that may be listed at all (None: all).  Biases are components the caller stacks
+        (utils/factors.stack_bias).  The shapes are checked against the resident X and W; with several ranks every rank keeps
+        all vectors and answers for the rows it is asked about."""
+        P = self._as_float32(user_vectors, "user_vectors")
+        Q = self._as_float32(item_vectors, "item_vectors")
+        if P.ndim != 2 or Q.ndim != 2 or P.shape[1] != Q.shape[1]:
+            raise ValueError(f"user and item vectors must be two matrices of one width, got {P.shape} and {Q.shape}")
+        dim = int(P.shape[1])
+        if not 1 <= dim <= self.FACTOR_MAX_DIM:
+            raise ValueError(f"factor vectors of 1..{self.FACTOR_MAX_DIM} components are supported, got {dim}")
+        n_items = int(self._W["n_items"]) if self._W else (self.n_items if self._X else int(Q.shape[0]))
+        if int(Q.shape[0]) != n_items:
+            raise ValueError(f"item_vectors must have one row per item of the catalogue ({n_items}), got {Q.shape[0]}")
+        d_index = None
+        if user_index is not None:
+            idx = np.asarray(user_index, dtype=np.int64)
+            if not self._X or idx.shape != (self.n_users,):
+                raise ValueError(f"user_index must hold one entry per row of the resident X, got {idx.shape}")
+            d_index = self.be.to_dev(np.where((idx >= 0) & (idx < P.shape[0]), idx, -1).astype(np.int32))
+        d_mask = None
+        if item_mask is not None:
+            d_mask = self._upload_item_mask(item_mask, n_items)
+        self._F = {"p": self.be.to_dev(P), "qt": self.be.to_dev(np.ascontiguousarray(Q.T)), "index": d_index, "mask": d_mask,
+                   "dim": dim, "n_p": int(P.shape[0]), "n_items": n_items}
+
+    def _upload_item_mask(self, item_mask, n_items: int):
+        m = np.asarray(item_mask)
+        if m.shape != (n_items,):
+            raise ValueError(f"item_mask must hold one entry per item ({n_items}), got {m.shape}")
+        return self.be.to_dev((m != 0).astype(np.uint8))
+
+    def clear_factors(self) -> None:
+        self._F = {}
+
+    def has_factors(self) -> bool:
+        return bool(getattr(self, "_F", None))
+
+    def factor_topk_device(self, d_rows, n_rows: int, top_k: int, filter_interacted: bool = True, item_mask=None,
+                           item_splits: int = 0):
+        """Device tensors (ids[n_rows, top_k] int32, scores[n_rows, top_k] float32, count[n_rows] int32): per row `d_rows[r]`
+        of the resident X (int32 device tensor; None = rows 0 .. n_rows-1) the best top_k items by the dot product of the
+        row's vector with the item vectors -- a float32 fmaf chain over ascending components -- among the items the resident
+        mask and `item_mask` (a uint8 device tensor over the items, or None) admit and, with `filter_interacted`, the row does
+        not store; the larger score first, the lower id among equal ones; -1 / -inf behind count.  A row without a vector, or
+        outside X, gets an empty list.  The contract is the comment of rtrec_factor_topk in include/rtrec_amd_ext.h.
+        `item_splits`: catalogue chunks per row block, 0 = the library's choice; the answer never depends on it."""
+        be, torch = self.be, self.be.torch
+        if not self.has_factors():
+            raise RuntimeError("set_factors() must be called before factor_topk")
+        if not self._X:
+            raise RuntimeError("set_interactions() must be called before factor_topk")
+        F = self._F
+        top_k, n_rows = int(top_k), int(n_rows)
+        if not 1 <= top_k <= self.FACTOR_MAX_K:
+            raise ValueError(f"factor_topk: top_k must lie in 1..{self.FACTOR_MAX_K}, got {top_k}")
+        if not 0 <= int(item_splits) <= 64:
+            raise ValueError(f"factor_topk: item_splits must lie in 0..64, got {item_splits}")
+        if self._W and F["n_items"] != int(self._W["n_items"]):
+            raise ValueError(f"the resident factors cover {F['n_items']} items, W has {self._W['n_items']}: call set_factors() again")
+        if F["index"] is not None and int(F["index"].numel()) != self.n_users:
+            raise ValueError(f"the resident user_index covers {int(F['index'].numel())} rows, X has {self.n_users}: call set_factors() again")
+        mask = F["mask"]
+        if item_mask is not None:
+            if int(item_mask.numel()) != F["n_items"]:
+                raise ValueError(f"item_mask must hold one entry per item ({F['n_items']})")
+            mask = item_mask if mask is None else (item_mask.to(torch.uint8) * mask)
+        ids = be.empty((n_rows, top_k), torch.int32)
+        scores = be.empty((n_rows, top_k), torch.float32)
+        count = be.zeros((n_rows,), torch.int32)
+        if n_rows == 0:
+            return ids, scores, count
+        be.factor_topk(d_rows, F["index"], self.n_users, F["p"], F["qt"], F["n_items"], F["dim"], mask,
+                       self._x_csr() if filter_interacted else None, bool(filter_interacted), top_k, ids, scores, count,
+                       item_splits=int(item_splits))
+        return ids, scores, count
+
+    def factor_topk_rows(self, row_ids: Sequence[int], top_k: int = 10, filter_interacted: bool = True,
+                         item_mask: Optional[np.ndarray] = None, item_splits: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """factor_topk_device for host row ids (a row outside X gets an empty list): numpy (ids[B, top_k], scores, count[B])."""
+        rows = np.asarray(row_ids, dtype=np.int64).reshape(-1)
+        d_rows = self._up(np.where((rows >= 0) & (rows < self.n_users), rows, -1).astype(np.int32))
+        d_mask = None if item_mask is None else self._upload_item_mask(item_mask, self._F["n_items"] if self._F else self.n_items)
+        out = self.factor_topk_device(d_rows, len(rows), top_k, filter_interacted, d_mask, item_splits)
         return tuple(t.cpu().numpy() for t in out)
 
     # ------------------------------------------------------------------------------ catalogue ranks of held-out items

@@ -24,6 +24,8 @@ class SLIM(BaseModel):
         self.recorded_item_ids: set = set()
         self._x_on_device: Optional[Tuple[int, float]] = None   # (store version, max_timestamp) of the GPU copy
         self._dev_x: Optional[DeviceInteractions] = None        # X resident in HBM (utils/device_store.py)
+        self._factors: Optional[Dict[str, np.ndarray]] = None   # vectors of a factor model the caller attached (attach_factors)
+        self._factors_on_device: Any = None                     # (what the engine's resident copy was built for, has-vector mask)
 
     # ------------------------------------------------------------ device-resident X
     def _store_tag(self) -> Any:
@@ -991,6 +993,25 @@ class SLIM(BaseModel):
         return (np.cumsum(ptr).astype(np.int32), np.array([i for _, i in keys], dtype=np.int32),
                 np.clip(np.array([last[key] for key in keys], dtype=np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32))
 
+    def _slim_pool_device(self, rows: np.ndarray, regular: np.ndarray, k_pool: int, filter_interacted: bool, mode: int):
+        """SLIM's side of a blend as device tensors (ids[B, k_pool] int32, scores float32, counts[B] int32): the scoring kernels'
+        lists for the user rows `rows` where `regular`, empty lists for the others (users without a row)."""
+        eng = self.model.engine
+        torch = eng.be.torch
+        B = len(rows)
+        pos = np.flatnonzero(regular)
+        if len(pos) == B:                          # SLIM's lists go from the scoring kernels into the blend kernel as they are
+            b_ids, b_sc, b_cnt = eng.score_topk_device(None, B, k_pool, filter_interacted, mode, d_rows=eng._up(rows))
+            return b_ids, b_sc.to(torch.float32), b_cnt
+        b_ids = eng.be.zeros((B, k_pool), torch.int32)
+        b_sc = eng.be.zeros((B, k_pool), torch.float32)
+        b_cnt = eng.be.zeros((B,), torch.int32)
+        if len(pos):
+            i, s_, c = eng.score_topk_device(None, len(pos), k_pool, filter_interacted, mode, d_rows=eng._up(rows[pos]))
+            at = eng._up(pos.astype(np.int64))
+            b_ids[at], b_sc[at], b_cnt[at] = i, s_.to(torch.float32), c
+        return b_ids, b_sc, b_cnt
+
     def recommend_blended_batch(self, users: List[Any], other_items: List[List[Any]], other_scores: List[List[float]], top_k: int = 10,
                                 pool: Optional[int] = None, weighting: Any = "contacts",
                                 contact_counts: Optional[Iterable[Tuple[Any, Any, int]]] = None, similarity_weight_factor: float = 2.0,
@@ -1042,7 +1063,6 @@ class SLIM(BaseModel):
         out_cnt = np.zeros(B, dtype=np.int32)
         if B:
             eng = self.model.engine
-            torch = eng.be.torch
             n_users = self.interactions.shape[0]
             uid, cold = self._user_rows(users)
             regular = ~cold & (uid >= 0) & (uid < n_users)
@@ -1052,18 +1072,7 @@ class SLIM(BaseModel):
             k_pool = self._pool_width(what, pool, mode)
             self._sync_interactions()
             rows = np.where(regular, uid, -1).astype(np.int32)
-            pos = np.flatnonzero(regular)
-            if len(pos) == B:                      # SLIM's lists go from the scoring kernels into the blend kernel as they are
-                b_ids, b_sc, b_cnt = eng.score_topk_device(None, B, k_pool, filter_interacted, mode, d_rows=eng._up(rows))
-                b_sc = b_sc.to(torch.float32)
-            else:                                  # users without a row have an empty SLIM side
-                b_ids = eng.be.zeros((B, k_pool), torch.int32)
-                b_sc = eng.be.zeros((B, k_pool), torch.float32)
-                b_cnt = eng.be.zeros((B,), torch.int32)
-                if len(pos):
-                    i, s_, c = eng.score_topk_device(None, len(pos), k_pool, filter_interacted, mode, d_rows=eng._up(rows[pos]))
-                    at = eng._up(pos.astype(np.int64))
-                    b_ids[at], b_sc[at], b_cnt[at] = i, s_.to(torch.float32), c
+            b_ids, b_sc, b_cnt = self._slim_pool_device(rows, regular, k_pool, filter_interacted, mode)
             cn = self._contact_csr(contact_counts, eng.n_users) if contacts else None      # (one row per row of the resident X)
             keep = min(top_k, a_ids.shape[1] + k_pool)
             ids, value, source, count = eng.blend_device(eng._up(a_ids), eng._up(a_sc), eng._up(a_cnt), b_ids, b_sc, b_cnt, keep, weight,
@@ -1107,6 +1116,204 @@ class SLIM(BaseModel):
         ids, value, _, count = self.model.engine.blend_lists(A[0], A[1], Bl[0], Bl[1], A[2], Bl[2], keep=keep, weight_b=w, mnz=mnz)
         raw_of = self._raw_of(self.item_ids)
         return [[(raw_of(int(i)), float(v)) for i, v in zip(ids[b, :count[b]], value[b, :count[b]])] for b in range(len(ids))]
+
+    # ------------------------------------------------------------ factor scorer and hybrid lists (the reference's hybrid, one pass)
+    FACTOR_MAX_K = 128          # list length rtrec_factor_topk selects
+
+    def attach_factors(self, users: Iterable[Any], user_vectors: Any, items: Iterable[Any], item_vectors: Any) -> "SLIM":
+        """Bring the vectors of a factor model somebody else trained (an exported LightFM or ALS model, an item2vec table, any
+        embedding): `user_vectors` [len(users), dim] and `item_vectors` [len(items), dim] for the raw ids `users` / `items`;
+        biases are components the caller stacks (utils/factors.stack_bias).  Ids the model does not know are dropped (an id
+        given twice keeps its last vector); a known user without a vector gets an empty factor list, a known item without a
+        vector is never listed by the factor scorer.  Values that are not float32 numbers are refused.  The vectors are
+        uploaded on first use and travel with a pickle of the model."""
+        from ..engine import SlimEngine
+        users, items = list(users), list(items)
+        P = SlimEngine._as_float32(user_vectors, "user_vectors")
+        Q = SlimEngine._as_float32(item_vectors, "item_vectors")
+        if P.ndim != 2 or Q.ndim != 2 or P.shape[1] != Q.shape[1] or P.shape[0] != len(users) or Q.shape[0] != len(items):
+            raise ValueError(f"attach_factors needs one vector per id and one width on both sides, got {P.shape} for {len(users)} "
+                             f"users and {Q.shape} for {len(items)} items")
+        if not 1 <= P.shape[1] <= SlimEngine.FACTOR_MAX_DIM:
+            raise ValueError(f"factor vectors of 1..{SlimEngine.FACTOR_MAX_DIM} components are supported, got {P.shape[1]}")
+        uid = self._ids_or_minus_one(users, self._known_user_id)
+        iid = self._ids_or_minus_one(items, self.item_ids.get_id)
+        self._factors = {"user_rows": uid[uid >= 0], "user_vectors": np.ascontiguousarray(P[uid >= 0]),
+                         "item_rows": iid[iid >= 0], "item_vectors": np.ascontiguousarray(Q[iid >= 0])}
+        self._factors_on_device = None
+        return self
+
+    def detach_factors(self) -> "SLIM":
+        self._factors = None
+        self._factors_on_device = None
+        if self.model._engine is not None:
+            self.model._engine.clear_factors()
+        return self
+
+    def has_factors(self) -> bool:
+        return self._factors is not None
+
+    def _sync_factors(self, what: str) -> np.ndarray:
+        """Make the engine's resident vectors current for the resident X and W (interactions synced by the caller); returns the
+        bool array over X's rows: this row has a vector."""
+        if self._factors is None:
+            raise RuntimeError(f"attach_factors() must be called before {what}.")
+        eng, F = self.model.engine, self._factors
+        n_users, n_items = eng.n_users, self.model.n_items_fitted
+        stamp = (id(F), n_users, n_items, id(eng))
+        if self._factors_on_device is None or self._factors_on_device[0] != stamp or not eng.has_factors():
+            dim = F["user_vectors"].shape[1]
+            index = np.full(n_users, -1, dtype=np.int64)
+            ok = F["user_rows"] < n_users
+            index[F["user_rows"][ok]] = np.flatnonzero(ok)
+            Q = np.zeros((n_items, dim), dtype=np.float32)
+            mask = np.zeros(n_items, dtype=np.uint8)
+            ok = F["item_rows"] < n_items
+            Q[F["item_rows"][ok]] = F["item_vectors"][ok]
+            mask[F["item_rows"][ok]] = 1
+            eng.set_factors(F["user_vectors"], Q, user_index=index, item_mask=mask)
+            self._factors_on_device = (stamp, index >= 0)
+        return self._factors_on_device[1]
+
+    def recommend_factor_batch(self, users: List[Any], top_k: int = 10, filter_interacted: bool = True,
+                               candidate_items: Optional[List[Any]] = None, as_arrays: bool = False) -> Any:
+        """The second scorer alone: per user the `top_k` items by the dot product of the attached user and item vectors (the
+        reference's implicit.topk call of its hybrid model) -- a float32 fused multiply-add chain over ascending components,
+        the larger score first, the lower internal item id among equal scores -- among the items that have a vector, that
+        `candidate_items` (raw ids, unknown ones dropped; None: all) names and, with `filter_interacted`, that the user has
+        not touched.  One device pass (csrc/factor_topk.hip; the contract is the comment of rtrec_factor_topk in
+        include/rtrec_amd_ext.h).  An unknown user, a user outside the matrix and a user without a vector get the cold-start
+        list `recommend_batch` gives unknown users (scores 0).  Raises ValueError unless 1 <= top_k <= 128.
+
+        Returns one list of raw item ids per user, or with `as_arrays=True` (ids[B, top_k] int64 INTERNAL item ids,
+        scores[B, top_k] float32, counts[B]); -1 / -inf behind counts[b]."""
+        what = "recommend_factor_batch"
+        top_k = int(top_k)
+        if not 1 <= top_k <= self.FACTOR_MAX_K:
+            raise ValueError(f"{what} needs 1 <= top_k <= {self.FACTOR_MAX_K} (what the factor kernel selects), got {top_k}")
+        if not self.model.is_fitted:
+            raise RuntimeError(f"Model must be fitted before calling {what}.")
+        if self._factors is None:
+            raise RuntimeError(f"attach_factors() must be called before {what}.")
+        arr = self._int_user_array(users)
+        users = arr if arr is not None else list(users)
+        B = len(users)
+        out_ids = np.full((B, top_k), -1, dtype=np.int64)
+        out_sc = np.full((B, top_k), -np.inf, dtype=np.float32)
+        out_cnt = np.zeros(B, dtype=np.int32)
+        if B:
+            eng = self.model.engine
+            n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
+            uid, cold = self._user_rows(users)
+            regular = ~cold & (uid >= 0) & (uid < n_users)
+            self.model._sync_weights()
+            self._sync_interactions()
+            has_vec = self._sync_factors(what)
+            served = regular.copy()
+            served[regular] = has_vec[uid[regular]]
+            cand = None
+            if candidate_items is not None:
+                cand = self._ids_or_minus_one(candidate_items, self.item_ids.get_id, n_items)
+                cand = np.unique(cand[cand >= 0])
+            if not served.all():
+                cold_list = self._recommend_cold_batch([None], candidate_item_ids=None if cand is None else cand.tolist(),
+                                                       top_k=top_k)[0][:top_k]
+                out_ids[~served, :len(cold_list)] = np.asarray(cold_list, dtype=np.int64)[None, :]
+                out_sc[~served, :len(cold_list)] = 0.0
+                out_cnt[~served] = len(cold_list)
+            if served.any():
+                mask = None
+                if cand is not None:
+                    mask = np.zeros(n_items, dtype=np.uint8)
+                    mask[cand] = 1
+                pos = np.flatnonzero(served)
+                ids, sc, cnt = eng.factor_topk_rows(uid[pos], top_k, filter_interacted, item_mask=mask)
+                out_ids[pos], out_sc[pos], out_cnt[pos] = ids, sc, cnt
+        if as_arrays:
+            return out_ids, out_sc, out_cnt
+        raw_of = self._raw_of(self.item_ids)
+        id_rows, cnts = out_ids.tolist(), out_cnt.tolist()
+        return [[raw_of(i) for i in id_rows[b][:cnts[b]]] for b in range(B)]
+
+    def recommend_factor(self, user: Any, top_k: int = 10, filter_interacted: bool = True,
+                         candidate_items: Optional[List[Any]] = None) -> List[Any]:
+        """recommend_factor_batch for one user."""
+        return self.recommend_factor_batch([user], top_k=top_k, filter_interacted=filter_interacted, candidate_items=candidate_items)[0]
+
+    def recommend_hybrid_batch(self, users: List[Any], top_k: int = 10, pool: Optional[int] = None, weighting: Any = "contacts",
+                               contact_counts: Optional[Iterable[Tuple[Any, Any, int]]] = None, similarity_weight_factor: float = 2.0,
+                               mnz: bool = False, filter_interacted: bool = True, as_arrays: bool = False) -> Any:
+        """The reference's hybrid list in one device pass: the factor scorer's top-`pool` (recommend_factor_batch's list, from
+        the attached vectors) and SLIM's top-`pool` are blended as `recommend_blended_batch` blends a brought list with SLIM's
+        -- both min-max normalised, SLIM's part weighted per item (`weighting`, `contact_counts`, `similarity_weight_factor`,
+        `mnz` as there), the union sorted by the summed value, the factor scorer's items first among equal values -- and cut
+        to `top_k`.  Factor top-k, SLIM's scoring pass and the blend kernel hand their lists on in HBM; only `top_k` per user
+        are downloaded.  `pool` defaults to `top_k`, as in the reference.  An unknown user has no row, so both sides and the
+        list are empty; a known user without a vector gets SLIM's side alone.  With several ranks every rank computes the same
+        lists (the scoring pass is the usual collective; the factor lists are computed locally, no exchange).
+
+        Raises ValueError unless 1 <= top_k and 1 <= pool <= 128: the factor kernel keeps a user's candidates in LDS and
+        selects at most 128 per user (SLIM's side alone would take 1024); and for what `recommend_blended_batch` refuses.
+
+        Returns what `recommend_blended_batch` returns: one list of raw item ids per user, or with `as_arrays=True`
+        (ids[B, top_k] int64 INTERNAL item ids, value[B, top_k] float32, source[B, top_k] int32 -- 1: only the factor scorer
+        holds the item, 2: only SLIM, 3: both -- counts[B]); -1 / -inf / 0 behind counts[b]."""
+        from .._native import TOPK_DENSE, TOPK_SPARSE
+        what = "recommend_hybrid_batch"
+        top_k = int(top_k)
+        pool = top_k if pool is None else int(pool)
+        if top_k < 1 or not 1 <= pool <= self.FACTOR_MAX_K:
+            raise ValueError(f"{what} needs top_k >= 1 and 1 <= pool <= {self.FACTOR_MAX_K}, got top_k={top_k} and pool={pool}: the "
+                             f"factor kernel keeps each user's candidates in LDS and selects at most {self.FACTOR_MAX_K} per user")
+        contacts, weight = self._blend_weight(weighting, what)
+        k = float(similarity_weight_factor)
+        if not k >= 0.0:
+            raise ValueError(f"{what}: similarity_weight_factor must not be negative or NaN, got {similarity_weight_factor}")
+        if not self.model.is_fitted:
+            raise RuntimeError(f"Model must be fitted before calling {what}.")
+        if self._factors is None:
+            raise RuntimeError(f"attach_factors() must be called before {what}.")
+        arr = self._int_user_array(users)
+        users = arr if arr is not None else list(users)
+        B = len(users)
+        out_ids = np.full((B, top_k), -1, dtype=np.int64)
+        out_val = np.full((B, top_k), -np.inf, dtype=np.float32)
+        out_src = np.zeros((B, top_k), dtype=np.int32)
+        out_cnt = np.zeros(B, dtype=np.int32)
+        if B:
+            eng = self.model.engine
+            n_users = self.interactions.shape[0]
+            uid, cold = self._user_rows(users)
+            regular = ~cold & (uid >= 0) & (uid < n_users)
+            self.model._sync_weights()
+            eng._whole_w("blend")
+            mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+            k_pool = self._pool_width(what, pool, mode)
+            self._sync_interactions()
+            self._sync_factors(what)
+            rows = np.where(regular, uid, -1).astype(np.int32)
+            d_rows = eng._up(rows)
+            a_ids, a_sc, a_cnt = eng.factor_topk_device(d_rows, B, k_pool, filter_interacted)     # (row -1: an empty list)
+            b_ids, b_sc, b_cnt = self._slim_pool_device(rows, regular, k_pool, filter_interacted, mode)
+            cn = self._contact_csr(contact_counts, eng.n_users) if contacts else None
+            keep = min(top_k, 2 * k_pool)
+            ids, value, source, count = eng.blend_device(a_ids, a_sc, a_cnt, b_ids, b_sc, b_cnt, keep, weight, contacts, k, mnz,
+                                                         d_rows=d_rows, cn=None if cn is None else tuple(eng._up(a) for a in cn))
+            out_ids[:, :keep], out_val[:, :keep] = ids.cpu().numpy(), value.cpu().numpy()
+            out_src[:, :keep], out_cnt[:] = source.cpu().numpy(), count.cpu().numpy()
+        if as_arrays:
+            return out_ids, out_val, out_src, out_cnt
+        raw_of = self._raw_of(self.item_ids)
+        id_rows, cnts = out_ids.tolist(), out_cnt.tolist()
+        return [[raw_of(i) for i in id_rows[b][:cnts[b]]] for b in range(B)]
+
+    def recommend_hybrid(self, user: Any, top_k: int = 10, pool: Optional[int] = None, weighting: Any = "contacts",
+                         contact_counts: Optional[Iterable[Tuple[Any, Any, int]]] = None, similarity_weight_factor: float = 2.0,
+                         mnz: bool = False, filter_interacted: bool = True) -> List[Any]:
+        """recommend_hybrid_batch for one user."""
+        return self.recommend_hybrid_batch([user], top_k=top_k, pool=pool, weighting=weighting, contact_counts=contact_counts,
+                                           similarity_weight_factor=similarity_weight_factor, mnz=mnz,
+                                           filter_interacted=filter_interacted)[0]
 
     # ------------------------------------------------------------ list quality (an extension: the reference has none)
     QUALITY_MAX_LIST = 1024     # list length rtrec_slim_list_quality measures
@@ -1296,8 +1503,11 @@ class SLIM(BaseModel):
 
     # ------------------------------------------------------------ persistence (slim.py:117-149)
     def _serialize(self) -> dict:
-        return {"model": self.model, "interactions": self.interactions, "user_ids": self.user_ids,
+        data = {"model": self.model, "interactions": self.interactions, "user_ids": self.user_ids,
                 "item_ids": self.item_ids, "feature_store": self.feature_store}
+        if self._factors is not None:           # (only when attached: a model without vectors serialises as it always did)
+            data["factors"] = self._factors
+        return data
 
     @classmethod
     def _deserialize(cls, data: dict) -> "SLIM":
@@ -1307,4 +1517,5 @@ class SLIM(BaseModel):
         instance.user_ids = data["user_ids"]
         instance.item_ids = data["item_ids"]
         instance.feature_store = data["feature_store"]
+        instance._factors = data.get("factors")
         return instance

@@ -26,6 +26,8 @@ is written on top of them; they are also the interface for callers that already 
     torch.ops.rtrec_amd.diversify_lists     (extension surface, include/rtrec_amd_ext.h) per list: the greedy MMR order over W's similarities
     torch.ops.rtrec_amd.list_quality        (extension surface) per list: intra-list similarity sum, linked pairs, weight sum; the catalogue exposure
     torch.ops.rtrec_amd.catalogue_ranks     (extension surface) per held-out (row, item): the columns of the dense score row above it and tied with it
+    torch.ops.rtrec_amd.blend_lists         (extension surface) per row: the union of two lists, each min-max normalised, the second weighted per item, re-ranked
+    torch.ops.rtrec_amd.factor_topk         (extension surface) per row: dense user vector x dense item vectors (f32 MFMA = the fmaf chain), filtered top-k, fused
 
 The registration lives in csrc/torch_ops.cpp (TORCH_LIBRARY / TORCH_LIBRARY_IMPL: librtrec_amd_ops.so, built by
 rtrec_amd/build.py with the host compiler); importing this module loads it and binds it to the C-ABI library
@@ -62,9 +64,10 @@ EXPORT_OF = {"column_sqnorms": "rtrec_slim_column_sqnorms", "fit_workspace_init"
              "score_pairs": "rtrec_slim_score_pairs"}
 
 # The extension surface (include/rtrec_amd_ext.h, _native.EXT_EXPORTS): the same rules -- one op per kernel-launching export
-EXT_OPS = ["diversify_lists", "list_quality", "catalogue_ranks", "blend_lists"]
+EXT_OPS = ["diversify_lists", "list_quality", "catalogue_ranks", "blend_lists", "factor_topk"]
 EXT_EXPORT_OF = {"diversify_lists": "rtrec_slim_diversify_lists", "list_quality": "rtrec_slim_list_quality",
-                 "catalogue_ranks": "rtrec_slim_catalogue_ranks", "blend_lists": "rtrec_slim_blend_lists"}
+                 "catalogue_ranks": "rtrec_slim_catalogue_ranks", "blend_lists": "rtrec_slim_blend_lists",
+                 "factor_topk": "rtrec_factor_topk"}
 
 
 def _load() -> None:

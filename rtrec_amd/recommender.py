@@ -175,6 +175,42 @@ class Recommender:
                                                   contact_counts=contact_counts, similarity_weight_factor=similarity_weight_factor,
                                                   mnz=mnz, filter_interacted=filter_interacted, as_arrays=as_arrays)
 
+    def attach_factors(self, users: List[Any], user_vectors: Any, items: List[Any], item_vectors: Any) -> "Recommender":
+        """Bring the vectors of a factor model trained elsewhere (SLIM.attach_factors): the second scorer of recommend_hybrid."""
+        self.model.attach_factors(users, user_vectors, items, item_vectors)
+        return self
+
+    def detach_factors(self) -> "Recommender":
+        self.model.detach_factors()
+        return self
+
+    def recommend_factor(self, user: Any, top_k: int = 10, filter_interacted: bool = True,
+                         candidate_items: Optional[List[Any]] = None) -> List[Any]:
+        """The attached factor model's own top-k for one user -- SLIM.recommend_factor."""
+        return self.model.recommend_factor(user, top_k=top_k, filter_interacted=filter_interacted, candidate_items=candidate_items)
+
+    def recommend_factor_batch(self, users: List[Any], top_k: int = 10, filter_interacted: bool = True,
+                               candidate_items: Optional[List[Any]] = None, as_arrays: bool = False) -> Any:
+        """SLIM.recommend_factor_batch: dense vectors against dense vectors, top-k per user, one device pass."""
+        return self.model.recommend_factor_batch(users, top_k=top_k, filter_interacted=filter_interacted,
+                                                 candidate_items=candidate_items, as_arrays=as_arrays)
+
+    def recommend_hybrid(self, user: Any, top_k: int = 10, pool: Optional[int] = None, weighting: Any = "contacts",
+                         contact_counts: Any = None, similarity_weight_factor: float = 2.0, mnz: bool = False,
+                         filter_interacted: bool = True) -> List[Any]:
+        """The reference's hybrid list for one user: the factor model's list blended with SLIM's -- SLIM.recommend_hybrid."""
+        return self.model.recommend_hybrid(user, top_k=top_k, pool=pool, weighting=weighting, contact_counts=contact_counts,
+                                           similarity_weight_factor=similarity_weight_factor, mnz=mnz,
+                                           filter_interacted=filter_interacted)
+
+    def recommend_hybrid_batch(self, users: List[Any], top_k: int = 10, pool: Optional[int] = None, weighting: Any = "contacts",
+                               contact_counts: Any = None, similarity_weight_factor: float = 2.0, mnz: bool = False,
+                               filter_interacted: bool = True, as_arrays: bool = False) -> Any:
+        """SLIM.recommend_hybrid_batch: factor top-k, SLIM's lists and the blend in one device pass."""
+        return self.model.recommend_hybrid_batch(users, top_k=top_k, pool=pool, weighting=weighting, contact_counts=contact_counts,
+                                                 similarity_weight_factor=similarity_weight_factor, mnz=mnz,
+                                                 filter_interacted=filter_interacted, as_arrays=as_arrays)
+
     def blend_batch(self, items_a: List[List[Any]], scores_a: List[List[float]], items_b: List[List[Any]], scores_b: List[List[float]],
                     top_k: int = 10, weight: float = 1.0, mnz: bool = False) -> Any:
         """SLIM.blend_batch: the same blend for two lists per row the caller brings, with a constant weight."""

@@ -29,6 +29,10 @@ the GPU), POST /recommend (one user's top-k).  Differences, all forced by the de
     reference's hybrid merge): {"user": ..., "items": [...], "scores": [...], "top_k", "pool" or absent = top_k, "weighting":
     "contacts" or a number, "contact_counts": [[item, count], ...] or absent, "similarity_weight_factor", "mnz", "filter_interacted"}
     -> {"user": ..., "items": [...]} (SLIM.recommend_blended); same token check as /rerank, answered under the model lock, not coalesced;
+  * POST /recommend_hybrid is an addition (the list of the factor model attached to the served model blended with SLIM's, the
+    reference's hybrid recommendation): {"user": ..., "top_k", "pool" or absent = top_k, "weighting", "contact_counts",
+    "similarity_weight_factor", "mnz", "filter_interacted"} -> {"user": ..., "items": [...]} (SLIM.recommend_hybrid; a model
+    without attached vectors is the shell's 500); same token check as /rerank, answered under the model lock, not coalesced;
   * concurrent POST /recommend calls are coalesced (`RecommendCoalescer`): requests that arrive within a bounded
     wait (RTREC_AMD_COALESCE_MS, default 1 ms; 0 = only what queued up behind the model lock) share ONE
     recommend_batch launch per (top_k, filter_interacted) group; each caller gets exactly what its own
@@ -109,6 +113,17 @@ class BlendedRequest(BaseModel):
     user: Any
     items: List[Any]
     scores: List[float]
+    top_k: int = 10
+    pool: Optional[int] = None
+    weighting: Any = "contacts"
+    contact_counts: Optional[List[Tuple[Any, int]]] = None
+    similarity_weight_factor: float = 2.0
+    mnz: bool = False
+    filter_interacted: bool = True
+
+
+class HybridRequest(BaseModel):
+    user: Any
     top_k: int = 10
     pool: Optional[int] = None
     weighting: Any = "contacts"
@@ -354,6 +369,15 @@ def build_router(gate: ModelGate) -> APIRouter:
             request.user, request.items, request.scores, top_k=request.top_k, pool=request.pool, weighting=request.weighting,
             contact_counts=counts, similarity_weight_factor=request.similarity_weight_factor, mnz=request.mnz,
             filter_interacted=request.filter_interacted))
+        return {"user": request.user, "items": items}
+
+    @api.post("/recommend_hybrid")
+    def recommend_hybrid(request: HybridRequest, x_token: str = Header()):
+        _authorise(x_token)
+        counts = None if request.contact_counts is None else [(request.user, i, n) for i, n in request.contact_counts]
+        items = gate.call("Recommend hybrid", lambda m: m.recommend_hybrid(
+            request.user, top_k=request.top_k, pool=request.pool, weighting=request.weighting, contact_counts=counts,
+            similarity_weight_factor=request.similarity_weight_factor, mnz=request.mnz, filter_interacted=request.filter_interacted))
         return {"user": request.user, "items": items}
 
     return api
