@@ -73,6 +73,9 @@ def lib() -> C.CDLL:
         L.slim_oracle_fit_column_sgd.argtypes = [C.c_int32, C.c_int32, _f32p, _i32p, _i32p, C.c_int32, C.c_double, C.c_double,
                                                  C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _i32p, _f32p,
                                                  C.POINTER(C.c_int32)]
+        L.slim_oracle_sgd.restype = C.c_int32
+        L.slim_oracle_sgd.argtypes = [C.c_int32, C.c_int32, _f32p, _i32p, _i32p, _f32p, C.c_double, C.c_double, C.c_double,
+                                      C.c_double, C.c_double, C.c_int32, C.c_uint32, _f32p]
         L.slim_oracle_fit_columns_mt.restype = C.c_int32
         L.slim_oracle_fit_columns_mt.argtypes = [C.c_int32, C.c_int32, _f32p, _i32p, _i32p, C.c_int32, _i32p,
                                                  C.c_double, C.c_double, C.c_double, C.c_int32, C.c_uint32,
@@ -128,6 +131,25 @@ def feature_scores(X_csc, y: np.ndarray, skip_col: int) -> np.ndarray:
     scores = np.empty(max(n_items, 1), dtype=np.float32)
     lib().slim_oracle_feature_scores(n_items, d, i, p, y, int(skip_col), scores)
     return scores[:n_items]
+
+
+def sgd(X_csr, y, alpha, l1_ratio, eta0, power_t, tol, max_iter, seed):
+    """slim_oracle_sgd on an explicit CSR matrix over the selected features and a dense y: (w float32[n_features], n_iter;
+    -1: a non-finite weight).  A row's entries are summed in the order they are STORED and their column indices need not
+    ascend (the oracle walks X_indices as given), so the arrays are handed over untouched: no sort, no duplicate merge.
+    `seed` is the xorshift seed itself (sklearn_seed(random_state)); tol = -inf is SGDRegressor's tol=None."""
+    n_samples, n_features = X_csr.shape
+    ptr = np.ascontiguousarray(X_csr.indptr, dtype=np.int32)
+    nnz = int(ptr[-1])
+    d = np.ascontiguousarray(X_csr.data[:nnz], dtype=np.float32) if nnz else np.zeros(1, np.float32)
+    i = np.ascontiguousarray(X_csr.indices[:nnz], dtype=np.int32) if nnz else np.zeros(1, np.int32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    assert y.shape == (n_samples,) and ptr.shape == (n_samples + 1,)
+    assert nnz == 0 or (0 <= int(i.min()) and int(i.max()) < n_features)
+    w = np.zeros(max(n_features, 1), dtype=np.float32)
+    n_iter = lib().slim_oracle_sgd(n_samples, n_features, d, i, ptr, y, float(alpha), float(l1_ratio), float(eta0),
+                                   float(power_t), float(tol), int(max_iter), int(seed) & 0xffffffff, w)
+    return w[:n_features], int(n_iter)
 
 
 def fit_columns_sgd(X_csc, cols, alpha=0.1, l1_ratio=0.1, eta0=0.001, tol=1e-4, max_iter=100, random_state=43,

@@ -516,8 +516,11 @@ class SlimEngine:
                 break
         n_iter = d_niter.cpu().numpy()
         if (n_iter < 0).any():
+            # n_iter follows d_t, the order fit_columns processed the targets in (longest column first), not the caller's:
+            # name the first column of the caller's list that failed, as a fit column by column would
+            failed = set(d_t.cpu().numpy()[n_iter < 0].tolist())
             raise ValueError("Floating-point under-/overflow occurred during the SGD fit of column "
-                             f"{int(targets[np.flatnonzero(n_iter < 0)[0]])}. Scaling input data with StandardScaler or "
+                             f"{next(int(j) for j in targets if int(j) in failed)}. Scaling input data with StandardScaler or "
                              "MinMaxScaler might help.")
         return d_t, d_sel, d_w, d_cnt, n_iter
 

@@ -479,6 +479,31 @@ def test_custom_ops_refuse_mistyped_tensors():
     for k, call in enumerate(bad_calls):
         with pytest.raises((RuntimeError, NotImplementedError)):
             call()
+    # fit_sgd_epochs: every tensor slot in turn with another dtype and as a host tensor, and a cap outside 1..256 -- each a
+    # RuntimeError before anything is launched.  The well-typed call is a 2 x 2 matrix, one target, one feature, one epoch.
+    def sgd_args():
+        return [torch.tensor([0, 1, 2], dtype=torch.int32, device=dev), i32(1, 2), f32(1, 2), i32(1), torch.ones(1, 1, dtype=torch.int32, device=dev),
+                torch.ones(1, dtype=torch.int32, device=dev), 2, 2, 2, 1, 0, 1, 1, 1e-4, f64(2), torch.ones(2, dtype=torch.float64, device=dev),
+                torch.ones(2, dtype=torch.float64, device=dev), f64(2), i32(3), f32(1), f32(1, 1), f32(1, 1),
+                torch.full((1,), float("inf"), dtype=torch.float64, device=dev), i32(1), i32(1), i32(1)]
+    tensor_slots = [k for k, a in enumerate(sgd_args()) if isinstance(a, torch.Tensor)]
+    assert len(tensor_slots) == 18
+    other = {torch.int32: torch.float32, torch.float32: torch.int32, torch.float64: torch.float32}
+    for k in tensor_slots:
+        for spoil in (lambda t: t.to(other[t.dtype]), lambda t: t.cpu()):
+            args = sgd_args()
+            args[k] = spoil(args[k])
+            with pytest.raises(RuntimeError):
+                ops.fit_sgd_epochs(*args)
+    for cap in (257, 0):
+        args = sgd_args()
+        args[9] = cap
+        with pytest.raises(RuntimeError):
+            ops.fit_sgd_epochs(*args)
+    args = sgd_args()
+    ops.fit_sgd_epochs(*args)
+    torch.cuda.synchronize()
+    assert int(args[-2].item()) == 1 and int(args[-1].item()) == 0          # max_iter = 1 reached, nobody unfinished
     # and a well-typed call goes through
     vals = torch.arange(8, dtype=torch.float32, device=dev)
     out = f32(1)

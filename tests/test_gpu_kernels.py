@@ -803,6 +803,18 @@ def test_fit_path_randomised_parity():
     assert run(40, seed=5, log=messages.append) == 0, messages
 
 
+def test_sgd_path_randomised_parity():
+    """tools/fuzz_fit.py run_sgd: random shapes, K 1..256, penalties, learning rates, epochs, tol, seeds and signed ratings
+    through SlimEngine.fit_columns_sgd -- feature sets, coefficient bits and n_iter against the oracle.  Seed 4 is the first
+    seed whose first 12 configurations hold all of: a K above 192 on a 300-item matrix, a K in 65..128, tol=None, negative
+    ratings, and eta0 = 0.3 with alpha = 1.0 (tests/test_sgd_host.py asserts that on the CPU); they also hold the fuzzer's
+    largest shape, 2500 users at 40 epochs.  Measured on the MI355X: 12 configurations 0.72 s, the 40 run here 0.88 s."""
+    from tests.test_sgd_host import FUZZ_N, FUZZ_SEED
+    from tools.fuzz_fit import run_sgd
+    messages = []
+    assert run_sgd(FUZZ_N, seed=FUZZ_SEED, log=messages.append) == 0, messages
+
+
 @pytest.mark.parametrize("case", range(7))
 def test_optim_sgd_on_the_gpu_matches_the_reference(case):
     """optim="sgd" (slim_elastic.py:209-222: scikit-learn SGDRegressor behind FeatureSelectionWrapper) on the device

@@ -61,15 +61,11 @@ def run(iters: int, seed: int, log=print) -> int:
     return bad
 
 
-def run_sgd(iters: int, seed: int, log=print) -> int:
-    """optim="sgd": csrc/fit_sgd.hip against slim_oracle_sgd -- random shapes, K 1..256 (one, two, four features per lane), penalties, learning rates (large ones
-    drive the weight scale through its resets), epochs, tol (None: no early stop), seeds, signed ratings."""
-    from oracle import slim_oracle as so
-    from rtrec_amd.engine import SlimEngine
+def sgd_configs(iters: int, seed: int):
+    """The configurations run_sgd(iters, seed) runs, in its order: drawn on the host before any device work (the generator's
+    stream does not depend on a result), so a caller can see what a seed covers without a GPU."""
     from rtrec_amd.synth import interaction_matrix
     rng = np.random.default_rng(seed)
-    bad = 0
-    t0 = time.time()
     for it in range(iters):
         U = int(rng.choice([40, 150, 600, 2500]))
         I = int(rng.choice([8, 20, 90, 300]))
@@ -82,14 +78,28 @@ def run_sgd(iters: int, seed: int, log=print) -> int:
         tol = [None, 1e-4, 1e-2][int(rng.integers(0, 3))]
         rs = int(rng.integers(0, 2 ** 31 - 1))
         X = interaction_matrix(U, I, draws, seed=int(rng.integers(1, 10 ** 6)), float_ratings=bool(rng.integers(0, 2)))
-        if rng.random() < 0.3:
+        negative = bool(rng.random() < 0.3)
+        if negative:
             X.data = (X.data * np.where(rng.random(X.nnz) < 0.25, -1.0, 1.0)).astype(np.float32)
-        Xc = X.tocsc(); Xc.sort_indices()
-        eng = SlimEngine(device="cuda:0")
-        eng.set_interactions(Xc, X)
         n_t = int(rng.integers(1, min(I, 40) + 1))
         cols = np.sort(rng.choice(I, n_t, replace=False))
         cfg = dict(alpha=alpha, l1_ratio=l1_ratio, eta0=eta0, max_iter=max_iter, random_state=rs, nn_feature_selection=K)
+        yield dict(it=it, U=U, I=I, draws=draws, tol=tol, negative=negative, X=X, cols=cols, cfg=cfg)
+
+
+def run_sgd(iters: int, seed: int, log=print) -> int:
+    """optim="sgd": csrc/fit_sgd.hip against slim_oracle_sgd -- random shapes, K 1..256 (one, two, four features per lane), penalties, learning rates (large ones
+    drive the weight scale through its resets), epochs, tol (None: no early stop), seeds, signed ratings."""
+    from oracle import slim_oracle as so
+    from rtrec_amd.engine import SlimEngine
+    bad = 0
+    t0 = time.time()
+    for c in sgd_configs(iters, seed):
+        it, U, I, draws, tol, X, cols, cfg = (c[k] for k in ("it", "U", "I", "draws", "tol", "X", "cols", "cfg"))
+        n_t = len(cols)
+        Xc = X.tocsc(); Xc.sort_indices()
+        eng = SlimEngine(device="cuda:0")
+        eng.set_interactions(Xc, X)
         try:
             tg, items, coef, count, n_iter = eng.fit_columns_sgd(cols, tol=tol, **cfg)
             got_err = None
