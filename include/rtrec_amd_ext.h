@@ -237,6 +237,47 @@ int rtrec_factor_topk(int32_t n_rows, const int32_t *d_row_ids, const int32_t *d
                       int32_t filter_interacted, int32_t top_k, int32_t item_splits, int32_t *d_out_ids, float *d_out_scores,
                       int32_t *d_out_count, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * FEATURE REPRESENTATIONS  (sparse feature rows times a dense per-feature table: the vectors rtrec_factor_topk scores.)
+ * The reference's hybrid model never reads an entity's vector from a table: it builds a sparse feature row per user or item --
+ * the identity column plus the columns of its tags -- and multiplies it into LightFM's per-feature embedding and bias tables
+ * (get_user_representations(features) = features * user_biases, features * user_embeddings; scipy's csr_matvec / csr_matvecs).
+ * This call is that product, written where rtrec_factor_topk reads: training the tables is not part of this library.
+ *   rows        a CSR of feature rows d_f_ptr[n_f_rows + 1] / d_f_col[nnz] / d_f_val[nnz] (int32 / int32 / float32);
+ *               d_f_val == NULL: every value is 1.  Offsets are clamped to [0, nnz], so a malformed CSR gives wrong answers,
+ *               never an out-of-range read.  Job r takes row d_job_rows[r] (d_job_rows == NULL: row r); a value outside
+ *               [0, n_f_rows) means the job has no row.  Rows may repeat among the jobs
+ *   table       d_e[n_features][e_stride] float32 of dim_e components (e_stride >= dim_e), d_bias[n_features] float32
+ *   sum         per component c: s = +0.0f, then for the stored entries of the row IN STORAGE ORDER
+ *               s = fl(s + fl(v * e[col][c])): two correctly rounded operations per entry, never contracted to a fused
+ *               multiply-add, float32 denormals kept -- scipy's loop, so equal to `csr @ table` bit for bit.  b is the same
+ *               chain over d_bias.  An entry whose column lies outside [0, n_features) is skipped (the reference ignores the
+ *               features it has not learned); equal columns are not merged, each stored entry adds once
+ *   has         1 when the job's row stores at least one entry that is not skipped, whatever its value; else 0
+ *   layout      RTREC_FEATURE_PLAIN: width = dim_e, slots e[0 .. dim_e).  RTREC_FEATURE_USER: width = dim_e + 2, slots
+ *               [b, 1.0f, e...].  RTREC_FEATURE_ITEM: width = dim_e + 2, slots [1.0f, b, e...] -- the reference's stacking,
+ *               whose dot product is b_u + b_i + e_u . e_i (utils/factors.stack_bias).  A job with has == 0 gets +0.0f in
+ *               EVERY slot, the constant included, so that a missing vector scores 0 against everything
+ * Out, every slot of every job written: slot c of job r is d_out[r * row_stride + c * comp_stride].  Either comp_stride == 1
+ * and row_stride >= width (row-major: the user matrix d_p of rtrec_factor_topk) or row_stride == 1 and comp_stride >= n_jobs
+ * (component-major: its item matrix d_qt); what lies between the slots is not touched.  d_has[n_jobs] (uint8) may be NULL.
+ * layout outside the three above, dim_e < 1 or width > 256 (the limit of rtrec_factor_topk): RTREC_ERR_UNSUPPORTED.  Negative
+ * sizes, e_stride < dim_e, output strides of neither form, NULL required arrays (d_f_ptr with n_f_rows > 0, d_f_col with
+ * nnz > 0, d_e -- and d_bias with a stacking layout -- with n_features > 0, d_out): RTREC_ERR_INVALID_ARG.  n_jobs == 0:
+ * RTREC_OK before any pointer check.  No global state, no environment variable, no allocation, no synchronisation.  The results
+ * never depend on the grid or on scheduling: a slot is one sequential chain computed by one thread.
+ * csrc/feature_repr.hip, feature_repr_kernel: one thread per output slot (job = t / width, slot = t % width), so a wave carries
+ * 64 / width short rows; the lanes of a job share the reads of its offsets, columns and values and read neighbouring components
+ * of a table row; plain loads and stores, no LDS, no atomics.
+ * ------------------------------------------------------------------------------------- */
+#define RTREC_FEATURE_PLAIN 0
+#define RTREC_FEATURE_USER 1
+#define RTREC_FEATURE_ITEM 2
+int rtrec_feature_repr(int32_t n_jobs, const int32_t *d_job_rows, int32_t n_f_rows, const int32_t *d_f_ptr, const int32_t *d_f_col,
+                       const float *d_f_val, int64_t nnz, const float *d_e, int64_t e_stride, int32_t n_features, int32_t dim_e,
+                       const float *d_bias, int32_t layout, float *d_out, int64_t row_stride, int64_t comp_stride, uint8_t *d_has,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

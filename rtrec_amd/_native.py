@@ -18,6 +18,7 @@ _lib: Optional[C.CDLL] = None
 RTREC_OK = 0
 TOPK_SPARSE, TOPK_DENSE, TOPK_CANDIDATES = 0, 1, 2
 BLEND_CONSTANT, BLEND_CONTACTS = 0, 1      # weight_mode of rtrec_slim_blend_lists (include/rtrec_amd_ext.h)
+FEATURE_PLAIN, FEATURE_USER, FEATURE_ITEM = 0, 1, 2      # layout of rtrec_feature_repr (include/rtrec_amd_ext.h)
 _STATUS = {0: "ok", -1: "invalid argument", -2: "unsupported parameter", -3: "workspace too small",
            -4: "kernel launch failed"}
 
@@ -54,6 +55,7 @@ EXT_EXPORTS = [
     "rtrec_slim_catalogue_ranks",
     "rtrec_slim_blend_lists",
     "rtrec_factor_topk",
+    "rtrec_feature_repr",
 ]
 
 
@@ -231,6 +233,8 @@ def load() -> C.CDLL:
     L.rtrec_factor_topk.restype = C.c_int
     L.rtrec_factor_topk.argtypes = [i32, vp, vp, i32, vp, C.c_int64, i32, vp, C.c_int64, i32, i32, vp, vp, vp, C.c_int64, i32, i32, i32,
                                     vp, vp, vp, vp, C.c_size_t, vp]
+    L.rtrec_feature_repr.restype = C.c_int
+    L.rtrec_feature_repr.argtypes = [i32, vp, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, i32, i32, vp, i32, vp, C.c_int64, C.c_int64, vp, vp]
     _lib = L
     return L
 

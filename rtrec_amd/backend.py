@@ -336,6 +336,15 @@ class HipBackend:
         self.ops.factor_topk(row_ids, p_index, int(n_x_rows), p, qt, int(n_items), int(dim), item_mask, xb[0], xb[1],
                              bool(filter_interacted), int(top_k), splits, ids, scores, count, ws)
 
+    def feature_repr(self, job_rows, f_csr, table, dim_e, bias, layout, n_jobs, out, row_stride, comp_stride, has):
+        """Per job: its sparse feature row (row job_rows[r] of `f_csr` = (ptr, col, val or None); job_rows None: row r) times the
+        per-feature `table` [n_features, >= dim_e] -- an ordered, unfused float32 chain per slot -- stacked by `layout`
+        (_native.FEATURE_PLAIN / FEATURE_USER / FEATURE_ITEM, the latter two with `bias` [n_features]) and written to
+        out.flatten()[r * row_stride + c * comp_stride]; has [n_jobs] uint8 or None (csrc/feature_repr.hip;
+        include/rtrec_amd_ext.h)."""
+        self.ops.feature_repr(job_rows, f_csr[0], f_csr[1], f_csr[2], table, int(dim_e), bias, int(layout), int(n_jobs), out,
+                              int(row_stride), int(comp_stride), has)
+
     def audience_workspace_bytes(self, n_users, n_q, top_n):
         return int(self.lib.rtrec_slim_audience_workspace_bytes(n_users, n_q, top_n))
 

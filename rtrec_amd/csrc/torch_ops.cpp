@@ -56,6 +56,7 @@ struct Abi {
     decltype(&rtrec_slim_catalogue_ranks) catalogue_ranks = nullptr;
     decltype(&rtrec_slim_blend_lists) blend_lists = nullptr;
     decltype(&rtrec_factor_topk) factor_topk = nullptr;
+    decltype(&rtrec_feature_repr) feature_repr = nullptr;
 };
 Abi g_abi;
 
@@ -729,6 +730,48 @@ void factor_topk(const OT &row_ids, const OT &p_index, int64_t n_x_rows, const a
           "rtrec_factor_topk");
 }
 
+// f_ptr [n_f_rows + 1] / f_col [nnz] / f_val [nnz] (absent = all ones): the feature rows as a CSR; e [n_features, >= dim_e] float32
+// and bias [n_features] (needed by layout 1 / 2): the per-feature table; job_rows [n_jobs] names the row of a job (absent = row r);
+// slot c of job r is written to out.flatten()[r * row_stride + c * comp_stride] (out: any contiguous float32 tensor that holds the
+// last slot), has [n_jobs] uint8 (include/rtrec_amd_ext.h, "FEATURE REPRESENTATIONS").
+void feature_repr(const OT &job_rows, const at::Tensor &f_ptr, const at::Tensor &f_col, const OT &f_val, const at::Tensor &e, int64_t dim_e,
+                  const OT &bias, int64_t layout, int64_t n_jobs, at::Tensor out, int64_t row_stride, int64_t comp_stride, const OT &has_out) {
+    TORCH_CHECK(layout >= 0 && layout <= 2, "feature_repr: layout must be 0 (plain), 1 (user stacking) or 2 (item stacking), got ", layout);
+    const int64_t width = dim_e + (layout == 0 ? 0 : 2);
+    TORCH_CHECK(dim_e >= 1 && width <= 256, "feature_repr: dim_e must lie in 1..", 256 - (layout == 0 ? 0 : 2), ", got ", dim_e);
+    TORCH_CHECK(n_jobs >= 0 && n_jobs <= INT32_MAX, "feature_repr: n_jobs must lie in 0..2^31-1");
+    TORCH_CHECK(f_ptr.numel() >= 1 && f_ptr.numel() - 1 <= INT32_MAX, "feature_repr: f_ptr must hold n_f_rows + 1 offsets");
+    TORCH_CHECK(e.dim() == 2 && e.size(1) >= dim_e && e.size(0) <= INT32_MAX, "feature_repr: e must be [n_features, >= dim_e]");
+    const auto has = [](const OT &t) { return t.has_value() && t->defined(); };
+    TORCH_CHECK(!has(f_val) || f_val->numel() == f_col.numel(), "feature_repr: f_val must hold one value per entry of f_col");
+    TORCH_CHECK(!has(job_rows) || job_rows->numel() == n_jobs, "feature_repr: job_rows must hold one entry per job");
+    TORCH_CHECK(layout == 0 || (has(bias) && bias->numel() == e.size(0)), "feature_repr: a stacking layout needs one bias per feature");
+    TORCH_CHECK((comp_stride == 1 && row_stride >= width) || (row_stride == 1 && comp_stride >= n_jobs),
+                "feature_repr: the output is row-major (comp_stride 1, row_stride >= width) or component-major (row_stride 1, "
+                "comp_stride >= n_jobs), got row_stride ", row_stride, " and comp_stride ", comp_stride);
+    TORCH_CHECK(n_jobs == 0 || out.numel() > (n_jobs - 1) * row_stride + (width - 1) * comp_stride,
+                "feature_repr: out does not hold the last slot");
+    if (has(has_out)) {
+        TORCH_CHECK(has_out->numel() >= n_jobs && (has_out->scalar_type() == at::kByte || has_out->scalar_type() == at::kBool),
+                    "feature_repr: has must hold one uint8 / bool entry per job");
+        check_tensor<void>(*has_out);
+    }
+    check_tensor<const int32_t>(f_ptr); check_tensor<const int32_t>(f_col); check_tensor<const float>(e); check_tensor<float>(out);
+    if (has(f_val)) check_tensor<const float>(*f_val);
+    if (has(bias)) check_tensor<const float>(*bias);
+    if (has(job_rows)) check_tensor<const int32_t>(*job_rows);
+    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&f_ptr, &f_col, &e})
+        TORCH_CHECK(t->device() == out.device(), "feature_repr: all tensors must live on one device");
+    for (const OT *t : std::initializer_list<const OT *>{&job_rows, &f_val, &bias, &has_out})
+        TORCH_CHECK(!has(*t) || (*t)->device() == out.device(), "feature_repr: all tensors must live on one device");
+    check(abi().feature_repr(static_cast<int32_t>(n_jobs), ptr<const int32_t>(job_rows), static_cast<int32_t>(f_ptr.numel() - 1),
+                             ptr<const int32_t>(f_ptr), ptr<const int32_t>(f_col), ptr<const float>(f_val), f_col.numel(),
+                             ptr<const float>(e), e.size(1), static_cast<int32_t>(e.size(0)), static_cast<int32_t>(dim_e),
+                             ptr<const float>(bias), static_cast<int32_t>(layout), ptr<float>(out), row_stride, comp_stride,
+                             has(has_out) && has_out->numel() > 0 ? static_cast<uint8_t *>(has_out->data_ptr()) : nullptr, stream_of(out)),
+          "rtrec_feature_repr");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -766,6 +809,7 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.catalogue_ranks, "rtrec_slim_catalogue_ranks");
         bind_one(h, a.blend_lists, "rtrec_slim_blend_lists");
         bind_one(h, a.factor_topk, "rtrec_factor_topk");
+        bind_one(h, a.feature_repr, "rtrec_feature_repr");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -844,6 +888,8 @@ TORCH_LIBRARY(rtrec_amd, m) {
     m.def("factor_topk(Tensor? row_ids, Tensor? p_index, int n_x_rows, Tensor p, Tensor qt, int n_items, int dim, Tensor? item_mask, "
           "Tensor? xb_ptr, Tensor? xb_col, bool filter_interacted, int top_k, int item_splits, Tensor(a!) ids, Tensor(b!) scores, "
           "Tensor(c!) count, Tensor(d!)? workspace) -> ()");
+    m.def("feature_repr(Tensor? job_rows, Tensor f_ptr, Tensor f_col, Tensor? f_val, Tensor e, int dim_e, Tensor? bias, int layout, "
+          "int n_jobs, Tensor(a!) out, int row_stride, int comp_stride, Tensor(b!)? has) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -874,4 +920,5 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("catalogue_ranks", &catalogue_ranks);
     m.impl("blend_lists", &blend_lists);
     m.impl("factor_topk", &factor_topk);
+    m.impl("feature_repr", &feature_repr);
 }

@@ -1952,21 +1952,170 @@ class SlimEngine:
             raise ValueError(f"item_mask must hold one entry per item ({n_items}), got {m.shape}")
         return self.be.to_dev((m != 0).astype(np.uint8))
 
+    @staticmethod
+    def _feature_csr(features, n_cols: int, what: str) -> sp.csr_matrix:
+        """`features` as a float32 CSR over `n_cols` table rows, its entries in the order they are stored (the kernel adds them
+        in that order: nothing is sorted or merged here)."""
+        F = features if sp.isspmatrix_csr(features) else sp.csr_matrix(features)
+        if F.shape[1] != n_cols:
+            raise ValueError(f"{what} must have one column per row of its table ({n_cols}), got {F.shape[1]}")
+        if F.nnz >= 2 ** 31:
+            raise ValueError(f"{what} stores {F.nnz} entries; offsets are int32")
+        if F.dtype != np.float32:
+            F = sp.csr_matrix((SlimEngine._as_float32(F.data, what), F.indices, F.indptr), shape=F.shape)
+        return F
+
+    def _upload_feature_csr(self, F: sp.csr_matrix):
+        """(ptr, col, val or None) device tensors of a feature CSR; all-ones values are not uploaded (d_f_val == NULL)."""
+        val = None if (F.data == 1.0).all() else self._up(np.ascontiguousarray(F.data, dtype=np.float32))
+        return self._up(F.indptr.astype(np.int32)), self._up(F.indices.astype(np.int32)), val
+
+    def _feature_table(self, table, bias, what: str) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        E = self._as_float32(table, f"{what}_table")
+        if E.ndim != 2:
+            raise ValueError(f"{what}_table must be a matrix [features, components], got {E.shape}")
+        b = None
+        if bias is not None:
+            b = self._as_float32(bias, f"{what}_bias").reshape(-1)
+            if b.shape[0] != E.shape[0]:
+                raise ValueError(f"{what}_bias must hold one entry per row of {what}_table ({E.shape[0]}), got {b.shape[0]}")
+        return E, b
+
+    def set_feature_factors(self, user_features, user_table, item_features, item_table, user_bias=None, item_bias=None) -> None:
+        """The vectors of a factor model with feature rows, computed on the device: `user_features` is a scipy CSR with one row
+        per row of the resident X and one column per row of `user_table` [user features, dim_e] (float32 numbers: LightFM's
+        user_embeddings), `item_features` / `item_table` the same over the items of W; `user_bias` / `item_bias` [features]
+        go in on both sides or on neither and are stacked as the reference stacks them ([b, 1, e...] . [1, b, e...]).  An
+        entity's vector is its feature row times the table, entry by entry in storage order with a separately rounded
+        multiply and add (csrc/feature_repr.hip; the comment of rtrec_feature_repr in include/rtrec_amd_ext.h), written
+        straight into the matrices factor_topk reads -- the item matrix component-major, no host transpose.  A row without
+        an entry in range has no vector (users) or is never listed (items).  The tables stay on the device for
+        feature_vectors_device().  Leaves the engine as set_factors() leaves it."""
+        from ._native import FEATURE_ITEM, FEATURE_PLAIN, FEATURE_USER
+        be, torch = self.be, self.be.torch
+        if (user_bias is None) != (item_bias is None):
+            raise ValueError("biases go in on both sides or on neither: the stacked slots pair a bias with a constant 1")
+        Eu, bu = self._feature_table(user_table, user_bias, "user")
+        Ei, bi = self._feature_table(item_table, item_bias, "item")
+        if Eu.shape[1] != Ei.shape[1]:
+            raise ValueError(f"user_table and item_table must have one width, got {Eu.shape} and {Ei.shape}")
+        dim_e = int(Eu.shape[1])
+        dim = dim_e + (2 if bu is not None else 0)
+        if dim_e < 1 or dim > self.FACTOR_MAX_DIM:
+            raise ValueError(f"factor vectors of 1..{self.FACTOR_MAX_DIM} components are supported (the two bias slots included), got {dim}")
+        if not self._X:
+            raise RuntimeError("set_interactions() must be called before set_feature_factors")
+        n_users = self.n_users
+        n_items = int(self._W["n_items"]) if self._W else self.n_items
+        Fu = self._feature_csr(user_features, Eu.shape[0], "user_features")
+        Fi = self._feature_csr(item_features, Ei.shape[0], "item_features")
+        if Fu.shape[0] != n_users:
+            raise ValueError(f"user_features must have one row per row of the resident X ({n_users}), got {Fu.shape[0]}")
+        if Fi.shape[0] != n_items:
+            raise ValueError(f"item_features must have one row per item of the catalogue ({n_items}), got {Fi.shape[0]}")
+        sides = {"user": {"e": be.to_dev(Eu), "bias": None if bu is None else be.to_dev(bu), "dim_e": dim_e,
+                          "layout": FEATURE_PLAIN if bu is None else FEATURE_USER},
+                 "item": {"e": be.to_dev(Ei), "bias": None if bi is None else be.to_dev(bi), "dim_e": dim_e,
+                          "layout": FEATURE_PLAIN if bi is None else FEATURE_ITEM}}
+        p = be.empty((n_users, dim), torch.float32)
+        p_has = be.empty((n_users,), torch.uint8)
+        qt = be.empty((dim, n_items), torch.float32)
+        q_has = be.empty((n_items,), torch.uint8)
+        if n_users:
+            be.feature_repr(None, self._upload_feature_csr(Fu), sides["user"]["e"], dim_e, sides["user"]["bias"], sides["user"]["layout"],
+                            n_users, p, dim, 1, p_has)
+        if n_items:
+            be.feature_repr(None, self._upload_feature_csr(Fi), sides["item"]["e"], dim_e, sides["item"]["bias"], sides["item"]["layout"],
+                            n_items, qt, 1, n_items, q_has)
+        rows = torch.arange(n_users, dtype=torch.int32, device=p.device)
+        index = torch.where(p_has != 0, rows, torch.full_like(rows, -1))
+        self._F = {"p": p, "qt": qt, "index": index, "mask": q_has, "dim": dim, "n_p": n_users, "n_items": n_items, "tables": sides}
+
+    def feature_vectors_device(self, features_csr, side: str = "user"):
+        """(vectors[n, dim] float32, has[n] uint8) device tensors for ad-hoc feature rows -- request-time tags, cold users --
+        against the table set_feature_factors() kept for `side` ("user" or "item"): the same chain, the same stacking."""
+        be, torch = self.be, self.be.torch
+        tables = self._F.get("tables") if self.has_factors() else None
+        if tables is None:
+            raise RuntimeError("set_feature_factors() must be called before feature_vectors_device")
+        if side not in tables:
+            raise ValueError(f"side must be 'user' or 'item', got {side!r}")
+        T = tables[side]
+        F = self._feature_csr(features_csr, int(T["e"].shape[0]), "features_csr")
+        n, dim = int(F.shape[0]), int(self._F["dim"])
+        vec = be.empty((n, dim), torch.float32)
+        has = be.empty((n,), torch.uint8)
+        if n:
+            be.feature_repr(None, self._upload_feature_csr(F), T["e"], T["dim_e"], T["bias"], T["layout"], n, vec, dim, 1, has)
+        return vec, has
+
     def clear_factors(self) -> None:
         self._F = {}
 
     def has_factors(self) -> bool:
         return bool(getattr(self, "_F", None))
 
+    def _factor_topk_brought(self, rows: np.ndarray, vectors, vector_has, mask, filter_interacted: bool, top_k: int,
+                             item_splits: int, ids, scores, count) -> None:
+        """The jobs of factor_topk_device that bring their own vectors (`vectors` [n_rows, >= dim], `vector_has` [n_rows] uint8
+        or None).  A job whose row lies outside X is a cold user: its vector is scored over the catalogue with nothing
+        filtered (the op with row_ids = NULL and the brought matrix as `p`).  A job with a row of X -- request-time tags of a
+        known user -- is scored against that row: a temporary index over X's rows points into the brought matrix, and since
+        an index names one vector per row, a batch that names a row twice is split into rounds in which each row occurs once."""
+        be, torch = self.be, self.be.torch
+        F = self._F
+        dev = vectors.device
+        n_users = self.n_users
+
+        def run(pos: np.ndarray, warm: bool) -> None:
+            whole = len(pos) == len(rows)
+            d_pos = None if whole else be.to_dev(pos.astype(np.int64))
+            p = vectors if whole else vectors.index_select(0, d_pos)
+            local = torch.arange(len(pos), dtype=torch.int32, device=dev)
+            if vector_has is not None:
+                h = vector_has if whole else vector_has.index_select(0, d_pos)
+                local = torch.where(h != 0, local, torch.full_like(local, -1))
+            o_ids, o_sc = (ids, scores) if whole else (be.empty((len(pos), top_k), torch.int32), be.empty((len(pos), top_k), torch.float32))
+            o_cnt = count if whole else be.zeros((len(pos),), torch.int32)
+            if warm:
+                d_x = be.to_dev(rows[pos].astype(np.int64))
+                index = torch.full((n_users,), -1, dtype=torch.int32, device=dev)
+                index[d_x] = local
+                be.factor_topk(d_x.to(torch.int32), index, n_users, p, F["qt"], F["n_items"], F["dim"], mask,
+                               self._x_csr() if filter_interacted else None, bool(filter_interacted), top_k, o_ids, o_sc, o_cnt,
+                               item_splits=item_splits)
+            else:
+                be.factor_topk(None, local if vector_has is not None else None, len(pos), p, F["qt"], F["n_items"], F["dim"], mask,
+                               None, False, top_k, o_ids, o_sc, o_cnt, item_splits=item_splits)
+            if not whole:
+                ids[d_pos], scores[d_pos], count[d_pos] = o_ids, o_sc, o_cnt
+
+        in_x = (rows >= 0) & (rows < n_users)
+        if (~in_x).any():
+            run(np.flatnonzero(~in_x), False)
+        if in_x.any():
+            pos = np.flatnonzero(in_x)
+            order = np.argsort(rows[pos], kind="stable")
+            srt = rows[pos][order]
+            first = np.r_[0, np.flatnonzero(np.diff(srt)) + 1]
+            occ = np.empty(len(pos), dtype=np.int64)          # the how-manieth job of its row
+            occ[order] = np.arange(len(pos)) - np.repeat(first, np.diff(np.r_[first, len(pos)]))
+            for k in range(int(occ.max()) + 1):
+                run(pos[occ == k], True)
+
     def factor_topk_device(self, d_rows, n_rows: int, top_k: int, filter_interacted: bool = True, item_mask=None,
-                           item_splits: int = 0):
+                           item_splits: int = 0, vectors=None, vector_has=None):
         """Device tensors (ids[n_rows, top_k] int32, scores[n_rows, top_k] float32, count[n_rows] int32): per row `d_rows[r]`
         of the resident X (int32 device tensor; None = rows 0 .. n_rows-1) the best top_k items by the dot product of the
         row's vector with the item vectors -- a float32 fmaf chain over ascending components -- among the items the resident
         mask and `item_mask` (a uint8 device tensor over the items, or None) admit and, with `filter_interacted`, the row does
         not store; the larger score first, the lower id among equal ones; -1 / -inf behind count.  A row without a vector, or
         outside X, gets an empty list.  The contract is the comment of rtrec_factor_topk in include/rtrec_amd_ext.h.
-        `item_splits`: catalogue chunks per row block, 0 = the library's choice; the answer never depends on it."""
+        `item_splits`: catalogue chunks per row block, 0 = the library's choice; the answer never depends on it.
+        `vectors` [n_rows, dim] (a float32 device tensor, e.g. from feature_vectors_device) makes every job bring its own
+        vector instead of the resident one of its row, `vector_has` [n_rows] uint8 says which jobs have one (None: all): a
+        job with a row of X is scored against that row as usual, a job WITHOUT one (row < 0 or beyond X: a cold user) is
+        scored over the catalogue with nothing filtered.  `d_rows` may then be a host array (it is read on the host)."""
         be, torch = self.be, self.be.torch
         if not self.has_factors():
             raise RuntimeError("set_factors() must be called before factor_topk")
@@ -1992,18 +2141,34 @@ class SlimEngine:
         count = be.zeros((n_rows,), torch.int32)
         if n_rows == 0:
             return ids, scores, count
+        if vectors is not None:
+            if vectors.dim() != 2 or int(vectors.shape[0]) != n_rows or int(vectors.shape[1]) < F["dim"] or vectors.dtype != torch.float32:
+                raise ValueError(f"vectors must be a float32 tensor [n_rows = {n_rows}, >= dim = {F['dim']}], got {tuple(vectors.shape)}")
+            if vector_has is not None and int(vector_has.numel()) != n_rows:
+                raise ValueError(f"vector_has must hold one entry per job ({n_rows})")
+            rows = (np.arange(n_rows) if d_rows is None else
+                    np.asarray(d_rows.cpu().numpy() if hasattr(d_rows, "cpu") else d_rows)).astype(np.int64).reshape(-1)
+            if len(rows) != n_rows:
+                raise ValueError(f"d_rows must hold one entry per job ({n_rows})")
+            self._factor_topk_brought(rows, vectors.contiguous(), vector_has, mask, bool(filter_interacted), top_k, int(item_splits),
+                                      ids, scores, count)
+            return ids, scores, count
         be.factor_topk(d_rows, F["index"], self.n_users, F["p"], F["qt"], F["n_items"], F["dim"], mask,
                        self._x_csr() if filter_interacted else None, bool(filter_interacted), top_k, ids, scores, count,
                        item_splits=int(item_splits))
         return ids, scores, count
 
     def factor_topk_rows(self, row_ids: Sequence[int], top_k: int = 10, filter_interacted: bool = True,
-                         item_mask: Optional[np.ndarray] = None, item_splits: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """factor_topk_device for host row ids (a row outside X gets an empty list): numpy (ids[B, top_k], scores, count[B])."""
+                         item_mask: Optional[np.ndarray] = None, item_splits: int = 0, vectors=None, vector_has=None
+                         ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """factor_topk_device for host row ids (a row outside X gets an empty list -- or, with brought `vectors`, is a cold
+        user): numpy (ids[B, top_k], scores, count[B])."""
         rows = np.asarray(row_ids, dtype=np.int64).reshape(-1)
-        d_rows = self._up(np.where((rows >= 0) & (rows < self.n_users), rows, -1).astype(np.int32))
+        rows = np.where((rows >= 0) & (rows < self.n_users), rows, -1).astype(np.int32)
+        d_rows = rows if vectors is not None else self._up(rows)
         d_mask = None if item_mask is None else self._upload_item_mask(item_mask, self._F["n_items"] if self._F else self.n_items)
-        out = self.factor_topk_device(d_rows, len(rows), top_k, filter_interacted, d_mask, item_splits)
+        out = self.factor_topk_device(d_rows, len(rows), top_k, filter_interacted, d_mask, item_splits, vectors=vectors,
+                                      vector_has=vector_has)
         return tuple(t.cpu().numpy() for t in out)
 
     # ------------------------------------------------------------------------------ catalogue ranks of held-out items

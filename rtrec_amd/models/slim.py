@@ -1143,6 +1143,76 @@ class SLIM(BaseModel):
         self._factors_on_device = None
         return self
 
+    def attach_feature_factors(self, users: Iterable[Any], user_tags: Iterable[Any], user_table: Any, items: Iterable[Any],
+                               item_tags: Iterable[Any], item_table: Any, user_bias: Any = None, item_bias: Any = None) -> "SLIM":
+        """Bring the per-FEATURE tables of a factor model trained with feature rows (an exported LightFM model trained the
+        reference's way: `model.user_embeddings` / `model.user_biases` go in as they are): `user_table`
+        [len(users) + len(user_tags), dim_e] holds first the identity rows of the raw ids `users`, then the rows of the tag
+        strings `user_tags`; `item_table` the same for `items` / `item_tags`; `user_bias` / `item_bias` (one entry per table
+        row) go in on both sides or on neither.  Where attach_factors() wants one finished vector per id, the vector of an
+        entity is computed here, on the device (csrc/feature_repr.hip): its feature row -- the identity column, then the
+        columns of its tags (utils/factors.feature_rows) -- times the table, stacked [b, 1, e...] / [1, b, e...] as the
+        reference stacks biases.  The tags are those registered with register_user_feature / register_item_feature; a tag
+        registered or cleared later is seen by the next call.  `users_tags` of recommend_factor_batch /
+        recommend_hybrid_batch replace a user's registered tags for one call and give an unknown user a vector of its own.
+        Ids the model does not know are dropped (their table rows are never read); a tag the table does not know is
+        skipped.  Values that are not float32 numbers are refused.  Travels with a pickle of the model; detach_factors()
+        clears it."""
+        from ..engine import SlimEngine
+        users, items, user_tags, item_tags = list(users), list(items), list(user_tags), list(item_tags)
+        if (user_bias is None) != (item_bias is None):
+            raise ValueError("attach_feature_factors takes biases on both sides or on neither: the stacked vectors pair a bias "
+                             "with a constant 1 on the other side")
+        tables = {}
+        for side, ids, tags, table, bias in (("user", users, user_tags, user_table, user_bias), ("item", items, item_tags, item_table, item_bias)):
+            E = SlimEngine._as_float32(table, f"{side}_table")
+            if E.ndim != 2 or E.shape[0] != len(ids) + len(tags):
+                raise ValueError(f"{side}_table needs one row per id and then one per tag ({len(ids)} + {len(tags)}), got {E.shape}")
+            b = None
+            if bias is not None:
+                b = SlimEngine._as_float32(bias, f"{side}_bias").reshape(-1)
+                if b.shape[0] != E.shape[0]:
+                    raise ValueError(f"{side}_bias needs one entry per row of {side}_table ({E.shape[0]}), got {b.shape[0]}")
+            tables[side] = (E, b)
+        dim_e = tables["user"][0].shape[1]
+        if tables["item"][0].shape[1] != dim_e:
+            raise ValueError(f"user_table and item_table must have one width, got {tables['user'][0].shape} and {tables['item'][0].shape}")
+        dim = dim_e + (2 if user_bias is not None else 0)
+        if dim_e < 1 or dim > SlimEngine.FACTOR_MAX_DIM:
+            raise ValueError(f"factor vectors of 1..{SlimEngine.FACTOR_MAX_DIM} components are supported (the two bias slots "
+                             f"included), got {dim}")
+        uid = self._ids_or_minus_one(users, self._known_user_id)
+        iid = self._ids_or_minus_one(items, self.item_ids.get_id)
+        self._factors = {"kind": "features",
+                         "user_rows": uid[uid >= 0], "user_cols": np.flatnonzero(uid >= 0), "user_tags": user_tags,
+                         "user_table": tables["user"][0], "user_bias": tables["user"][1],
+                         "item_rows": iid[iid >= 0], "item_cols": np.flatnonzero(iid >= 0), "item_tags": item_tags,
+                         "item_table": tables["item"][0], "item_bias": tables["item"][1]}
+        self._factors_on_device = None
+        return self
+
+    def has_feature_factors(self) -> bool:
+        return self._factors is not None and self._factors.get("kind") == "features"
+
+    def _feature_rows_of(self, side: str, ids: np.ndarray, tags: Optional[List[Any]] = None):
+        """The feature rows (utils/factors.feature_rows) of the internal ids `ids` of `side` ("user" / "item"; a negative id:
+        an entity without an identity, a cold user) against the attached table: with `tags` None the tags registered in the
+        feature store, else one tag list per id that REPLACES them."""
+        from ..utils.factors import feature_rows
+        F = self._factors
+        n_ids = int(F[f"{side}_table"].shape[0]) - len(F[f"{side}_tags"])
+        tag_cols = {t: n_ids + j for j, t in enumerate(F[f"{side}_tags"])}
+        ids = np.asarray(ids, dtype=np.int64)
+        rows, cols = F[f"{side}_rows"], F[f"{side}_cols"]
+        ident_of = np.full(max(int(rows.max()) + 1 if len(rows) else 0, int(ids.max()) + 1 if len(ids) else 0, 1), -1, dtype=np.int64)
+        ident_of[rows] = cols
+        ident = np.where(ids >= 0, ident_of[np.maximum(ids, 0)], -1)
+        if tags is None:
+            store = self.feature_store._users if side == "user" else self.feature_store._items
+            vocab, by_entity = store.vocab, store.by_entity
+            tags = [[vocab[f] for f in by_entity.get(int(e), ())] if by_entity else () for e in ids]
+        return feature_rows(ident, tags, tag_cols, int(F[f"{side}_table"].shape[0]))
+
     def detach_factors(self) -> "SLIM":
         self._factors = None
         self._factors_on_device = None
@@ -1160,6 +1230,16 @@ class SLIM(BaseModel):
             raise RuntimeError(f"attach_factors() must be called before {what}.")
         eng, F = self.model.engine, self._factors
         n_users, n_items = eng.n_users, self.model.n_items_fitted
+        if F.get("kind") == "features":
+            # the vectors are computed on the device from the tables and the registered tags: a tag registered or cleared
+            # since (FeatureStore.version) makes them stale, as the reference rebuilds its feature matrices per call
+            stamp = (id(F), n_users, n_items, id(eng), id(self.feature_store), self.feature_store.version)
+            if self._factors_on_device is None or self._factors_on_device[0] != stamp or not eng.has_factors():
+                eng.set_feature_factors(self._feature_rows_of("user", np.arange(n_users)), F["user_table"],
+                                        self._feature_rows_of("item", np.arange(n_items)), F["item_table"],
+                                        user_bias=F["user_bias"], item_bias=F["item_bias"])
+                self._factors_on_device = (stamp, eng._F["index"].cpu().numpy() >= 0)
+            return self._factors_on_device[1]
         stamp = (id(F), n_users, n_items, id(eng))
         if self._factors_on_device is None or self._factors_on_device[0] != stamp or not eng.has_factors():
             dim = F["user_vectors"].shape[1]
@@ -1175,8 +1255,31 @@ class SLIM(BaseModel):
             self._factors_on_device = (stamp, index >= 0)
         return self._factors_on_device[1]
 
+    def _checked_users_tags(self, what: str, users: Any, users_tags: Any) -> Optional[List[List[Any]]]:
+        """`users_tags` of a recommend_factor / recommend_hybrid call as one list of tags per user, or None."""
+        if users_tags is None:
+            return None
+        if not self.has_feature_factors():
+            why = ("no factor model is attached" if self._factors is None else
+                   "attach_factors() brought one finished vector per id, which a tag cannot change")
+            raise ValueError(f"{what}: users_tags needs the per-feature tables of attach_feature_factors(): {why}")
+        if any(isinstance(t, (str, bytes)) for t in users_tags):
+            raise ValueError(f"{what}: users_tags holds one LIST of tags per user, got a string")
+        users_tags = [[] if t is None else list(t) for t in users_tags]
+        if len(users_tags) != len(users):
+            raise ValueError(f"{what}: users_tags must hold one list of tags per user, got {len(users_tags)} lists for {len(users)} users")
+        return users_tags
+
+    def _brought_user_vectors(self, uid: np.ndarray, regular: np.ndarray, users_tags: List[List[Any]]):
+        """The vectors of one call with `users_tags` (device tensors: vectors[B, dim], has[B] uint8): a known user's identity
+        column plus the tags of the call (its registered tags are replaced, as in the reference's _recommend_hot_batch), an
+        unknown user's tags alone (_cold_user_features)."""
+        rows = self._feature_rows_of("user", np.where(regular, uid, -1), users_tags)
+        return self.model.engine.feature_vectors_device(rows, "user")
+
     def recommend_factor_batch(self, users: List[Any], top_k: int = 10, filter_interacted: bool = True,
-                               candidate_items: Optional[List[Any]] = None, as_arrays: bool = False) -> Any:
+                               candidate_items: Optional[List[Any]] = None, as_arrays: bool = False,
+                               users_tags: Optional[List[List[Any]]] = None) -> Any:
         """The second scorer alone: per user the `top_k` items by the dot product of the attached user and item vectors (the
         reference's implicit.topk call of its hybrid model) -- a float32 fused multiply-add chain over ascending components,
         the larger score first, the lower internal item id among equal scores -- among the items that have a vector, that
@@ -1185,12 +1288,19 @@ class SLIM(BaseModel):
         include/rtrec_amd_ext.h).  An unknown user, a user outside the matrix and a user without a vector get the cold-start
         list `recommend_batch` gives unknown users (scores 0).  Raises ValueError unless 1 <= top_k <= 128.
 
+        `users_tags` (attach_feature_factors() only; ValueError otherwise): one list of tag strings per user that REPLACES
+        the user's registered tags for this call (an empty list: the identity alone), as in the reference.  An unknown user
+        whose tags the table knows gets the list of its tag-only vector over the catalogue (or `candidate_items`), nothing
+        filtered, scores as computed: the reference's cold start.  An unknown user without such a tag gets the cold-start
+        list as before.
+
         Returns one list of raw item ids per user, or with `as_arrays=True` (ids[B, top_k] int64 INTERNAL item ids,
         scores[B, top_k] float32, counts[B]); -1 / -inf behind counts[b]."""
         what = "recommend_factor_batch"
         top_k = int(top_k)
         if not 1 <= top_k <= self.FACTOR_MAX_K:
             raise ValueError(f"{what} needs 1 <= top_k <= {self.FACTOR_MAX_K} (what the factor kernel selects), got {top_k}")
+        users_tags = self._checked_users_tags(what, users, users_tags)
         if not self.model.is_fitted:
             raise RuntimeError(f"Model must be fitted before calling {what}.")
         if self._factors is None:
@@ -1209,8 +1319,13 @@ class SLIM(BaseModel):
             self.model._sync_weights()
             self._sync_interactions()
             has_vec = self._sync_factors(what)
-            served = regular.copy()
-            served[regular] = has_vec[uid[regular]]
+            vec = None
+            if users_tags is not None:
+                vec, d_has = self._brought_user_vectors(uid, regular, users_tags)
+                served = d_has.cpu().numpy() != 0
+            else:
+                served = regular.copy()
+                served[regular] = has_vec[uid[regular]]
             cand = None
             if candidate_items is not None:
                 cand = self._ids_or_minus_one(candidate_items, self.item_ids.get_id, n_items)
@@ -1227,7 +1342,12 @@ class SLIM(BaseModel):
                     mask = np.zeros(n_items, dtype=np.uint8)
                     mask[cand] = 1
                 pos = np.flatnonzero(served)
-                ids, sc, cnt = eng.factor_topk_rows(uid[pos], top_k, filter_interacted, item_mask=mask)
+                if vec is not None:                           # (a user without a row of X: scored unfiltered, the cold start)
+                    at = None if len(pos) == B else eng._up(pos.astype(np.int64))
+                    ids, sc, cnt = eng.factor_topk_rows(np.where(regular, uid, -1)[pos], top_k, filter_interacted, item_mask=mask,
+                                                        vectors=vec if at is None else vec.index_select(0, at))
+                else:
+                    ids, sc, cnt = eng.factor_topk_rows(uid[pos], top_k, filter_interacted, item_mask=mask)
                 out_ids[pos], out_sc[pos], out_cnt[pos] = ids, sc, cnt
         if as_arrays:
             return out_ids, out_sc, out_cnt
@@ -1236,13 +1356,15 @@ class SLIM(BaseModel):
         return [[raw_of(i) for i in id_rows[b][:cnts[b]]] for b in range(B)]
 
     def recommend_factor(self, user: Any, top_k: int = 10, filter_interacted: bool = True,
-                         candidate_items: Optional[List[Any]] = None) -> List[Any]:
-        """recommend_factor_batch for one user."""
-        return self.recommend_factor_batch([user], top_k=top_k, filter_interacted=filter_interacted, candidate_items=candidate_items)[0]
+                         candidate_items: Optional[List[Any]] = None, user_tags: Optional[List[Any]] = None) -> List[Any]:
+        """recommend_factor_batch for one user (`user_tags`: this user's list of `users_tags`)."""
+        return self.recommend_factor_batch([user], top_k=top_k, filter_interacted=filter_interacted, candidate_items=candidate_items,
+                                           users_tags=None if user_tags is None else [user_tags])[0]
 
     def recommend_hybrid_batch(self, users: List[Any], top_k: int = 10, pool: Optional[int] = None, weighting: Any = "contacts",
                                contact_counts: Optional[Iterable[Tuple[Any, Any, int]]] = None, similarity_weight_factor: float = 2.0,
-                               mnz: bool = False, filter_interacted: bool = True, as_arrays: bool = False) -> Any:
+                               mnz: bool = False, filter_interacted: bool = True, as_arrays: bool = False,
+                               users_tags: Optional[List[List[Any]]] = None) -> Any:
         """The reference's hybrid list in one device pass: the factor scorer's top-`pool` (recommend_factor_batch's list, from
         the attached vectors) and SLIM's top-`pool` are blended as `recommend_blended_batch` blends a brought list with SLIM's
         -- both min-max normalised, SLIM's part weighted per item (`weighting`, `contact_counts`, `similarity_weight_factor`,
@@ -1251,6 +1373,11 @@ class SLIM(BaseModel):
         are downloaded.  `pool` defaults to `top_k`, as in the reference.  An unknown user has no row, so both sides and the
         list are empty; a known user without a vector gets SLIM's side alone.  With several ranks every rank computes the same
         lists (the scoring pass is the usual collective; the factor lists are computed locally, no exchange).
+
+        `users_tags` (attach_feature_factors() only; ValueError otherwise): one list of tag strings per user that REPLACES
+        the user's registered tags on the factor side for this call, as in the reference.  An unknown user whose tags the
+        table knows gets the factor list of its tag-only vector ALONE -- over the whole catalogue, nothing filtered, cut to
+        `top_k`, the scores as computed, source 1: the reference's cold start.
 
         Raises ValueError unless 1 <= top_k and 1 <= pool <= 128: the factor kernel keeps a user's candidates in LDS and
         selects at most 128 per user (SLIM's side alone would take 1024); and for what `recommend_blended_batch` refuses.
@@ -1269,6 +1396,7 @@ class SLIM(BaseModel):
         k = float(similarity_weight_factor)
         if not k >= 0.0:
             raise ValueError(f"{what}: similarity_weight_factor must not be negative or NaN, got {similarity_weight_factor}")
+        users_tags = self._checked_users_tags(what, users, users_tags)
         if not self.model.is_fitted:
             raise RuntimeError(f"Model must be fitted before calling {what}.")
         if self._factors is None:
@@ -1293,7 +1421,11 @@ class SLIM(BaseModel):
             self._sync_factors(what)
             rows = np.where(regular, uid, -1).astype(np.int32)
             d_rows = eng._up(rows)
-            a_ids, a_sc, a_cnt = eng.factor_topk_device(d_rows, B, k_pool, filter_interacted)     # (row -1: an empty list)
+            if users_tags is None:
+                a_ids, a_sc, a_cnt = eng.factor_topk_device(d_rows, B, k_pool, filter_interacted)     # (row -1: an empty list)
+            else:                       # the vectors of this call's tags; a user without a row is scored unfiltered (cold start)
+                vec, d_has = self._brought_user_vectors(uid, regular, users_tags)
+                a_ids, a_sc, a_cnt = eng.factor_topk_device(rows, B, k_pool, filter_interacted, vectors=vec, vector_has=d_has)
             b_ids, b_sc, b_cnt = self._slim_pool_device(rows, regular, k_pool, filter_interacted, mode)
             cn = self._contact_csr(contact_counts, eng.n_users) if contacts else None
             keep = min(top_k, 2 * k_pool)
@@ -1301,6 +1433,17 @@ class SLIM(BaseModel):
                                                          d_rows=d_rows, cn=None if cn is None else tuple(eng._up(a) for a in cn))
             out_ids[:, :keep], out_val[:, :keep] = ids.cpu().numpy(), value.cpu().numpy()
             out_src[:, :keep], out_cnt[:] = source.cpu().numpy(), count.cpu().numpy()
+            if users_tags is not None and not regular.all():
+                # an unknown user has no SLIM side: it gets the factor list of its tags alone, scores as computed (the
+                # reference's _recommend_cold_batch), not a min-max normalised copy of it
+                pos = np.flatnonzero(~regular)
+                at = eng._up(pos.astype(np.int64))
+                kc = min(keep, k_pool)
+                c_ids, c_sc = a_ids.index_select(0, at).cpu().numpy()[:, :kc], a_sc.index_select(0, at).cpu().numpy()[:, :kc]
+                c_cnt = np.minimum(a_cnt.index_select(0, at).cpu().numpy(), kc)
+                out_ids[pos], out_val[pos], out_src[pos] = -1, -np.inf, 0
+                out_ids[pos, :kc], out_val[pos, :kc], out_cnt[pos] = c_ids, c_sc, c_cnt
+                out_src[pos, :kc] = (np.arange(kc)[None, :] < c_cnt[:, None]).astype(np.int32)
         if as_arrays:
             return out_ids, out_val, out_src, out_cnt
         raw_of = self._raw_of(self.item_ids)
@@ -1309,11 +1452,12 @@ class SLIM(BaseModel):
 
     def recommend_hybrid(self, user: Any, top_k: int = 10, pool: Optional[int] = None, weighting: Any = "contacts",
                          contact_counts: Optional[Iterable[Tuple[Any, Any, int]]] = None, similarity_weight_factor: float = 2.0,
-                         mnz: bool = False, filter_interacted: bool = True) -> List[Any]:
-        """recommend_hybrid_batch for one user."""
+                         mnz: bool = False, filter_interacted: bool = True, user_tags: Optional[List[Any]] = None) -> List[Any]:
+        """recommend_hybrid_batch for one user (`user_tags`: this user's list of `users_tags`)."""
         return self.recommend_hybrid_batch([user], top_k=top_k, pool=pool, weighting=weighting, contact_counts=contact_counts,
                                            similarity_weight_factor=similarity_weight_factor, mnz=mnz,
-                                           filter_interacted=filter_interacted)[0]
+                                           filter_interacted=filter_interacted,
+                                           users_tags=None if user_tags is None else [user_tags])[0]
 
     # ------------------------------------------------------------ list quality (an extension: the reference has none)
     QUALITY_MAX_LIST = 1024     # list length rtrec_slim_list_quality measures

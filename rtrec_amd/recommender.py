@@ -180,36 +180,50 @@ class Recommender:
         self.model.attach_factors(users, user_vectors, items, item_vectors)
         return self
 
+    def attach_feature_factors(self, users: List[Any], user_tags: List[Any], user_table: Any, items: List[Any], item_tags: List[Any],
+                               item_table: Any, user_bias: Any = None, item_bias: Any = None) -> "Recommender":
+        """Bring the per-feature tables of a factor model trained with tags (SLIM.attach_feature_factors): the vectors are computed
+        on the device from the identity and tag rows, and `user_tags` of recommend_factor / recommend_hybrid work."""
+        self.model.attach_feature_factors(users, user_tags, user_table, items, item_tags, item_table, user_bias=user_bias,
+                                          item_bias=item_bias)
+        return self
+
     def detach_factors(self) -> "Recommender":
         self.model.detach_factors()
         return self
 
     def recommend_factor(self, user: Any, top_k: int = 10, filter_interacted: bool = True,
-                         candidate_items: Optional[List[Any]] = None) -> List[Any]:
+                         candidate_items: Optional[List[Any]] = None, user_tags: Optional[List[Any]] = None) -> List[Any]:
         """The attached factor model's own top-k for one user -- SLIM.recommend_factor."""
-        return self.model.recommend_factor(user, top_k=top_k, filter_interacted=filter_interacted, candidate_items=candidate_items)
+        kw = {} if user_tags is None else {"user_tags": user_tags}
+        return self.model.recommend_factor(user, top_k=top_k, filter_interacted=filter_interacted, candidate_items=candidate_items, **kw)
 
     def recommend_factor_batch(self, users: List[Any], top_k: int = 10, filter_interacted: bool = True,
-                               candidate_items: Optional[List[Any]] = None, as_arrays: bool = False) -> Any:
+                               candidate_items: Optional[List[Any]] = None, as_arrays: bool = False,
+                               users_tags: Optional[List[List[Any]]] = None) -> Any:
         """SLIM.recommend_factor_batch: dense vectors against dense vectors, top-k per user, one device pass."""
+        kw = {} if users_tags is None else {"users_tags": users_tags}
         return self.model.recommend_factor_batch(users, top_k=top_k, filter_interacted=filter_interacted,
-                                                 candidate_items=candidate_items, as_arrays=as_arrays)
+                                                 candidate_items=candidate_items, as_arrays=as_arrays, **kw)
 
     def recommend_hybrid(self, user: Any, top_k: int = 10, pool: Optional[int] = None, weighting: Any = "contacts",
                          contact_counts: Any = None, similarity_weight_factor: float = 2.0, mnz: bool = False,
-                         filter_interacted: bool = True) -> List[Any]:
+                         filter_interacted: bool = True, user_tags: Optional[List[Any]] = None) -> List[Any]:
         """The reference's hybrid list for one user: the factor model's list blended with SLIM's -- SLIM.recommend_hybrid."""
+        kw = {} if user_tags is None else {"user_tags": user_tags}
         return self.model.recommend_hybrid(user, top_k=top_k, pool=pool, weighting=weighting, contact_counts=contact_counts,
                                            similarity_weight_factor=similarity_weight_factor, mnz=mnz,
-                                           filter_interacted=filter_interacted)
+                                           filter_interacted=filter_interacted, **kw)
 
     def recommend_hybrid_batch(self, users: List[Any], top_k: int = 10, pool: Optional[int] = None, weighting: Any = "contacts",
                                contact_counts: Any = None, similarity_weight_factor: float = 2.0, mnz: bool = False,
-                               filter_interacted: bool = True, as_arrays: bool = False) -> Any:
+                               filter_interacted: bool = True, as_arrays: bool = False,
+                               users_tags: Optional[List[List[Any]]] = None) -> Any:
         """SLIM.recommend_hybrid_batch: factor top-k, SLIM's lists and the blend in one device pass."""
+        kw = {} if users_tags is None else {"users_tags": users_tags}
         return self.model.recommend_hybrid_batch(users, top_k=top_k, pool=pool, weighting=weighting, contact_counts=contact_counts,
                                                  similarity_weight_factor=similarity_weight_factor, mnz=mnz,
-                                                 filter_interacted=filter_interacted, as_arrays=as_arrays)
+                                                 filter_interacted=filter_interacted, as_arrays=as_arrays, **kw)
 
     def blend_batch(self, items_a: List[List[Any]], scores_a: List[List[float]], items_b: List[List[Any]], scores_b: List[List[float]],
                     top_k: int = 10, weight: float = 1.0, mnz: bool = False) -> Any:

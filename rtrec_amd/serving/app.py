@@ -31,8 +31,9 @@ the GPU), POST /recommend (one user's top-k).  Differences, all forced by the de
     -> {"user": ..., "items": [...]} (SLIM.recommend_blended); same token check as /rerank, answered under the model lock, not coalesced;
   * POST /recommend_hybrid is an addition (the list of the factor model attached to the served model blended with SLIM's, the
     reference's hybrid recommendation): {"user": ..., "top_k", "pool" or absent = top_k, "weighting", "contact_counts",
-    "similarity_weight_factor", "mnz", "filter_interacted"} -> {"user": ..., "items": [...]} (SLIM.recommend_hybrid; a model
-    without attached vectors is the shell's 500); same token check as /rerank, answered under the model lock, not coalesced;
+    "similarity_weight_factor", "mnz", "filter_interacted", "user_tags": [...] or absent} -> {"user": ..., "items": [...]}
+    (SLIM.recommend_hybrid; a model without attached vectors is the shell's 500, and so is "user_tags" on a model without the
+    tables of attach_feature_factors); same token check as /rerank, answered under the model lock, not coalesced;
   * concurrent POST /recommend calls are coalesced (`RecommendCoalescer`): requests that arrive within a bounded
     wait (RTREC_AMD_COALESCE_MS, default 1 ms; 0 = only what queued up behind the model lock) share ONE
     recommend_batch launch per (top_k, filter_interacted) group; each caller gets exactly what its own
@@ -131,6 +132,7 @@ class HybridRequest(BaseModel):
     similarity_weight_factor: float = 2.0
     mnz: bool = False
     filter_interacted: bool = True
+    user_tags: Optional[List[str]] = None
 
 
 class RecommendationResponse(BaseModel):
@@ -375,9 +377,11 @@ def build_router(gate: ModelGate) -> APIRouter:
     def recommend_hybrid(request: HybridRequest, x_token: str = Header()):
         _authorise(x_token)
         counts = None if request.contact_counts is None else [(request.user, i, n) for i, n in request.contact_counts]
+        tags = {} if request.user_tags is None else {"user_tags": request.user_tags}
         items = gate.call("Recommend hybrid", lambda m: m.recommend_hybrid(
             request.user, top_k=request.top_k, pool=request.pool, weighting=request.weighting, contact_counts=counts,
-            similarity_weight_factor=request.similarity_weight_factor, mnz=request.mnz, filter_interacted=request.filter_interacted))
+            similarity_weight_factor=request.similarity_weight_factor, mnz=request.mnz, filter_interacted=request.filter_interacted,
+            **tags))
         return {"user": request.user, "items": items}
 
     return api

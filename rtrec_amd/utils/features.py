@@ -4,6 +4,8 @@ SLIM never reads features; the reference keeps the registry on every model so th
 register_user_feature / register_item_feature work uniformly
 (/root/reference/rtrec/models/base.py:36-70, /root/reference/rtrec/utils/features.py:9-224).
 This is the thin host-side equivalent: same method names and return shapes.
+SLIM's own scores still never read it; the factor scorer does, once per-feature tables are attached
+(SLIM.attach_feature_factors builds an entity's feature row from the tags registered here).
 """
 from __future__ import annotations
 
@@ -109,6 +111,18 @@ class FeatureStore:
         self._users = _Side()
         self._items = _Side()
 
+    @property
+    def version(self) -> int:
+        """How often tags were registered or cleared on this object: what a reader that caches something derived from the
+        tags (SLIM._sync_factors) compares.  Not part of the pickle: a loaded store starts at 0 again, like its readers."""
+        return self.__dict__.get("_version", 0)
+
+    def _changed(self) -> None:
+        self.__dict__["_version"] = self.version + 1
+
+    def __getstate__(self):
+        return {k: v for k, v in self.__dict__.items() if k != "_version"}
+
     def __setstate__(self, state):
         # reference layout: user_features / item_features (IndexedSet) + *_feature_map dicts
         if "user_features" in state:
@@ -142,15 +156,19 @@ class FeatureStore:
 
     def clear_user_features(self, user_ids: Optional[List[int]] = None) -> None:
         self._users.clear(user_ids)
+        self._changed()
 
     def clear_item_features(self, item_ids: Optional[List[int]] = None) -> None:
         self._items.clear(item_ids)
+        self._changed()
 
     def put_user_features(self, user_id: int, user_tags: List[str], append: bool = False) -> None:
         self._users.put(user_id, user_tags, append)
+        self._changed()
 
     def put_item_features(self, item_id: int, item_tags: List[str], append: bool = False) -> None:
         self._items.put(item_id, item_tags, append)
+        self._changed()
 
     def get_user_feature_repr(self, user_tags: List[str]) -> csr_matrix:
         return self._users.repr(user_tags)

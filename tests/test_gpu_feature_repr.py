@@ -1,0 +1,170 @@
+"""Tag features for the factor scorer on the GPU (csrc/feature_repr.hip, torch.ops.rtrec_amd.feature_repr,
+SlimEngine.set_feature_factors, SLIM.attach_feature_factors) against the host models of tests/test_feature_repr_host.py: every
+output slot by its bits after adding +0.0f (the sign of a zero is not part of the contract), `has` with ==.  The output buffers
+are poisoned before every call (every slot of every job must be written) and are wider than the slots, with seeded values
+between and behind them that must survive.  tests/test_feature_repr_host.py shows that the data tells the contract's chain --
+ordered, a separately rounded multiply and add, float32 throughout -- from a fused, a reordered and a widened one."""
+import numpy as np
+import pytest
+
+from tests.test_factor_host import F32, bits
+from tests.test_feature_repr_host import (ITEM, PLAIN, USER, adversarial_case, check_engine_feature_factors, check_feature_api, check_serving,
+                                          feature_model, fma32, repr_fast, repr_plain, same_bits)
+
+pytestmark = pytest.mark.gpu
+
+
+def run_op(ptr, col, val, E, bias=None, layout=PLAIN, job_rows=None, n_jobs=None, component_major=False, pad=3, e_pad=2, seed=0):
+    """torch.ops.rtrec_amd.feature_repr on host arrays, as the host models take them: (out[n_jobs, width], has[n_jobs]).  The
+    output strides are `pad` wider than the widths and the table's stride `e_pad` wider than dim_e; everything outside the slots
+    is seeded and checked to be untouched."""
+    import torch
+    from rtrec_amd import ops  # noqa: F401  (registers torch.ops.rtrec_amd.*)
+    E = np.asarray(E, F32)
+    n_features, dim_e = E.shape
+    n_jobs = (len(job_rows) if job_rows is not None else len(ptr) - 1) if n_jobs is None else n_jobs
+    width = dim_e + (0 if layout == PLAIN else 2)
+    rng = np.random.default_rng(seed)
+    Ed = np.concatenate([E, rng.standard_normal((n_features, e_pad)).astype(F32) * 100], axis=1) if e_pad else E
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to("cuda:0")
+    if component_major:
+        shape, row_stride, comp_stride = (width + pad, n_jobs + pad), 1, n_jobs + pad
+    else:
+        shape, row_stride, comp_stride = (n_jobs + pad, width + pad), width + pad, 1
+    poison = (rng.standard_normal(shape).astype(F32) * 1000 + 7).astype(F32)                  # every slot must be written ...
+    out = up(poison, np.float32)
+    has = torch.full((n_jobs + pad,), 77, dtype=torch.uint8, device="cuda:0")
+    torch.ops.rtrec_amd.feature_repr(None if job_rows is None else up(job_rows, np.int32), up(ptr, np.int32), up(col, np.int32),
+                                     None if val is None else up(val, np.float32), up(Ed, np.float32), dim_e,
+                                     None if bias is None else up(bias, np.float32), layout, n_jobs, out, row_stride, comp_stride, has)
+    torch.cuda.synchronize()
+    got, h = out.cpu().numpy(), has.cpu().numpy()
+    slots = got[:width, :n_jobs].T if component_major else got[:n_jobs, :width]
+    outside = np.ones(shape, bool)
+    if component_major:
+        outside[:width, :n_jobs] = False
+    else:
+        outside[:n_jobs, :width] = False
+    assert np.array_equal(got[outside].view(np.int32), poison[outside].view(np.int32)), "a value outside the slots was overwritten"   # ... and nothing else
+    assert (h[n_jobs:] == 77).all()
+    return np.ascontiguousarray(slots), h[:n_jobs]
+
+
+def check(got, want, what=""):
+    assert np.array_equal(got[1], want[1]), (what, "has", np.flatnonzero(got[1] != want[1])[:5])
+    same = (bits(got[0]) == bits(want[0])) | (np.isnan(got[0]) & np.isnan(want[0]))
+    assert same.all(), (what, "slots", np.argwhere(~same)[:5], got[0][~same][:3], want[0][~same][:3])
+
+
+# ---------------------------------------------------------------------------------------------- 1. the chain, bit for bit
+@pytest.fixture(scope="module")
+def mixed_rows():
+    """One CSR whose rows hold 0, 1, 2, 65 and 300 entries (mixed, 134 rows), columns partly out of range or negative, and
+    the table it multiplies: rows spanning 2^-8 .. 2^8 in scale, so that every add rounds."""
+    rng = np.random.default_rng(17)
+    n_features = 400
+    lens = np.array([0, 1, 2, 65, 300, 1, 2, 0, 4, 3] * 13 + [300, 0, 65, 1])
+    ptr = np.r_[0, np.cumsum(lens)].astype(np.int32)
+    col = np.concatenate([rng.permutation(n_features)[:n] for n in lens] + [np.zeros(0, np.int64)]).astype(np.int32)      # unsorted: storage order counts
+    col[rng.random(len(col)) < 0.05] = n_features + 3                    # beyond the table
+    col[rng.random(len(col)) < 0.05] = -1                                # negative
+    col[ptr[1]] = n_features                                             # a row whose only entry is skipped: has = 0
+    val = rng.choice(np.array([1, 1, 2, 3, 0.5], F32), len(col)).astype(F32)
+    scale = F32(2.0) ** rng.integers(-8, 9, n_features).astype(F32)
+    table = (rng.standard_normal((n_features, 254)).astype(F32) * scale[:, None]).astype(F32)
+    bias = (rng.standard_normal(n_features).astype(F32) * scale).astype(F32)
+    return ptr, col, val, table, bias
+
+
+@pytest.mark.parametrize("dim_e", [1, 2, 12, 13, 64, 254])
+def test_every_slot_is_the_ordered_unfused_chain(mixed_rows, dim_e):
+    """All three layouts, both orientations, values given and NULL, n_jobs 1, 63, 64, 65 and 130 (job rows with -1, out-of-range
+    values and repeats for the odd counts), against the vectorised host model; the plain host model on the first rows."""
+    ptr, col, val, table, bias = mixed_rows
+    E = np.ascontiguousarray(table[:, :dim_e])
+    rng = np.random.default_rng(dim_e)
+    n_f_rows = len(ptr) - 1
+    fused_differs = 0
+    for layout in (PLAIN, USER, ITEM):
+        for n_jobs in (1, 63, 64, 65, 130):
+            jobs = None
+            if n_jobs in (63, 65, 130):
+                jobs = rng.integers(0, n_f_rows, n_jobs).astype(np.int32)
+                jobs[::9], jobs[1::13], jobs[2::17], jobs[5] = -1, n_f_rows, 2 ** 31 - 1, jobs[6]
+                jobs[:5] = [4, 4, 3, 0, 1]
+            for component_major in (False, True):
+                v = val if (n_jobs + component_major) % 2 else None
+                want = repr_fast(ptr, col, v, E, bias, layout, jobs, n_jobs)
+                got = run_op(ptr, col, v, E, bias, layout, jobs, n_jobs, component_major, seed=n_jobs)
+                check(got, want, (dim_e, layout, n_jobs, component_major))
+                assert 0 < want[1].sum() or n_jobs == 1
+                if v is not None and n_jobs == 130:
+                    fused = repr_fast(ptr, col, v, E, bias, layout, jobs, n_jobs, step=lambda s, a, e: fma32(a, e, s))[0]
+                    fused_differs += int((bits(fused) != bits(want[0])).sum())
+        few = np.array([4, 3, 0, 1, 2, -1, 8], np.int32)                  # (the 300-entry row, one multiply and add at a time)
+        check(run_op(ptr, col, val, E, bias, layout, few), repr_plain(ptr, col, val, E, bias, layout, few), (dim_e, layout, "plain"))
+    print(f"dim_e {dim_e}: a fused chain would differ in {fused_differs} slots")
+    assert fused_differs > 0
+
+
+def test_the_adversarial_case_of_the_host_file_and_denormals():
+    ptr, col, val, E, bias = adversarial_case()
+    for component_major in (False, True):
+        check(run_op(ptr, col, val, E, bias, USER, component_major=component_major), repr_plain(ptr, col, val, E, bias, USER), "adversarial")
+    E2 = np.array([[2.0 ** -70, 2.0 ** -75], [2.0 ** -72, 2.0 ** -78], [2.0 ** -130, 2.0 ** -149]], F32)
+    ptr2, col2 = np.array([0, 3, 5], np.int32), np.array([0, 1, 2, 0, 2], np.int32)
+    val2 = np.array([2.0 ** -70, 2.0 ** -70, 1.0, 2.0 ** -60, 1.0], F32)
+    got = run_op(ptr2, col2, val2, E2)
+    check(got, repr_plain(ptr2, col2, val2, E2), "denormals")
+    assert (got[0] > 0).all() and (got[0] < np.finfo(F32).tiny).all()
+
+
+def test_empty_inputs_and_the_ops_own_checks():
+    import torch
+    from rtrec_amd import ops  # noqa: F401
+    dev = "cuda:0"
+    i32 = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)
+    f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+    # n_jobs == 0 is RTREC_OK whatever else is empty; a table without features gives zeros and has = 0
+    torch.ops.rtrec_amd.feature_repr(None, i32(1), i32(0), None, f32(0, 4), 4, None, PLAIN, 0, f32(0), 4, 1, None)
+    got = run_op(np.array([0, 2], np.int32), np.array([0, 1], np.int32), None, np.zeros((0, 3), F32), np.zeros(0, F32), USER)
+    assert not got[0].any() and got[1].tolist() == [0]
+    got = run_op(np.array([0], np.int32), np.zeros(0, np.int32), None, np.ones((2, 3), F32), None, PLAIN, np.array([0, 5], np.int32))
+    assert not got[0].any() and got[1].tolist() == [0, 0]
+
+    def call(jobs=None, ptr=None, col=None, val=None, e=None, dim_e=4, bias=None, layout=PLAIN, n_jobs=3, out=None, rs=4, cs=1, has=None):
+        torch.ops.rtrec_amd.feature_repr(jobs, i32(4) if ptr is None else ptr, i32(5) if col is None else col, val, f32(6, 4) if e is None else e,
+                                         dim_e, bias, layout, n_jobs, f32(3, 4) if out is None else out, rs, cs, has)
+
+    call()
+    for kw in (dict(layout=3), dict(dim_e=0), dict(dim_e=5), dict(layout=USER), dict(layout=USER, bias=f32(5), out=f32(3, 6), rs=6),
+               dict(rs=3), dict(rs=1, cs=2), dict(cs=2), dict(out=f32(2, 4)), dict(out=f32(3, 4).double()), dict(out=f32(3, 4).cpu()),
+               dict(e=f32(6, 4).double()), dict(e=f32(4, 6).t()), dict(ptr=i32(4).long()), dict(col=f32(5)), dict(val=f32(4)),
+               dict(val=i32(5)), dict(jobs=i32(2)), dict(jobs=i32(3).long()), dict(has=i32(3)), dict(n_jobs=-1),
+               dict(has=torch.zeros(2, dtype=torch.uint8, device=dev)), dict(ptr=i32(0))):
+        with pytest.raises(RuntimeError):
+            call(**kw)
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------------------------------------- 2. the engine
+def test_engine_set_feature_factors_equals_set_factors_fed_the_host_product():
+    m, batch = feature_model(cpu=False)
+    m.recommend_batch([batch[0][0]])
+    check_engine_feature_factors(m.model.engine, m.model.n_items_fitted)
+
+
+# ---------------------------------------------------------------------------------------------- 3. the API on the device
+@pytest.mark.parametrize("strings", [False, True])
+def test_attach_feature_factors_equals_the_host_path(strings):
+    """The fitted fixture model of tests/test_factor_host.py on the device: attach_feature_factors against attach_factors fed the
+    host-computed stacked vectors; tags registered after the attach; users_tags for known users (one user twice in a batch);
+    unknown users with and without tags; the pickle."""
+    m, batch = feature_model(strings, cpu=False)
+    check_feature_api(m, batch, strings)
+
+
+# ---------------------------------------------------------------------------------------------- 4. serving
+def test_recommend_hybrid_route_with_user_tags_on_the_device():
+    m, batch = feature_model(cpu=False)
+    check_serving(m, batch)
