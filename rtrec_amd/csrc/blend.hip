@@ -14,7 +14,7 @@
 //               multiply and one rounded add each (-ffp-contract=off: never fused); with mnz the entries of both lists double
 //   order       the larger value first, among == values the earlier entry of the union; a NaN value is never listed
 //
-// Mapping.  One row per workgroup of 1 or 4 waves, grid-stride over the rows.  Ids and scores of both lists go to LDS; the two
+// Mapping (the frame is list_stage.hip.h's).  Ids and scores of both lists go to LDS; the two
 // effective lengths and then the four extremes are found by a reduction (__shfl_xor inside a wave, one LDS slot per wave across
 // the workgroup: min and max of floats do not depend on the order they are taken in).  After that the positions of both lists
 // are numbered through, e = p for A and na + q for B, and thread t owns e = t, t + NT, ...: the owner looks for its id at the
@@ -30,14 +30,13 @@
 // per CU and occupancy hides the latency.  No other mapping has been measured.
 // Malformed input cannot read out of range: CSR offsets are clamped to the arrays' lengths, counts to [0, ka] / [0, kb], a row id
 // outside [0, n_x_rows) is an empty row, and an id outside [0, n_items) ends its list.
-#include "row_lookup.hip.h"
+#include "list_stage.hip.h"
 #include "../../include/rtrec_amd_ext.h"
 
 namespace rtrec {
 namespace {
 
 constexpr int kBlendMaxList = 1024;     // ka / kb limit: the LDS arrays of the widest instantiation
-constexpr int kBlendMaxGrid = 65536;    // workgroups per launch; rows beyond it are reached by the grid stride
 constexpr float kBlendFltMax = 3.402823466e+38f;
 
 // the smallest / largest of v over the workgroup, the same in every thread; `slot` holds one entry per wave and is free again
@@ -81,9 +80,7 @@ __global__ __launch_bounds__(WAVES * 64) void blend_lists_kernel(
     const int tid = static_cast<int>(threadIdx.x);
     const float inf = __builtin_huge_valf(), nan = __builtin_nanf("");
     for (long long r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        int ca = a_counts[r], cb = b_counts[r];
-        ca = ca < 0 ? 0 : (ca > ka ? ka : ca);
-        cb = cb < 0 ? 0 : (cb > kb ? kb : cb);
+        const int ca = clamp_count(a_counts[r], ka), cb = clamp_count(b_counts[r], kb);
         // ---- both lists to LDS; a list ends in front of its first invalid position
         int na = ca, nb = cb;
         for (int p = tid; p < ca; p += NT) {
@@ -120,16 +117,13 @@ __global__ __launch_bounds__(WAVES * 64) void blend_lists_kernel(
         const int32_t *xcol = xb_col, *ccol = cn_col, *cval = cn_val;
         int xlen = 0, clen = 0;
         if (contacts) {
-            const long long u = row_ids ? static_cast<long long>(row_ids[r]) : r;
-            if (u >= 0 && u < n_x_rows) {
-                long long s = xb_ptr[u], e = xb_ptr[u + 1];
-                clamp_span(s, e, xb_nnz);
-                xcol = xb_col + s; xlen = static_cast<int>(e - s < 0x7fffffffll ? e - s : 0x7fffffffll);
-                if (cn_ptr) {
-                    long long cs = cn_ptr[u], ce = cn_ptr[u + 1];
-                    clamp_span(cs, ce, cn_nnz);
-                    ccol = cn_col + cs; cval = cn_val + cs; clen = static_cast<int>(ce - cs < 0x7fffffffll ? ce - cs : 0x7fffffffll);
-                }
+            const long long u = row_behind(row_ids, r);
+            long long s;
+            xlen = csr_row(xb_ptr, u, n_x_rows, xb_nnz, s);
+            xcol = xb_col + s;
+            if (cn_ptr) {
+                clen = csr_row(cn_ptr, u, n_x_rows, cn_nnz, s);
+                ccol = cn_col + s; cval = cn_val + s;
             }
         }
         // the weight of item `id` of B
@@ -180,29 +174,14 @@ __global__ __launch_bounds__(WAVES * 64) void blend_lists_kernel(
             if (e < ne4) lval[e] = v;
             listed += __popcll(__ballot(v == v));
         }
-        if constexpr (WAVES > 1) {      // the waves' numbers of listed entries meet in the slots
-            __syncthreads();
-            if ((tid & 63) == 0) islot[tid >> 6] = listed;
-            __syncthreads();
-            listed = 0;
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) listed += islot[w];
-        } else {
-            __syncthreads();            // all values are in LDS
-        }
+        __syncthreads();                // all values are in LDS; the slots' last readers are done
+        listed = block_sum<WAVES>(listed, islot, tid);
         const int n_out = listed < keep ? listed : keep;
-        // ---- rank by counting: the values are read at wave-uniform addresses (LDS broadcasts)
+        // ---- rank by counting
         for (int e = tid; e < ne; e += NT) {
             const float v = lval[e];
             if (v != v) continue;
-            int rank = 0;
-            for (int f = 0; f < ne4; f += 4) {
-                const float4 o = *reinterpret_cast<const float4 *>(&lval[f]);
-                rank += (o.x > v || (o.x == v && f < e)) ? 1 : 0;
-                rank += (o.y > v || (o.y == v && f + 1 < e)) ? 1 : 0;
-                rank += (o.z > v || (o.z == v && f + 2 < e)) ? 1 : 0;
-                rank += (o.w > v || (o.w == v && f + 3 < e)) ? 1 : 0;
-            }
+            const int rank = rank_by_count<false>(lval, ne4, e, v);       // among == values the earlier entry first
             if (rank < keep) {
                 const int id = e < na ? lida[e] : lidb[e - na];
                 int src = 2;
@@ -225,11 +204,6 @@ __global__ __launch_bounds__(WAVES * 64) void blend_lists_kernel(
     }
 }
 
-template <int WAVES, int CAP, typename... Args>
-void launch_blend(int grid, hipStream_t st, Args... args) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(blend_lists_kernel<WAVES, CAP>), dim3(grid), dim3(WAVES * 64), 0, st, args...);
-}
-
 }  // namespace
 }  // namespace rtrec
 
@@ -245,7 +219,7 @@ extern "C" int rtrec_slim_blend_lists(int32_t n_rows, int32_t n_items, const int
     using namespace rtrec;
     if (n_rows < 0 || n_items < 0 || n_x_rows < 0 || xb_nnz < 0 || cn_nnz < 0) return RTREC_ERR_INVALID_ARG;
     if (ka < 1 || ka > kBlendMaxList || kb < 1 || kb > kBlendMaxList || keep < 1 || keep > ka + kb) return RTREC_ERR_UNSUPPORTED;
-    if (waves_per_row != 0 && waves_per_row != 1 && waves_per_row != 4) return RTREC_ERR_UNSUPPORTED;
+    if (!list_waves_valid(waves_per_row)) return RTREC_ERR_UNSUPPORTED;
     if (weight_mode != RTREC_BLEND_CONSTANT && weight_mode != RTREC_BLEND_CONTACTS) return RTREC_ERR_UNSUPPORTED;
     if (a_ids_stride < ka || a_scores_stride < ka || b_ids_stride < kb || b_scores_stride < kb) return RTREC_ERR_INVALID_ARG;
     if (!(weight_b >= 0.0f) || !(k >= 0.0)) return RTREC_ERR_INVALID_ARG;                  // (a NaN fails the compare)
@@ -254,29 +228,19 @@ extern "C" int rtrec_slim_blend_lists(int32_t n_rows, int32_t n_items, const int
     if (!d_out_ids || !d_out_value || !d_out_source || !d_out_count) return RTREC_ERR_INVALID_ARG;
     const int contacts = weight_mode == RTREC_BLEND_CONTACTS;
     if (contacts) {
-        if ((n_x_rows > 0 && !d_xb_ptr) || (xb_nnz > 0 && !d_xb_col)) return RTREC_ERR_INVALID_ARG;
-        if (d_cn_ptr && cn_nnz > 0 && (!d_cn_col || !d_cn_val)) return RTREC_ERR_INVALID_ARG;
+        if (!csr_present(n_x_rows, d_xb_ptr, xb_nnz, d_xb_col, d_xb_col)) return RTREC_ERR_INVALID_ARG;      // (X comes without values)
+        if (d_cn_ptr && !csr_present(0, d_cn_ptr, cn_nnz, d_cn_col, d_cn_val)) return RTREC_ERR_INVALID_ARG;
     }
     (void)hipGetLastError();
-    // waves_per_row == 0: the rule of rtrec_slim_score_pairs (four waves while a row's block has a CU to itself -- 256 CUs -- and
-    // the longer list has work for more than one wave).  The rule is BORROWED from that kernel's measurement
-    // (profiles/rerank_c3s.json); tools/blend_bench.py times both forms for this kernel on all users x two lists of 10.  The
-    // crossover is not measured; the answer never depends on the choice.
     const int longer = ka > kb ? ka : kb;
-    const int waves = waves_per_row != 0 ? waves_per_row : (n_rows <= 256 && longer > 64) ? 4 : 1;
-    const int grid = n_rows < kBlendMaxGrid ? n_rows : kBlendMaxGrid;
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define RTREC_BLEND_LAUNCH(W, C)                                                                                                        \
-    launch_blend<W, C>(grid, st, n_rows, n_items, d_a_ids, static_cast<long long>(a_ids_stride), d_a_scores,                            \
-                       static_cast<long long>(a_scores_stride), d_a_counts, ka, d_b_ids, static_cast<long long>(b_ids_stride), d_b_scores, \
-                       static_cast<long long>(b_scores_stride), d_b_counts, kb, keep, weight_b, contacts, k, mnz != 0 ? 1 : 0, d_row_ids,   \
-                       d_xb_ptr, d_xb_col, n_x_rows, static_cast<long long>(xb_nnz), d_cn_ptr, d_cn_col, d_cn_val,                       \
-                       static_cast<long long>(cn_nnz), d_out_ids, d_out_value, d_out_source, d_out_count)
-    if (waves == 4) {
-        if (longer <= 256) RTREC_BLEND_LAUNCH(4, 256); else RTREC_BLEND_LAUNCH(4, 1024);
-    } else {
-        if (longer <= 64) RTREC_BLEND_LAUNCH(1, 64); else if (longer <= 256) RTREC_BLEND_LAUNCH(1, 256); else RTREC_BLEND_LAUNCH(1, 1024);
-    }
-#undef RTREC_BLEND_LAUNCH
+    list_dispatch(list_waves(waves_per_row, n_rows, longer), longer, [&](auto W, auto CAP) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(blend_lists_kernel<W(), CAP()>), dim3(list_grid(n_rows)), dim3(W() * 64), 0, st, n_rows, n_items,
+                           d_a_ids, static_cast<long long>(a_ids_stride), d_a_scores, static_cast<long long>(a_scores_stride), d_a_counts,
+                           ka, d_b_ids, static_cast<long long>(b_ids_stride), d_b_scores, static_cast<long long>(b_scores_stride),
+                           d_b_counts, kb, keep, weight_b, contacts, k, mnz != 0 ? 1 : 0, d_row_ids, d_xb_ptr, d_xb_col, n_x_rows,
+                           static_cast<long long>(xb_nnz), d_cn_ptr, d_cn_col, d_cn_val, static_cast<long long>(cn_nnz), d_out_ids,
+                           d_out_value, d_out_source, d_out_count);
+    });
     return launch_status();
 }

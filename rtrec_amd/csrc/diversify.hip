@@ -10,7 +10,7 @@
 //               fused); the winner is the largest v, the EARLIER position among == values (lists arrive best first); a NaN v is
 //               skipped; afterwards pen[p] = max(pen[p], sim(id[p], id[winner])) for every other competing position
 //
-// Mapping.  One row per workgroup of 1 or 4 waves, grid-stride over the rows; thread t owns the positions t, t + NT, ...: their
+// Mapping (the frame is list_stage.hip.h's).  Thread t owns the positions t, t + NT, ...: their
 // ids (-1 once a position does not compete any more), lambda * score and penalties live in LDS and are written by their owner
 // only.  A step is an arg-max (each thread over its positions, __shfl_xor across the wave, one LDS slot per wave across the
 // workgroup) under a strict order, so the winner is unique and nothing depends on scheduling or on the wave count; then the
@@ -21,7 +21,7 @@
 // (3 KiB + 1 KiB of staged column each) and occupancy hides the latency.
 // Malformed input cannot read out of range: CSC offsets are clamped to [0, wc_nnz], counts to [0, list_k], and an id outside
 // [0, n_items) never competes.
-#include "row_lookup.hip.h"
+#include "list_stage.hip.h"
 #include "../../include/rtrec_amd_ext.h"
 
 namespace rtrec {
@@ -29,19 +29,12 @@ namespace {
 
 constexpr int kDivMaxList = 1024;       // list_k limit: the LDS arrays of the widest instantiation
 constexpr int kDivStage = 128;          // entries of the winner's column staged in LDS per step
-constexpr int kDivMaxGrid = 65536;      // workgroups per launch; rows beyond it are reached by the grid stride
 
 // a beats b: the larger value, among == values the earlier position (p < 0: no candidate)
 __device__ __forceinline__ bool div_beats(float va, int pa, float vb, int pb) {
     if (pa < 0) return false;
     if (pb < 0) return true;
     return va > vb || (va == vb && pa < pb);
-}
-
-// pen <- max(pen, |w|) with fmaxf's rule for a NaN w (it is ignored); pen itself is never NaN
-__device__ __forceinline__ void div_raise(float &pen, float w) {
-    const float a = __builtin_fabsf(w);
-    if (a > pen) pen = a;
 }
 
 template <int WAVES, int CAP>
@@ -63,8 +56,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) vo
     const float oml = __fsub_rn(1.0f, lambda);
     const float inf = __builtin_huge_valf();
     for (long long r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        int cnt = counts[r];
-        cnt = cnt < 0 ? 0 : (cnt > list_k ? list_k : cnt);
+        const int cnt = clamp_count(counts[r], list_k);
         for (int p = tid; p < list_k; p += NT) {
             int id = -1;
             float s = 0.0f;
@@ -114,7 +106,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) vo
             // ---- the winner's column of W, staged while it fits
             long long cs = wc_ptr[idc], ce = wc_ptr[idc + 1];
             clamp_span(cs, ce, wc_nnz);
-            const int clen = static_cast<int>(ce - cs < 0x7fffffffll ? ce - cs : 0x7fffffffll);
+            const int clen = span_len(cs, ce);
             const bool staged = clen <= kDivStage;
             if (staged) for (int q = tid; q < clen; q += NT) { crow[q] = wc_row[cs + q]; cval[q] = wc_val[cs + q]; }
             __syncthreads();            // the column is staged; every thread has read the slots, the winner's id and its penalty
@@ -125,11 +117,11 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) vo
                 if (idp == idc) { lid[p] = -1; continue; }
                 float pen = lpen[p], w;
                 if (staged ? find_sorted(crow, cval, clen, idp, w) : find_sorted(wc_row + cs, wc_val + cs, clen, idp, w))
-                    div_raise(pen, w);                                    // W[id[p], winner]
+                    raise_abs(pen, w);                                    // W[id[p], winner]
                 long long s = wc_ptr[idp], e = wc_ptr[idp + 1];
                 clamp_span(s, e, wc_nnz);
-                const int len = static_cast<int>(e - s < 0x7fffffffll ? e - s : 0x7fffffffll);
-                if (find_sorted(wc_row + s, wc_val + s, len, idc, w)) div_raise(pen, w);    // W[winner, id[p]]
+                const int len = span_len(s, e);
+                if (find_sorted(wc_row + s, wc_val + s, len, idc, w)) raise_abs(pen, w);    // W[winner, id[p]]
                 lpen[p] = pen;
             }
         }
@@ -143,16 +135,6 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) vo
     }
 }
 
-template <int WAVES, int CAP>
-void launch_diversify(int grid, hipStream_t st, int n_rows, int n_items, const int32_t *wc_ptr, const int32_t *wc_row,
-                      const float *wc_val, long long wc_nnz, const int32_t *ids, long long ids_stride, const float *scores,
-                      long long scores_stride, int list_k, const int32_t *counts, int keep, float lambda, int32_t *out_order,
-                      float *out_value, float *out_penalty, int32_t *out_count) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(diversify_lists_kernel<WAVES, CAP>), dim3(grid), dim3(WAVES * 64), 0, st, n_rows, n_items,
-                       wc_ptr, wc_row, wc_val, wc_nnz, ids, ids_stride, scores, scores_stride, list_k, counts, keep, lambda,
-                       out_order, out_value, out_penalty, out_count);
-}
-
 }  // namespace
 }  // namespace rtrec
 
@@ -164,28 +146,19 @@ extern "C" int rtrec_slim_diversify_lists(int32_t n_rows, int32_t n_items, const
     using namespace rtrec;
     if (n_rows < 0 || n_items < 0 || wc_nnz < 0) return RTREC_ERR_INVALID_ARG;
     if (list_k < 1 || list_k > kDivMaxList || keep < 1 || keep > list_k) return RTREC_ERR_UNSUPPORTED;
-    if (waves_per_row != 0 && waves_per_row != 1 && waves_per_row != 4) return RTREC_ERR_UNSUPPORTED;
+    if (!list_waves_valid(waves_per_row)) return RTREC_ERR_UNSUPPORTED;
     if (ids_stride < list_k || scores_stride < list_k) return RTREC_ERR_INVALID_ARG;
     if (!(lambda >= 0.0f && lambda <= 1.0f)) return RTREC_ERR_INVALID_ARG;            // (a NaN lambda fails both compares)
     if (n_rows == 0) return RTREC_OK;
     if (!d_ids || !d_scores || !d_counts || !d_out_order || !d_out_value || !d_out_penalty || !d_out_count) return RTREC_ERR_INVALID_ARG;
-    if ((n_items > 0 && !d_wc_ptr) || (wc_nnz > 0 && (!d_wc_row || !d_wc_val))) return RTREC_ERR_INVALID_ARG;
+    if (!csc_present(n_items, d_wc_ptr, wc_nnz, d_wc_row, d_wc_val)) return RTREC_ERR_INVALID_ARG;
     (void)hipGetLastError();
-    // waves_per_row == 0: the rule of rtrec_slim_score_pairs (four waves while a row's block has a CU to itself -- 256 CUs -- and
-    // the list has work for more than one wave).  The rule is BORROWED from that kernel's measurement (profiles/rerank_c3s.json);
-    // tools/diverse_bench.py times both ends of it for this kernel (all users x a pool of 50, one row x a pool of 500) and
-    // DESIGN 3.5 reports what it found.  The crossover is not measured; the answer never depends on the choice.
-    const int waves = waves_per_row != 0 ? waves_per_row : (n_rows <= 256 && list_k > 64) ? 4 : 1;
-    const int grid = n_rows < kDivMaxGrid ? n_rows : kDivMaxGrid;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long nnz = static_cast<long long>(wc_nnz), is = static_cast<long long>(ids_stride), ss = static_cast<long long>(scores_stride);
-#define RTREC_DIV_LAUNCH(W, C) launch_diversify<W, C>(grid, st, n_rows, n_items, d_wc_ptr, d_wc_row, d_wc_val, nnz, d_ids, is, d_scores, \
-                                                      ss, list_k, d_counts, keep, lambda, d_out_order, d_out_value, d_out_penalty, d_out_count)
-    if (waves == 4) {
-        if (list_k <= 256) RTREC_DIV_LAUNCH(4, 256); else RTREC_DIV_LAUNCH(4, 1024);
-    } else {
-        if (list_k <= 64) RTREC_DIV_LAUNCH(1, 64); else if (list_k <= 256) RTREC_DIV_LAUNCH(1, 256); else RTREC_DIV_LAUNCH(1, 1024);
-    }
-#undef RTREC_DIV_LAUNCH
+    list_dispatch(list_waves(waves_per_row, n_rows, list_k), list_k, [&](auto W, auto CAP) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(diversify_lists_kernel<W(), CAP()>), dim3(list_grid(n_rows)), dim3(W() * 64), 0, st, n_rows,
+                           n_items, d_wc_ptr, d_wc_row, d_wc_val, nnz, d_ids, is, d_scores, ss, list_k, d_counts, keep, lambda,
+                           d_out_order, d_out_value, d_out_penalty, d_out_count);
+    });
     return launch_status();
 }

@@ -14,7 +14,7 @@
 //   at most 64 entries is probed once and kept in registers; a longer one is probed again every round.
 // Malformed input cannot read out of range: CSR / CSC offsets are clamped to the arrays' lengths, a row id outside
 // [0, n_x_rows) is an empty row and an item id outside [0, n_items) has no column.
-#include "row_lookup.hip.h"
+#include "list_stage.hip.h"
 #include "../../include/rtrec_amd.h"
 
 namespace rtrec {
@@ -66,19 +66,14 @@ __global__ __launch_bounds__(64) void explain_topk_kernel(
     const int lane = lane_id();
     const float ninf = -__builtin_huge_valf();
     for (long long r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        const long long u = row_ids ? static_cast<long long>(row_ids[r]) : r;
         ExplainRow row;
-        row.col = xb_col; row.val = xb_val; row.len = 0;
-        if (u >= 0 && u < n_x_rows) {
-            long long b = xb_ptr[u], e = xb_ptr[u + 1];
-            clamp_span(b, e, xb_nnz);
-            row.col = xb_col + b; row.val = xb_val + b; row.len = static_cast<int>(e - b);
-        }
+        long long b;
+        row.len = csr_row(xb_ptr, row_behind(row_ids, r), n_x_rows, xb_nnz, b);
+        row.col = xb_col + b; row.val = xb_val + b;
         row.in_regs = row.len <= 64;
         row.reg_col = 0x7fffffff; row.reg_val = 0.0f;
         if (row.in_regs && lane < row.len) { row.reg_col = row.col[lane]; row.reg_val = row.val[lane]; }
-        int cnt = counts[r];
-        cnt = cnt < 0 ? 0 : (cnt > list_k ? list_k : cnt);
+        const int cnt = clamp_count(counts[r], list_k);
         for (int p = 0; p < list_k; ++p) {
             const int item = p < cnt ? ids[r * ids_stride + p] : -1;
             long long s = 0, e = 0;
@@ -137,12 +132,11 @@ extern "C" int rtrec_slim_explain_topk(int32_t n_rows, const int32_t *d_row_ids,
     if (ids_stride < list_k) return RTREC_ERR_INVALID_ARG;
     if (n_rows == 0) return RTREC_OK;
     if (!d_ids || !d_counts || !d_out_items || !d_out_contrib || !d_out_support) return RTREC_ERR_INVALID_ARG;
-    if ((n_x_rows > 0 && !d_xb_ptr) || (xb_nnz > 0 && (!d_xb_col || !d_xb_val))) return RTREC_ERR_INVALID_ARG;
-    if ((n_items > 0 && !d_wc_ptr) || (wc_nnz > 0 && (!d_wc_row || !d_wc_val))) return RTREC_ERR_INVALID_ARG;
+    if (!csr_present(n_x_rows, d_xb_ptr, xb_nnz, d_xb_col, d_xb_val)) return RTREC_ERR_INVALID_ARG;
+    if (!csc_present(n_items, d_wc_ptr, wc_nnz, d_wc_row, d_wc_val)) return RTREC_ERR_INVALID_ARG;
     (void)hipGetLastError();
-    const int grid = n_rows < 65536 ? n_rows : 65536;
-    hipLaunchKernelGGL(explain_topk_kernel, dim3(grid), dim3(64), 0, static_cast<hipStream_t>(stream), n_rows, d_row_ids, d_xb_ptr,
-                       d_xb_col, d_xb_val, n_x_rows, static_cast<long long>(xb_nnz), n_items, d_wc_ptr, d_wc_row, d_wc_val,
+    hipLaunchKernelGGL(explain_topk_kernel, dim3(list_grid(n_rows)), dim3(64), 0, static_cast<hipStream_t>(stream), n_rows, d_row_ids,
+                       d_xb_ptr, d_xb_col, d_xb_val, n_x_rows, static_cast<long long>(xb_nnz), n_items, d_wc_ptr, d_wc_row, d_wc_val,
                        static_cast<long long>(wc_nnz), d_ids, static_cast<long long>(ids_stride), list_k, d_counts, top_m, d_out_items,
                        d_out_contrib, d_out_support);
     return rtrec::launch_status();

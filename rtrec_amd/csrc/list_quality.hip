@@ -8,7 +8,7 @@
 //   s_p         the float32 sum from +0 of sim(id_p, id_q) over the counted q < p, ascending, one rounded add each (__fadd_rn)
 //   sim_sum     the float32 sum from +0 of the s_p, ascending p; weight_sum the same over item_weight[id_p]
 //
-// Mapping.  One row per workgroup of 1 or 4 waves, grid-stride over the rows; thread t owns the positions t, t + NT, ...  The
+// Mapping (the frame is list_stage.hip.h's).  Thread t owns the positions t, t + NT, ...  The
 // ids go to LDS, every position looks for its id at a lower position (the de-duplication is a function of the ids alone, so
 // the counted set is the same in every mapping), then the owner of p caches the span of column id_p in LDS, walks the counted
 // q < p with two binary searches each -- id_q in its own column, id_p in column id_q -- and leaves s_p, its linked pairs and its
@@ -18,20 +18,13 @@
 // short lists keep 32 one-wave workgroups per CU and occupancy hides the latency.  No other mapping has been measured.
 // Malformed input cannot read out of range: CSC offsets are clamped to [0, wc_nnz], counts to [0, list_k], and an id outside
 // [0, n_items) is never counted.
-#include "row_lookup.hip.h"
+#include "list_stage.hip.h"
 #include "../../include/rtrec_amd_ext.h"
 
 namespace rtrec {
 namespace {
 
 constexpr int kQualMaxList = 1024;      // list_k limit: the LDS arrays of the widest instantiation
-constexpr int kQualMaxGrid = 65536;     // workgroups per launch; rows beyond it are reached by the grid stride
-
-// sim <- max(sim, |w|) with fmaxf's rule for a NaN w (it is ignored); sim itself is never NaN
-__device__ __forceinline__ void qual_raise(float &sim, float w) {
-    const float a = __builtin_fabsf(w);
-    if (a > sim) sim = a;
-}
 
 template <int WAVES, int CAP>
 __global__ __launch_bounds__(WAVES * 64) void list_quality_kernel(
@@ -49,8 +42,7 @@ __global__ __launch_bounds__(WAVES * 64) void list_quality_kernel(
     __shared__ float lw[CAP];           // item_weight[id_p]
     const int tid = static_cast<int>(threadIdx.x);
     for (long long r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        int cnt = counts[r];
-        cnt = cnt < 0 ? 0 : (cnt > list_k ? list_k : cnt);
+        const int cnt = clamp_count(counts[r], list_k);
         for (int p = tid; p < list_k; p += NT) {
             int id = -1;
             if (p < cnt) id = ids[r * ids_stride + p];
@@ -97,8 +89,8 @@ __global__ __launch_bounds__(WAVES * 64) void list_quality_kernel(
                     const int idq = lid[q];
                     if (idq < 0) continue;
                     float sim = 0.0f, w;
-                    if (find_sorted(prow, pval, plen, idq, w)) qual_raise(sim, w);                          // W[id_q, id_p]
-                    if (find_sorted(wc_row + lcs[q], wc_val + lcs[q], llen[q], idp, w)) qual_raise(sim, w);  // W[id_p, id_q]
+                    if (find_sorted(prow, pval, plen, idq, w)) raise_abs(sim, w);                          // W[id_q, id_p]
+                    if (find_sorted(wc_row + lcs[q], wc_val + lcs[q], llen[q], idp, w)) raise_abs(sim, w);  // W[id_p, id_q]
                     sp = __fadd_rn(sp, sim);
                     linked += sim > 0.0f ? 1 : 0;
                 }
@@ -129,16 +121,6 @@ __global__ __launch_bounds__(WAVES * 64) void list_quality_kernel(
     }
 }
 
-template <int WAVES, int CAP>
-void launch_quality(int grid, hipStream_t st, int n_rows, int n_items, const int32_t *wc_ptr, const int32_t *wc_row,
-                    const float *wc_val, long long wc_nnz, const int32_t *ids, long long ids_stride, int list_k,
-                    const int32_t *counts, const float *item_weight, int32_t *exposure, int32_t *out_n, float *out_sim_sum,
-                    int32_t *out_linked, float *out_weight_sum) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(list_quality_kernel<WAVES, CAP>), dim3(grid), dim3(WAVES * 64), 0, st, n_rows, n_items, wc_ptr,
-                       wc_row, wc_val, wc_nnz, ids, ids_stride, list_k, counts, item_weight, exposure, out_n, out_sim_sum, out_linked,
-                       out_weight_sum);
-}
-
 }  // namespace
 }  // namespace rtrec
 
@@ -150,27 +132,18 @@ extern "C" int rtrec_slim_list_quality(int32_t n_rows, int32_t n_items, const in
     using namespace rtrec;
     if (n_rows < 0 || n_items < 0 || wc_nnz < 0) return RTREC_ERR_INVALID_ARG;
     if (list_k < 1 || list_k > kQualMaxList) return RTREC_ERR_UNSUPPORTED;
-    if (waves_per_row != 0 && waves_per_row != 1 && waves_per_row != 4) return RTREC_ERR_UNSUPPORTED;
+    if (!list_waves_valid(waves_per_row)) return RTREC_ERR_UNSUPPORTED;
     if (ids_stride < list_k) return RTREC_ERR_INVALID_ARG;
     if (n_rows == 0) return RTREC_OK;
     if (!d_ids || !d_counts || !d_out_n || !d_out_sim_sum || !d_out_linked || !d_out_weight_sum) return RTREC_ERR_INVALID_ARG;
-    if ((n_items > 0 && !d_wc_ptr) || (wc_nnz > 0 && (!d_wc_row || !d_wc_val))) return RTREC_ERR_INVALID_ARG;
+    if (!csc_present(n_items, d_wc_ptr, wc_nnz, d_wc_row, d_wc_val)) return RTREC_ERR_INVALID_ARG;
     (void)hipGetLastError();
-    // waves_per_row == 0: the rule of rtrec_slim_score_pairs (four waves while a row's block has a CU to itself -- 256 CUs -- and
-    // the list has work for more than one wave).  The rule is BORROWED from that kernel's measurement (profiles/rerank_c3s.json);
-    // tools/quality_bench.py times both ends of it for this kernel (all users x a top-10 list, one list of 500).  The crossover
-    // is not measured; the answer never depends on the choice.
-    const int waves = waves_per_row != 0 ? waves_per_row : (n_rows <= 256 && list_k > 64) ? 4 : 1;
-    const int grid = n_rows < kQualMaxGrid ? n_rows : kQualMaxGrid;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long nnz = static_cast<long long>(wc_nnz), is = static_cast<long long>(ids_stride);
-#define RTREC_QUAL_LAUNCH(W, C) launch_quality<W, C>(grid, st, n_rows, n_items, d_wc_ptr, d_wc_row, d_wc_val, nnz, d_ids, is, list_k, d_counts, \
-                                                     d_item_weight, d_exposure, d_out_n, d_out_sim_sum, d_out_linked, d_out_weight_sum)
-    if (waves == 4) {
-        if (list_k <= 256) RTREC_QUAL_LAUNCH(4, 256); else RTREC_QUAL_LAUNCH(4, 1024);
-    } else {
-        if (list_k <= 64) RTREC_QUAL_LAUNCH(1, 64); else if (list_k <= 256) RTREC_QUAL_LAUNCH(1, 256); else RTREC_QUAL_LAUNCH(1, 1024);
-    }
-#undef RTREC_QUAL_LAUNCH
+    list_dispatch(list_waves(waves_per_row, n_rows, list_k), list_k, [&](auto W, auto CAP) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(list_quality_kernel<W(), CAP()>), dim3(list_grid(n_rows)), dim3(W() * 64), 0, st, n_rows,
+                           n_items, d_wc_ptr, d_wc_row, d_wc_val, nnz, d_ids, is, list_k, d_counts, d_item_weight, d_exposure, d_out_n,
+                           d_out_sim_sum, d_out_linked, d_out_weight_sum);
+    });
     return launch_status();
 }

@@ -1,6 +1,7 @@
 // rtrec_amd/csrc/row_lookup.hip.h -- "is item j stored in this sorted row, and with which value": the search of the request
 // kernels (score_pairs, score_refine, score_first_touch) and the span rule of those that guard against malformed offsets
-// (explain, audience, score_pairs).
+// (explain, audience, score_pairs).  The frame around these for the kernels that take one list per row -- the clamped row of X,
+// the counts, the wave count and the dispatch -- is list_stage.hip.h, which includes this header.
 //
 // The functions are inlined into their callers, so the address space follows the argument: handed an LDS array they read LDS
 // (ds_read), handed a global pointer they load from global memory.  A caller with a staged and an unstaged form of a row calls

@@ -11,7 +11,7 @@
 //   ranking      position p beats q if score[p] > score[q], or the scores are == and p > q (the LATER position first: DESIGN D1,
 //                the rule of CANDIDATES mode); NaN scores and, with filter_interacted, items stored in the row do not compete
 //
-// Mapping.  One row per workgroup of 1 or 4 waves; threads take list positions, strided by the workgroup's thread count.  A
+// Mapping (the frame is list_stage.hip.h's).  Threads take list positions, strided by the workgroup's thread count.  A
 // thread walks its item's column of W in entry order and looks each j up in the user's row by binary search -- the row is
 // staged in LDS up to kPairsRow1 / kPairsRow4 entries and searched in global memory beyond that -- and adds the hits into its
 // accumulator, so the order of the sum is the column's and a column of any length works.  The same search answers "is item i
@@ -22,7 +22,7 @@
 // 32 waves per CU fit the CU's 160 KiB in either form, so LDS never limits the occupancy.
 // Malformed input cannot read out of range: CSR / CSC offsets are clamped to the arrays' lengths, counts to [0, list_k], a row
 // id outside [0, n_x_rows) is an empty row and an item id outside [0, n_items) an empty position.
-#include "row_lookup.hip.h"
+#include "list_stage.hip.h"
 #include "../../include/rtrec_amd.h"
 
 namespace rtrec {
@@ -48,19 +48,13 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) vo
     const float nan = __builtin_nanf("");
     const int k4 = (list_k + 3) & ~3;                                     // the ranking reads the scores four at a time
     for (long long r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        const long long u = row_ids ? static_cast<long long>(row_ids[r]) : r;
-        const int32_t *rcol = xb_col;
-        const float *rval = xb_val;
-        int len = 0;
-        if (u >= 0 && u < n_x_rows) {
-            long long b = xb_ptr[u], e = xb_ptr[u + 1];
-            clamp_span(b, e, xb_nnz);
-            rcol = xb_col + b; rval = xb_val + b; len = static_cast<int>(e - b);
-        }
+        long long b;
+        const int len = csr_row(xb_ptr, row_behind(row_ids, r), n_x_rows, xb_nnz, b);
+        const int32_t *rcol = xb_col + b;
+        const float *rval = xb_val + b;
         const bool staged = len <= ROW;
         if (staged) for (int q = tid; q < len; q += NT) { lcol[q] = rcol[q]; lval[q] = rval[q]; }
-        int cnt = counts[r];
-        cnt = cnt < 0 ? 0 : (cnt > list_k ? list_k : cnt);
+        const int cnt = clamp_count(counts[r], list_k);
         __syncthreads();                                                  // the staged row is visible to every wave
         // x = the row's value at item j, if the row stores j
         auto lookup = [&](int j, float &x) -> bool {
@@ -97,27 +91,13 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) vo
         }
         if (top_k > 0) {
             __syncthreads();                                              // all scores are in LDS; the staged row is not needed any more
-            int n_out = competing;                                        // (one wave: the ballots have counted the whole list)
-            if constexpr (WAVES > 1) {                                    // the waves' numbers of competitors meet in the row's slots
-                if ((tid & 63) == 0) lcol[tid >> 6] = competing;
-                __syncthreads();
-                n_out = 0;
-#pragma unroll
-                for (int w = 0; w < WAVES; ++w) n_out += lcol[w];
-            }
+            int n_out = block_sum<WAVES>(competing, lcol, tid);           // the waves' numbers of competitors meet in the row's slots
             n_out = n_out < top_k ? n_out : top_k;
-            // ---- rank by counting: the scores are read at wave-uniform addresses (LDS broadcasts)
+            // ---- rank by counting
             for (int p = tid; p < list_k; p += NT) {
                 const float v = sc[p];
                 if (v != v) continue;
-                int rank = 0;
-                for (int q = 0; q < k4; q += 4) {
-                    const float4 o = *reinterpret_cast<const float4 *>(&sc[q]);
-                    rank += (o.x > v || (o.x == v && q > p)) ? 1 : 0;
-                    rank += (o.y > v || (o.y == v && q + 1 > p)) ? 1 : 0;
-                    rank += (o.z > v || (o.z == v && q + 2 > p)) ? 1 : 0;
-                    rank += (o.w > v || (o.w == v && q + 3 > p)) ? 1 : 0;
-                }
+                const int rank = rank_by_count<true>(sc, k4, p, v);       // among == scores the LATER position first
                 if (rank < top_k) out_order[r * top_k + rank] = p;
             }
             for (int t = n_out + tid; t < top_k; t += NT) out_order[r * top_k + t] = -1;
@@ -141,18 +121,14 @@ extern "C" int rtrec_slim_score_pairs(int32_t n_rows, const int32_t *d_row_ids, 
     using namespace rtrec;
     if (n_rows < 0 || n_x_rows < 0 || xb_nnz < 0 || n_items < 0 || wc_nnz < 0) return RTREC_ERR_INVALID_ARG;
     if (list_k < 1 || list_k > kPairsMaxList || top_k < 0 || top_k > list_k) return RTREC_ERR_UNSUPPORTED;
-    if (waves_per_row != 0 && waves_per_row != 1 && waves_per_row != 4) return RTREC_ERR_UNSUPPORTED;
+    if (!list_waves_valid(waves_per_row)) return RTREC_ERR_UNSUPPORTED;
     if (ids_stride < list_k) return RTREC_ERR_INVALID_ARG;
     if (n_rows == 0) return RTREC_OK;
     if (!d_ids || !d_counts || !d_out_scores || !d_out_support || (top_k > 0 && (!d_out_order || !d_out_count))) return RTREC_ERR_INVALID_ARG;
-    if ((n_x_rows > 0 && !d_xb_ptr) || (xb_nnz > 0 && (!d_xb_col || !d_xb_val))) return RTREC_ERR_INVALID_ARG;
-    if ((n_items > 0 && !d_wc_ptr) || (wc_nnz > 0 && (!d_wc_row || !d_wc_val))) return RTREC_ERR_INVALID_ARG;
+    if (!csr_present(n_x_rows, d_xb_ptr, xb_nnz, d_xb_col, d_xb_val)) return RTREC_ERR_INVALID_ARG;
+    if (!csc_present(n_items, d_wc_ptr, wc_nnz, d_wc_row, d_wc_val)) return RTREC_ERR_INVALID_ARG;
     (void)hipGetLastError();
-    // waves_per_row == 0 (profiles/rerank_c3s.json): all users x 100 candidates run 2.41 ms with one wave per row and 2.81 ms
-    // with four, one row x 500 candidates 0.31 ms and 0.09 ms.  Four waves only pay while a row's block has a CU to itself
-    // (256 CUs) and the list has work for more than one wave; the answer never depends on the choice.
-    const int waves = waves_per_row != 0 ? waves_per_row : (n_rows <= 256 && list_k > 64) ? 4 : 1;
-    const int grid = n_rows < 65536 ? n_rows : 65536;
+    const int waves = list_waves(waves_per_row, n_rows, list_k), grid = list_grid(n_rows);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (waves == 4)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(score_pairs_kernel<4, kPairsRow4>), dim3(grid), dim3(256), 0, st, n_rows, d_row_ids, d_xb_ptr,

@@ -381,57 +381,82 @@ void ordered_sums(const at::Tensor &values, const at::Tensor &offsets, int64_t m
                              static_cast<int32_t>(mode), ptr<float>(out), stream_of(out)), "rtrec_slim_ordered_sums");
 }
 
+// ---- the checks of the ops from here down
+bool has(const OT &t) { return t.has_value() && t->defined(); }
+
+// The pointer a slot of element type T takes.  Every tensor is checked even when it is empty (ptr<> skips those: the ops above hand
+// it empty placeholders): an empty call is still a typed call.  nullptr for an empty or absent tensor.
+template <typename T>
+T *cptr(const at::Tensor &t) {
+    check_tensor<T>(t);
+    return t.numel() == 0 ? nullptr : static_cast<T *>(t.data_ptr());
+}
+template <typename T>
+T *cptr(const OT &t) { return has(t) ? cptr<T>(*t) : nullptr; }
+
+void one_device(const char *op, const at::Tensor &ref, std::initializer_list<const at::Tensor *> tensors,
+                std::initializer_list<const OT *> optionals = {}) {
+    for (const at::Tensor *t : tensors) TORCH_CHECK(t->device() == ref.device(), op, ": all tensors must live on one device");
+    for (const OT *t : optionals) TORCH_CHECK(!has(*t) || (*t)->device() == ref.device(), op, ": all tensors must live on one device");
+}
+
+void check_waves(const char *op, int64_t w) {
+    TORCH_CHECK(w == 0 || w == 1 || w == 4, op, ": waves_per_row must be 0, 1 or 4, got ", w);
+}
+
+void check_rows_items(const char *op, int64_t rows, int64_t n_items) {
+    TORCH_CHECK(rows <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, op, ": too many rows or items");
+}
+
+// One list per row: <name>ids [n_rows, >= k], <name>scores of that form (or null), counts [n_rows] (null: the caller checks them);
+// kname is what the messages call k.  rows < 0: ids decides the row count, which is returned.
+int64_t check_list(const char *op, const char *name, const char *kname, const at::Tensor &ids, const at::Tensor *scores,
+                   const at::Tensor *counts, int64_t k, int64_t rows = -1) {
+    TORCH_CHECK(ids.dim() == 2 && (rows < 0 || ids.size(0) == rows) && ids.size(1) >= k, op, ": ", name, "ids must be [n_rows, >= ", kname, "]");
+    rows = ids.size(0);
+    TORCH_CHECK(!scores || (scores->dim() == 2 && scores->size(0) == rows && scores->size(1) >= k), op, ": ", name,
+                "scores must be [n_rows, >= ", kname, "]");
+    TORCH_CHECK(!counts || counts->numel() == rows, op, ": ", name, "counts must hold one entry per row");
+    return rows;
+}
+
 // ids / counts: the lists of score_topk; truth_* the ground truth as CSR over the same rows (include/rtrec_amd.h).  rel is an
 // int64 tensor that receives the uint64 relevance words.
 void rank_metrics(const at::Tensor &ids, const at::Tensor &counts, const at::Tensor &truth_ptr, const at::Tensor &truth_items,
                   const at::Tensor &truth_len, const at::Tensor &discount, const at::Tensor &ideal, int64_t size, at::Tensor metrics,
                   at::Tensor tp, at::Tensor rel) {
     TORCH_CHECK(size >= 1 && size <= 64, "rank_metrics: size must lie in 1..64, got ", size);
-    TORCH_CHECK(ids.dim() == 2 && ids.size(1) >= size, "rank_metrics: ids must be [n_rows, >= size]");
-    const int64_t n = ids.size(0);
+    const int64_t n = check_list("rank_metrics", "", "size", ids, nullptr, nullptr, size);
     TORCH_CHECK(n <= INT32_MAX, "rank_metrics: too many rows");
     TORCH_CHECK(truth_ptr.numel() == n + 1, "rank_metrics: truth_ptr must hold n_rows + 1 entries, got ", truth_ptr.numel());
     TORCH_CHECK(counts.numel() == n && truth_len.numel() == n, "rank_metrics: counts and truth_len must hold one entry per row");
     TORCH_CHECK(discount.numel() == size && ideal.numel() == size + 1, "rank_metrics: discount[size] and ideal[size + 1] expected");
     TORCH_CHECK(metrics.numel() == n * 8 && tp.numel() == n && rel.numel() == n, "rank_metrics: outputs must be metrics[n_rows, 8], tp[n_rows], rel[n_rows]");
-    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
-    check_tensor<const int32_t>(ids); check_tensor<const int32_t>(counts); check_tensor<const int64_t>(truth_ptr);
-    check_tensor<const int32_t>(truth_items); check_tensor<const int32_t>(truth_len); check_tensor<const double>(discount);
-    check_tensor<const double>(ideal); check_tensor<double>(metrics); check_tensor<int32_t>(tp); check_tensor<int64_t>(rel);
-    check(abi().rank_metrics(static_cast<int32_t>(n), static_cast<int32_t>(size), ptr<const int32_t>(ids), static_cast<int32_t>(ids.size(1)),
-                             ptr<const int32_t>(counts), ptr<const int64_t>(truth_ptr), ptr<const int32_t>(truth_items), truth_items.numel(),
-                             ptr<const int32_t>(truth_len), ptr<const double>(discount), ptr<const double>(ideal),
-                             reinterpret_cast<uint64_t *>(ptr<int64_t>(rel)), ptr<int32_t>(tp), ptr<double>(metrics), stream_of(metrics)),
+    check(abi().rank_metrics(static_cast<int32_t>(n), static_cast<int32_t>(size), cptr<const int32_t>(ids), static_cast<int32_t>(ids.size(1)),
+                             cptr<const int32_t>(counts), cptr<const int64_t>(truth_ptr), cptr<const int32_t>(truth_items), truth_items.numel(),
+                             cptr<const int32_t>(truth_len), cptr<const double>(discount), cptr<const double>(ideal),
+                             reinterpret_cast<uint64_t *>(cptr<int64_t>(rel)), cptr<int32_t>(tp), cptr<double>(metrics), stream_of(metrics)),
           "rtrec_rank_metrics");
 }
 
 // One CSC matrix of n_items columns: ptr [n_items + 1], row and val of one length, int32 / float32 (checked even when empty).
-void check_csc(const char *op, const char *name, const at::Tensor &cptr, const at::Tensor &crow, const at::Tensor &cval, int64_t n_items) {
-    TORCH_CHECK(cptr.numel() == n_items + 1 && cval.numel() == crow.numel(), op, ": ", name, "_ptr must hold n_items + 1 entries, ", name,
+void check_csc(const char *op, const char *name, const at::Tensor &colptr, const at::Tensor &crow, const at::Tensor &cval, int64_t n_items) {
+    TORCH_CHECK(colptr.numel() == n_items + 1 && cval.numel() == crow.numel(), op, ": ", name, "_ptr must hold n_items + 1 entries, ", name,
                 "_row and ", name, "_val one length");
-    check_tensor<const int32_t>(cptr); check_tensor<const int32_t>(crow); check_tensor<const float>(cval);
+    check_tensor<const int32_t>(colptr); check_tensor<const int32_t>(crow); check_tensor<const float>(cval);
 }
 
-// The inputs explain_topk and score_pairs share: ids [n_rows, >= list_k] / counts [n_rows], optional row_ids [n_rows], X as a CSR
-// triple, W as a CSC triple of n_items columns, all on ids' device.  Every tensor is checked even when it is empty (ptr<> skips
-// those): an empty call is still a typed call.  Returns n_rows.
+// The inputs explain_topk and score_pairs share: one list per row, optional row_ids [n_rows], X as a CSR triple, W as a CSC triple
+// of n_items columns, all on ids' device.  Returns n_rows.
 int64_t check_lists_x_w(const char *op, const OT &row_ids, const at::Tensor &xb_ptr, const at::Tensor &xb_col, const at::Tensor &xb_val,
                         int64_t n_items, const at::Tensor &wc_ptr, const at::Tensor &wc_row, const at::Tensor &wc_val,
                         const at::Tensor &ids, const at::Tensor &counts, int64_t list_k) {
-    TORCH_CHECK(ids.dim() == 2 && ids.size(1) >= list_k, op, ": ids must be [n_rows, >= list_k]");
-    const int64_t n = ids.size(0);
-    const bool has_rows = row_ids.has_value() && row_ids->defined();
-    TORCH_CHECK(n <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, op, ": too many rows or items");
-    TORCH_CHECK(counts.numel() == n, op, ": counts must hold one entry per row");
-    TORCH_CHECK(!has_rows || row_ids->numel() == n, op, ": row_ids must hold one entry per row");
+    const int64_t n = check_list(op, "", "list_k", ids, nullptr, &counts, list_k);
+    check_rows_items(op, n, n_items);
+    TORCH_CHECK(!has(row_ids) || row_ids->numel() == n, op, ": row_ids must hold one entry per row");
     TORCH_CHECK(xb_ptr.numel() >= 1 && xb_val.numel() == xb_col.numel(), op, ": xb_ptr / xb_col / xb_val are not one CSR matrix");
-    check_tensor<const int32_t>(xb_ptr); check_tensor<const int32_t>(xb_col); check_tensor<const float>(xb_val);
     check_csc(op, "wc", wc_ptr, wc_row, wc_val, n_items);
-    check_tensor<const int32_t>(ids); check_tensor<const int32_t>(counts);
-    if (has_rows) check_tensor<const int32_t>(*row_ids);
-    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&xb_ptr, &xb_col, &xb_val, &wc_ptr, &wc_row, &wc_val, &counts})
-        TORCH_CHECK(t->device() == ids.device(), op, ": all tensors must live on one device");
-    TORCH_CHECK(!has_rows || row_ids->device() == ids.device(), op, ": all tensors must live on one device");
+    one_device(op, ids, {&xb_ptr, &xb_col, &xb_val, &wc_ptr, &wc_row, &wc_val, &counts}, {&row_ids});
     return n;
 }
 
@@ -445,12 +470,11 @@ void explain_topk(const OT &row_ids, const at::Tensor &xb_ptr, const at::Tensor 
     const int64_t n = check_lists_x_w("explain_topk", row_ids, xb_ptr, xb_col, xb_val, n_items, wc_ptr, wc_row, wc_val, ids, counts, list_k);
     TORCH_CHECK(items.numel() == n * list_k * top_m && contrib.numel() == n * list_k * top_m && support.numel() == n * list_k,
                 "explain_topk: outputs must be items[n_rows, list_k, top_m], contrib[same], support[n_rows, list_k]");
-    check_tensor<int32_t>(items); check_tensor<float>(contrib); check_tensor<int32_t>(support);
-    check(abi().explain_topk(static_cast<int32_t>(n), ptr<const int32_t>(row_ids), ptr<const int32_t>(xb_ptr), ptr<const int32_t>(xb_col),
-                             ptr<const float>(xb_val), static_cast<int32_t>(xb_ptr.numel() - 1), xb_col.numel(), static_cast<int32_t>(n_items),
-                             ptr<const int32_t>(wc_ptr), ptr<const int32_t>(wc_row), ptr<const float>(wc_val), wc_row.numel(),
-                             ptr<const int32_t>(ids), ids.size(1), static_cast<int32_t>(list_k), ptr<const int32_t>(counts),
-                             static_cast<int32_t>(top_m), ptr<int32_t>(items), ptr<float>(contrib), ptr<int32_t>(support), stream_of(items)),
+    check(abi().explain_topk(static_cast<int32_t>(n), cptr<const int32_t>(row_ids), cptr<const int32_t>(xb_ptr), cptr<const int32_t>(xb_col),
+                             cptr<const float>(xb_val), static_cast<int32_t>(xb_ptr.numel() - 1), xb_col.numel(), static_cast<int32_t>(n_items),
+                             cptr<const int32_t>(wc_ptr), cptr<const int32_t>(wc_row), cptr<const float>(wc_val), wc_row.numel(),
+                             cptr<const int32_t>(ids), ids.size(1), static_cast<int32_t>(list_k), cptr<const int32_t>(counts),
+                             static_cast<int32_t>(top_m), cptr<int32_t>(items), cptr<float>(contrib), cptr<int32_t>(support), stream_of(items)),
           "rtrec_slim_explain_topk");
 }
 
@@ -467,23 +491,15 @@ void audience_topk(const at::Tensor &items, int64_t n_users, const at::Tensor &x
     check_csc("audience_topk", "xc", xc_ptr, xc_row, xc_val, n_items);             // (n_items is wc_ptr's: X must have W's columns)
     check_csc("audience_topk", "wc", wc_ptr, wc_row, wc_val, n_items);
     TORCH_CHECK(xc_row.numel() <= INT32_MAX && wc_row.numel() <= INT32_MAX, "audience_topk: xc_row and wc_row must be shorter than 2^31");
-    const bool masked = user_mask.has_value() && user_mask->defined();
-    TORCH_CHECK(!masked || user_mask->numel() == (n_users + 31) / 32, "audience_topk: user_mask must hold (n_users + 31) / 32 words");
+    TORCH_CHECK(!has(user_mask) || user_mask->numel() == (n_users + 31) / 32, "audience_topk: user_mask must hold (n_users + 31) / 32 words");
     TORCH_CHECK(users.numel() == n * top_n && scores.numel() == n * top_n && count.numel() == n && eligible.numel() == n,
                 "audience_topk: outputs must be users[n_q, top_n], scores[same], count[n_q], eligible[n_q]");
-    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
-    check_tensor<const int32_t>(items);
-    if (masked) check_tensor<const int32_t>(*user_mask);
-    check_tensor<int32_t>(users); check_tensor<float>(scores); check_tensor<int32_t>(count); check_tensor<int32_t>(eligible);
-    check_tensor<void>(ws);
-    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&xc_ptr, &xc_row, &xc_val, &wc_ptr, &wc_row, &wc_val, &users, &scores, &count, &eligible, &ws})
-        TORCH_CHECK(t->device() == items.device(), "audience_topk: all tensors must live on one device");
-    TORCH_CHECK(!masked || user_mask->device() == items.device(), "audience_topk: all tensors must live on one device");
-    check(abi().audience_topk(static_cast<int32_t>(n), ptr<const int32_t>(items), static_cast<int32_t>(n_users), static_cast<int32_t>(n_items),
-                              ptr<const int32_t>(xc_ptr), ptr<const int32_t>(xc_row), ptr<const float>(xc_val), xc_row.numel(),
-                              ptr<const int32_t>(wc_ptr), ptr<const int32_t>(wc_row), ptr<const float>(wc_val), wc_row.numel(),
-                              static_cast<int32_t>(top_n), filter_interacted ? 1 : 0, ptr<const int32_t>(user_mask), ptr<int32_t>(users),
-                              ptr<float>(scores), ptr<int32_t>(count), ptr<int32_t>(eligible), ptr<void>(ws),
+    one_device("audience_topk", items, {&xc_ptr, &xc_row, &xc_val, &wc_ptr, &wc_row, &wc_val, &users, &scores, &count, &eligible, &ws}, {&user_mask});
+    check(abi().audience_topk(static_cast<int32_t>(n), cptr<const int32_t>(items), static_cast<int32_t>(n_users), static_cast<int32_t>(n_items),
+                              cptr<const int32_t>(xc_ptr), cptr<const int32_t>(xc_row), cptr<const float>(xc_val), xc_row.numel(),
+                              cptr<const int32_t>(wc_ptr), cptr<const int32_t>(wc_row), cptr<const float>(wc_val), wc_row.numel(),
+                              static_cast<int32_t>(top_n), filter_interacted ? 1 : 0, cptr<const int32_t>(user_mask), cptr<int32_t>(users),
+                              cptr<float>(scores), cptr<int32_t>(count), cptr<int32_t>(eligible), cptr<void>(ws),
                               static_cast<size_t>(ws.numel() * ws.element_size()), stream_of(users)),
           "rtrec_slim_audience_topk");
 }
@@ -497,20 +513,18 @@ void score_pairs(const OT &row_ids, const at::Tensor &xb_ptr, const at::Tensor &
                  at::Tensor scores, at::Tensor support, at::Tensor order, at::Tensor count) {
     TORCH_CHECK(list_k >= 1 && list_k <= 1024, "score_pairs: list_k must lie in 1..1024, got ", list_k);
     TORCH_CHECK(top_k >= 0 && top_k <= list_k, "score_pairs: top_k must lie in 0..list_k, got ", top_k);
-    TORCH_CHECK(waves_per_row == 0 || waves_per_row == 1 || waves_per_row == 4, "score_pairs: waves_per_row must be 0, 1 or 4, got ", waves_per_row);
+    check_waves("score_pairs", waves_per_row);
     const int64_t n = check_lists_x_w("score_pairs", row_ids, xb_ptr, xb_col, xb_val, n_items, wc_ptr, wc_row, wc_val, ids, counts, list_k);
     TORCH_CHECK(scores.numel() == n * list_k && support.numel() == n * list_k, "score_pairs: scores and support must be [n_rows, list_k]");
     TORCH_CHECK(order.numel() == n * top_k && count.numel() == (top_k > 0 ? n : count.numel()) && (count.numel() == n || count.numel() == 0),
                 "score_pairs: outputs must be order[n_rows, top_k] and count[n_rows] (count may be empty when top_k == 0)");
-    check_tensor<float>(scores); check_tensor<int32_t>(support); check_tensor<int32_t>(order); check_tensor<int32_t>(count);
-    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&scores, &support, &order, &count})
-        TORCH_CHECK(t->device() == ids.device(), "score_pairs: all tensors must live on one device");
-    check(abi().score_pairs(static_cast<int32_t>(n), ptr<const int32_t>(row_ids), ptr<const int32_t>(xb_ptr), ptr<const int32_t>(xb_col),
-                            ptr<const float>(xb_val), static_cast<int32_t>(xb_ptr.numel() - 1), xb_col.numel(), static_cast<int32_t>(n_items),
-                            ptr<const int32_t>(wc_ptr), ptr<const int32_t>(wc_row), ptr<const float>(wc_val), wc_row.numel(),
-                            ptr<const int32_t>(ids), ids.size(1), static_cast<int32_t>(list_k), ptr<const int32_t>(counts),
-                            static_cast<int32_t>(top_k), filter_interacted ? 1 : 0, static_cast<int32_t>(waves_per_row), ptr<float>(scores),
-                            ptr<int32_t>(support), ptr<int32_t>(order), ptr<int32_t>(count), stream_of(scores)),
+    one_device("score_pairs", ids, {&scores, &support, &order, &count});
+    check(abi().score_pairs(static_cast<int32_t>(n), cptr<const int32_t>(row_ids), cptr<const int32_t>(xb_ptr), cptr<const int32_t>(xb_col),
+                            cptr<const float>(xb_val), static_cast<int32_t>(xb_ptr.numel() - 1), xb_col.numel(), static_cast<int32_t>(n_items),
+                            cptr<const int32_t>(wc_ptr), cptr<const int32_t>(wc_row), cptr<const float>(wc_val), wc_row.numel(),
+                            cptr<const int32_t>(ids), ids.size(1), static_cast<int32_t>(list_k), cptr<const int32_t>(counts),
+                            static_cast<int32_t>(top_k), filter_interacted ? 1 : 0, static_cast<int32_t>(waves_per_row), cptr<float>(scores),
+                            cptr<int32_t>(support), cptr<int32_t>(order), cptr<int32_t>(count), stream_of(scores)),
           "rtrec_slim_score_pairs");
 }
 
@@ -522,25 +536,18 @@ void diversify_lists(const at::Tensor &wc_ptr, const at::Tensor &wc_row, const a
     TORCH_CHECK(list_k >= 1 && list_k <= 1024, "diversify_lists: list_k must lie in 1..1024, got ", list_k);
     TORCH_CHECK(keep >= 1 && keep <= list_k, "diversify_lists: keep must lie in 1..list_k, got ", keep);
     TORCH_CHECK(lam >= 0.0 && lam <= 1.0, "diversify_lists: lam must lie in [0, 1], got ", lam);
-    TORCH_CHECK(waves_per_row == 0 || waves_per_row == 1 || waves_per_row == 4, "diversify_lists: waves_per_row must be 0, 1 or 4, got ", waves_per_row);
-    TORCH_CHECK(ids.dim() == 2 && ids.size(1) >= list_k, "diversify_lists: ids must be [n_rows, >= list_k]");
-    const int64_t n = ids.size(0);
-    TORCH_CHECK(scores.dim() == 2 && scores.size(0) == n && scores.size(1) >= list_k, "diversify_lists: scores must be [n_rows, >= list_k]");
-    TORCH_CHECK(n <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, "diversify_lists: too many rows or items");
-    TORCH_CHECK(counts.numel() == n, "diversify_lists: counts must hold one entry per row");
+    check_waves("diversify_lists", waves_per_row);
+    const int64_t n = check_list("diversify_lists", "", "list_k", ids, &scores, &counts, list_k);
+    check_rows_items("diversify_lists", n, n_items);
     TORCH_CHECK(order.numel() == n * keep && value.numel() == n * keep && penalty.numel() == n * keep && count.numel() == n,
                 "diversify_lists: outputs must be order[n_rows, keep], value[same], penalty[same], count[n_rows]");
-    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
     check_csc("diversify_lists", "wc", wc_ptr, wc_row, wc_val, n_items);
-    check_tensor<const int32_t>(ids); check_tensor<const float>(scores); check_tensor<const int32_t>(counts);
-    check_tensor<int32_t>(order); check_tensor<float>(value); check_tensor<float>(penalty); check_tensor<int32_t>(count);
-    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&wc_ptr, &wc_row, &wc_val, &scores, &counts, &order, &value, &penalty, &count})
-        TORCH_CHECK(t->device() == ids.device(), "diversify_lists: all tensors must live on one device");
-    check(abi().diversify_lists(static_cast<int32_t>(n), static_cast<int32_t>(n_items), ptr<const int32_t>(wc_ptr), ptr<const int32_t>(wc_row),
-                                ptr<const float>(wc_val), wc_row.numel(), ptr<const int32_t>(ids), ids.size(1), ptr<const float>(scores),
-                                scores.size(1), static_cast<int32_t>(list_k), ptr<const int32_t>(counts), static_cast<int32_t>(keep),
-                                static_cast<float>(lam), static_cast<int32_t>(waves_per_row), ptr<int32_t>(order), ptr<float>(value),
-                                ptr<float>(penalty), ptr<int32_t>(count), stream_of(order)),
+    one_device("diversify_lists", ids, {&wc_ptr, &wc_row, &wc_val, &scores, &counts, &order, &value, &penalty, &count});
+    check(abi().diversify_lists(static_cast<int32_t>(n), static_cast<int32_t>(n_items), cptr<const int32_t>(wc_ptr), cptr<const int32_t>(wc_row),
+                                cptr<const float>(wc_val), wc_row.numel(), cptr<const int32_t>(ids), ids.size(1), cptr<const float>(scores),
+                                scores.size(1), static_cast<int32_t>(list_k), cptr<const int32_t>(counts), static_cast<int32_t>(keep),
+                                static_cast<float>(lam), static_cast<int32_t>(waves_per_row), cptr<int32_t>(order), cptr<float>(value),
+                                cptr<float>(penalty), cptr<int32_t>(count), stream_of(order)),
           "rtrec_slim_diversify_lists");
 }
 
@@ -551,31 +558,20 @@ void list_quality(const at::Tensor &wc_ptr, const at::Tensor &wc_row, const at::
                   const at::Tensor &counts, int64_t list_k, const OT &item_weight, int64_t waves_per_row, at::Tensor n, at::Tensor sim_sum,
                   at::Tensor linked, at::Tensor weight_sum, const OT &exposure) {
     TORCH_CHECK(list_k >= 1 && list_k <= 1024, "list_quality: list_k must lie in 1..1024, got ", list_k);
-    TORCH_CHECK(waves_per_row == 0 || waves_per_row == 1 || waves_per_row == 4, "list_quality: waves_per_row must be 0, 1 or 4, got ", waves_per_row);
-    TORCH_CHECK(ids.dim() == 2 && ids.size(1) >= list_k, "list_quality: ids must be [n_rows, >= list_k]");
-    const int64_t rows = ids.size(0);
-    TORCH_CHECK(rows <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, "list_quality: too many rows or items");
-    TORCH_CHECK(counts.numel() == rows, "list_quality: counts must hold one entry per row");
+    check_waves("list_quality", waves_per_row);
+    const int64_t rows = check_list("list_quality", "", "list_k", ids, nullptr, &counts, list_k);
+    check_rows_items("list_quality", rows, n_items);
     TORCH_CHECK(n.numel() == rows && sim_sum.numel() == rows && linked.numel() == rows && weight_sum.numel() == rows,
                 "list_quality: outputs must be n[n_rows], sim_sum[n_rows], linked[n_rows], weight_sum[n_rows]");
-    const bool weighted = item_weight.has_value() && item_weight->defined(), exposed = exposure.has_value() && exposure->defined();
-    TORCH_CHECK(!weighted || item_weight->numel() == n_items, "list_quality: item_weight must hold n_items entries");
-    TORCH_CHECK(!exposed || exposure->numel() == n_items, "list_quality: exposure must hold n_items entries");
-    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
+    TORCH_CHECK(!has(item_weight) || item_weight->numel() == n_items, "list_quality: item_weight must hold n_items entries");
+    TORCH_CHECK(!has(exposure) || exposure->numel() == n_items, "list_quality: exposure must hold n_items entries");
     check_csc("list_quality", "wc", wc_ptr, wc_row, wc_val, n_items);
-    check_tensor<const int32_t>(ids); check_tensor<const int32_t>(counts);
-    check_tensor<int32_t>(n); check_tensor<float>(sim_sum); check_tensor<int32_t>(linked); check_tensor<float>(weight_sum);
-    if (weighted) check_tensor<const float>(*item_weight);
-    if (exposed) check_tensor<int32_t>(*exposure);
-    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&wc_ptr, &wc_row, &wc_val, &counts, &n, &sim_sum, &linked, &weight_sum})
-        TORCH_CHECK(t->device() == ids.device(), "list_quality: all tensors must live on one device");
-    TORCH_CHECK((!weighted || item_weight->device() == ids.device()) && (!exposed || exposure->device() == ids.device()),
-                "list_quality: all tensors must live on one device");
-    check(abi().list_quality(static_cast<int32_t>(rows), static_cast<int32_t>(n_items), ptr<const int32_t>(wc_ptr), ptr<const int32_t>(wc_row),
-                             ptr<const float>(wc_val), wc_row.numel(), ptr<const int32_t>(ids), ids.size(1), static_cast<int32_t>(list_k),
-                             ptr<const int32_t>(counts), ptr<const float>(item_weight), ptr<int32_t>(exposure),
-                             static_cast<int32_t>(waves_per_row), ptr<int32_t>(n), ptr<float>(sim_sum), ptr<int32_t>(linked),
-                             ptr<float>(weight_sum), stream_of(n)),
+    one_device("list_quality", ids, {&wc_ptr, &wc_row, &wc_val, &counts, &n, &sim_sum, &linked, &weight_sum}, {&item_weight, &exposure});
+    check(abi().list_quality(static_cast<int32_t>(rows), static_cast<int32_t>(n_items), cptr<const int32_t>(wc_ptr), cptr<const int32_t>(wc_row),
+                             cptr<const float>(wc_val), wc_row.numel(), cptr<const int32_t>(ids), ids.size(1), static_cast<int32_t>(list_k),
+                             cptr<const int32_t>(counts), cptr<const float>(item_weight), cptr<int32_t>(exposure),
+                             static_cast<int32_t>(waves_per_row), cptr<int32_t>(n), cptr<float>(sim_sum), cptr<int32_t>(linked),
+                             cptr<float>(weight_sum), stream_of(n)),
           "rtrec_slim_list_quality");
 }
 
@@ -589,7 +585,7 @@ void catalogue_ranks(const at::Tensor &scores, int64_t n_items, const OT &row_id
     TORCH_CHECK(mode == RTREC_TOPK_SPARSE || mode == RTREC_TOPK_DENSE, "catalogue_ranks: mode must be 0 (SPARSE) or 1 (DENSE), got ", mode);
     TORCH_CHECK(scores.dim() == 2, "catalogue_ranks: scores must be [n_rows, >= n_items]");
     const int64_t rows = scores.size(0), n_tg = tg_items.numel();
-    TORCH_CHECK(rows <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, "catalogue_ranks: too many rows or items");
+    check_rows_items("catalogue_ranks", rows, n_items);
     TORCH_CHECK(scores.size(1) >= n_items, "catalogue_ranks: scores must be [n_rows, >= n_items]");
     TORCH_CHECK(scores.scalar_type() == at::kFloat || scores.scalar_type() == at::kDouble, "catalogue_ranks: scores must be float32 or float64, got ",
                 scores.scalar_type());
@@ -597,23 +593,15 @@ void catalogue_ranks(const at::Tensor &scores, int64_t n_items, const OT &row_id
     TORCH_CHECK(above.numel() == n_tg && tied.numel() == n_tg && score.numel() == n_tg && competing.numel() == rows,
                 "catalogue_ranks: outputs must be above[n_tg], tied[n_tg], score[n_tg], competing[n_rows]");
     TORCH_CHECK(xb_ptr.numel() >= 1 && xb_ptr.numel() - 1 <= INT32_MAX, "catalogue_ranks: xb_ptr must hold n_x_rows + 1 offsets");
-    const bool with_rows = row_ids.has_value() && row_ids->defined();
-    TORCH_CHECK(!with_rows || row_ids->numel() == rows, "catalogue_ranks: row_ids must hold one entry per row");
-    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
+    TORCH_CHECK(!has(row_ids) || row_ids->numel() == rows, "catalogue_ranks: row_ids must hold one entry per row");
+    one_device("catalogue_ranks", scores, {&xb_ptr, &xb_col, &tg_ptr, &tg_items, &above, &tied, &score, &competing}, {&row_ids});
     const bool f64 = scores.scalar_type() == at::kDouble;
-    if (f64) check_tensor<const double>(scores); else check_tensor<const float>(scores);
-    check_tensor<const int32_t>(xb_ptr); check_tensor<const int32_t>(xb_col);
-    check_tensor<const int64_t>(tg_ptr); check_tensor<const int32_t>(tg_items);
-    check_tensor<int32_t>(above); check_tensor<int32_t>(tied); check_tensor<double>(score); check_tensor<int32_t>(competing);
-    if (with_rows) check_tensor<const int32_t>(*row_ids);
-    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&xb_ptr, &xb_col, &tg_ptr, &tg_items, &above, &tied, &score, &competing})
-        TORCH_CHECK(t->device() == scores.device(), "catalogue_ranks: all tensors must live on one device");
-    TORCH_CHECK(!with_rows || row_ids->device() == scores.device(), "catalogue_ranks: all tensors must live on one device");
-    check(abi().catalogue_ranks(static_cast<int32_t>(rows), static_cast<int32_t>(n_items), ptr<const void>(scores), scores.size(1), f64 ? 1 : 0,
-                                ptr<const int32_t>(row_ids), ptr<const int32_t>(xb_ptr), ptr<const int32_t>(xb_col),
+    const void *d_scores = f64 ? static_cast<const void *>(cptr<const double>(scores)) : cptr<const float>(scores);
+    check(abi().catalogue_ranks(static_cast<int32_t>(rows), static_cast<int32_t>(n_items), d_scores, scores.size(1), f64 ? 1 : 0,
+                                cptr<const int32_t>(row_ids), cptr<const int32_t>(xb_ptr), cptr<const int32_t>(xb_col),
                                 static_cast<int32_t>(xb_ptr.numel() - 1), xb_col.numel(), filter_interacted ? 1 : 0, static_cast<int32_t>(mode),
-                                ptr<const int64_t>(tg_ptr), ptr<const int32_t>(tg_items), n_tg, ptr<int32_t>(above), ptr<int32_t>(tied),
-                                ptr<double>(score), ptr<int32_t>(competing), stream_of(competing)),
+                                cptr<const int64_t>(tg_ptr), cptr<const int32_t>(tg_items), n_tg, cptr<int32_t>(above), cptr<int32_t>(tied),
+                                cptr<double>(score), cptr<int32_t>(competing), stream_of(competing)),
           "rtrec_slim_catalogue_ranks");
 }
 
@@ -628,17 +616,13 @@ void blend_lists(int64_t n_items, const at::Tensor &a_ids, const at::Tensor &a_s
     TORCH_CHECK(ka >= 1 && ka <= 1024 && kb >= 1 && kb <= 1024, "blend_lists: ka and kb must lie in 1..1024, got ", ka, " and ", kb);
     TORCH_CHECK(keep >= 1 && keep <= ka + kb, "blend_lists: keep must lie in 1..ka+kb, got ", keep);
     TORCH_CHECK(weight_b >= 0.0 && k >= 0.0, "blend_lists: weight_b and k must lie in [0, inf], got ", weight_b, " and ", k);
-    TORCH_CHECK(waves_per_row == 0 || waves_per_row == 1 || waves_per_row == 4, "blend_lists: waves_per_row must be 0, 1 or 4, got ", waves_per_row);
-    TORCH_CHECK(a_ids.dim() == 2 && a_ids.size(1) >= ka, "blend_lists: a_ids must be [n_rows, >= ka]");
-    const int64_t rows = a_ids.size(0);
-    TORCH_CHECK(a_scores.dim() == 2 && a_scores.size(0) == rows && a_scores.size(1) >= ka, "blend_lists: a_scores must be [n_rows, >= ka]");
-    TORCH_CHECK(b_ids.dim() == 2 && b_ids.size(0) == rows && b_ids.size(1) >= kb, "blend_lists: b_ids must be [n_rows, >= kb]");
-    TORCH_CHECK(b_scores.dim() == 2 && b_scores.size(0) == rows && b_scores.size(1) >= kb, "blend_lists: b_scores must be [n_rows, >= kb]");
-    TORCH_CHECK(rows <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX, "blend_lists: too many rows or items");
+    check_waves("blend_lists", waves_per_row);
+    const int64_t rows = check_list("blend_lists", "a_", "ka", a_ids, &a_scores, nullptr, ka);
+    check_list("blend_lists", "b_", "kb", b_ids, &b_scores, nullptr, kb, rows);
+    check_rows_items("blend_lists", rows, n_items);
     TORCH_CHECK(a_counts.numel() == rows && b_counts.numel() == rows, "blend_lists: a_counts and b_counts must hold one entry per row");
     TORCH_CHECK(ids.numel() == rows * keep && value.numel() == rows * keep && source.numel() == rows * keep && count.numel() == rows,
                 "blend_lists: outputs must be ids[n_rows, keep], value[same], source[same], count[n_rows]");
-    const auto has = [](const OT &t) { return t.has_value() && t->defined(); };
     int64_t n_x_rows = 0, xb_nnz = 0, cn_nnz = 0;
     if (contacts) {
         TORCH_CHECK(has(xb_ptr) && has(xb_col), "blend_lists: contacts need xb_ptr and xb_col");
@@ -646,35 +630,26 @@ void blend_lists(int64_t n_items, const at::Tensor &a_ids, const at::Tensor &a_s
         n_x_rows = xb_ptr->numel() - 1;
         xb_nnz = xb_col->numel();
         TORCH_CHECK(!has(row_ids) || row_ids->numel() == rows, "blend_lists: row_ids must hold one entry per row");
-        check_tensor<const int32_t>(*xb_ptr); check_tensor<const int32_t>(*xb_col);
-        if (has(row_ids)) check_tensor<const int32_t>(*row_ids);
         if (has(cn_ptr)) {
             TORCH_CHECK(has(cn_col) && has(cn_val), "blend_lists: cn_ptr comes with cn_col and cn_val");
             TORCH_CHECK(cn_ptr->numel() == n_x_rows + 1, "blend_lists: cn_ptr must hold n_x_rows + 1 offsets");
             TORCH_CHECK(cn_col->numel() == cn_val->numel(), "blend_lists: cn_col and cn_val must have one length");
             cn_nnz = cn_col->numel();
-            check_tensor<const int32_t>(*cn_ptr); check_tensor<const int32_t>(*cn_col); check_tensor<const int32_t>(*cn_val);
         }
-        for (const OT *t : std::initializer_list<const OT *>{&row_ids, &xb_ptr, &xb_col, &cn_ptr, &cn_col, &cn_val})
-            TORCH_CHECK(!has(*t) || (*t)->device() == a_ids.device(), "blend_lists: all tensors must live on one device");
+        one_device("blend_lists", a_ids, {}, {&row_ids, &xb_ptr, &xb_col, &cn_ptr, &cn_col, &cn_val});
     }
-    // every tensor is checked even when it is empty (ptr<> skips those): an empty call is still a typed call
-    check_tensor<const int32_t>(a_ids); check_tensor<const float>(a_scores); check_tensor<const int32_t>(a_counts);
-    check_tensor<const int32_t>(b_ids); check_tensor<const float>(b_scores); check_tensor<const int32_t>(b_counts);
-    check_tensor<int32_t>(ids); check_tensor<float>(value); check_tensor<int32_t>(source); check_tensor<int32_t>(count);
-    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&a_scores, &a_counts, &b_ids, &b_scores, &b_counts, &ids, &value, &source, &count})
-        TORCH_CHECK(t->device() == a_ids.device(), "blend_lists: all tensors must live on one device");
+    one_device("blend_lists", a_ids, {&a_scores, &a_counts, &b_ids, &b_scores, &b_counts, &ids, &value, &source, &count});
     const bool counted = contacts && has(cn_ptr);
-    check(abi().blend_lists(static_cast<int32_t>(rows), static_cast<int32_t>(n_items), ptr<const int32_t>(a_ids), a_ids.size(1),
-                            ptr<const float>(a_scores), a_scores.size(1), ptr<const int32_t>(a_counts), static_cast<int32_t>(ka),
-                            ptr<const int32_t>(b_ids), b_ids.size(1), ptr<const float>(b_scores), b_scores.size(1), ptr<const int32_t>(b_counts),
+    check(abi().blend_lists(static_cast<int32_t>(rows), static_cast<int32_t>(n_items), cptr<const int32_t>(a_ids), a_ids.size(1),
+                            cptr<const float>(a_scores), a_scores.size(1), cptr<const int32_t>(a_counts), static_cast<int32_t>(ka),
+                            cptr<const int32_t>(b_ids), b_ids.size(1), cptr<const float>(b_scores), b_scores.size(1), cptr<const int32_t>(b_counts),
                             static_cast<int32_t>(kb), static_cast<int32_t>(keep), static_cast<float>(weight_b),
                             contacts ? RTREC_BLEND_CONTACTS : RTREC_BLEND_CONSTANT, k, mnz ? 1 : 0,
-                            contacts ? ptr<const int32_t>(row_ids) : nullptr, contacts ? ptr<const int32_t>(xb_ptr) : nullptr,
-                            contacts ? ptr<const int32_t>(xb_col) : nullptr, static_cast<int32_t>(n_x_rows), xb_nnz,
-                            counted ? ptr<const int32_t>(cn_ptr) : nullptr, counted ? ptr<const int32_t>(cn_col) : nullptr,
-                            counted ? ptr<const int32_t>(cn_val) : nullptr, cn_nnz, static_cast<int32_t>(waves_per_row), ptr<int32_t>(ids),
-                            ptr<float>(value), ptr<int32_t>(source), ptr<int32_t>(count), stream_of(count)),
+                            contacts ? cptr<const int32_t>(row_ids) : nullptr, contacts ? cptr<const int32_t>(xb_ptr) : nullptr,
+                            contacts ? cptr<const int32_t>(xb_col) : nullptr, static_cast<int32_t>(n_x_rows), xb_nnz,
+                            counted ? cptr<const int32_t>(cn_ptr) : nullptr, counted ? cptr<const int32_t>(cn_col) : nullptr,
+                            counted ? cptr<const int32_t>(cn_val) : nullptr, cn_nnz, static_cast<int32_t>(waves_per_row), cptr<int32_t>(ids),
+                            cptr<float>(value), cptr<int32_t>(source), cptr<int32_t>(count), stream_of(count)),
           "rtrec_slim_blend_lists");
 }
 
@@ -695,38 +670,25 @@ void factor_topk(const OT &row_ids, const OT &p_index, int64_t n_x_rows, const a
     TORCH_CHECK(p.dim() == 2 && p.size(1) >= dim && p.size(0) <= INT32_MAX, "factor_topk: p must be [n_p_rows, >= dim]");
     TORCH_CHECK(qt.dim() == 2 && qt.size(0) >= dim && qt.size(1) >= n_items, "factor_topk: qt must be [>= dim, >= n_items]");
     TORCH_CHECK(ids.numel() == rows * top_k && scores.numel() == rows * top_k, "factor_topk: outputs must be ids[n_rows, top_k], scores[same], count[n_rows]");
-    const auto has = [](const OT &t) { return t.has_value() && t->defined(); };
     TORCH_CHECK(!has(row_ids) || row_ids->numel() == rows, "factor_topk: row_ids must hold one entry per job");
     TORCH_CHECK(!has(p_index) || p_index->numel() == n_x_rows, "factor_topk: p_index must hold one entry per row of X");
-    if (has(item_mask)) {
-        TORCH_CHECK(item_mask->numel() >= n_items && (item_mask->scalar_type() == at::kByte || item_mask->scalar_type() == at::kBool),
-                    "factor_topk: item_mask must hold one uint8 / bool entry per item");
-        check_tensor<void>(*item_mask);
-    }
+    TORCH_CHECK(!has(item_mask) || (item_mask->numel() >= n_items && (item_mask->scalar_type() == at::kByte || item_mask->scalar_type() == at::kBool)),
+                "factor_topk: item_mask must hold one uint8 / bool entry per item");
     int64_t xb_nnz = 0;
     if (filter_interacted) {
         TORCH_CHECK(has(xb_ptr) && has(xb_col), "factor_topk: filter_interacted needs xb_ptr and xb_col");
         TORCH_CHECK(xb_ptr->numel() == n_x_rows + 1, "factor_topk: xb_ptr must hold n_x_rows + 1 offsets");
         xb_nnz = xb_col->numel();
-        check_tensor<const int32_t>(*xb_ptr); check_tensor<const int32_t>(*xb_col);
     }
-    check_tensor<const float>(p); check_tensor<const float>(qt);
-    check_tensor<int32_t>(ids); check_tensor<float>(scores); check_tensor<int32_t>(count);
-    if (has(row_ids)) check_tensor<const int32_t>(*row_ids);
-    if (has(p_index)) check_tensor<const int32_t>(*p_index);
-    if (has(workspace)) check_tensor<void>(*workspace);
-    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&p, &qt, &ids, &scores})
-        TORCH_CHECK(t->device() == count.device(), "factor_topk: all tensors must live on one device");
-    for (const OT *t : std::initializer_list<const OT *>{&row_ids, &p_index, &item_mask, &xb_ptr, &xb_col, &workspace})
-        TORCH_CHECK(!has(*t) || (*t)->device() == count.device(), "factor_topk: all tensors must live on one device");
+    one_device("factor_topk", count, {&p, &qt, &ids, &scores}, {&row_ids, &p_index, &item_mask, &xb_ptr, &xb_col, &workspace});
     const size_t ws_bytes = has(workspace) ? static_cast<size_t>(workspace->numel()) * workspace->element_size() : 0;
-    check(abi().factor_topk(static_cast<int32_t>(rows), ptr<const int32_t>(row_ids), ptr<const int32_t>(p_index),
-                            static_cast<int32_t>(n_x_rows), ptr<const float>(p), p.size(1), static_cast<int32_t>(p.size(0)),
-                            ptr<const float>(qt), qt.size(1), static_cast<int32_t>(n_items), static_cast<int32_t>(dim),
-                            has(item_mask) && item_mask->numel() > 0 ? static_cast<const uint8_t *>(item_mask->data_ptr()) : nullptr,
-                            filter_interacted ? ptr<const int32_t>(xb_ptr) : nullptr, filter_interacted ? ptr<const int32_t>(xb_col) : nullptr,
+    check(abi().factor_topk(static_cast<int32_t>(rows), cptr<const int32_t>(row_ids), cptr<const int32_t>(p_index),
+                            static_cast<int32_t>(n_x_rows), cptr<const float>(p), p.size(1), static_cast<int32_t>(p.size(0)),
+                            cptr<const float>(qt), qt.size(1), static_cast<int32_t>(n_items), static_cast<int32_t>(dim),
+                            static_cast<const uint8_t *>(cptr<const void>(item_mask)),
+                            filter_interacted ? cptr<const int32_t>(xb_ptr) : nullptr, filter_interacted ? cptr<const int32_t>(xb_col) : nullptr,
                             xb_nnz, filter_interacted ? 1 : 0, static_cast<int32_t>(top_k), static_cast<int32_t>(item_splits),
-                            ptr<int32_t>(ids), ptr<float>(scores), ptr<int32_t>(count), ptr<void>(workspace), ws_bytes, stream_of(count)),
+                            cptr<int32_t>(ids), cptr<float>(scores), cptr<int32_t>(count), cptr<void>(workspace), ws_bytes, stream_of(count)),
           "rtrec_factor_topk");
 }
 
@@ -742,7 +704,6 @@ void feature_repr(const OT &job_rows, const at::Tensor &f_ptr, const at::Tensor 
     TORCH_CHECK(n_jobs >= 0 && n_jobs <= INT32_MAX, "feature_repr: n_jobs must lie in 0..2^31-1");
     TORCH_CHECK(f_ptr.numel() >= 1 && f_ptr.numel() - 1 <= INT32_MAX, "feature_repr: f_ptr must hold n_f_rows + 1 offsets");
     TORCH_CHECK(e.dim() == 2 && e.size(1) >= dim_e && e.size(0) <= INT32_MAX, "feature_repr: e must be [n_features, >= dim_e]");
-    const auto has = [](const OT &t) { return t.has_value() && t->defined(); };
     TORCH_CHECK(!has(f_val) || f_val->numel() == f_col.numel(), "feature_repr: f_val must hold one value per entry of f_col");
     TORCH_CHECK(!has(job_rows) || job_rows->numel() == n_jobs, "feature_repr: job_rows must hold one entry per job");
     TORCH_CHECK(layout == 0 || (has(bias) && bias->numel() == e.size(0)), "feature_repr: a stacking layout needs one bias per feature");
@@ -751,24 +712,14 @@ void feature_repr(const OT &job_rows, const at::Tensor &f_ptr, const at::Tensor 
                 "comp_stride >= n_jobs), got row_stride ", row_stride, " and comp_stride ", comp_stride);
     TORCH_CHECK(n_jobs == 0 || out.numel() > (n_jobs - 1) * row_stride + (width - 1) * comp_stride,
                 "feature_repr: out does not hold the last slot");
-    if (has(has_out)) {
-        TORCH_CHECK(has_out->numel() >= n_jobs && (has_out->scalar_type() == at::kByte || has_out->scalar_type() == at::kBool),
-                    "feature_repr: has must hold one uint8 / bool entry per job");
-        check_tensor<void>(*has_out);
-    }
-    check_tensor<const int32_t>(f_ptr); check_tensor<const int32_t>(f_col); check_tensor<const float>(e); check_tensor<float>(out);
-    if (has(f_val)) check_tensor<const float>(*f_val);
-    if (has(bias)) check_tensor<const float>(*bias);
-    if (has(job_rows)) check_tensor<const int32_t>(*job_rows);
-    for (const at::Tensor *t : std::initializer_list<const at::Tensor *>{&f_ptr, &f_col, &e})
-        TORCH_CHECK(t->device() == out.device(), "feature_repr: all tensors must live on one device");
-    for (const OT *t : std::initializer_list<const OT *>{&job_rows, &f_val, &bias, &has_out})
-        TORCH_CHECK(!has(*t) || (*t)->device() == out.device(), "feature_repr: all tensors must live on one device");
-    check(abi().feature_repr(static_cast<int32_t>(n_jobs), ptr<const int32_t>(job_rows), static_cast<int32_t>(f_ptr.numel() - 1),
-                             ptr<const int32_t>(f_ptr), ptr<const int32_t>(f_col), ptr<const float>(f_val), f_col.numel(),
-                             ptr<const float>(e), e.size(1), static_cast<int32_t>(e.size(0)), static_cast<int32_t>(dim_e),
-                             ptr<const float>(bias), static_cast<int32_t>(layout), ptr<float>(out), row_stride, comp_stride,
-                             has(has_out) && has_out->numel() > 0 ? static_cast<uint8_t *>(has_out->data_ptr()) : nullptr, stream_of(out)),
+    TORCH_CHECK(!has(has_out) || (has_out->numel() >= n_jobs && (has_out->scalar_type() == at::kByte || has_out->scalar_type() == at::kBool)),
+                "feature_repr: has must hold one uint8 / bool entry per job");
+    one_device("feature_repr", out, {&f_ptr, &f_col, &e}, {&job_rows, &f_val, &bias, &has_out});
+    check(abi().feature_repr(static_cast<int32_t>(n_jobs), cptr<const int32_t>(job_rows), static_cast<int32_t>(f_ptr.numel() - 1),
+                             cptr<const int32_t>(f_ptr), cptr<const int32_t>(f_col), cptr<const float>(f_val), f_col.numel(),
+                             cptr<const float>(e), e.size(1), static_cast<int32_t>(e.size(0)), static_cast<int32_t>(dim_e),
+                             cptr<const float>(bias), static_cast<int32_t>(layout), cptr<float>(out), row_stride, comp_stride,
+                             static_cast<uint8_t *>(cptr<void>(has_out)), stream_of(out)),
           "rtrec_feature_repr");
 }
 

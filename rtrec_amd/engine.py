@@ -1594,19 +1594,37 @@ class SlimEngine:
         """The resident X as the (ptr, col, val) device tensors an `xb` argument stands for."""
         return self._X["rptr"], self._X["rcol"], self._X["rval"]
 
-    def _upload_lists(self, row_ids, item_ids, counts, xb):
-        """The host side of explain_rows / score_pairs_rows: (B, k, device rows, device ids, device counts) for the lists
-        `item_ids` [B, k] of the rows `row_ids`; counts default to k, a row outside the matrix becomes -1 (no row)."""
-        row_ids = np.asarray(row_ids, dtype=np.int64)
+    @staticmethod
+    def _host_lists(item_ids, scores=None, counts=None, n_rows: Optional[int] = None,
+                    shape_error: str = "item_ids (and scores) must be [B, k] arrays of one shape"):
+        """The lists a caller brings, as the kernels take them: contiguous int32 ids [B, k], float32 scores of that shape (None
+        stays None) and int32 counts [B] (default k).  `n_rows`: the B the caller expects; `shape_error`: what to say when
+        the ids or the scores do not have the shape."""
         item_ids = np.ascontiguousarray(item_ids, dtype=np.int32)
-        if item_ids.ndim != 2 or item_ids.shape[0] != len(row_ids):
-            raise ValueError("item_ids must be [len(row_ids), k]")
+        if scores is not None:
+            scores = np.ascontiguousarray(scores, dtype=np.float32)
+        if (item_ids.ndim != 2 or (n_rows is not None and item_ids.shape[0] != n_rows)
+                or (scores is not None and scores.shape != item_ids.shape)):
+            raise ValueError(shape_error)
         B, k = item_ids.shape
         counts = np.full(B, k, dtype=np.int32) if counts is None else np.asarray(counts, dtype=np.int32)
         if counts.shape != (B,):
             raise ValueError("counts must hold one entry per row")
-        n_x = self.n_users if xb is None else int(xb[0].shape[0]) - 1
-        rows32 = np.where((row_ids >= 0) & (row_ids < n_x), row_ids, -1).astype(np.int32)
+        return item_ids, scores, counts
+
+    @staticmethod
+    def _rows32(row_ids, n_x: int) -> np.ndarray:
+        """`row_ids` as int32, -1 (no row) for a row outside the n_x rows of X."""
+        rows = np.asarray(row_ids, dtype=np.int64)
+        return np.where((rows >= 0) & (rows < n_x), rows, -1).astype(np.int32)
+
+    def _upload_lists(self, row_ids, item_ids, counts, xb):
+        """The host side of explain_rows / score_pairs_rows: (B, k, device rows, device ids, device counts) for the lists
+        `item_ids` [B, k] of the rows `row_ids`; counts default to k, a row outside the matrix becomes -1 (no row)."""
+        row_ids = np.asarray(row_ids, dtype=np.int64)
+        item_ids, _, counts = self._host_lists(item_ids, None, counts, len(row_ids), "item_ids must be [len(row_ids), k]")
+        B, k = item_ids.shape
+        rows32 = self._rows32(row_ids, self.n_users if xb is None else int(xb[0].shape[0]) - 1)
         return B, k, self._up(rows32), self._up(item_ids), self._up(counts)
 
     def explain_device(self, d_rows, n_rows: int, xb, ids, counts, top_m: int):
@@ -1731,14 +1749,7 @@ class SlimEngine:
                         lam: float = 0.7) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """diversify_device for lists the caller brings: numpy (order[B, keep], value, penalty, count[B]) for `item_ids` [B, k]
         (-1 or an id outside W = an empty position) with the base scores `scores` [B, k]; counts default to k."""
-        item_ids = np.ascontiguousarray(item_ids, dtype=np.int32)
-        scores = np.ascontiguousarray(scores, dtype=np.float32)
-        if item_ids.ndim != 2 or scores.shape != item_ids.shape:
-            raise ValueError("item_ids and scores must be two [B, k] arrays of one shape")
-        B, k = item_ids.shape
-        counts = np.full(B, k, dtype=np.int32) if counts is None else np.asarray(counts, dtype=np.int32)
-        if counts.shape != (B,):
-            raise ValueError("counts must hold one entry per row")
+        item_ids, scores, counts = self._host_lists(item_ids, scores, counts)
         out = self.diversify_device(self._up(item_ids), self._up(scores), self._up(counts), keep, lam)
         return tuple(t.cpu().numpy() for t in out)
 
@@ -1799,13 +1810,7 @@ class SlimEngine:
         """list_quality_device for lists the caller brings: numpy (n[B], sim_sum[B], linked[B], weight_sum[B], exposure[W's
         n_items] or None) for `item_ids` [B, k] (-1 or an id outside W = an empty position); counts default to k,
         `item_weight` [W's n_items] float32 or None; `novelty=True` weighs with item_novelty_device() instead."""
-        item_ids = np.ascontiguousarray(item_ids, dtype=np.int32)
-        if item_ids.ndim != 2:
-            raise ValueError("item_ids must be a [B, k] array")
-        B, k = item_ids.shape
-        counts = np.full(B, k, dtype=np.int32) if counts is None else np.asarray(counts, dtype=np.int32)
-        if counts.shape != (B,):
-            raise ValueError("counts must hold one entry per row")
+        item_ids, _, counts = self._host_lists(item_ids, None, counts)
         dw = self._whole_w("list_quality")
         if novelty and item_weight is not None:
             raise ValueError("list_quality: pass item_weight or novelty=True, not both")
@@ -1870,16 +1875,7 @@ class SlimEngine:
         list); counts default to the widths.  `row_ids` given: B is weighted by the contacts of those rows of the resident X
         (a row outside the matrix has none), with the counts of `contact_counts` (a CSR of integers over X's rows, or None)
         where it stores one; otherwise by `weight_b`."""
-        lists = []
-        for ids_, sc_, cnt_ in ((a_ids, a_scores, a_counts), (b_ids, b_scores, b_counts)):
-            ids_ = np.ascontiguousarray(ids_, dtype=np.int32)
-            sc_ = np.ascontiguousarray(sc_, dtype=np.float32)
-            if ids_.ndim != 2 or sc_.shape != ids_.shape:
-                raise ValueError("ids and scores of a list must be two [B, k] arrays of one shape")
-            cnt_ = np.full(ids_.shape[0], ids_.shape[1], dtype=np.int32) if cnt_ is None else np.asarray(cnt_, dtype=np.int32)
-            if cnt_.shape != (ids_.shape[0],):
-                raise ValueError("counts must hold one entry per row")
-            lists.append((ids_, sc_, cnt_))
+        lists = [self._host_lists(a_ids, a_scores, a_counts), self._host_lists(b_ids, b_scores, b_counts)]
         if lists[0][0].shape[0] != lists[1][0].shape[0]:
             raise ValueError("both lists must have one row per row")
         contacts = row_ids is not None
@@ -1890,7 +1886,7 @@ class SlimEngine:
             rows = np.asarray(row_ids, dtype=np.int64)
             if rows.shape != (lists[0][0].shape[0],):
                 raise ValueError("row_ids must hold one entry per row")
-            d_rows = self._up(np.where((rows >= 0) & (rows < self.n_users), rows, -1).astype(np.int32))
+            d_rows = self._up(self._rows32(rows, self.n_users))
             if contact_counts is not None:
                 C = sp.csr_matrix(contact_counts)
                 if C.shape[0] != self.n_users:

@@ -13,7 +13,7 @@ from tests.test_rerank_host import _batch
 pytestmark = pytest.mark.gpu
 
 WAVES = [1, 4, 0]
-GRID_CAP = 65536                         # kBlendMaxGrid of csrc/blend.hip: workgroups per launch
+GRID_CAP = 65536                         # kListMaxGrid of csrc/list_stage.hip.h: workgroups per launch
 
 
 def run_op(n_items, A, B, keep, weight_b=1.0, contacts=None, k=2.0, mnz=False, waves=0, ka=None, kb=None):

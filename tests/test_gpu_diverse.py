@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 WAVES = [1, 4]
 STAGE = 128                              # kDivStage of csrc/diversify.hip: entries of the winner's column staged in LDS per step
-GRID_CAP = 65536                         # kDivMaxGrid: workgroups per launch
+GRID_CAP = 65536                         # kListMaxGrid: workgroups per launch
 
 
 def run_op(W, ids, scores, counts, list_k, keep, lam, waves=0):

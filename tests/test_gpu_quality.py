@@ -17,7 +17,7 @@ from tests.test_rerank_host import _batch
 pytestmark = pytest.mark.gpu
 
 WAVES = [1, 4]
-GRID_CAP = 65536                         # kQualMaxGrid of csrc/list_quality.hip: workgroups per launch
+GRID_CAP = 65536                         # kListMaxGrid of csrc/list_stage.hip.h: workgroups per launch
 
 
 def run_op(W, ids, counts, list_k, weight=None, exposure=True, waves=0):
