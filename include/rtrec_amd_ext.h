@@ -278,6 +278,101 @@ int rtrec_feature_repr(int32_t n_jobs, const int32_t *d_job_rows, int32_t n_f_ro
                        const float *d_bias, int32_t layout, float *d_out, int64_t row_stride, int64_t comp_stride, uint8_t *d_has,
                        void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * FACTOR NORMS  (one Euclidean norm per vector of a dense float32 matrix: the divisors of rtrec_factor_similar_topk.)
+ * Component c of vector r is d_v[r * row_stride + c * comp_stride]; the strides follow rtrec_feature_repr: either
+ * comp_stride == 1 and row_stride >= dim (row-major) or row_stride == 1 and comp_stride >= n (component-major, the item matrix
+ * d_qt of rtrec_factor_topk).
+ *   norm        n2 = +0.0f, then for c = 0 .. dim-1 ascending n2 = fmaf(v[c], v[c], n2): one correctly rounded fused
+ *               multiply-add per component, float32 denormals kept; d_out[r] = sqrt(n2), correctly rounded to float32 (a
+ *               denormal n2 included).  n2 is rtrec_factor_topk's score of the vector with itself, bit for bit.  NOT numpy's
+ *               norm: numpy rounds every square on its own and adds them in its pairwise order (DESIGN, divergences)
+ * dim in 1..256: RTREC_ERR_UNSUPPORTED otherwise.  Negative n, strides of neither form, NULL arrays: RTREC_ERR_INVALID_ARG.
+ * n == 0: RTREC_OK before any pointer check.  No global state, no environment variable, no allocation, no synchronisation.
+ * The results never depend on the grid or on scheduling: a norm is one sequential chain computed by one thread.
+ * csrc/factor_norms.hip, factor_norms_kernel: one thread per vector (component-major: neighbouring threads read neighbouring
+ * items); the root is taken in float64 and rounded once more, which cannot double-round wrongly (53 >= 2 * 24 + 2).
+ * ------------------------------------------------------------------------------------- */
+int rtrec_factor_norms(int32_t n, const float *d_v, int64_t row_stride, int64_t comp_stride, int32_t dim, float *d_out,
+                       void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * FACTOR SIMILAR TOP-K  (cosine top-k of item vectors against the whole catalogue, the query itself excluded.)
+ * The reference's hybrid model takes the factor side of similar_items from implicit.topk(items=target, query=q, k,
+ * item_norms=||target_i||, filter_items=[query]) (rtrec/models/hybrid.py, _similar_items): a float32 GEMM, each score divided
+ * by the item's norm, the query set to -FLT_MAX, a top-k; the division by ||q|| follows later.
+ *   targets     component c of item i is d_qt[c * qt_stride + i], qt_stride >= n_items, dim in 1..256.  A caller selects
+ *               components by offsetting the pointer: for the matrix rtrec_feature_repr writes with RTREC_FEATURE_ITEM
+ *               ([1, b, e...]) the reference's [b, e...] is d_qt + qt_stride with dim - 1.  d_norms[n_items] are the divisors
+ *               (rtrec_factor_norms of the same components)
+ *   queries     job r names item q = d_queries[r].  With d_p == NULL its vector is column q of d_qt and its norm d_norms[q];
+ *               a q outside [0, n_items) is a job without a vector and returns an empty list.  With d_p != NULL its vector is
+ *               row r of d_p[n_rows][p_stride] (p_stride >= dim) and its norm d_p_norms[r]; q only names what is excluded and
+ *               may be -1 (or d_queries NULL): then nothing is excluded
+ *   score       dot = +0.0f, then dot = fmaf(vq[c], v_i[c], dot) for c = 0 .. dim-1 ascending (rtrec_factor_topk's chain);
+ *               s1 = fl(dot / d_norms[i]): ONE correctly rounded float32 division, denormals kept
+ *   competing   0 <= i < n_items, i != q, d_item_mask == NULL or d_item_mask[i] != 0, and s1 is not NaN.  So a zero vector
+ *               (0 / 0) never competes; +-inf compete as numbers
+ *   order       the larger s1 first; among == (-0.0 == +0.0) the lower item id.  Strict, so a list is unique
+ *   written     s1 as it is when write_cosine == 0.  With write_cosine != 0 the written score is fl(s1 / norm_q), one more
+ *               correctly rounded division made where the final list is written (never on the partial list of a chunk), and a
+ *               job whose query norm is not > 0 (NaN included) returns an empty list.  The list's order is s1's either way
+ *   out_div     d_out_div != NULL: d_out_div[r] = the job's query norm (+0.0f for a job without a vector) -- the divisor
+ *               rtrec_similar_blend applies after its cut, as the reference does
+ * Out, every slot written: d_out_ids[n_rows][top_k] / d_out_scores[n_rows][top_k], behind the list -1 / -inf;
+ * d_out_count[r] = min(top_k, competing items).
+ * item_splits, d_workspace and workspace_bytes are rtrec_factor_topk's, RTREC_FACTOR_TOPK_WORKSPACE_BYTES included.
+ * dim in 1..256, top_k in 1..128, item_splits in 0..64: RTREC_ERR_UNSUPPORTED otherwise.  NULL required arrays (d_queries
+ * without d_p; d_p_norms with d_p; d_qt and d_norms with n_items > 0; d_workspace with item_splits > 1), negative sizes and
+ * strides below their widths: RTREC_ERR_INVALID_ARG.  A workspace too small for an explicit item_splits: RTREC_ERR_WORKSPACE.
+ * n_rows == 0: RTREC_OK before any pointer check.  No global state, no environment variable, no allocation, no
+ * synchronisation.  The results never depend on item_splits, on the grid or on scheduling.
+ * csrc/factor_similar.hip, factor_similar_kernel: factor_topk_kernel's scan (32 queries x one chunk per one-wave workgroup, the
+ * v_mfma_f32_32x32x2_f32 chain, threshold in registers, candidate buffer in LDS, ranks by counting) with another epilogue: a lane
+ * loads the 16 norms its accumulators map to, divides, then tests threshold, query and mask; factor_similar_merge_kernel merges
+ * the chunks and makes the cosine division.  No atomics.
+ * ------------------------------------------------------------------------------------- */
+int rtrec_factor_similar_topk(int32_t n_rows, const int32_t *d_queries, const float *d_p, int64_t p_stride, const float *d_p_norms,
+                              const float *d_qt, int64_t qt_stride, int32_t n_items, int32_t dim, const float *d_norms,
+                              const uint8_t *d_item_mask, int32_t top_k, int32_t item_splits, int32_t write_cosine,
+                              int32_t *d_out_ids, float *d_out_scores, int32_t *d_out_count, float *d_out_div, void *d_workspace,
+                              size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * SIMILAR BLEND  (the hybrid's similar_items after its two top-k calls: cut, exclude, divide, min-max, a FLOAT64 sum per id.)
+ * The reference's HybridSlimFM._similar_items cuts the factor list at -FLT_MAX, divides it by ||q||, drops the query, runs
+ * minmax_normalize on both lists, adds them per id into a defaultdict(float) (comb_sum: every += is a float64 addition) and
+ * returns sorted(..., reverse=True)[:top_k].  List A is the factor list, list B SLIM's; both arrive best first, in the form of
+ * rtrec_slim_blend_lists: ka / kb positions (1..1024) of ids and float32 scores per row, strides >= ka / kb, counts clamped to
+ * [0, ka] / [0, kb].
+ *   length      a list is cut at its first position that lies behind its count, whose id is outside [0, n_items), or whose
+ *               RAW score is not finite or is <= -FLT_MAX: rtrec_slim_blend_lists' rule, applied before any division
+ *   exclude     what remains loses every entry whose id == d_exclude[r] (both lists); d_exclude == NULL or -1 excludes nothing
+ *   divide      with d_a_div != NULL, A's scores become fl(s / d_a_div[r]), correctly rounded; a divisor that is not > 0 (NaN
+ *               included) makes A empty for that row
+ *   norm        per non-empty list, over what is left: rtrec_slim_blend_lists' float32 fl(fl(s - mn) / fl(fl(mx - mn) + 1e-8f)).
+ *               An EMPTY list contributes nothing -- the reference raises ValueError (min of an empty sequence) there
+ *   union       the entries stand in order of first appearance: A's distinct ids, then the ids only B holds.  The value is a
+ *               float64: 0.0, then + (double)normA[p] for EVERY occurrence of the id in A in ascending p, then
+ *               + (double)normB[q] for every occurrence in B in ascending q; each addition is rounded to float64.  (This is not
+ *               rtrec_slim_blend_lists, which adds in float32 and lets a repeat inside A keep its last score.)
+ *   order       the larger value first; == values (-0.0 == +0.0) keep the union's order.  A NaN value is never listed
+ * Out, every slot written: d_out_ids[n_rows][keep], d_out_value[n_rows][keep] (FLOAT64), d_out_source[n_rows][keep] (1 = only A
+ * holds the item, 2 = only B, 3 = both), d_out_count[r] = min(keep, the entries whose value is a number); behind it -1 / -inf / 0.
+ * ka and kb in 1..1024, keep in 1..ka+kb, waves_per_row in {0, 1, 4}: RTREC_ERR_UNSUPPORTED otherwise.  NULL required arrays
+ * (all but d_a_div and d_exclude), negative sizes and a stride below its list length: RTREC_ERR_INVALID_ARG.  n_rows == 0:
+ * RTREC_OK before any pointer check.  No global state, no environment variable, no allocation, no synchronisation.  The results
+ * never depend on waves_per_row, on the grid size or on scheduling.
+ * csrc/similar_blend.hip, similar_blend_kernel: one row per workgroup on list_stage.hip.h's frame; both lists, their normalised
+ * values and the union's doubles in LDS (32 bytes per position of the longer list); an excluded position is a hole, not squeezed
+ * out; the owner of an entry adds its occurrences in order; ranks by counting over the doubles; no atomics.
+ * ------------------------------------------------------------------------------------- */
+int rtrec_similar_blend(int32_t n_rows, int32_t n_items, const int32_t *d_a_ids, int64_t a_ids_stride, const float *d_a_scores,
+                        int64_t a_scores_stride, const int32_t *d_a_counts, int32_t ka, const float *d_a_div,
+                        const int32_t *d_b_ids, int64_t b_ids_stride, const float *d_b_scores, int64_t b_scores_stride,
+                        const int32_t *d_b_counts, int32_t kb, const int32_t *d_exclude, int32_t keep, int32_t waves_per_row,
+                        int32_t *d_out_ids, double *d_out_value, int32_t *d_out_source, int32_t *d_out_count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,9 @@ EXT_EXPORTS = [
     "rtrec_slim_blend_lists",
     "rtrec_factor_topk",
     "rtrec_feature_repr",
+    "rtrec_factor_norms",
+    "rtrec_factor_similar_topk",
+    "rtrec_similar_blend",
 ]
 
 
@@ -235,6 +238,14 @@ def load() -> C.CDLL:
                                     vp, vp, vp, vp, C.c_size_t, vp]
     L.rtrec_feature_repr.restype = C.c_int
     L.rtrec_feature_repr.argtypes = [i32, vp, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, i32, i32, vp, i32, vp, C.c_int64, C.c_int64, vp, vp]
+    L.rtrec_factor_norms.restype = C.c_int
+    L.rtrec_factor_norms.argtypes = [i32, vp, C.c_int64, C.c_int64, i32, vp, vp]
+    L.rtrec_factor_similar_topk.restype = C.c_int
+    L.rtrec_factor_similar_topk.argtypes = [i32, vp, vp, C.c_int64, vp, vp, C.c_int64, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp,
+                                            vp, C.c_size_t, vp]
+    L.rtrec_similar_blend.restype = C.c_int
+    L.rtrec_similar_blend.argtypes = [i32, i32, vp, C.c_int64, vp, C.c_int64, vp, i32, vp, vp, C.c_int64, vp, C.c_int64, vp, i32, vp,
+                                      i32, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -345,6 +345,30 @@ class HipBackend:
         self.ops.feature_repr(job_rows, f_csr[0], f_csr[1], f_csr[2], table, int(dim_e), bias, int(layout), int(n_jobs), out,
                               int(row_stride), int(comp_stride), has)
 
+    def factor_norms(self, v, n, dim, row_stride, comp_stride, out):
+        """Per vector: its Euclidean norm as the ordered fmaf chain of its squares and a correctly rounded root; component c of
+        vector r is v.flatten()[r * row_stride + c * comp_stride] (csrc/factor_norms.hip; include/rtrec_amd_ext.h)."""
+        self.ops.factor_norms(v, int(n), int(dim), int(row_stride), int(comp_stride), out)
+
+    def factor_similar_topk(self, queries, p, p_norms, qt, n_items, dim, norms, item_mask, top_k, write_cosine, ids, scores, count,
+                            div=None, item_splits=0):
+        """Per query item: the top_k items by fl(dot / norm_i) against the component-major item vectors `qt`, the query and the
+        masked items left out; the query's vector is column queries[r] of `qt`, or row r of `p` (with `p_norms`); `div` [n_rows]
+        receives the query norms, `write_cosine` divides the written scores by them (csrc/factor_similar.hip;
+        include/rtrec_amd_ext.h).  The workspace of a chunked call is factor_topk's."""
+        n_rows = int(count.numel())
+        splits = self.factor_splits(n_rows, n_items, item_splits)
+        ws = self.empty((n_rows * splits * (int(top_k) * 8 + 4),), self.torch.uint8) if splits > 1 else None
+        self.ops.factor_similar_topk(queries, p, p_norms, qt, int(n_items), int(dim), norms, item_mask, int(top_k), splits,
+                                     bool(write_cosine), ids, scores, count, div, ws)
+
+    def similar_blend(self, n_items, a_ids, a_scores, a_counts, ka, a_div, b_ids, b_scores, b_counts, kb, exclude, keep, out_ids,
+                      value, source, count, waves_per_row=0):
+        """Per row: list A and list B cut, `exclude[r]` taken out, A divided by `a_div[r]`, each min-max normalised in float32,
+        summed per item id in float64 (`value` is a float64 tensor), ranked (csrc/similar_blend.hip; include/rtrec_amd_ext.h)."""
+        self.ops.similar_blend(int(n_items), a_ids, a_scores, a_counts, int(ka), a_div, b_ids, b_scores, b_counts, int(kb), exclude,
+                               int(keep), int(waves_per_row), out_ids, value, source, count)
+
     def audience_workspace_bytes(self, n_users, n_q, top_n):
         return int(self.lib.rtrec_slim_audience_workspace_bytes(n_users, n_q, top_n))
 

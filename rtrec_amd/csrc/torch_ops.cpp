@@ -57,6 +57,9 @@ struct Abi {
     decltype(&rtrec_slim_blend_lists) blend_lists = nullptr;
     decltype(&rtrec_factor_topk) factor_topk = nullptr;
     decltype(&rtrec_feature_repr) feature_repr = nullptr;
+    decltype(&rtrec_factor_norms) factor_norms = nullptr;
+    decltype(&rtrec_factor_similar_topk) factor_similar_topk = nullptr;
+    decltype(&rtrec_similar_blend) similar_blend = nullptr;
 };
 Abi g_abi;
 
@@ -723,6 +726,88 @@ void feature_repr(const OT &job_rows, const at::Tensor &f_ptr, const at::Tensor 
           "rtrec_feature_repr");
 }
 
+// v: any contiguous float32 tensor; component c of vector r is v.flatten()[r * row_stride + c * comp_stride]; out [n] float32
+// (include/rtrec_amd_ext.h, "FACTOR NORMS").
+void factor_norms(const at::Tensor &v, int64_t n, int64_t dim, int64_t row_stride, int64_t comp_stride, at::Tensor out) {
+    TORCH_CHECK(dim >= 1 && dim <= 256, "factor_norms: dim must lie in 1..256, got ", dim);
+    TORCH_CHECK(n >= 0 && n <= INT32_MAX, "factor_norms: n must lie in 0..2^31-1");
+    TORCH_CHECK((comp_stride == 1 && row_stride >= dim) || (row_stride == 1 && comp_stride >= n),
+                "factor_norms: the vectors are row-major (comp_stride 1, row_stride >= dim) or component-major (row_stride 1, "
+                "comp_stride >= n), got row_stride ", row_stride, " and comp_stride ", comp_stride);
+    TORCH_CHECK(n == 0 || v.numel() > (n - 1) * row_stride + (dim - 1) * comp_stride, "factor_norms: v does not hold the last component");
+    TORCH_CHECK(out.numel() == n, "factor_norms: out must hold one entry per vector");
+    one_device("factor_norms", out, {&v});
+    check(abi().factor_norms(static_cast<int32_t>(n), cptr<const float>(v), row_stride, comp_stride, static_cast<int32_t>(dim),
+                             cptr<float>(out), stream_of(out)),
+          "rtrec_factor_norms");
+}
+
+// queries [n_rows] int32 (absent only with p); p [n_rows, >= dim] / p_norms [n_rows]: brought query vectors (absent: the vectors
+// are columns of qt); qt [>= dim, >= n_items] float32 component-major; norms [>= n_items]; item_mask [>= n_items] uint8 / bool;
+// the outputs are ids / scores [n_rows, top_k], count [n_rows] and, optionally, div [n_rows]; workspace as for factor_topk
+// (include/rtrec_amd_ext.h, "FACTOR SIMILAR TOP-K").
+void factor_similar_topk(const OT &queries, const OT &p, const OT &p_norms, const at::Tensor &qt, int64_t n_items, int64_t dim,
+                         const at::Tensor &norms, const OT &item_mask, int64_t top_k, int64_t item_splits, bool write_cosine,
+                         at::Tensor ids, at::Tensor scores, at::Tensor count, const OT &div, const OT &workspace) {
+    TORCH_CHECK(dim >= 1 && dim <= 256, "factor_similar_topk: dim must lie in 1..256, got ", dim);
+    TORCH_CHECK(top_k >= 1 && top_k <= 128, "factor_similar_topk: top_k must lie in 1..128, got ", top_k);
+    TORCH_CHECK(item_splits >= 0 && item_splits <= 64, "factor_similar_topk: item_splits must lie in 0..64, got ", item_splits);
+    const int64_t rows = count.numel();
+    check_rows_items("factor_similar_topk", rows, n_items);
+    TORCH_CHECK(qt.dim() == 2 && qt.size(0) >= dim && qt.size(1) >= n_items, "factor_similar_topk: qt must be [>= dim, >= n_items]");
+    TORCH_CHECK(norms.numel() >= n_items, "factor_similar_topk: norms must hold one entry per item");
+    TORCH_CHECK(ids.numel() == rows * top_k && scores.numel() == rows * top_k,
+                "factor_similar_topk: outputs must be ids[n_rows, top_k], scores[same], count[n_rows]");
+    TORCH_CHECK(!has(div) || div->numel() == rows, "factor_similar_topk: div must hold one entry per job");
+    if (has(p)) {
+        TORCH_CHECK(p->dim() == 2 && p->size(0) == rows && p->size(1) >= dim, "factor_similar_topk: p must be [n_rows, >= dim]");
+        TORCH_CHECK(has(p_norms) && p_norms->numel() == rows, "factor_similar_topk: p comes with p_norms, one entry per job");
+        TORCH_CHECK(!has(queries) || queries->numel() == rows, "factor_similar_topk: queries must hold one entry per job");
+    } else {
+        TORCH_CHECK(has(queries) && queries->numel() == rows, "factor_similar_topk: queries must hold one entry per job");
+    }
+    TORCH_CHECK(!has(item_mask) || (item_mask->numel() >= n_items && (item_mask->scalar_type() == at::kByte || item_mask->scalar_type() == at::kBool)),
+                "factor_similar_topk: item_mask must hold one uint8 / bool entry per item");
+    one_device("factor_similar_topk", count, {&qt, &norms, &ids, &scores}, {&queries, &p, &p_norms, &item_mask, &div, &workspace});
+    const size_t ws_bytes = has(workspace) ? static_cast<size_t>(workspace->numel()) * workspace->element_size() : 0;
+    const bool brought = has(p) && rows > 0;
+    check(abi().factor_similar_topk(static_cast<int32_t>(rows), cptr<const int32_t>(queries), brought ? cptr<const float>(p) : nullptr,
+                                    brought ? p->size(1) : 0, brought ? cptr<const float>(p_norms) : nullptr, cptr<const float>(qt),
+                                    qt.size(1), static_cast<int32_t>(n_items), static_cast<int32_t>(dim), cptr<const float>(norms),
+                                    static_cast<const uint8_t *>(cptr<const void>(item_mask)), static_cast<int32_t>(top_k),
+                                    static_cast<int32_t>(item_splits), write_cosine ? 1 : 0, cptr<int32_t>(ids), cptr<float>(scores),
+                                    cptr<int32_t>(count), cptr<float>(div), cptr<void>(workspace), ws_bytes, stream_of(count)),
+          "rtrec_factor_similar_topk");
+}
+
+// a_ids / a_scores [n_rows, >= ka] / a_counts [n_rows] and the same for b; a_div [n_rows] float32 and exclude [n_rows] int32 are
+// optional; the outputs are ids / source [n_rows, keep] int32, value [n_rows, keep] FLOAT64 and count [n_rows]
+// (include/rtrec_amd_ext.h, "SIMILAR BLEND").
+void similar_blend(int64_t n_items, const at::Tensor &a_ids, const at::Tensor &a_scores, const at::Tensor &a_counts, int64_t ka,
+                   const OT &a_div, const at::Tensor &b_ids, const at::Tensor &b_scores, const at::Tensor &b_counts, int64_t kb,
+                   const OT &exclude, int64_t keep, int64_t waves_per_row, at::Tensor ids, at::Tensor value, at::Tensor source,
+                   at::Tensor count) {
+    TORCH_CHECK(ka >= 1 && ka <= 1024 && kb >= 1 && kb <= 1024, "similar_blend: ka and kb must lie in 1..1024, got ", ka, " and ", kb);
+    TORCH_CHECK(keep >= 1 && keep <= ka + kb, "similar_blend: keep must lie in 1..ka+kb, got ", keep);
+    check_waves("similar_blend", waves_per_row);
+    const int64_t rows = check_list("similar_blend", "a_", "ka", a_ids, &a_scores, nullptr, ka);
+    check_list("similar_blend", "b_", "kb", b_ids, &b_scores, nullptr, kb, rows);
+    check_rows_items("similar_blend", rows, n_items);
+    TORCH_CHECK(a_counts.numel() == rows && b_counts.numel() == rows, "similar_blend: a_counts and b_counts must hold one entry per row");
+    TORCH_CHECK((!has(a_div) || a_div->numel() == rows) && (!has(exclude) || exclude->numel() == rows),
+                "similar_blend: a_div and exclude must hold one entry per row");
+    TORCH_CHECK(ids.numel() == rows * keep && value.numel() == rows * keep && source.numel() == rows * keep && count.numel() == rows,
+                "similar_blend: outputs must be ids[n_rows, keep], value[same], source[same], count[n_rows]");
+    one_device("similar_blend", a_ids, {&a_scores, &a_counts, &b_ids, &b_scores, &b_counts, &ids, &value, &source, &count}, {&a_div, &exclude});
+    check(abi().similar_blend(static_cast<int32_t>(rows), static_cast<int32_t>(n_items), cptr<const int32_t>(a_ids), a_ids.size(1),
+                              cptr<const float>(a_scores), a_scores.size(1), cptr<const int32_t>(a_counts), static_cast<int32_t>(ka),
+                              cptr<const float>(a_div), cptr<const int32_t>(b_ids), b_ids.size(1), cptr<const float>(b_scores),
+                              b_scores.size(1), cptr<const int32_t>(b_counts), static_cast<int32_t>(kb), cptr<const int32_t>(exclude),
+                              static_cast<int32_t>(keep), static_cast<int32_t>(waves_per_row), cptr<int32_t>(ids), cptr<double>(value),
+                              cptr<int32_t>(source), cptr<int32_t>(count), stream_of(count)),
+          "rtrec_similar_blend");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -761,6 +846,9 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.blend_lists, "rtrec_slim_blend_lists");
         bind_one(h, a.factor_topk, "rtrec_factor_topk");
         bind_one(h, a.feature_repr, "rtrec_feature_repr");
+        bind_one(h, a.factor_norms, "rtrec_factor_norms");
+        bind_one(h, a.factor_similar_topk, "rtrec_factor_similar_topk");
+        bind_one(h, a.similar_blend, "rtrec_similar_blend");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -841,6 +929,13 @@ TORCH_LIBRARY(rtrec_amd, m) {
           "Tensor(c!) count, Tensor(d!)? workspace) -> ()");
     m.def("feature_repr(Tensor? job_rows, Tensor f_ptr, Tensor f_col, Tensor? f_val, Tensor e, int dim_e, Tensor? bias, int layout, "
           "int n_jobs, Tensor(a!) out, int row_stride, int comp_stride, Tensor(b!)? has) -> ()");
+    m.def("factor_norms(Tensor v, int n, int dim, int row_stride, int comp_stride, Tensor(a!) out) -> ()");
+    m.def("factor_similar_topk(Tensor? queries, Tensor? p, Tensor? p_norms, Tensor qt, int n_items, int dim, Tensor norms, "
+          "Tensor? item_mask, int top_k, int item_splits, bool write_cosine, Tensor(a!) ids, Tensor(b!) scores, Tensor(c!) count, "
+          "Tensor(d!)? div, Tensor(e!)? workspace) -> ()");
+    m.def("similar_blend(int n_items, Tensor a_ids, Tensor a_scores, Tensor a_counts, int ka, Tensor? a_div, Tensor b_ids, "
+          "Tensor b_scores, Tensor b_counts, int kb, Tensor? exclude, int keep, int waves_per_row, Tensor(a!) ids, Tensor(b!) value, "
+          "Tensor(c!) source, Tensor(d!) count) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -872,4 +967,7 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("blend_lists", &blend_lists);
     m.impl("factor_topk", &factor_topk);
     m.impl("feature_repr", &feature_repr);
+    m.impl("factor_norms", &factor_norms);
+    m.impl("factor_similar_topk", &factor_similar_topk);
+    m.impl("similar_blend", &similar_blend);
 }

@@ -1526,14 +1526,23 @@ class SlimEngine:
 
     # ------------------------------------------------------------------------------ similar
     def similar_items(self, queries: Sequence[int], top_k: int = 10) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        if not self._W:
+            raise RuntimeError("Model must be fitted before calling similar_items.")
+        q = np.asarray(queries, dtype=np.int32)
+        if len(q) == 0:
+            return self._empty_lists(top_k)
+        ids, sc, cnt = self.similar_items_device(q, top_k)
+        return ids.cpu().numpy(), sc.cpu().numpy(), cnt.cpu().numpy()
+
+    def similar_items_device(self, queries: np.ndarray, top_k: int = 10):
+        """similar_items() where it leaves its answer: device tensors (ids[n, top_k] int32, scores[n, top_k] float32,
+        count[n] int32) for the internal item ids `queries` (at least one, all inside the catalogue)."""
         be, W = self.be, self._W
         if not W:
             raise RuntimeError("Model must be fitted before calling similar_items.")
         torch = be.torch
         q = np.asarray(queries, dtype=np.int32)
         n = len(q)
-        if n == 0:
-            return self._empty_lists(top_k)
         d_q = be.to_dev(q)
         ids = be.empty((n, top_k), torch.int32)
         sc = be.empty((n, top_k), torch.float32)
@@ -1551,7 +1560,7 @@ class SlimEngine:
             pick = be.to_dev(owner.astype(np.int64) * n + np.arange(n, dtype=np.int64))
             mine = allp[pick]
             ids, sc, cnt = mine[:, :top_k], mine[:, top_k:2 * top_k].view(torch.float32), mine[:, 2 * top_k]
-        return ids.cpu().numpy(), sc.cpu().numpy(), cnt.cpu().numpy()
+        return ids, sc, cnt
 
     # ------------------------------------------------------------------------------ explanations
     EXPLAIN_MAX_LIST = 64       # list_k / top_m limits of rtrec_slim_explain_topk
@@ -1569,6 +1578,7 @@ class SlimEngine:
         # (no third entry: the ranks are counted over the score rows this W gives, in float64 for a float64 W, whatever was uploaded)
         "catalogue_ranks": ("catalogue ranks need", "rank", None),
         "blend": ("blended lists need", "blend", "SLIM's side of a blend is its float32 scores"),
+        "similar_hybrid": ("hybrid similar items need", "serve them", "SLIM's side of the blend is W's float32 values"),
     }
 
     def _whole_w(self, call: str) -> DeviceWeights:
@@ -1941,6 +1951,7 @@ class SlimEngine:
             d_mask = self._upload_item_mask(item_mask, n_items)
         self._F = {"p": self.be.to_dev(P), "qt": self.be.to_dev(np.ascontiguousarray(Q.T)), "index": d_index, "mask": d_mask,
                    "dim": dim, "n_p": int(P.shape[0]), "n_items": n_items}
+        self._take_item_norms(0)
 
     def _upload_item_mask(self, item_mask, n_items: int):
         m = np.asarray(item_mask)
@@ -2026,6 +2037,7 @@ class SlimEngine:
         rows = torch.arange(n_users, dtype=torch.int32, device=p.device)
         index = torch.where(p_has != 0, rows, torch.full_like(rows, -1))
         self._F = {"p": p, "qt": qt, "index": index, "mask": q_has, "dim": dim, "n_p": n_users, "n_items": n_items, "tables": sides}
+        self._take_item_norms(1 if bi is not None else 0)       # (the reference's target matrix: [b, e...] of [1, b, e...])
 
     def feature_vectors_device(self, features_csr, side: str = "user"):
         """(vectors[n, dim] float32, has[n] uint8) device tensors for ad-hoc feature rows -- request-time tags, cold users --
@@ -2166,6 +2178,136 @@ class SlimEngine:
         out = self.factor_topk_device(d_rows, len(rows), top_k, filter_interacted, d_mask, item_splits, vectors=vectors,
                                       vector_has=vector_has)
         return tuple(t.cpu().numpy() for t in out)
+
+    # ------------------------------------------------------------------------------ similar items from the factor vectors
+    SIMILAR_BLEND_MAX_LIST = 1024       # ka / kb limit of rtrec_similar_blend
+
+    def _take_item_norms(self, first_component: int) -> None:
+        """The norms similar items will divide by, taken when the vectors are set or rebuilt.  A backend without factor_norms (a
+        CPU stand-in that predates it) leaves them to the first call of item_norms_device."""
+        if hasattr(self.be, "factor_norms"):
+            self.item_norms_device(first_component)
+
+    def item_norms_device(self, first_component: int = 0):
+        """norms[n_items] float32 of the resident item vectors over the components first_component .. dim-1 (csrc/factor_norms.hip:
+        the fmaf chain of the squares, a correctly rounded root).  set_factors / set_feature_factors take them for the first
+        component the reference uses (0, or 1 for feature factors with biases); another first component is taken on first use.
+        They are kept beside the vectors and dropped with them (a rebuild, clear_factors)."""
+        if not self.has_factors():
+            raise RuntimeError("set_factors() must be called before the item norms are taken")
+        F, first = self._F, int(first_component)
+        if not 0 <= first < F["dim"]:
+            raise ValueError(f"first_component must lie in 0..{F['dim'] - 1}, got {first_component}")
+        cache = F.setdefault("norms", {})
+        if first not in cache:
+            out = self.be.empty((F["n_items"],), self.be.torch.float32)
+            if F["n_items"]:
+                self.be.factor_norms(F["qt"][first:], F["n_items"], F["dim"] - first, 1, int(F["qt"].shape[1]), out)
+            cache[first] = out
+        return cache[first]
+
+    def similar_factor_device(self, queries: Sequence[int], top_k: int = 10, first_component: int = 0, vectors=None,
+                              write_cosine: bool = True, want_div: bool = False, item_mask=None, item_splits: int = 0):
+        """Device tensors (ids[n, top_k] int32, scores[n, top_k] float32, count[n] int32, div[n] float32 or None): per query
+        item (internal ids; one outside the catalogue has no vector) the top_k items by the cosine of the resident item
+        vectors over the components first_component .. dim-1, the query and the items without a vector left out; the larger
+        score first, the lower id among equal ones.  The ranking score is s1 = fl(dot / norm_i); with `write_cosine` the
+        written score is fl(s1 / norm_q), otherwise s1 itself, and `want_div` returns the query norms for
+        similar_blend.  `vectors` [n, dim] (a float32 device tensor of full-width vectors, e.g. feature_vectors_device(rows,
+        "item")) makes every job bring its own query vector; its id then only names what is excluded (-1: nothing).  The
+        contract is the comment of rtrec_factor_similar_topk in include/rtrec_amd_ext.h."""
+        be, torch = self.be, self.be.torch
+        if not self.has_factors():
+            raise RuntimeError("set_factors() must be called before similar_factor")
+        F = self._F
+        top_k, first = int(top_k), int(first_component)
+        if not 1 <= top_k <= self.FACTOR_MAX_K:
+            raise ValueError(f"similar_factor: top_k must lie in 1..{self.FACTOR_MAX_K}, got {top_k}")
+        if not 0 <= int(item_splits) <= 64:
+            raise ValueError(f"similar_factor: item_splits must lie in 0..64, got {item_splits}")
+        norms = self.item_norms_device(first)
+        q = np.asarray(queries, dtype=np.int64).reshape(-1)
+        n, n_items, dim = len(q), F["n_items"], F["dim"] - first
+        q = np.where((q >= 0) & (q < n_items), q, -1).astype(np.int32)
+        mask = F["mask"]
+        if item_mask is not None:
+            if int(item_mask.numel()) != n_items:
+                raise ValueError(f"item_mask must hold one entry per item ({n_items})")
+            mask = item_mask if mask is None else (item_mask.to(torch.uint8) * mask)
+        ids = be.empty((n, top_k), torch.int32)
+        scores = be.empty((n, top_k), torch.float32)
+        count = be.zeros((n,), torch.int32)
+        div = be.zeros((n,), torch.float32) if want_div else None
+        if n == 0:
+            return ids, scores, count, div
+        p = p_norms = None
+        if vectors is not None:
+            if vectors.dim() != 2 or int(vectors.shape[0]) != n or int(vectors.shape[1]) < F["dim"] or vectors.dtype != torch.float32:
+                raise ValueError(f"vectors must be a float32 tensor [n = {n}, >= dim = {F['dim']}], got {tuple(vectors.shape)}")
+            p = vectors[:, first:F["dim"]].contiguous()
+            p_norms = be.empty((n,), torch.float32)
+            be.factor_norms(p, n, dim, dim, 1, p_norms)
+        be.factor_similar_topk(self._up(q), p, p_norms, F["qt"][first:], n_items, dim, norms, mask, top_k, bool(write_cosine),
+                               ids, scores, count, div=div, item_splits=int(item_splits))
+        return ids, scores, count, div
+
+    def similar_blend_device(self, a_ids, a_scores, a_counts, a_div, b_ids, b_scores, b_counts, exclude, keep: int,
+                             n_items: Optional[int] = None, waves_per_row: int = 0):
+        """Device tensors (ids[n, keep] int32, value[n, keep] FLOAT64, source[n, keep] int32, count[n] int32): list A (the
+        factor side: s1 scores, divided here by `a_div[r]` after the cut) and list B (SLIM's) with `exclude[r]` taken out of
+        both, each min-max normalised in float32 and summed per item id in float64, the larger value first, the earlier entry of
+        the union among equal values.  `a_div` / `exclude` may be None.  The contract is the comment of rtrec_similar_blend in
+        include/rtrec_amd_ext.h."""
+        be, torch = self.be, self.be.torch
+        if n_items is None:
+            if not self._W:
+                raise RuntimeError("Model must be fitted before calling similar_blend.")
+            n_items = int(self._W["n_items"])
+        n_rows, ka, kb, keep = int(a_ids.shape[0]), int(a_ids.shape[-1]), int(b_ids.shape[-1]), int(keep)
+        if a_ids.dim() != 2 or b_ids.dim() != 2 or not 1 <= ka <= self.SIMILAR_BLEND_MAX_LIST or not 1 <= kb <= self.SIMILAR_BLEND_MAX_LIST:
+            raise ValueError(f"similar_blend: two lists of 1..{self.SIMILAR_BLEND_MAX_LIST} items per row are supported, got {ka} and {kb}")
+        if not 1 <= keep <= ka + kb:
+            raise ValueError(f"similar_blend: keep must lie in 1..{ka + kb} (both list lengths together), got {keep}")
+        if (tuple(a_scores.shape) != (n_rows, ka) or tuple(b_ids.shape) != (n_rows, kb) or tuple(b_scores.shape) != (n_rows, kb)
+                or int(a_counts.numel()) != n_rows or int(b_counts.numel()) != n_rows):
+            raise ValueError("similar_blend: scores must have the shape of their ids, both lists one row per row, counts one entry per row")
+        ids = be.empty((n_rows, keep), torch.int32)
+        value = be.empty((n_rows, keep), torch.float64)
+        source = be.empty((n_rows, keep), torch.int32)
+        count = be.zeros((n_rows,), torch.int32)
+        if n_rows:
+            be.similar_blend(n_items, a_ids.contiguous(), a_scores.contiguous(), a_counts.contiguous(), ka, a_div, b_ids.contiguous(),
+                             b_scores.contiguous(), b_counts.contiguous(), kb, exclude, keep, ids, value, source, count,
+                             waves_per_row=waves_per_row)
+        return ids, value, source, count
+
+    def similar_hybrid_device(self, queries: Sequence[int], top_k: int = 10, pool: Optional[int] = None, first_component: int = 0,
+                              vectors=None, item_splits: int = 0):
+        """The reference's hybrid similar_items in one device pass: the factor side's top-`pool` by s1 (similar_factor_device),
+        W's column top-`pool` (similar_items_device) and the blend (similar_blend_device) hand their lists on in HBM; only
+        (ids[n, keep], value[n, keep] float64, source, count[n]) with keep = min(top_k, 2 pool) are returned, as device
+        tensors.  A query outside the catalogue has an empty SLIM side (and, without `vectors`, an empty factor side)."""
+        be, torch = self.be, self.be.torch
+        top_k = int(top_k)
+        pool = top_k if pool is None else int(pool)
+        if top_k < 1 or not 1 <= pool <= self.FACTOR_MAX_K:
+            raise ValueError(f"similar_hybrid: top_k >= 1 and 1 <= pool <= {self.FACTOR_MAX_K} are supported, got {top_k} and {pool}")
+        self._whole_w("similar_hybrid")
+        n_items = int(self._W["n_items"])
+        if self.has_factors() and self._F["n_items"] != n_items:
+            raise ValueError(f"the resident factors cover {self._F['n_items']} items, W has {n_items}: call set_factors() again")
+        q = np.asarray(queries, dtype=np.int64).reshape(-1)
+        known = (q >= 0) & (q < n_items)
+        q = np.where(known, q, -1).astype(np.int32)
+        a_ids, a_sc, a_cnt, a_div = self.similar_factor_device(q, pool, first_component, vectors=vectors, write_cosine=False,
+                                                               want_div=True, item_splits=item_splits)
+        keep = min(top_k, 2 * pool)
+        if len(q) == 0:
+            return self.similar_blend_device(a_ids, a_sc, a_cnt, a_div, a_ids, a_sc, a_cnt, None, keep, n_items=n_items)
+        b_ids, b_sc, b_cnt = self.similar_items_device(np.where(known, q, 0), pool)
+        if not known.all():                                 # (W has no column for them: an empty list)
+            b_cnt = torch.where(self._up(known.astype(np.uint8)) != 0, b_cnt, torch.zeros_like(b_cnt))
+        return self.similar_blend_device(a_ids, a_sc, a_cnt, a_div, b_ids, b_sc, b_cnt, self._up(q), keep, n_items=n_items)
 
     # ------------------------------------------------------------------------------ catalogue ranks of held-out items
     RANKS_BLOCK_BYTES = 1 << 30     # the dense score block of one pass of catalogue_ranks_rows

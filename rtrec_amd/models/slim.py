@@ -1645,6 +1645,138 @@ class SLIM(BaseModel):
                              top_k: int = 10) -> List[List[Tuple[int, float]]]:
         return self.model.similar_items_batch(query_item_ids, top_k=top_k)
 
+    # ------------------------------------------------------------ similar items from the attached vectors, alone and blended with W's
+    def _similar_query(self, what: str, query_items: Any, query_items_tags: Any, first_component: Optional[int]):
+        """What the two similar_items_* calls share: (internal ids of the queries with -1 for unknown ones, the brought query
+        vectors or None, the first component).  Syncs weights, interactions and the resident vectors."""
+        if query_items_tags is not None:
+            if not self.has_feature_factors():
+                why = ("no factor model is attached" if self._factors is None else
+                       "attach_factors() brought one finished vector per id, which a tag cannot change")
+                raise ValueError(f"{what}: query_items_tags needs the per-feature tables of attach_feature_factors(): {why}")
+            if any(isinstance(t, (str, bytes)) for t in query_items_tags):
+                raise ValueError(f"{what}: query_items_tags holds one LIST of tags per query item, got a string")
+            query_items_tags = [[] if t is None else list(t) for t in query_items_tags]
+            if len(query_items_tags) != len(query_items):
+                raise ValueError(f"{what}: query_items_tags must hold one list of tags per query item, got {len(query_items_tags)} "
+                                 f"lists for {len(query_items)} items")
+        if not self.model.is_fitted:
+            raise RuntimeError(f"Model must be fitted before calling {what}.")
+        if self._factors is None:
+            raise RuntimeError(f"attach_factors() must be called before {what}.")
+        F = self._factors
+        dim = (F["item_table"].shape[1] + (2 if F["item_bias"] is not None else 0)) if self.has_feature_factors() else F["item_vectors"].shape[1]
+        if first_component is None:                 # the reference's target matrix: [b, e...] of a stacked [1, b, e...], else all
+            first_component = 1 if self.has_feature_factors() and F["item_bias"] is not None else 0
+        first_component = int(first_component)
+        if not 0 <= first_component < dim:
+            raise ValueError(f"{what}: first_component must lie in 0..{dim - 1}, got {first_component}")
+        if len(query_items) == 0:
+            return np.zeros(0, dtype=np.int64), None, first_component
+        if self.model.engine.world_size > 1:
+            raise ValueError(f"{what} reads the whole of W and all item vectors on one rank: gather the model with "
+                             "gather_item_similarity() and serve similar items from the gathered model")
+        n_items = self.model.n_items_fitted
+        qid = self._ids_or_minus_one(query_items, self.item_ids.get_id, n_items)
+        self.model._sync_weights()
+        self._sync_interactions()
+        self._sync_factors(what)
+        vec = None
+        if query_items_tags is not None:          # (a row without an entry the table knows gives the zero vector: an empty factor side)
+            vec, _ = self.model.engine.feature_vectors_device(self._feature_rows_of("item", qid, query_items_tags), "item")
+        return qid, vec, first_component
+
+    def similar_items_factor_batch(self, query_items: List[Any], top_k: int = 10, query_items_tags: Optional[List[List[Any]]] = None,
+                                   first_component: Optional[int] = None, as_arrays: bool = False) -> Any:
+        """"More like this" from the attached vectors alone: per query item the `top_k` items by cosine similarity of the item
+        vectors -- the factor side of the reference's HybridSlimFM._similar_items: a float32 fused multiply-add chain over
+        ascending components, divided by the item's norm (the ranking score), then by the query's; the query itself and the
+        items without a vector are never listed; the larger score first, the lower internal id among equal ones.  One device
+        pass (csrc/factor_similar.hip; the contract is the comment of rtrec_factor_similar_topk in include/rtrec_amd_ext.h).
+        `first_component` selects the components first_component .. dim-1; None is the reference's choice: 1 for feature
+        factors attached with biases (the stacked [1, b, e...] becomes [b, e...]), 0 otherwise -- a caller of attach_factors()
+        with stack_bias vectors passes 1.  `query_items_tags` (attach_feature_factors() only; ValueError otherwise): one list
+        of tag strings per query that REPLACES the item's registered tags for this call; an unknown item whose tags the table
+        knows is served from its tag-only vector.  An unknown item without such tags, and an item whose vector is zero, get [].
+        Raises ValueError unless 1 <= top_k <= 128, and with more than one rank.
+
+        Returns one list of (raw item id, float) pairs per query, or with `as_arrays=True` (ids[B, top_k] int64 INTERNAL item
+        ids, scores[B, top_k] float32, counts[B]); -1 / -inf behind counts[b]."""
+        what = "similar_items_factor_batch"
+        top_k = int(top_k)
+        if not 1 <= top_k <= self.FACTOR_MAX_K:
+            raise ValueError(f"{what} needs 1 <= top_k <= {self.FACTOR_MAX_K} (what the factor kernel selects), got {top_k}")
+        query_items = list(query_items)
+        qid, vec, first = self._similar_query(what, query_items, query_items_tags, first_component)
+        B = len(query_items)
+        out_ids = np.full((B, top_k), -1, dtype=np.int64)
+        out_sc = np.full((B, top_k), -np.inf, dtype=np.float32)
+        out_cnt = np.zeros(B, dtype=np.int32)
+        if B:
+            ids, sc, cnt, _ = self.model.engine.similar_factor_device(qid, top_k, first, vectors=vec, write_cosine=True)
+            out_ids[:], out_sc[:], out_cnt[:] = ids.cpu().numpy(), sc.cpu().numpy(), cnt.cpu().numpy()
+        if as_arrays:
+            return out_ids, out_sc, out_cnt
+        raw_of = self._raw_of(self.item_ids)
+        id_rows, sc_rows, cnts = out_ids.tolist(), out_sc.tolist(), out_cnt.tolist()
+        return [[(raw_of(i), s) for i, s in zip(id_rows[b][:cnts[b]], sc_rows[b][:cnts[b]])] for b in range(B)]
+
+    def similar_items_factor(self, query_item: Any, top_k: int = 10, query_item_tags: Optional[List[Any]] = None,
+                             first_component: Optional[int] = None) -> List[Tuple[Any, float]]:
+        """similar_items_factor_batch for one item (`query_item_tags`: this item's list of `query_items_tags`)."""
+        return self.similar_items_factor_batch([query_item], top_k=top_k, first_component=first_component,
+                                               query_items_tags=None if query_item_tags is None else [query_item_tags])[0]
+
+    def similar_items_hybrid_batch(self, query_items: List[Any], top_k: int = 10, pool: Optional[int] = None,
+                                   query_items_tags: Optional[List[List[Any]]] = None, first_component: Optional[int] = None,
+                                   as_arrays: bool = False) -> Any:
+        """The reference's hybrid similar_items (HybridSlimFM._similar_items) in one device pass: the factor side's top-`pool`
+        by cosine (similar_items_factor_batch's list) and the top-`pool` of W's column (similar_items) are each min-max
+        normalised in float32 and added per item in FLOAT64, as the reference's comb_sum does; the larger sum first, among equal
+        sums the factor side's items in their order, then SLIM's; cut to `top_k`.  The three kernels hand their lists on in HBM
+        (csrc/factor_similar.hip, similar_topk, csrc/similar_blend.hip); only `top_k` entries per query are downloaded.  `pool`
+        defaults to `top_k`, which is the reference.  `first_component` and `query_items_tags` as in
+        similar_items_factor_batch.  Where the reference raises ValueError (min of an empty list) an empty side contributes
+        nothing: an item whose column of W is empty gets the factor list alone, an item without a vector SLIM's list alone
+        (each normalised), an unknown item with tags the table knows its tag-only factor list, an unknown item without [].
+        SLIM.similar_items / similar_items_batch are unchanged: they still return W's column.
+        Raises ValueError unless top_k >= 1 and 1 <= pool <= 128; for a column-sharded W or more than one rank (gather the
+        model with gather_item_similarity()); and for a W uploaded from float64 values that are not float32 numbers.
+
+        Returns one list of (raw item id, float) pairs per query, or with `as_arrays=True` (ids[B, top_k] int64 INTERNAL item
+        ids, value[B, top_k] float64, source[B, top_k] int32 -- 1: only the factor side holds the item, 2: only SLIM, 3: both
+        -- counts[B]); -1 / -inf / 0 behind counts[b]."""
+        what = "similar_items_hybrid_batch"
+        top_k = int(top_k)
+        pool = top_k if pool is None else int(pool)
+        if top_k < 1 or not 1 <= pool <= self.FACTOR_MAX_K:
+            raise ValueError(f"{what} needs top_k >= 1 and 1 <= pool <= {self.FACTOR_MAX_K}, got top_k={top_k} and pool={pool}: the "
+                             f"factor kernel keeps each query's candidates in LDS and selects at most {self.FACTOR_MAX_K}")
+        query_items = list(query_items)
+        qid, vec, first = self._similar_query(what, query_items, query_items_tags, first_component)
+        B = len(query_items)
+        out_ids = np.full((B, top_k), -1, dtype=np.int64)
+        out_val = np.full((B, top_k), -np.inf, dtype=np.float64)
+        out_src = np.zeros((B, top_k), dtype=np.int32)
+        out_cnt = np.zeros(B, dtype=np.int32)
+        if B:
+            keep = min(top_k, 2 * pool)
+            ids, value, source, count = self.model.engine.similar_hybrid_device(qid, top_k, pool, first, vectors=vec)
+            out_ids[:, :keep], out_val[:, :keep] = ids.cpu().numpy(), value.cpu().numpy()
+            out_src[:, :keep], out_cnt[:] = source.cpu().numpy(), count.cpu().numpy()
+        if as_arrays:
+            return out_ids, out_val, out_src, out_cnt
+        raw_of = self._raw_of(self.item_ids)
+        id_rows, val_rows, cnts = out_ids.tolist(), out_val.tolist(), out_cnt.tolist()
+        return [[(raw_of(i), v) for i, v in zip(id_rows[b][:cnts[b]], val_rows[b][:cnts[b]])] for b in range(B)]
+
+    def similar_items_hybrid(self, query_item: Any, top_k: int = 10, pool: Optional[int] = None,
+                             query_item_tags: Optional[List[Any]] = None, first_component: Optional[int] = None
+                             ) -> List[Tuple[Any, float]]:
+        """similar_items_hybrid_batch for one item (`query_item_tags`: this item's list of `query_items_tags`)."""
+        return self.similar_items_hybrid_batch([query_item], top_k=top_k, pool=pool, first_component=first_component,
+                                               query_items_tags=None if query_item_tags is None else [query_item_tags])[0]
+
     # ------------------------------------------------------------ persistence (slim.py:117-149)
     def _serialize(self) -> dict:
         data = {"model": self.model, "interactions": self.interactions, "user_ids": self.user_ids,

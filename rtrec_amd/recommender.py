@@ -225,6 +225,32 @@ class Recommender:
                                                  similarity_weight_factor=similarity_weight_factor, mnz=mnz,
                                                  filter_interacted=filter_interacted, as_arrays=as_arrays, **kw)
 
+    def similar_items_factor(self, query_item: Any, top_k: int = 10, query_item_tags: Optional[List[Any]] = None,
+                             first_component: Optional[int] = None) -> List[Any]:
+        """The attached item vectors' own "more like this": (item, cosine) pairs -- SLIM.similar_items_factor."""
+        kw = {} if query_item_tags is None else {"query_item_tags": query_item_tags}
+        return self.model.similar_items_factor(query_item, top_k=top_k, first_component=first_component, **kw)
+
+    def similar_items_factor_batch(self, query_items: List[Any], top_k: int = 10, query_items_tags: Optional[List[List[Any]]] = None,
+                                   first_component: Optional[int] = None, as_arrays: bool = False) -> Any:
+        """SLIM.similar_items_factor_batch: cosine top-k of item vectors against the catalogue, one device pass."""
+        kw = {} if query_items_tags is None else {"query_items_tags": query_items_tags}
+        return self.model.similar_items_factor_batch(query_items, top_k=top_k, first_component=first_component, as_arrays=as_arrays, **kw)
+
+    def similar_items_hybrid(self, query_item: Any, top_k: int = 10, pool: Optional[int] = None,
+                             query_item_tags: Optional[List[Any]] = None, first_component: Optional[int] = None) -> List[Any]:
+        """The reference hybrid's similar_items for one item: (item, float) pairs -- SLIM.similar_items_hybrid."""
+        kw = {} if query_item_tags is None else {"query_item_tags": query_item_tags}
+        return self.model.similar_items_hybrid(query_item, top_k=top_k, pool=pool, first_component=first_component, **kw)
+
+    def similar_items_hybrid_batch(self, query_items: List[Any], top_k: int = 10, pool: Optional[int] = None,
+                                   query_items_tags: Optional[List[List[Any]]] = None, first_component: Optional[int] = None,
+                                   as_arrays: bool = False) -> Any:
+        """SLIM.similar_items_hybrid_batch: factor cosine top-k, W's column top-k and the float64 blend in one device pass."""
+        kw = {} if query_items_tags is None else {"query_items_tags": query_items_tags}
+        return self.model.similar_items_hybrid_batch(query_items, top_k=top_k, pool=pool, first_component=first_component,
+                                                     as_arrays=as_arrays, **kw)
+
     def blend_batch(self, items_a: List[List[Any]], scores_a: List[List[float]], items_b: List[List[Any]], scores_b: List[List[float]],
                     top_k: int = 10, weight: float = 1.0, mnz: bool = False) -> Any:
         """SLIM.blend_batch: the same blend for two lists per row the caller brings, with a constant weight."""

@@ -34,6 +34,12 @@ the GPU), POST /recommend (one user's top-k).  Differences, all forced by the de
     "similarity_weight_factor", "mnz", "filter_interacted", "user_tags": [...] or absent} -> {"user": ..., "items": [...]}
     (SLIM.recommend_hybrid; a model without attached vectors is the shell's 500, and so is "user_tags" on a model without the
     tables of attach_feature_factors); same token check as /rerank, answered under the model lock, not coalesced;
+  * POST /similar_items_hybrid is an addition (the reference hybrid's similar_items: the cosine list of the attached item
+    vectors and the list of W's column, each min-max normalised, added per item in float64): {"item": ..., "top_k", "pool" or
+    absent = top_k, "item_tags": [...] or absent, "first_component" or absent} -> {"item": ..., "items": [{"item": ...,
+    "score": ...}, ...]} (SLIM.similar_items_hybrid; a model without attached vectors is the shell's 500, and so is "item_tags"
+    on a model without the tables of attach_feature_factors); same token check as /rerank, answered under the model lock, not
+    coalesced;
   * concurrent POST /recommend calls are coalesced (`RecommendCoalescer`): requests that arrive within a bounded
     wait (RTREC_AMD_COALESCE_MS, default 1 ms; 0 = only what queued up behind the model lock) share ONE
     recommend_batch launch per (top_k, filter_interacted) group; each caller gets exactly what its own
@@ -133,6 +139,24 @@ class HybridRequest(BaseModel):
     mnz: bool = False
     filter_interacted: bool = True
     user_tags: Optional[List[str]] = None
+
+
+class SimilarHybridRequest(BaseModel):
+    item: Any
+    top_k: int = 10
+    pool: Optional[int] = None
+    item_tags: Optional[List[str]] = None
+    first_component: Optional[int] = None
+
+
+class ScoredItem(BaseModel):
+    item: Any
+    score: float
+
+
+class SimilarHybridResponse(BaseModel):
+    item: Any
+    items: List[ScoredItem]
 
 
 class RecommendationResponse(BaseModel):
@@ -383,6 +407,14 @@ def build_router(gate: ModelGate) -> APIRouter:
             similarity_weight_factor=request.similarity_weight_factor, mnz=request.mnz, filter_interacted=request.filter_interacted,
             **tags))
         return {"user": request.user, "items": items}
+
+    @api.post("/similar_items_hybrid", response_model=SimilarHybridResponse)
+    def similar_items_hybrid(request: SimilarHybridRequest, x_token: str = Header()):
+        _authorise(x_token)
+        tags = {} if request.item_tags is None else {"query_item_tags": request.item_tags}
+        pairs = gate.call("Similar items hybrid", lambda m: m.similar_items_hybrid(
+            request.item, top_k=request.top_k, pool=request.pool, first_component=request.first_component, **tags))
+        return {"item": request.item, "items": [{"item": i, "score": v} for i, v in pairs]}
 
     return api
 

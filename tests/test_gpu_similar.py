@@ -1,0 +1,328 @@
+"""The hybrid's similar_items on the GPU (csrc/factor_norms.hip, factor_similar.hip, similar_blend.hip; torch.ops.rtrec_amd.
+factor_norms / factor_similar_topk / similar_blend; SLIM.similar_items_factor_batch / similar_items_hybrid_batch) against the host
+models of tests/test_similar_host.py: ids, sources and counts with ==, float32 scores and float64 values by their bits after
+adding +0.0 (the sign of a zero is not part of the contract).  The output buffers are poisoned before every call (every slot
+must be written)."""
+import numpy as np
+import pytest
+
+from tests.test_factor_host import F32, rounding_vectors
+from tests.test_similar_host import (FLT_MAX, assert_same_blend, assert_same_lists, check_serving_and_facade, check_similar_api, golden_answer,
+                                     golden_cases, golden_inputs, host_blend, host_norms_fast, host_norms_plain, host_similar_fast,
+                                     lists_of, special_vectors, dbits)
+
+pytestmark = pytest.mark.gpu
+
+
+def _up(a, dt):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to("cuda:0")
+
+
+# ---------------------------------------------------------------------------------------------- 1. norms
+def run_norms(V, component_major, pad, seed=0):
+    import torch
+    from rtrec_amd import ops  # noqa: F401  (registers torch.ops.rtrec_amd.*)
+    V = np.asarray(V, F32)
+    n, dim = V.shape
+    rng = np.random.default_rng(seed)
+    if component_major:
+        M = (rng.standard_normal((dim, n + pad)) * 100).astype(F32)
+        M[:, :n] = V.T
+        rs, cs = 1, n + pad
+    else:
+        M = (rng.standard_normal((n, dim + pad)) * 100).astype(F32)
+        M[:, :dim] = V
+        rs, cs = dim + pad, 1
+    out = torch.full((n,), 7.0, dtype=torch.float32, device="cuda:0")
+    torch.ops.rtrec_amd.factor_norms(_up(M, np.float32), n, dim, rs, cs, out)
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+@pytest.mark.parametrize("dim", [1, 2, 3, 13, 64, 256])
+def test_norms_are_the_chain_and_a_correctly_rounded_root_bit_for_bit(dim):
+    V = special_vectors(97, dim, seed=dim)
+    want = host_norms_fast(V)
+    assert np.array_equal(want[:12].view(np.int32), host_norms_plain(V[:12]).view(np.int32))
+    assert want[1] == 0 and 0 < want[3] and np.isinf(want[5])
+    with np.errstate(all="ignore"):
+        n2 = (V[3].astype(np.float64) ** 2).sum()
+    assert 0 < n2 < 2.0 ** -126, "vector 3 must have a denormal sum of squares"
+    for component_major in (False, True):
+        for pad in (0, 5):
+            got = run_norms(V, component_major, pad)
+            assert np.array_equal(got.view(np.int32), want.view(np.int32)), (dim, component_major, pad, np.flatnonzero(got != want)[:5])
+
+
+# ---------------------------------------------------------------------------------------------- 2. the cosine top-k
+def run_similar(Q, norms, queries, top_k, P=None, p_norms=None, mask=None, write_cosine=False, splits=0, pad=0, want_div=True, seed=0):
+    """torch.ops.rtrec_amd.factor_similar_topk on host arrays, as the host models take them.  `pad` > 0: the strides are wider
+    than the widths (and qt has rows beyond dim), with seeded values behind them."""
+    import torch
+    from rtrec_amd import ops  # noqa: F401
+    Q = np.asarray(Q, F32)
+    n_items, dim = Q.shape
+    rng = np.random.default_rng(seed)
+    Qt = np.ascontiguousarray(Q.T)
+    if pad:
+        Qt = np.concatenate([Qt, rng.standard_normal((dim, pad)).astype(F32) * 100], axis=1)
+        Qt = np.concatenate([Qt, rng.standard_normal((pad, n_items + pad)).astype(F32) * 100], axis=0)
+    n = len(P) if P is not None else len(queries)
+    ids = torch.full((n, top_k), 12345, dtype=torch.int32, device="cuda:0")               # poisoned: every slot must be written
+    scores = torch.full((n, top_k), 7.0, dtype=torch.float32, device="cuda:0")
+    count = torch.full((n,), -7, dtype=torch.int32, device="cuda:0")
+    div = torch.full((n,), -7.0, dtype=torch.float32, device="cuda:0") if want_div else None
+    s_eff = splits if splits else 64
+    ws = torch.empty((n * s_eff * (top_k * 8 + 4),), dtype=torch.uint8, device="cuda:0") if s_eff > 1 else None
+    d_p = d_pn = None
+    if P is not None:
+        Pd = np.asarray(P, F32)
+        if pad:
+            Pd = np.concatenate([Pd, rng.standard_normal((n, pad)).astype(F32) * 100], axis=1)
+        d_p, d_pn = _up(Pd, np.float32), _up(p_norms, np.float32)
+    torch.ops.rtrec_amd.factor_similar_topk(None if queries is None else _up(queries, np.int32), d_p, d_pn, _up(Qt, np.float32), n_items, dim,
+                                            _up(norms, np.float32), None if mask is None else _up(np.asarray(mask) != 0, np.uint8), top_k,
+                                            splits, bool(write_cosine), ids, scores, count, div, ws)
+    torch.cuda.synchronize()
+    return ids.cpu().numpy(), scores.cpu().numpy(), count.cpu().numpy(), None if div is None else div.cpu().numpy()
+
+
+def same(got, want, what):
+    assert_same_lists(got, want, what)
+    if got[3] is not None:
+        assert np.array_equal(got[3].view(np.int32), np.asarray(want[3], F32).view(np.int32)), (what, "div")
+
+
+def test_operand_map_on_an_asymmetric_integer_matrix():
+    """A swapped row / column of the tile, a permuted k or a norm taken from the wrong item would show: the integer matrix is not
+    symmetric in any pair of its indices; the queries read from qt's columns and the same vectors brought as p give the same bits."""
+    dim, n_items = 32, 40
+    i, c = np.meshgrid(np.arange(n_items), np.arange(dim), indexing="ij")
+    Q = (i * 37 + c * 3 + (i * c) % 5 - 400).astype(F32)
+    norms = host_norms_fast(Q)
+    queries = np.r_[np.arange(n_items), [3]].astype(np.int32)                 # 41 jobs: two workgroups
+    want = host_similar_fast(Q, norms, queries, n_items)
+    assert (want[2] == n_items - 1).all()
+    for splits in (1, 2):
+        got = run_similar(Q, norms, queries, n_items, splits=splits)
+        same(got, want, f"columns, {splits} chunk(s)")
+        brought = run_similar(Q, norms, queries, n_items, P=Q[queries], p_norms=norms[queries], splits=splits, pad=3)
+        same(brought, want, f"brought, {splits} chunk(s)")
+    for r, q in enumerate(queries):
+        assert q not in got[0][r].tolist() and got[0][r, -1] == -1 and np.isneginf(got[1][r, -1])
+
+
+@pytest.mark.parametrize("dim", [1, 2, 3, 12, 13, 64, 255, 256])
+def test_every_s1_is_the_chain_and_one_division_bit_for_bit(dim):
+    """Every s1 of 96 x 95 pairs must carry the bits of fl(chain / norm) on vectors where another order, an unfused multiply, a
+    reciprocal or a wider accumulator changes them (tests/test_similar_host.py counts how often they do)."""
+    _, Q = rounding_vectors(1, 96, dim, seed=dim)
+    Q[5] = 0.0                                                                # a zero vector: never listed, and as a query empty with write_cosine
+    norms = host_norms_fast(Q)
+    queries = np.arange(96, dtype=np.int32)
+    want = host_similar_fast(Q, norms, queries, 95)
+    got = run_similar(Q, norms, queries, 95, splits=1)
+    same(got, want, f"dim {dim}")
+    assert not (got[0] == 5).any()
+    cos = run_similar(Q, norms, queries, 95, splits=1, write_cosine=True)
+    same(cos, host_similar_fast(Q, norms, queries, 95, write_cosine=True), f"dim {dim} cosine")
+    assert cos[2][5] == 0 and (cos[0][5] == -1).all()
+
+
+def test_s1_bits_beyond_one_compaction():
+    """130 items: at top_k 64 the 128-entry buffer is compacted before the last tile."""
+    _, Q = rounding_vectors(1, 130, 12, seed=77)
+    norms = host_norms_fast(Q)
+    queries = np.arange(130, dtype=np.int32)
+    for top_k in (64, 128):
+        want = host_similar_fast(Q, norms, queries, top_k)
+        for splits in (1, 3):
+            same(run_similar(Q, norms, queries, top_k, splits=splits), want, (top_k, splits))
+
+
+@pytest.fixture(scope="module")
+def selection_case():
+    rng = np.random.default_rng(55)
+    Q = rng.standard_normal((2100, 9)).astype(F32)
+    Q[[4, 700, 2099]] = 0.0                                                   # zero-norm items
+    norms = host_norms_fast(Q)
+    mask = (rng.random(2100) < 0.8).astype(np.uint8)
+    return Q, norms, mask
+
+
+@pytest.mark.parametrize("n_items", [70, 2100])
+def test_selection_chunks_mask_query_and_every_top_k(selection_case, n_items):
+    """33 queries (two workgroups) over 70 and 2,100 items -- more than 64 tiles, so item_splits = 0 really chunks; item_splits
+    1, 2 and 0 give identical outputs; the query is never listed; a mask; zero-norm items; top_k beyond n_items - 1."""
+    Q, norms, mask = selection_case[0][:n_items], selection_case[1][:n_items], selection_case[2][:n_items]
+    queries = np.r_[np.arange(0, n_items, max(1, n_items // 31))[:31], [4, n_items - 1]].astype(np.int32)
+    assert len(queries) == 33
+    for kw in (dict(), dict(mask=mask), dict(write_cosine=True)):
+        want = host_similar_fast(Q, norms, queries, 128, **kw)
+        for top_k in ((1, 10, 16, 17, 64, 65, 128) if not kw else (10, 128)):
+            w = (want[0][:, :top_k], want[1][:, :top_k], np.minimum(want[2], top_k), want[3])
+            base = None
+            for splits in (1, 2, 0):
+                got = run_similar(Q, norms, queries, top_k, splits=splits, pad=2 if splits == 2 else 0, **kw)
+                same(got, w, (n_items, top_k, splits, sorted(kw)))
+                base = got if base is None else base
+                assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(got[:3], base[:3]))
+            for r, q in enumerate(queries):
+                assert q not in got[0][r].tolist()
+            assert not np.isin(got[0], [4, 700, 2099]).any()
+    if n_items == 70:
+        assert (want[2][np.flatnonzero(queries != 4)] <= 69).all() and want[2].max() < 128      # top_k beyond n_items - 1
+
+
+def test_ties_unknown_queries_and_the_two_ways_to_divide():
+    Q = np.tile(np.array([[1.0, 2.0, 2.0]], F32), (3000, 1))                  # every s1 is equal: ids 0 .. top_k-1 without the query
+    norms = host_norms_fast(Q)
+    queries = np.array([0, 5, 2999, -1, 3000, 17], np.int32)
+    for top_k, splits in ((128, 0), (128, 1), (10, 3)):
+        want = host_similar_fast(Q, norms, queries, top_k, write_cosine=True)
+        got = run_similar(Q, norms, queries, top_k, write_cosine=True, splits=splits)
+        same(got, want, (top_k, splits))
+        assert got[0][1, :6].tolist() == [0, 1, 2, 3, 4, 6] and got[2].tolist() == [top_k, top_k, top_k, 0, 0, top_k] and (got[1][0] == 1.0).all()
+    # q = -1 with brought vectors excludes nothing; no queries at all with brought vectors
+    rng = np.random.default_rng(8)
+    Q = rng.standard_normal((200, 6)).astype(F32)
+    norms = host_norms_fast(Q)
+    P = rng.standard_normal((5, 6)).astype(F32)
+    P[3] = 0.0
+    pn = host_norms_fast(P)
+    for queries in (np.array([-1, 7, -1, 9, 200], np.int32), None):
+        for cosine in (False, True):
+            want = host_similar_fast(Q, norms, queries, 12, P=P, p_norms=pn, write_cosine=cosine)
+            same(run_similar(Q, norms, queries, 12, P=P, p_norms=pn, write_cosine=cosine, splits=2), want, (queries is None, cosine))
+            assert want[2][0] == 12 and (want[2][3] == (0 if cosine else 12))
+    # write_cosine against d_out_div: the same lists, the written score divided by what out_div reports
+    queries = np.arange(40, dtype=np.int32)
+    s1 = run_similar(Q, norms, queries, 10, splits=1)
+    cos = run_similar(Q, norms, queries, 10, write_cosine=True, splits=4)
+    assert np.array_equal(s1[0], cos[0]) and np.array_equal(s1[3], norms[:40]) and np.array_equal(cos[3], norms[:40])
+    assert np.array_equal((s1[1] / s1[3][:, None]).view(np.int32), cos[1].view(np.int32))
+
+
+# ---------------------------------------------------------------------------------------------- 3. the blend
+def run_blend(n_items, A, B, keep, a_div=None, exclude=None, waves=0, pad=0):
+    import torch
+    from rtrec_amd import ops  # noqa: F401
+    R, ka, kb = len(A[0]), A[0].shape[1], B[0].shape[1]
+
+    def wide(a, fill):
+        return np.concatenate([a, np.full((R, pad), fill, a.dtype)], axis=1) if pad else a
+
+    ids = torch.full((R, keep), 12345, dtype=torch.int32, device="cuda:0")               # poisoned: every slot must be written
+    value = torch.full((R, keep), 7.0, dtype=torch.float64, device="cuda:0")
+    source = torch.full((R, keep), 9, dtype=torch.int32, device="cuda:0")
+    count = torch.full((R,), -7, dtype=torch.int32, device="cuda:0")
+    torch.ops.rtrec_amd.similar_blend(n_items, _up(wide(A[0], 3), np.int32), _up(wide(A[1], F32(9.0)), np.float32), _up(A[2], np.int32), ka,
+                                      None if a_div is None else _up(a_div, np.float32), _up(wide(B[0], 3), np.int32),
+                                      _up(wide(B[1], F32(9.0)), np.float32), _up(B[2], np.int32), kb,
+                                      None if exclude is None else _up(exclude, np.int32), keep, waves, ids, value, source, count)
+    torch.cuda.synchronize()
+    return ids.cpu().numpy(), value.cpu().numpy(), source.cpu().numpy(), count.cpu().numpy()
+
+
+def test_the_whole_golden_file_equals_the_reference():
+    """One launch per (ka, kb) class: the 400 fixture queries (10 x 10) and the 60 small cases (up to 15 x 12), both wave counts."""
+    g, cases = golden_cases()
+    for lo, hi in ((0, g["n_fixture"]), (g["n_fixture"], len(cases))):
+        part = cases[lo:hi]
+        A, B, div, ex = golden_inputs(part)
+        keep = max(c["top_k"] for c in part)
+        n_items = part[0]["n_items"]
+        want = host_blend(n_items, A, B, keep, a_div=div, exclude=ex)
+        got = {w: run_blend(n_items, A, B, keep, a_div=div, exclude=ex, waves=w, pad=w) for w in (1, 4)}
+        assert_same_blend(got[1], want, "golden, one wave")
+        assert_same_blend(got[4], got[1], "golden, four waves")
+        for r, c in enumerate(part):                       # ... and what the reference itself returned
+            w_ids, w_val = golden_answer(c)
+            n = len(w_ids)
+            assert n == min(c["top_k"], got[1][3][r]) and got[1][0][r, :n].tolist() == w_ids, (lo + r)
+            assert np.array_equal(dbits(got[1][1][r, :n]), dbits(w_val)), (lo + r)
+
+
+@pytest.mark.parametrize("width", [1, 64, 65, 256, 257, 1024])
+def test_blend_of_every_list_class_with_seeded_repeats(width):
+    rng = np.random.default_rng(width)
+    R, n_items = 6, max(8, width // 2)                      # ids drawn from half the width: every list repeats ids
+    rows_a = [rng.integers(0, n_items, width).tolist() for _ in range(R)]
+    rows_b = [rng.integers(0, n_items, max(1, width - r)).tolist() for r in range(R)]
+    sc = lambda n: (-np.sort(-rng.standard_normal(n))).astype(F32).tolist()
+    A = lists_of(rows_a, [sc(len(r)) for r in rows_a], width)
+    B = lists_of(rows_b, [sc(len(r)) for r in rows_b], width)
+    div = (np.abs(rng.standard_normal(R)) + 0.5).astype(F32)
+    ex = rng.integers(-1, n_items, R).astype(np.int32)
+    keep = min(2 * width, n_items + 3)
+    want = host_blend(n_items, A, B, keep, a_div=div, exclude=ex)
+    one = run_blend(n_items, A, B, keep, a_div=div, exclude=ex, waves=1)
+    assert_same_blend(one, want, f"width {width}")
+    assert_same_blend(run_blend(n_items, A, B, keep, a_div=div, exclude=ex, waves=4, pad=2), one, f"width {width}, four waves")
+    assert_same_blend(run_blend(n_items, A, B, keep, a_div=div, exclude=ex, waves=0), one, f"width {width}, the library's choice")
+
+
+def test_blend_contract_edges_on_the_device():
+    none = lists_of([[]], [[]])
+    one = lists_of([[4, 6, 2]], [[3.0, 2.0, 1.0]])
+    flat = lists_of([[8, 1, 5]], [[0.7, 0.7, 0.7]])
+    rep_a, rep_b = lists_of([[3, 3, 9]], [[4.0, 2.0, 0.0]]), lists_of([[9, 9, 3]], [[1.0, 0.5, 0.0]])
+    A, B = lists_of([[5, 2, 7]], [[9.0, 2.0, 1.0]]), lists_of([[7, 5, 1]], [[3.0, 2.0, 1.0]])
+    cut_a, cut_b = lists_of([[5, 2, 7, 8]], [[9.0, 2.0, -FLT_MAX, 1.0]]), lists_of([[7, 24, 1]], [[3.0, 2.0, 1.0]])
+    big = lists_of([[5, 2]], [[3.0e38, -3.0e38]])
+    for waves in (1, 4):
+        for a, b, keep, kw in ((none, none, 2, {}), (one, none, 4, {}), (none, one, 3, {}), (flat, flat, 6, {}), (rep_a, rep_b, 6, {}),
+                               (A, B, 6, dict(exclude=np.array([5], np.int32))), (A, B, 6, dict(exclude=np.array([-1], np.int32))),
+                               (A, B, 6, dict(a_div=np.array([0.0], F32))), (A, B, 6, dict(a_div=np.array([-2.0], F32))),
+                               (A, B, 6, dict(a_div=np.array([np.nan], F32))), (A, B, 6, dict(a_div=np.array([4.0], F32))),
+                               (cut_a, cut_b, 6, dict(a_div=np.array([1e-30], F32))), ((cut_a[0], cut_a[1], np.array([1], np.int32)), cut_b, 6, {}),
+                               ((cut_a[0], cut_a[1], np.array([-3], np.int32)), (cut_b[0], cut_b[1], np.array([99], np.int32)), 6, {}),
+                               (big, none, 3, {}), (one, one, 6, {})):
+            want = host_blend(24, a, b, keep, **kw)
+            got = run_blend(24, a, b, keep, waves=waves, **kw)
+            assert_same_blend(got, want, (waves, keep, sorted(kw)))
+            assert not np.isnan(got[1]).any()
+
+
+# ---------------------------------------------------------------------------------------------- 4. the API on the device
+def gpu_model(strings=False):
+    from tests.test_factor_host import fitted_model
+    return fitted_model(strings, cpu=False)
+
+
+@pytest.mark.parametrize("strings", [False, True])
+def test_similar_items_factor_and_hybrid_batch_equal_the_host_path(strings):
+    """Every item of the golden fixture model as a query: host top-k -> host SLIM similar -> host blend, with finished vectors and
+    with feature tables, with and without biases; query_items_tags, an unknown item, an item without a vector, pool > top_k."""
+    m, batch = gpu_model(strings)
+    queries = check_similar_api(m, batch, strings)
+    eng = m.model.engine
+    known = [q for q in queries if m.item_ids.get_id(q) is not None]
+    qid = np.array([m.item_ids.get_id(q) for q in known])
+    base = [t.cpu().numpy() for t in eng.similar_factor_device(qid, 20, 0)[:3]]
+    for splits in (1, 2, 9):
+        got = [t.cpu().numpy() for t in eng.similar_factor_device(qid, 20, 0, item_splits=splits)[:3]]
+        assert all(np.array_equal(a, b) for a, b in zip(got, base)), splits
+    # the norms are taken with the vectors, stand beside them, and a rebuild or clear_factors drops them
+    rng = np.random.default_rng(3)
+    P, Q = rng.standard_normal((eng.n_users, 6)).astype(F32), rng.standard_normal((m.model.n_items_fitted, 6)).astype(F32)
+    eng.set_factors(P, Q)
+    assert set(eng._F["norms"]) == {0}
+    n0 = eng.item_norms_device(0)
+    assert eng.item_norms_device(0) is n0 and np.array_equal(n0.cpu().numpy().view(np.int32), host_norms_fast(Q).view(np.int32))
+    assert np.array_equal(eng.item_norms_device(2).cpu().numpy().view(np.int32), host_norms_fast(Q[:, 2:]).view(np.int32))
+    eng.set_factors(P, Q * F32(3.0))
+    assert set(eng._F["norms"]) == {0} and eng.item_norms_device(0) is not n0
+    assert np.array_equal(eng.item_norms_device(0).cpu().numpy().view(np.int32), host_norms_fast(Q * F32(3.0)).view(np.int32))
+    m.detach_factors()
+    assert not eng.has_factors() and "norms" not in eng._F
+
+
+def test_the_serving_route_and_the_recommender_on_the_device():
+    from tests.test_feature_repr_host import attach_tables, seeded_tables
+    m, batch = gpu_model()
+    t = seeded_tables(batch)
+    attach_tables(m, t)
+    assert set(m.similar_items_hybrid(t["all_items"][4])) and set(m.model.engine._F["norms"]) == {1}      # biased tables: [b, e...]
+    check_serving_and_facade(m, t["all_items"][4], t["all_items"][:9])
