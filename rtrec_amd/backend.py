@@ -323,15 +323,19 @@ class HipBackend:
         s = int(item_splits) if item_splits else min(64, (self.FACTOR_AUTO_BLOCKS + blocks - 1) // blocks)
         return max(1, min(s, (int(n_items) + 31) // 32))
 
+    def factor_workspace(self, n_rows, n_items, top_k, item_splits=0):
+        """(splits, workspace) of a factor scan call: factor_splits' chunks and, for more than one, the uint8 tensor their partial
+        lists live in (RTREC_FACTOR_TOPK_WORKSPACE_BYTES of include/rtrec_amd_ext.h), else None."""
+        splits = self.factor_splits(n_rows, n_items, item_splits)
+        return splits, (self.empty((int(n_rows) * splits * (int(top_k) * 8 + 4),), self.torch.uint8) if splits > 1 else None)
+
     def factor_topk(self, row_ids, p_index, n_x_rows, p, qt, n_items, dim, item_mask, xb, filter_interacted, top_k, ids, scores,
                     count, item_splits=0):
         """Per job: the top_k items by the fmaf chain of its vector (row p_index[x] of `p`, x = row_ids[r]) against the
         component-major item vectors `qt`, the mask and -- with `filter_interacted` -- the row of X = `xb` (ptr, col, val; val
-        is not read) applied (csrc/factor_topk.hip; include/rtrec_amd_ext.h).  The partial lists of a chunked call live in a
-        workspace allocated here: RTREC_FACTOR_TOPK_WORKSPACE_BYTES of the header."""
-        n_rows = int(count.numel())
-        splits = self.factor_splits(n_rows, n_items, item_splits)
-        ws = self.empty((n_rows * splits * (int(top_k) * 8 + 4),), self.torch.uint8) if splits > 1 else None
+        is not read) applied (csrc/factor_topk.hip; include/rtrec_amd_ext.h).  The partial lists of a chunked call live in
+        factor_workspace's tensor."""
+        splits, ws = self.factor_workspace(int(count.numel()), n_items, top_k, item_splits)
         xb = (None, None) if xb is None else xb
         self.ops.factor_topk(row_ids, p_index, int(n_x_rows), p, qt, int(n_items), int(dim), item_mask, xb[0], xb[1],
                              bool(filter_interacted), int(top_k), splits, ids, scores, count, ws)
@@ -356,9 +360,7 @@ class HipBackend:
         masked items left out; the query's vector is column queries[r] of `qt`, or row r of `p` (with `p_norms`); `div` [n_rows]
         receives the query norms, `write_cosine` divides the written scores by them (csrc/factor_similar.hip;
         include/rtrec_amd_ext.h).  The workspace of a chunked call is factor_topk's."""
-        n_rows = int(count.numel())
-        splits = self.factor_splits(n_rows, n_items, item_splits)
-        ws = self.empty((n_rows * splits * (int(top_k) * 8 + 4),), self.torch.uint8) if splits > 1 else None
+        splits, ws = self.factor_workspace(int(count.numel()), n_items, top_k, item_splits)
         self.ops.factor_similar_topk(queries, p, p_norms, qt, int(n_items), int(dim), norms, item_mask, int(top_k), splits,
                                      bool(write_cosine), ids, scores, count, div, ws)
 

@@ -11,8 +11,8 @@
 //   out         s1, or fl(s1 / norm_q) with write_cosine -- divided once, where the final list is written (the merge kernel
 //               of a chunked call, the scan kernel otherwise), never on partial lists
 //
-// What is built.  The scan of factor_topk_kernel (factor_topk.hip; that file is not touched, so the strict-order compare and
-// the count-and-compact step stand twice for now): one wave per workgroup, 32 queries x one chunk of 32-item tiles, a tile is
+// What is built.  The scan of factor_topk_kernel (factor_topk.hip), in a kernel of its own (factor_scan.hip.h says why; the
+// limits, the strict order, the host plan and the dispatch are that header's): one wave per workgroup, 32 queries x one chunk of 32-item tiles, a tile is
 // one chain of v_mfma_f32_32x32x2_f32 with the items as the A operand read straight from d_qt and the queries' vectors as B in
 // ceil(dim / 2) VGPRs (classes of 8 / 32 / 128 for dim <= 16 / 64 / 256), a threshold in registers, a candidate buffer in LDS
 // (CAP = 64 / 128 / 224 entries for top_k <= 16 / 64 / 128, rows CAP + 1 apart: 32 queries appending at one position hit 32
@@ -34,22 +34,10 @@
 // tile's A operand.  No variant was measured against this one.
 // Malformed input cannot read out of range: a query outside [0, n_items) is a job without a vector (or, with brought vectors,
 // excludes nothing), item ids are generated, never read, and norms / mask are read only for ids < n_items.
-#include "row_lookup.hip.h"
-#include "../../include/rtrec_amd_ext.h"
+#include "factor_scan.hip.h"
 
 namespace rtrec {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kSimilarMaxDim = 256;
-constexpr int kSimilarMaxK = 128;
-constexpr int kSimilarMaxSplits = 64;
-constexpr int kSimilarMergeGrid = 65536;
-constexpr int kSimilarAutoBlocks = 1024;     // item_splits == 0: chunks are added until this many workgroups exist (4 per CU)
-
-// a beats b under the strict order (factor_topk.hip's factor_beats)
-__device__ __forceinline__ bool similar_beats(float sa, int ia, float sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
 
 // the norm of job r's query vector; +0.0f for a job without a vector
 __device__ __forceinline__ float similar_query_norm(long long r, const int32_t *queries, const float *p_norms, const float *norms,
@@ -111,7 +99,7 @@ __global__ __launch_bounds__(64) void factor_similar_kernel(
             const float os = lsc[u * LD + f];
             const int oi = lid[u * LD + f];
 #pragma unroll
-            for (int t = 0; t < EPL; ++t) rk[t] += similar_beats(os, oi, es[t], ei[t]) ? 1 : 0;
+            for (int t = 0; t < EPL; ++t) rk[t] += factor_beats(os, oi, es[t], ei[t]) ? 1 : 0;
         }
         __syncthreads();                            // every read of the old order is done
 #pragma unroll
@@ -167,7 +155,7 @@ __global__ __launch_bounds__(64) void factor_similar_kernel(
             bool ok = false;
             if (has && it < n_items) {
                 s = __fdiv_rn(acc[g], norms[it]);
-                ok = s == s && it != q && similar_beats(s, it, ts, ti) && (!item_mask || item_mask[it] != 0);
+                ok = s == s && it != q && factor_beats(s, it, ts, ti) && (!item_mask || item_mask[it] != 0);
             }
             acc[g] = s;
             if (ok) m |= 1u << g;
@@ -249,7 +237,7 @@ __global__ __launch_bounds__(64) void factor_similar_merge_kernel(
                 int lo = 0, hi = cnt[o];            // the first position of list o that does not beat (s, id)
                 while (lo < hi) {
                     const int mid = (lo + hi) >> 1;
-                    if (similar_beats(sc[o * top_k + mid], ids[o * top_k + mid], s, id)) lo = mid + 1; else hi = mid;
+                    if (factor_beats(sc[o * top_k + mid], ids[o * top_k + mid], s, id)) lo = mid + 1; else hi = mid;
                 }
                 rank += lo;
             }
@@ -264,11 +252,6 @@ __global__ __launch_bounds__(64) void factor_similar_merge_kernel(
     }
 }
 
-template <int DP, int CAP, typename... Args>
-void launch_similar(dim3 grid, hipStream_t st, Args... args) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(factor_similar_kernel<DP, CAP>), grid, dim3(64), 0, st, args...);
-}
-
 }  // namespace
 }  // namespace rtrec
 
@@ -279,59 +262,26 @@ extern "C" int rtrec_factor_similar_topk(int32_t n_rows, const int32_t *d_querie
                                          float *d_out_div, void *d_workspace, size_t workspace_bytes, void *stream) {
     using namespace rtrec;
     if (n_rows < 0 || n_items < 0) return RTREC_ERR_INVALID_ARG;
-    if (dim < 1 || dim > kSimilarMaxDim || top_k < 1 || top_k > kSimilarMaxK || item_splits < 0 || item_splits > kSimilarMaxSplits)
-        return RTREC_ERR_UNSUPPORTED;
+    if (!factor_limits_ok(dim, top_k, item_splits)) return RTREC_ERR_UNSUPPORTED;
     if (qt_stride < n_items || (d_p && p_stride < dim)) return RTREC_ERR_INVALID_ARG;
     if (n_rows == 0) return RTREC_OK;
     if (!d_out_ids || !d_out_scores || !d_out_count) return RTREC_ERR_INVALID_ARG;
     if (d_p ? !d_p_norms : !d_queries) return RTREC_ERR_INVALID_ARG;
     if (n_items > 0 && (!d_qt || !d_norms)) return RTREC_ERR_INVALID_ARG;
-    const int n_tiles = (n_items + 31) / 32;
-    const long long blocks = (static_cast<long long>(n_rows) + 31) / 32;
-    const size_t per_split = RTREC_FACTOR_TOPK_WORKSPACE_BYTES(n_rows, top_k, 1);
-    int splits = item_splits;
-    if (item_splits == 0) {
-        // rtrec_factor_topk's rule: chunks until kSimilarAutoBlocks workgroups exist, as far as the workspace reaches.  The
-        // figure is not measured, and the answer never depends on it.
-        const long long want = (kSimilarAutoBlocks + blocks - 1) / blocks;
-        splits = static_cast<int>(want < kSimilarMaxSplits ? want : kSimilarMaxSplits);
-        const size_t fits = d_workspace ? workspace_bytes / per_split : 0;
-        if (static_cast<size_t>(splits) > fits) splits = static_cast<int>(fits);
-        if (splits < 2) splits = 1;
-    } else if (item_splits > 1) {
-        if (!d_workspace) return RTREC_ERR_INVALID_ARG;
-        if (workspace_bytes < per_split * static_cast<size_t>(item_splits)) return RTREC_ERR_WORKSPACE;
-    }
-    if (splits > n_tiles) splits = n_tiles > 0 ? n_tiles : 1;      // (no empty chunks)
-    const int tiles_per_chunk = n_tiles > 0 ? (n_tiles + splits - 1) / splits : 0;
+    const FactorPlan pl = factor_plan(n_rows, n_items, top_k, item_splits, d_out_ids, d_out_scores, d_out_count, d_workspace,
+                                      workspace_bytes);
+    if (pl.status != RTREC_OK) return pl.status;
     (void)hipGetLastError();
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int32_t *k_ids = d_out_ids, *k_count = d_out_count;
-    float *k_scores = d_out_scores;
-    if (splits > 1) {
-        const size_t cells = static_cast<size_t>(n_rows) * static_cast<size_t>(splits) * static_cast<size_t>(top_k);
-        k_ids = static_cast<int32_t *>(d_workspace);
-        k_scores = reinterpret_cast<float *>(k_ids + cells);
-        k_count = reinterpret_cast<int32_t *>(k_scores + cells);
-    }
     const int cosine = write_cosine != 0 ? 1 : 0;
-    const dim3 grid(static_cast<unsigned int>(blocks), static_cast<unsigned int>(splits));
-#define RTREC_SIMILAR_LAUNCH(DP, CAP)                                                                                              \
-    launch_similar<DP, CAP>(grid, st, n_rows, d_queries, d_p, static_cast<long long>(p_stride), d_p_norms, d_qt,                     \
-                            static_cast<long long>(qt_stride), n_items, dim, d_norms, d_item_mask, top_k, splits, tiles_per_chunk,   \
-                            cosine, k_ids, k_scores, k_count, d_out_div)
-#define RTREC_SIMILAR_LAUNCH_K(DP)                                                                                                 \
-    do {                                                                                                                           \
-        if (top_k <= 16) RTREC_SIMILAR_LAUNCH(DP, 64); else if (top_k <= 64) RTREC_SIMILAR_LAUNCH(DP, 128); else RTREC_SIMILAR_LAUNCH(DP, 224); \
-    } while (0)
-    if (dim <= 16) RTREC_SIMILAR_LAUNCH_K(8); else if (dim <= 64) RTREC_SIMILAR_LAUNCH_K(32); else RTREC_SIMILAR_LAUNCH_K(128);
-#undef RTREC_SIMILAR_LAUNCH_K
-#undef RTREC_SIMILAR_LAUNCH
-    if (splits > 1) {
-        const int mgrid = n_rows < kSimilarMergeGrid ? n_rows : kSimilarMergeGrid;
-        hipLaunchKernelGGL(factor_similar_merge_kernel, dim3(mgrid), dim3(64), 0, st, n_rows, top_k, splits, k_ids, k_scores, k_count,
-                           cosine, d_queries, d_p ? d_p_norms : static_cast<const float *>(nullptr), d_norms, n_items, d_out_ids,
+    factor_dispatch(dim, top_k, [&](auto DP, auto CAP) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(factor_similar_kernel<DP(), CAP()>), pl.grid, dim3(64), 0, st, n_rows, d_queries, d_p,
+                           static_cast<long long>(p_stride), d_p_norms, d_qt, static_cast<long long>(qt_stride), n_items, dim, d_norms,
+                           d_item_mask, top_k, pl.splits, pl.tiles_per_chunk, cosine, pl.ids, pl.scores, pl.count, d_out_div);
+    });
+    if (pl.splits > 1)
+        hipLaunchKernelGGL(factor_similar_merge_kernel, dim3(pl.merge_grid), dim3(64), 0, st, n_rows, top_k, pl.splits, pl.ids, pl.scores,
+                           pl.count, cosine, d_queries, d_p ? d_p_norms : static_cast<const float *>(nullptr), d_norms, n_items, d_out_ids,
                            d_out_scores, d_out_count);
-    }
     return launch_status();
 }

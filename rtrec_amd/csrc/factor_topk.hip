@@ -38,22 +38,10 @@
 // top_k).  The rounding-order test passes with the MFMA, so the __fmaf_rn fallback was not built.
 // Not tried: several waves per workgroup sharing the users, staging d_qt through LDS, prefetching the next tile's A operand,
 // raising the threshold without a compaction.  No variant was measured against this one.
-#include "row_lookup.hip.h"
-#include "../../include/rtrec_amd_ext.h"
+#include "factor_scan.hip.h"
 
 namespace rtrec {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kFactorMaxDim = 256;
-constexpr int kFactorMaxK = 128;
-constexpr int kFactorMaxSplits = 64;
-constexpr int kFactorMergeGrid = 65536;
-constexpr int kFactorAutoBlocks = 1024;      // item_splits == 0: chunks are added until this many workgroups exist (4 per CU)
-
-// a beats b under the strict order
-__device__ __forceinline__ bool factor_beats(float sa, int ia, float sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
 
 template <int DP, int CAP>
 __global__ __launch_bounds__(64) void factor_topk_kernel(
@@ -248,11 +236,6 @@ __global__ __launch_bounds__(64) void factor_merge_kernel(int n_rows, int top_k,
     }
 }
 
-template <int DP, int CAP, typename... Args>
-void launch_factor(dim3 grid, hipStream_t st, Args... args) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(factor_topk_kernel<DP, CAP>), grid, dim3(64), 0, st, args...);
-}
-
 }  // namespace
 }  // namespace rtrec
 
@@ -264,58 +247,26 @@ extern "C" int rtrec_factor_topk(int32_t n_rows, const int32_t *d_row_ids, const
                                  void *d_workspace, size_t workspace_bytes, void *stream) {
     using namespace rtrec;
     if (n_rows < 0 || n_x_rows < 0 || n_p_rows < 0 || n_items < 0 || xb_nnz < 0) return RTREC_ERR_INVALID_ARG;
-    if (dim < 1 || dim > kFactorMaxDim || top_k < 1 || top_k > kFactorMaxK || item_splits < 0 || item_splits > kFactorMaxSplits)
-        return RTREC_ERR_UNSUPPORTED;
+    if (!factor_limits_ok(dim, top_k, item_splits)) return RTREC_ERR_UNSUPPORTED;
     if (p_stride < dim || qt_stride < n_items) return RTREC_ERR_INVALID_ARG;
     if (n_rows == 0) return RTREC_OK;
     if (!d_out_ids || !d_out_scores || !d_out_count) return RTREC_ERR_INVALID_ARG;
     if ((n_p_rows > 0 && !d_p) || (n_items > 0 && !d_qt)) return RTREC_ERR_INVALID_ARG;
     const int filter = filter_interacted != 0 ? 1 : 0;
     if (filter && ((n_x_rows > 0 && !d_xb_ptr) || (xb_nnz > 0 && !d_xb_col))) return RTREC_ERR_INVALID_ARG;
-    const int n_tiles = (n_items + 31) / 32;
-    const long long blocks = (static_cast<long long>(n_rows) + 31) / 32;
-    const size_t per_split = RTREC_FACTOR_TOPK_WORKSPACE_BYTES(n_rows, top_k, 1);
-    int splits = item_splits;
-    if (item_splits == 0) {
-        // the library's choice: chunks until kFactorAutoBlocks workgroups exist, as far as the workspace reaches.  The figure is
-        // four one-wave workgroups per CU; it is not measured, and the answer never depends on it.
-        const long long want = (kFactorAutoBlocks + blocks - 1) / blocks;
-        splits = static_cast<int>(want < kFactorMaxSplits ? want : kFactorMaxSplits);
-        const size_t fits = d_workspace ? workspace_bytes / per_split : 0;
-        if (static_cast<size_t>(splits) > fits) splits = static_cast<int>(fits);
-        if (splits < 2) splits = 1;
-    } else if (item_splits > 1) {
-        if (!d_workspace) return RTREC_ERR_INVALID_ARG;
-        if (workspace_bytes < per_split * static_cast<size_t>(item_splits)) return RTREC_ERR_WORKSPACE;
-    }
-    if (splits > n_tiles) splits = n_tiles > 0 ? n_tiles : 1;      // (no empty chunks)
-    const int tiles_per_chunk = n_tiles > 0 ? (n_tiles + splits - 1) / splits : 0;
+    const FactorPlan pl = factor_plan(n_rows, n_items, top_k, item_splits, d_out_ids, d_out_scores, d_out_count, d_workspace,
+                                      workspace_bytes);
+    if (pl.status != RTREC_OK) return pl.status;
     (void)hipGetLastError();
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int32_t *k_ids = d_out_ids, *k_count = d_out_count;
-    float *k_scores = d_out_scores;
-    if (splits > 1) {
-        const size_t cells = static_cast<size_t>(n_rows) * static_cast<size_t>(splits) * static_cast<size_t>(top_k);
-        k_ids = static_cast<int32_t *>(d_workspace);
-        k_scores = reinterpret_cast<float *>(k_ids + cells);
-        k_count = reinterpret_cast<int32_t *>(k_scores + cells);
-    }
-    const dim3 grid(static_cast<unsigned int>(blocks), static_cast<unsigned int>(splits));
-#define RTREC_FACTOR_LAUNCH(DP, CAP)                                                                                              \
-    launch_factor<DP, CAP>(grid, st, n_rows, d_row_ids, d_p_index, n_x_rows, d_p, static_cast<long long>(p_stride), n_p_rows, d_qt, \
-                           static_cast<long long>(qt_stride), n_items, dim, d_item_mask, d_xb_ptr, d_xb_col,                        \
-                           static_cast<long long>(xb_nnz), filter, top_k, splits, tiles_per_chunk, k_ids, k_scores, k_count)
-#define RTREC_FACTOR_LAUNCH_K(DP)                                                                                                 \
-    do {                                                                                                                          \
-        if (top_k <= 16) RTREC_FACTOR_LAUNCH(DP, 64); else if (top_k <= 64) RTREC_FACTOR_LAUNCH(DP, 128); else RTREC_FACTOR_LAUNCH(DP, 224); \
-    } while (0)
-    if (dim <= 16) RTREC_FACTOR_LAUNCH_K(8); else if (dim <= 64) RTREC_FACTOR_LAUNCH_K(32); else RTREC_FACTOR_LAUNCH_K(128);
-#undef RTREC_FACTOR_LAUNCH_K
-#undef RTREC_FACTOR_LAUNCH
-    if (splits > 1) {
-        const int mgrid = n_rows < kFactorMergeGrid ? n_rows : kFactorMergeGrid;
-        hipLaunchKernelGGL(factor_merge_kernel, dim3(mgrid), dim3(64), 0, st, n_rows, top_k, splits, k_ids, k_scores, k_count,
+    factor_dispatch(dim, top_k, [&](auto DP, auto CAP) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(factor_topk_kernel<DP(), CAP()>), pl.grid, dim3(64), 0, st, n_rows, d_row_ids, d_p_index, n_x_rows,
+                           d_p, static_cast<long long>(p_stride), n_p_rows, d_qt, static_cast<long long>(qt_stride), n_items, dim,
+                           d_item_mask, d_xb_ptr, d_xb_col, static_cast<long long>(xb_nnz), filter, top_k, pl.splits, pl.tiles_per_chunk,
+                           pl.ids, pl.scores, pl.count);
+    });
+    if (pl.splits > 1)
+        hipLaunchKernelGGL(factor_merge_kernel, dim3(pl.merge_grid), dim3(64), 0, st, n_rows, top_k, pl.splits, pl.ids, pl.scores, pl.count,
                            d_out_ids, d_out_scores, d_out_count);
-    }
     return launch_status();
 }

@@ -656,6 +656,20 @@ void blend_lists(int64_t n_items, const at::Tensor &a_ids, const at::Tensor &a_s
           "rtrec_slim_blend_lists");
 }
 
+// What factor_topk and factor_similar_topk share (the scan of csrc/factor_scan.hip.h): the ranges of dim, top_k and item_splits,
+// qt [>= dim, >= n_items], ids / scores [n_rows, top_k], item_mask [>= n_items] uint8 / bool.  Returns the workspace's bytes.
+size_t check_factor_scan(const char *op, int64_t dim, int64_t top_k, int64_t item_splits, int64_t rows, int64_t n_items, const at::Tensor &qt,
+                         const at::Tensor &ids, const at::Tensor &scores, const OT &item_mask, const OT &workspace) {
+    TORCH_CHECK(dim >= 1 && dim <= 256, op, ": dim must lie in 1..256, got ", dim);
+    TORCH_CHECK(top_k >= 1 && top_k <= 128, op, ": top_k must lie in 1..128, got ", top_k);
+    TORCH_CHECK(item_splits >= 0 && item_splits <= 64, op, ": item_splits must lie in 0..64, got ", item_splits);
+    TORCH_CHECK(qt.dim() == 2 && qt.size(0) >= dim && qt.size(1) >= n_items, op, ": qt must be [>= dim, >= n_items]");
+    TORCH_CHECK(ids.numel() == rows * top_k && scores.numel() == rows * top_k, op, ": outputs must be ids[n_rows, top_k], scores[same], count[n_rows]");
+    TORCH_CHECK(!has(item_mask) || (item_mask->numel() >= n_items && (item_mask->scalar_type() == at::kByte || item_mask->scalar_type() == at::kBool)),
+                op, ": item_mask must hold one uint8 / bool entry per item");
+    return has(workspace) ? static_cast<size_t>(workspace->numel()) * workspace->element_size() : 0;
+}
+
 // p [n_p_rows, >= dim] float32: one vector per row; qt [>= dim, >= n_items] float32: the item vectors component-major; one job
 // per entry of count: row_ids names its row of X (absent = row r), p_index [n_x_rows] the vector of a row of X (absent = row x);
 // item_mask [>= n_items] uint8 / bool; xb_* the rows of X as a CSR without values (only with filter_interacted); the outputs are
@@ -664,19 +678,13 @@ void blend_lists(int64_t n_items, const at::Tensor &a_ids, const at::Tensor &a_s
 void factor_topk(const OT &row_ids, const OT &p_index, int64_t n_x_rows, const at::Tensor &p, const at::Tensor &qt, int64_t n_items,
                  int64_t dim, const OT &item_mask, const OT &xb_ptr, const OT &xb_col, bool filter_interacted, int64_t top_k,
                  int64_t item_splits, at::Tensor ids, at::Tensor scores, at::Tensor count, const OT &workspace) {
-    TORCH_CHECK(dim >= 1 && dim <= 256, "factor_topk: dim must lie in 1..256, got ", dim);
-    TORCH_CHECK(top_k >= 1 && top_k <= 128, "factor_topk: top_k must lie in 1..128, got ", top_k);
-    TORCH_CHECK(item_splits >= 0 && item_splits <= 64, "factor_topk: item_splits must lie in 0..64, got ", item_splits);
     const int64_t rows = count.numel();
+    const size_t ws_bytes = check_factor_scan("factor_topk", dim, top_k, item_splits, rows, n_items, qt, ids, scores, item_mask, workspace);
     TORCH_CHECK(rows <= INT32_MAX && n_items >= 0 && n_items < INT32_MAX && n_x_rows >= 0 && n_x_rows < INT32_MAX,
                 "factor_topk: too many rows or items");
     TORCH_CHECK(p.dim() == 2 && p.size(1) >= dim && p.size(0) <= INT32_MAX, "factor_topk: p must be [n_p_rows, >= dim]");
-    TORCH_CHECK(qt.dim() == 2 && qt.size(0) >= dim && qt.size(1) >= n_items, "factor_topk: qt must be [>= dim, >= n_items]");
-    TORCH_CHECK(ids.numel() == rows * top_k && scores.numel() == rows * top_k, "factor_topk: outputs must be ids[n_rows, top_k], scores[same], count[n_rows]");
     TORCH_CHECK(!has(row_ids) || row_ids->numel() == rows, "factor_topk: row_ids must hold one entry per job");
     TORCH_CHECK(!has(p_index) || p_index->numel() == n_x_rows, "factor_topk: p_index must hold one entry per row of X");
-    TORCH_CHECK(!has(item_mask) || (item_mask->numel() >= n_items && (item_mask->scalar_type() == at::kByte || item_mask->scalar_type() == at::kBool)),
-                "factor_topk: item_mask must hold one uint8 / bool entry per item");
     int64_t xb_nnz = 0;
     if (filter_interacted) {
         TORCH_CHECK(has(xb_ptr) && has(xb_col), "factor_topk: filter_interacted needs xb_ptr and xb_col");
@@ -684,7 +692,6 @@ void factor_topk(const OT &row_ids, const OT &p_index, int64_t n_x_rows, const a
         xb_nnz = xb_col->numel();
     }
     one_device("factor_topk", count, {&p, &qt, &ids, &scores}, {&row_ids, &p_index, &item_mask, &xb_ptr, &xb_col, &workspace});
-    const size_t ws_bytes = has(workspace) ? static_cast<size_t>(workspace->numel()) * workspace->element_size() : 0;
     check(abi().factor_topk(static_cast<int32_t>(rows), cptr<const int32_t>(row_ids), cptr<const int32_t>(p_index),
                             static_cast<int32_t>(n_x_rows), cptr<const float>(p), p.size(1), static_cast<int32_t>(p.size(0)),
                             cptr<const float>(qt), qt.size(1), static_cast<int32_t>(n_items), static_cast<int32_t>(dim),
@@ -749,15 +756,10 @@ void factor_norms(const at::Tensor &v, int64_t n, int64_t dim, int64_t row_strid
 void factor_similar_topk(const OT &queries, const OT &p, const OT &p_norms, const at::Tensor &qt, int64_t n_items, int64_t dim,
                          const at::Tensor &norms, const OT &item_mask, int64_t top_k, int64_t item_splits, bool write_cosine,
                          at::Tensor ids, at::Tensor scores, at::Tensor count, const OT &div, const OT &workspace) {
-    TORCH_CHECK(dim >= 1 && dim <= 256, "factor_similar_topk: dim must lie in 1..256, got ", dim);
-    TORCH_CHECK(top_k >= 1 && top_k <= 128, "factor_similar_topk: top_k must lie in 1..128, got ", top_k);
-    TORCH_CHECK(item_splits >= 0 && item_splits <= 64, "factor_similar_topk: item_splits must lie in 0..64, got ", item_splits);
     const int64_t rows = count.numel();
+    const size_t ws_bytes = check_factor_scan("factor_similar_topk", dim, top_k, item_splits, rows, n_items, qt, ids, scores, item_mask, workspace);
     check_rows_items("factor_similar_topk", rows, n_items);
-    TORCH_CHECK(qt.dim() == 2 && qt.size(0) >= dim && qt.size(1) >= n_items, "factor_similar_topk: qt must be [>= dim, >= n_items]");
     TORCH_CHECK(norms.numel() >= n_items, "factor_similar_topk: norms must hold one entry per item");
-    TORCH_CHECK(ids.numel() == rows * top_k && scores.numel() == rows * top_k,
-                "factor_similar_topk: outputs must be ids[n_rows, top_k], scores[same], count[n_rows]");
     TORCH_CHECK(!has(div) || div->numel() == rows, "factor_similar_topk: div must hold one entry per job");
     if (has(p)) {
         TORCH_CHECK(p->dim() == 2 && p->size(0) == rows && p->size(1) >= dim, "factor_similar_topk: p must be [n_rows, >= dim]");
@@ -766,10 +768,7 @@ void factor_similar_topk(const OT &queries, const OT &p, const OT &p_norms, cons
     } else {
         TORCH_CHECK(has(queries) && queries->numel() == rows, "factor_similar_topk: queries must hold one entry per job");
     }
-    TORCH_CHECK(!has(item_mask) || (item_mask->numel() >= n_items && (item_mask->scalar_type() == at::kByte || item_mask->scalar_type() == at::kBool)),
-                "factor_similar_topk: item_mask must hold one uint8 / bool entry per item");
     one_device("factor_similar_topk", count, {&qt, &norms, &ids, &scores}, {&queries, &p, &p_norms, &item_mask, &div, &workspace});
-    const size_t ws_bytes = has(workspace) ? static_cast<size_t>(workspace->numel()) * workspace->element_size() : 0;
     const bool brought = has(p) && rows > 0;
     check(abi().factor_similar_topk(static_cast<int32_t>(rows), cptr<const int32_t>(queries), brought ? cptr<const float>(p) : nullptr,
                                     brought ? p->size(1) : 0, brought ? cptr<const float>(p_norms) : nullptr, cptr<const float>(qt),

@@ -2111,6 +2111,22 @@ class SlimEngine:
             for k in range(int(occ.max()) + 1):
                 run(pos[occ == k], True)
 
+    def _factor_scan_front(self, name: str, n_rows: int, top_k: int, item_splits: int, item_mask):
+        """The common front of factor_topk_device and similar_factor_device: the ranges of top_k and item_splits, the resident
+        mask merged with `item_mask`, and the outputs: (mask, ids[n_rows, top_k], scores[same], count[n_rows])."""
+        be, torch, F = self.be, self.be.torch, self._F
+        if not 1 <= top_k <= self.FACTOR_MAX_K:
+            raise ValueError(f"{name}: top_k must lie in 1..{self.FACTOR_MAX_K}, got {top_k}")
+        if not 0 <= int(item_splits) <= 64:
+            raise ValueError(f"{name}: item_splits must lie in 0..64, got {item_splits}")
+        mask = F["mask"]
+        if item_mask is not None:
+            if int(item_mask.numel()) != F["n_items"]:
+                raise ValueError(f"item_mask must hold one entry per item ({F['n_items']})")
+            mask = item_mask if mask is None else (item_mask.to(torch.uint8) * mask)
+        return (mask, be.empty((n_rows, top_k), torch.int32), be.empty((n_rows, top_k), torch.float32),
+                be.zeros((n_rows,), torch.int32))
+
     def factor_topk_device(self, d_rows, n_rows: int, top_k: int, filter_interacted: bool = True, item_mask=None,
                            item_splits: int = 0, vectors=None, vector_has=None):
         """Device tensors (ids[n_rows, top_k] int32, scores[n_rows, top_k] float32, count[n_rows] int32): per row `d_rows[r]`
@@ -2131,22 +2147,11 @@ class SlimEngine:
             raise RuntimeError("set_interactions() must be called before factor_topk")
         F = self._F
         top_k, n_rows = int(top_k), int(n_rows)
-        if not 1 <= top_k <= self.FACTOR_MAX_K:
-            raise ValueError(f"factor_topk: top_k must lie in 1..{self.FACTOR_MAX_K}, got {top_k}")
-        if not 0 <= int(item_splits) <= 64:
-            raise ValueError(f"factor_topk: item_splits must lie in 0..64, got {item_splits}")
+        mask, ids, scores, count = self._factor_scan_front("factor_topk", n_rows, top_k, item_splits, item_mask)
         if self._W and F["n_items"] != int(self._W["n_items"]):
             raise ValueError(f"the resident factors cover {F['n_items']} items, W has {self._W['n_items']}: call set_factors() again")
         if F["index"] is not None and int(F["index"].numel()) != self.n_users:
             raise ValueError(f"the resident user_index covers {int(F['index'].numel())} rows, X has {self.n_users}: call set_factors() again")
-        mask = F["mask"]
-        if item_mask is not None:
-            if int(item_mask.numel()) != F["n_items"]:
-                raise ValueError(f"item_mask must hold one entry per item ({F['n_items']})")
-            mask = item_mask if mask is None else (item_mask.to(torch.uint8) * mask)
-        ids = be.empty((n_rows, top_k), torch.int32)
-        scores = be.empty((n_rows, top_k), torch.float32)
-        count = be.zeros((n_rows,), torch.int32)
         if n_rows == 0:
             return ids, scores, count
         if vectors is not None:
@@ -2221,22 +2226,11 @@ class SlimEngine:
             raise RuntimeError("set_factors() must be called before similar_factor")
         F = self._F
         top_k, first = int(top_k), int(first_component)
-        if not 1 <= top_k <= self.FACTOR_MAX_K:
-            raise ValueError(f"similar_factor: top_k must lie in 1..{self.FACTOR_MAX_K}, got {top_k}")
-        if not 0 <= int(item_splits) <= 64:
-            raise ValueError(f"similar_factor: item_splits must lie in 0..64, got {item_splits}")
-        norms = self.item_norms_device(first)
         q = np.asarray(queries, dtype=np.int64).reshape(-1)
         n, n_items, dim = len(q), F["n_items"], F["dim"] - first
         q = np.where((q >= 0) & (q < n_items), q, -1).astype(np.int32)
-        mask = F["mask"]
-        if item_mask is not None:
-            if int(item_mask.numel()) != n_items:
-                raise ValueError(f"item_mask must hold one entry per item ({n_items})")
-            mask = item_mask if mask is None else (item_mask.to(torch.uint8) * mask)
-        ids = be.empty((n, top_k), torch.int32)
-        scores = be.empty((n, top_k), torch.float32)
-        count = be.zeros((n,), torch.int32)
+        mask, ids, scores, count = self._factor_scan_front("similar_factor", n, top_k, item_splits, item_mask)
+        norms = self.item_norms_device(first)
         div = be.zeros((n,), torch.float32) if want_div else None
         if n == 0:
             return ids, scores, count, div

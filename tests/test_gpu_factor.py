@@ -138,6 +138,24 @@ def test_scores_that_rise_with_the_item_id_beat_the_threshold_every_time(top_k):
             assert_same(run_op(P, Q, top_k, splits=splits), want, (name, top_k, splits))
 
 
+def test_the_merge_fills_one_list_from_four_short_chunks():
+    """One job, 97 items in four chunks of one tile (32, 32, 32 and 1 items), top_k 64: every partial list is shorter than top_k
+    and the merge takes entries of all four; with a mask that admits 50 items the list ends in a
+    -1 / -inf tail."""
+    rng = np.random.default_rng(97)
+    P = rng.standard_normal((1, 5)).astype(F32)
+    Q = rng.standard_normal((97, 5)).astype(F32)
+    Q[96] = 10 * P[0]                                                     # the last chunk's only item is the best of all
+    mask = np.zeros(97, np.uint8)
+    mask[rng.permutation(96)[:49]] = 1
+    mask[96] = 1
+    for m, n in ((None, 64), (mask, 50)):
+        want = host_model_fast(P, Q, 64, mask=m)
+        assert want[2][0] == n and want[0][0, 0] == 96 and set(want[0][0, :n] // 32) == {0, 1, 2, 3}
+        assert (want[0][0, n:] == -1).all() and np.isneginf(want[1][0, n:]).all()
+        assert_same(run_op(P, Q, 64, mask=m, splits=4), want, ("masked" if m is not None else "all", n))
+
+
 # ---------------------------------------------------------------------------------------------- 6. filter, mask and rows
 def test_filter_mask_rows_strides_and_specials():
     rng = np.random.default_rng(66)

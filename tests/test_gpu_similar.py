@@ -9,7 +9,7 @@ import pytest
 from tests.test_factor_host import F32, rounding_vectors
 from tests.test_similar_host import (FLT_MAX, assert_same_blend, assert_same_lists, check_serving_and_facade, check_similar_api, golden_answer,
                                      golden_cases, golden_inputs, host_blend, host_norms_fast, host_norms_plain, host_similar_fast,
-                                     lists_of, special_vectors, dbits)
+                                     lists_of, one_scan_cases, special_vectors, dbits)
 
 pytestmark = pytest.mark.gpu
 
@@ -202,6 +202,25 @@ def test_ties_unknown_queries_and_the_two_ways_to_divide():
     cos = run_similar(Q, norms, queries, 10, write_cosine=True, splits=4)
     assert np.array_equal(s1[0], cos[0]) and np.array_equal(s1[3], norms[:40]) and np.array_equal(cos[3], norms[:40])
     assert np.array_equal((s1[1] / s1[3][:, None]).view(np.int32), cos[1].view(np.int32))
+
+
+def test_the_two_entry_points_run_the_same_scan():
+    """The two kernels are one scan written twice (csrc/factor_scan.hip.h says why).  Unit item norms, no queries, no mask, no
+    cosine: factor_similar_topk must return factor_topk's ids, counts and score bits (x / 1.0f is exact), and both the host
+    model's (tests/test_similar_host.py, one_scan_cases, shows the premise on the host)."""
+    from tests.test_factor_host import assert_same
+    from tests.test_gpu_factor import run_op
+    for name, P, Q, p_norms, want in one_scan_cases():
+        ones = np.ones(len(Q), F32)
+        for top_k in (10, 128):
+            for splits in (1, 3):
+                sim = run_similar(Q, ones, None, top_k, P=P, p_norms=p_norms, splits=splits)
+                top = run_op(P, Q, top_k, splits=splits)
+                what = (name, top_k, splits)
+                assert np.array_equal(sim[0], top[0]) and np.array_equal(sim[2], top[2]), what
+                assert np.array_equal(sim[1].view(np.int32), top[1].view(np.int32)) and np.array_equal(sim[3], p_norms), what
+                assert_same(top, want[top_k], what)
+                assert_same(sim[:3], want[top_k], what)
 
 
 # ---------------------------------------------------------------------------------------------- 3. the blend

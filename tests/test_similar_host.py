@@ -358,6 +358,41 @@ def test_both_similar_models_agree_on_long_chains_and_ties():
         assert cnt[0] == 9 and ids[0, :9].tolist() == list(range(9)) and (ids[0, 9:] == -1).all() and np.isneginf(sc[0, 9:]).all()
 
 
+_ONE_SCAN = []
+
+
+def one_scan_cases():
+    """[(name, P, Q, p_norms, {top_k: host_model_fast's answer})] on which rtrec_factor_similar_topk with item norms of 1.0f, no
+    queries, no mask and no cosine must BE rtrec_factor_topk without a filter (x / 1.0f is exact): 33 jobs (a second workgroup with
+    one live lane) x 161 items (five whole tiles and one item) at dim 13 (odd: a zero-padded k-step), once on rounding_vectors and
+    once with small-integer scores that rise with the item id (exact in float32, so every item beats the threshold and a 64-entry
+    buffer compacts several times within 161 items at top_k 10).  Computed once; tests/test_gpu_similar.py runs both ops on them."""
+    from tests.test_factor_host import host_model_fast
+    if not _ONE_SCAN:
+        rng = np.random.default_rng(131)
+        P, Q = rounding_vectors(33, 161, 13, seed=131)
+        P2 = rng.integers(1, 5, (33, 13)).astype(F32)
+        Q2 = (np.arange(161)[:, None] * (1 + np.arange(13)[None, :] % 3)).astype(F32)
+        for name, p, q in (("rounding", P, Q), ("rising", P2, Q2)):
+            p_norms = (rng.random(33) * 9 + 0.5).astype(F32)                      # any positive values: they are not read for s1
+            _ONE_SCAN.append((name, p, q, p_norms, {k: host_model_fast(p, q, k) for k in (10, 128)}))
+    return _ONE_SCAN
+
+
+def test_similar_with_unit_norms_is_the_factor_model():
+    """The premise of the one-scan GPU test, shown with the two host models: with unit item norms and nothing excluded,
+    host_similar_fast equals host_model_fast, ids, counts and score bits."""
+    for name, P, Q, p_norms, want in one_scan_cases():
+        ones = np.ones(len(Q), F32)
+        for top_k in (10, 128):
+            ids, sc, cnt, div = host_similar_fast(Q, ones, None, top_k, P=P, p_norms=p_norms)
+            w_ids, w_sc, w_cnt = want[top_k]
+            assert np.array_equal(ids, w_ids) and np.array_equal(cnt, w_cnt) and (cnt == top_k).all(), (name, top_k)
+            assert np.array_equal(sc.view(np.int32), w_sc.view(np.int32)) and np.array_equal(div, p_norms), (name, top_k)
+        if name == "rising":
+            assert (want[10][0] == np.arange(160, 150, -1)).all() and (np.diff(host_scores(P, Q), axis=1) > 0).all()
+
+
 # ---------------------------------------------------------------------------------------------- pinning: what the roundings are worth
 def test_other_ways_to_divide_change_bits_of_s1():
     rng = np.random.default_rng(12)
