@@ -1536,24 +1536,14 @@ __global__ __launch_bounds__(64, FIT_WAVES_PER_SIMD) void fit_columns_kernel(Fit
 // element-wise residual update, the R = y materialisation and the scratch reset are split over
 // all threads.  Results are bit-identical to the single-wave kernel.
 // =============================================================================================
-#ifndef MW_FOLD_GROUP
-#define MW_FOLD_GROUP 4
-#endif
-constexpr int kFoldGroup = MW_FOLD_GROUP;   // chunks the consumer folds per loop iteration (power of two)
+constexpr int kFoldGroup = 4;    // chunks the consumer folds per loop iteration
 constexpr int kMwWaves = 8;
 constexpr int kMwThreads = kMwWaves * 64;
-#ifndef MW_IDLE_WAVE4
-#define MW_IDLE_WAVE4 0
-#endif
-// MW_IDLE_WAVE4 (A/B): wave 4 shares SIMD 0 with the consumer (waves go to SIMD wave % 4); it then takes no part in the folds
-constexpr int kProducers = MW_IDLE_WAVE4 ? kMwWaves - 2 : kMwWaves - 1;
+constexpr int kProducers = kMwWaves - 1;
 constexpr int kProdDepth = 8;    // chunks a producer wave keeps in flight
 constexpr int kMwMaxTargets = 2048;  // calls with at most this many targets use the multi-wave kernel
 constexpr int kColWalkMinRows = 1024;  // targets with at least this many users take the column-walk X^T y
 constexpr int kRing = 128;       // ring slots of 64 products (>= kProducers * kProdDepth, power of 2)
-#ifndef MW_CHAIN_ALL_LANES
-#define MW_CHAIN_ALL_LANES 0
-#endif
 #ifndef MW_SPEC_GROUPS
 #define MW_SPEC_GROUPS 4
 #endif
@@ -1664,7 +1654,7 @@ __device__ float mw_fold(const int *__restrict__ crow, const float *__restrict__
                 }
                 if (lane == 0) lds_store_release(M.done, seq + min(c + Cp, n_chunks));
             }
-        } else if (n_chunks > 0 && (MW_CHAIN_ALL_LANES || lane < 16)) {
+        } else if (n_chunks > 0 && lane < 16) {
             // A group's four chunks are four consecutive ring slots (seq and every group start are multiples of four, the ring
             // holds 128): one base address per group for the products and one for the flags.  Two groups per loop turn with the
             // registers of A and B swapping roles (round 5: the sixteen v_mov of `A = B`, the per-chunk slot arithmetic, one loop
@@ -1751,7 +1741,7 @@ __device__ float mw_fold(const int *__restrict__ crow, const float *__restrict__
                 }
             }
         };
-        int g0 = MW_IDLE_WAVE4 ? (wave < 4 ? wave - 1 : (wave == 4 ? n_groups : wave - 2)) : wave - 1;
+        int g0 = wave - 1;
         if (g0 < n_groups) load_idx(g0, rr, xx);
         for (; g0 < n_groups; g0 += kGroupStride) {
             float prod[kProdDepth];
