@@ -195,7 +195,7 @@ int rtrec_slim_blend_lists(int32_t n_rows, int32_t n_items, const int32_t *d_a_i
  * FACTOR TOP-K  (dense user vectors against dense item vectors: the best top_k items per job, scored and selected in one pass.)
  * The reference's hybrid model takes its second list from implicit.topk(items=item_vector, query=user_vector, k,
  * filter_query_items) (rtrec/models/hybrid.py): a float32 GEMM and a top-k per row with the interacted items filtered.  This
- * call does that for vectors the caller brings; training a factor model is not part of this library.
+ * call does that for vectors the caller brings, or for the ones rtrec_factor_gram / rtrec_factor_als_solve below have trained.
  *   vectors     job r names row x = d_row_ids[r] of X (d_row_ids == NULL: x = r).  Its vector is row d_p_index[x] of
  *               d_p[n_p_rows][p_stride] (d_p_index == NULL: row x); d_p_index holds n_x_rows entries.  A job has no vector when x
  *               lies outside [0, n_x_rows), when its index is -1, or when its index lies outside [0, n_p_rows): it returns an
@@ -242,7 +242,8 @@ int rtrec_factor_topk(int32_t n_rows, const int32_t *d_row_ids, const int32_t *d
  * The reference's hybrid model never reads an entity's vector from a table: it builds a sparse feature row per user or item --
  * the identity column plus the columns of its tags -- and multiplies it into LightFM's per-feature embedding and bias tables
  * (get_user_representations(features) = features * user_biases, features * user_embeddings; scipy's csr_matvec / csr_matvecs).
- * This call is that product, written where rtrec_factor_topk reads: training the tables is not part of this library.
+ * This call is that product, written where rtrec_factor_topk reads: training per-feature tables is not part of this library
+ * (rtrec_factor_als_solve learns one vector per user and item, no tag tables).
  *   rows        a CSR of feature rows d_f_ptr[n_f_rows + 1] / d_f_col[nnz] / d_f_val[nnz] (int32 / int32 / float32);
  *               d_f_val == NULL: every value is 1.  Offsets are clamped to [0, nnz], so a malformed CSR gives wrong answers,
  *               never an out-of-range read.  Job r takes row d_job_rows[r] (d_job_rows == NULL: row r); a value outside
@@ -372,6 +373,72 @@ int rtrec_similar_blend(int32_t n_rows, int32_t n_items, const int32_t *d_a_ids,
                         const int32_t *d_b_ids, int64_t b_ids_stride, const float *d_b_scores, int64_t b_scores_stride,
                         const int32_t *d_b_counts, int32_t kb, const int32_t *d_exclude, int32_t keep, int32_t waves_per_row,
                         int32_t *d_out_ids, double *d_out_value, int32_t *d_out_source, int32_t *d_out_count, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * FACTOR GRAM  (V^T V + reg I of one side's vectors: the constant part of every row's system in an ALS half-step.)
+ * The reference's hybrid model owns its second model (HybridSlimFM.fit / bulk_fit call LightFMWrapper.fit_partial); LightFM's
+ * WARP / hogwild SGD is not reproducible and serialises badly on a GPU.  This library trains the vectors rtrec_factor_topk
+ * scores by implicit-feedback alternating least squares instead (Hu, Koren, Volinsky 2008): deterministic, dense, and pinned
+ * operation by operation.  A HALF-STEP solves one side against the other side held fixed: this call, then
+ * rtrec_factor_als_solve.  The fixed side is d_v[n_v][v_stride] row-major float32, v_stride >= dim (what lies between dim and
+ * v_stride is never read).
+ *   chunk       the rows of V are cut into chunks of 1024 -- a constant of this contract: chunk c is rows
+ *               [1024 c, min(n_v, 1024 c + 1024))
+ *   partial     part_c[a][b] = +0.0f, then part_c[a][b] = fmaf(v_r[a], v_r[b], part_c[a][b]) for the rows r of chunk c ascending:
+ *               one correctly rounded fused multiply-add per row, float32 denormals kept
+ *   sum         G[a][b] = +0.0f, then G[a][b] = fl(G[a][b] + part_c[a][b]) for c ascending, one rounded add each; finally
+ *               G[a][a] = fl(G[a][a] + reg)
+ * Out: d_gram[dim][dim] float32, every element written.  It is symmetric bit for bit (a product commutes).  n_v == 0 gives
+ * reg * I.  The partials live in d_workspace: RTREC_FACTOR_GRAM_WORKSPACE_BYTES(n_v, dim) bytes (a macro, not an entry point,
+ * as RTREC_FACTOR_TOPK_WORKSPACE_BYTES; none for n_v == 0).
+ * dim in 1..64: RTREC_ERR_UNSUPPORTED otherwise.  Negative n_v, v_stride < dim, a reg that is negative or NaN, NULL d_gram, NULL
+ * d_v or d_workspace with n_v > 0: RTREC_ERR_INVALID_ARG.  A workspace too small: RTREC_ERR_WORKSPACE.  No global state, no
+ * environment variable, no allocation, no synchronisation.  The results never depend on the grid or on scheduling.
+ * csrc/factor_gram.hip: factor_gram_partial_kernel, one one-wave workgroup per chunk, a 32 x 32 tile is one chain of
+ * v_mfma_f32_32x32x2_f32 over ascending rows (that fmaf chain bit for bit), the three lower tiles for dim > 32;
+ * factor_gram_sum_kernel adds the partials, one thread per element.  No atomics.
+ * ------------------------------------------------------------------------------------- */
+#define RTREC_FACTOR_GRAM_WORKSPACE_BYTES(n_v, dim) \
+    ((((size_t)(n_v) + 1023u) / 1024u) * (size_t)(dim) * (size_t)(dim) * 4u)
+int rtrec_factor_gram(int32_t n_v, const float *d_v, int64_t v_stride, int32_t dim, float reg, float *d_gram, void *d_workspace,
+                      size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * FACTOR ALS SOLVE  (per row of R: build G + sum w y y^T and sum (1 + w) y, factor by Cholesky, solve -- every operation pinned.)
+ * The second call of a half-step.  R is a CSR d_r_ptr[n_rows + 1] / d_r_idx[nnz] / d_r_val[nnz] (int32 / int32 / float32): X's
+ * CSR for the user half-step, X's CSC read as a CSR of X^T for the item half-step.  The fixed side is d_v[n_v][v_stride] as for
+ * rtrec_factor_gram, d_gram[dim][dim] what that call wrote for it.  Job r names row x = d_job_rows[r] (d_job_rows == NULL:
+ * x = r).  Offsets are clamped to [0, nnz], so a malformed CSR gives wrong answers, never an out-of-range read.
+ *   usable      a stored entry (i, val) of row x is usable when 0 <= i < n_v and w = fl(alpha * val) satisfies w > 0: NaN and
+ *               non-positive values are skipped, and the row of V a skipped entry names is never read
+ *   build       only the lower triangle a >= b is defined.  A[a][b] = G[a][b], then over the usable entries IN STORAGE ORDER
+ *               A[a][b] = fmaf(fl(w * y_i[a]), y_i[b], A[a][b]) (y_i = row i of V);  rhs[a] = +0.0f, then
+ *               rhs[a] = fmaf(fl(1.0f + w), y_i[a], rhs[a])
+ *   Cholesky    left-looking, every element one chain.  For j = 0 .. dim-1: d = A[j][j], then d = fmaf(-L[j][k], L[j][k], d) for
+ *               k = 0 .. j-1; if !(d > 0) or d is not finite the job BREAKS DOWN; L[j][j] = sqrt(d), correctly rounded; for
+ *               i > j: s = A[i][j], then s = fmaf(-L[i][k], L[j][k], s) for k ascending, L[i][j] = fl(s / L[j][j]): one correctly
+ *               rounded division
+ *   forward     for j ascending: s = rhs[j], then s = fmaf(-L[j][k], z[k], s) for k = 0 .. j-1; z[j] = fl(s / L[j][j])
+ *   backward    for j = dim-1 .. 0: s = z[j], then s = fmaf(-L[k][j], x[k], s) for k = dim-1 down to j+1; x[j] = fl(s / L[j][j])
+ * Float32 denormals are kept; nothing is contracted or reordered beyond what is written here.
+ * Out: the vector is written in place at d_out[x * out_stride + c], c in [0, dim); what lies between dim and out_stride is not
+ * touched.  d_status[r] (uint8): 0 = solved; 1 = x lies outside [0, n_rows) (nothing else is written), or the row has no usable
+ * entry (the vector is all +0.0f); 2 = breakdown, or a component that is not finite (the vector is all +0.0f).  Jobs must name
+ * distinct rows, otherwise the result is unspecified.  The sign of a zero is not part of the contract.
+ * dim in 1..64: RTREC_ERR_UNSUPPORTED otherwise.  Negative sizes, strides below dim, an alpha that is not > 0 (NaN included):
+ * RTREC_ERR_INVALID_ARG, as are NULL required arrays (d_gram, d_out, d_status; d_r_ptr with n_rows > 0; d_r_idx and d_r_val with
+ * nnz > 0; d_v with n_v > 0).  n_jobs == 0: RTREC_OK before any pointer check.  No global state, no environment variable, no
+ * allocation, no synchronisation.  The results never depend on the grid or on scheduling: a job is one sequential chain
+ * computed by one wave.
+ * csrc/factor_als.hip, factor_als_solve_kernel: one wave per job; the build is one chain of v_mfma_f32_32x32x2_f32 per 32 x 32
+ * tile with the accumulator initialised from G (A operand fl(w * y[a]), B operand y[b], k over the entries, two per
+ * instruction; one tile for dim <= 32, the three lower ones for dim <= 64), which is that fmaf chain bit for bit; zero
+ * operands stand where the chain has no term; rhs is a VALU chain; the accumulators go to LDS as A and Cholesky and both
+ * substitutions run with lane = row.  No atomics.
+ * ------------------------------------------------------------------------------------- */
+int rtrec_factor_als_solve(int32_t n_jobs, const int32_t *d_job_rows, int32_t n_rows, const int32_t *d_r_ptr, const int32_t *d_r_idx,
+                           const float *d_r_val, int64_t nnz, const float *d_v, int64_t v_stride, int32_t n_v, int32_t dim,
+                           const float *d_gram, float alpha, float *d_out, int64_t out_stride, uint8_t *d_status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,8 @@ EXT_EXPORTS = [
     "rtrec_factor_norms",
     "rtrec_factor_similar_topk",
     "rtrec_similar_blend",
+    "rtrec_factor_gram",
+    "rtrec_factor_als_solve",
 ]
 
 
@@ -246,6 +248,11 @@ def load() -> C.CDLL:
     L.rtrec_similar_blend.restype = C.c_int
     L.rtrec_similar_blend.argtypes = [i32, i32, vp, C.c_int64, vp, C.c_int64, vp, i32, vp, vp, C.c_int64, vp, C.c_int64, vp, i32, vp,
                                       i32, i32, vp, vp, vp, vp, vp]
+    L.rtrec_factor_gram.restype = C.c_int
+    L.rtrec_factor_gram.argtypes = [i32, vp, C.c_int64, i32, C.c_float, vp, vp, C.c_size_t, vp]
+    L.rtrec_factor_als_solve.restype = C.c_int
+    L.rtrec_factor_als_solve.argtypes = [i32, vp, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, i32, i32, vp, C.c_float, vp, C.c_int64,
+                                         vp, vp]
     _lib = L
     return L
 

@@ -371,6 +371,23 @@ class HipBackend:
         self.ops.similar_blend(int(n_items), a_ids, a_scores, a_counts, int(ka), a_div, b_ids, b_scores, b_counts, int(kb), exclude,
                                int(keep), int(waves_per_row), out_ids, value, source, count)
 
+    GRAM_CHUNK = 1024        # rows of V per partial Gram: the contract constant of rtrec_factor_gram
+
+    def factor_gram(self, v, n_v, dim, reg, gram):
+        """gram[dim, dim] = V^T V + reg I of the row-major vectors `v` [>= n_v, >= dim]: fmaf chains per chunk of 1024 rows, the
+        partials added in ascending order (csrc/factor_gram.hip; include/rtrec_amd_ext.h).  The partials live in a tensor of
+        RTREC_FACTOR_GRAM_WORKSPACE_BYTES(n_v, dim) bytes."""
+        chunks = (int(n_v) + self.GRAM_CHUNK - 1) // self.GRAM_CHUNK
+        ws = self.empty((chunks * int(dim) * int(dim) * 4,), self.torch.uint8) if chunks else None
+        self.ops.factor_gram(v, int(n_v), int(dim), float(reg), gram, ws)
+
+    def factor_als_solve(self, job_rows, n_jobs, r_csr, v, n_v, dim, gram, alpha, out, status):
+        """Per job: row job_rows[r] (None: row r) of R = `r_csr` (ptr, idx, val) solved against the fixed side `v` and its
+        `gram`: the pinned build, Cholesky and substitutions of rtrec_factor_als_solve, the vector written in place into `out`
+        [>= n_rows, >= dim], one uint8 `status` per job (csrc/factor_als.hip; include/rtrec_amd_ext.h)."""
+        self.ops.factor_als_solve(job_rows, int(n_jobs), r_csr[0], r_csr[1], r_csr[2], v, int(n_v), int(dim), gram, float(alpha),
+                                  out, status)
+
     def audience_workspace_bytes(self, n_users, n_q, top_n):
         return int(self.lib.rtrec_slim_audience_workspace_bytes(n_users, n_q, top_n))
 

@@ -60,6 +60,8 @@ struct Abi {
     decltype(&rtrec_factor_norms) factor_norms = nullptr;
     decltype(&rtrec_factor_similar_topk) factor_similar_topk = nullptr;
     decltype(&rtrec_similar_blend) similar_blend = nullptr;
+    decltype(&rtrec_factor_gram) factor_gram = nullptr;
+    decltype(&rtrec_factor_als_solve) factor_als_solve = nullptr;
 };
 Abi g_abi;
 
@@ -807,6 +809,51 @@ void similar_blend(int64_t n_items, const at::Tensor &a_ids, const at::Tensor &a
           "rtrec_similar_blend");
 }
 
+// v [>= n_v, v_stride >= dim] float32 row-major: the fixed side of a half-step; gram [dim, dim]; workspace: the partials,
+// RTREC_FACTOR_GRAM_WORKSPACE_BYTES(n_v, dim) bytes, absent only with n_v == 0 (include/rtrec_amd_ext.h, "FACTOR GRAM").
+void factor_gram(const at::Tensor &v, int64_t n_v, int64_t dim, double reg, at::Tensor gram, const OT &workspace) {
+    TORCH_CHECK(dim >= 1 && dim <= 64, "factor_gram: dim must lie in 1..64, got ", dim);
+    TORCH_CHECK(n_v >= 0 && n_v <= INT32_MAX, "factor_gram: n_v must lie in 0..2^31-1");
+    TORCH_CHECK(v.dim() == 2 && v.size(0) >= n_v && v.size(1) >= dim, "factor_gram: v must be [>= n_v, >= dim]");
+    TORCH_CHECK(reg >= 0.0, "factor_gram: reg must be a number >= 0, got ", reg);
+    TORCH_CHECK(gram.numel() == dim * dim, "factor_gram: gram must be [dim, dim]");
+    const size_t need = RTREC_FACTOR_GRAM_WORKSPACE_BYTES(n_v, dim);
+    const size_t ws_bytes = has(workspace) ? static_cast<size_t>(workspace->numel()) * workspace->element_size() : 0;
+    TORCH_CHECK(ws_bytes >= need, "factor_gram: the workspace holds ", ws_bytes, " bytes, RTREC_FACTOR_GRAM_WORKSPACE_BYTES(n_v, dim) = ", need);
+    one_device("factor_gram", gram, {&v}, {&workspace});
+    check(abi().factor_gram(static_cast<int32_t>(n_v), cptr<const float>(v), v.size(1), static_cast<int32_t>(dim), static_cast<float>(reg),
+                            cptr<float>(gram), cptr<void>(workspace), ws_bytes, stream_of(gram)),
+          "rtrec_factor_gram");
+}
+
+// r_ptr [n_rows + 1] / r_idx [nnz] / r_val [nnz]: R as a CSR (int32 / int32 / float32); v [>= n_v, v_stride >= dim] the fixed side
+// and gram [dim, dim] its rtrec_factor_gram; job_rows [n_jobs] names the row of a job (absent = row r); out [>= n_rows, out_stride >=
+// dim] float32 is written in place, status [n_jobs] uint8 (include/rtrec_amd_ext.h, "FACTOR ALS SOLVE").
+void factor_als_solve(const OT &job_rows, int64_t n_jobs, const at::Tensor &r_ptr, const at::Tensor &r_idx, const at::Tensor &r_val,
+                      const at::Tensor &v, int64_t n_v, int64_t dim, const at::Tensor &gram, double alpha, at::Tensor out,
+                      at::Tensor status) {
+    TORCH_CHECK(dim >= 1 && dim <= 64, "factor_als_solve: dim must lie in 1..64, got ", dim);
+    TORCH_CHECK(n_jobs >= 0 && n_jobs <= INT32_MAX && n_v >= 0 && n_v <= INT32_MAX, "factor_als_solve: n_jobs and n_v must lie in 0..2^31-1");
+    TORCH_CHECK(r_ptr.numel() >= 1 && r_ptr.numel() - 1 <= INT32_MAX, "factor_als_solve: r_ptr must hold n_rows + 1 offsets");
+    const int64_t n_rows = r_ptr.numel() - 1;
+    TORCH_CHECK(r_val.numel() == r_idx.numel(), "factor_als_solve: r_val must hold one value per entry of r_idx");
+    TORCH_CHECK(v.dim() == 2 && v.size(0) >= n_v && v.size(1) >= dim, "factor_als_solve: v must be [>= n_v, >= dim]");
+    TORCH_CHECK(gram.numel() == dim * dim, "factor_als_solve: gram must be [dim, dim]");
+    TORCH_CHECK(alpha > 0.0, "factor_als_solve: alpha must be a number > 0, got ", alpha);
+    TORCH_CHECK(out.dim() == 2 && out.size(0) >= n_rows && out.size(1) >= dim, "factor_als_solve: out must be [>= n_rows, >= dim]");
+    TORCH_CHECK(!has(job_rows) || job_rows->numel() == n_jobs, "factor_als_solve: job_rows must hold one entry per job");
+    TORCH_CHECK(has(job_rows) || n_jobs <= n_rows, "factor_als_solve: without job_rows there is at most one job per row");
+    TORCH_CHECK(status.numel() >= n_jobs && (status.scalar_type() == at::kByte || status.scalar_type() == at::kBool),
+                "factor_als_solve: status must hold one uint8 / bool entry per job");
+    one_device("factor_als_solve", out, {&r_ptr, &r_idx, &r_val, &v, &gram, &status}, {&job_rows});
+    check(abi().factor_als_solve(static_cast<int32_t>(n_jobs), cptr<const int32_t>(job_rows), static_cast<int32_t>(n_rows),
+                                 cptr<const int32_t>(r_ptr), cptr<const int32_t>(r_idx), cptr<const float>(r_val), r_idx.numel(),
+                                 cptr<const float>(v), v.size(1), static_cast<int32_t>(n_v), static_cast<int32_t>(dim),
+                                 cptr<const float>(gram), static_cast<float>(alpha), cptr<float>(out), out.size(1),
+                                 static_cast<uint8_t *>(cptr<void>(status)), stream_of(out)),
+          "rtrec_factor_als_solve");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -848,6 +895,8 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.factor_norms, "rtrec_factor_norms");
         bind_one(h, a.factor_similar_topk, "rtrec_factor_similar_topk");
         bind_one(h, a.similar_blend, "rtrec_similar_blend");
+        bind_one(h, a.factor_gram, "rtrec_factor_gram");
+        bind_one(h, a.factor_als_solve, "rtrec_factor_als_solve");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -935,6 +984,9 @@ TORCH_LIBRARY(rtrec_amd, m) {
     m.def("similar_blend(int n_items, Tensor a_ids, Tensor a_scores, Tensor a_counts, int ka, Tensor? a_div, Tensor b_ids, "
           "Tensor b_scores, Tensor b_counts, int kb, Tensor? exclude, int keep, int waves_per_row, Tensor(a!) ids, Tensor(b!) value, "
           "Tensor(c!) source, Tensor(d!) count) -> ()");
+    m.def("factor_gram(Tensor v, int n_v, int dim, float reg, Tensor(a!) gram, Tensor(b!)? workspace) -> ()");
+    m.def("factor_als_solve(Tensor? job_rows, int n_jobs, Tensor r_ptr, Tensor r_idx, Tensor r_val, Tensor v, int n_v, int dim, "
+          "Tensor gram, float alpha, Tensor(a!) out, Tensor(b!) status) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -969,4 +1021,6 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("factor_norms", &factor_norms);
     m.impl("factor_similar_topk", &factor_similar_topk);
     m.impl("similar_blend", &similar_blend);
+    m.impl("factor_gram", &factor_gram);
+    m.impl("factor_als_solve", &factor_als_solve);
 }

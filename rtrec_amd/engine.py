@@ -2059,6 +2059,7 @@ class SlimEngine:
 
     def clear_factors(self) -> None:
         self._F = {}
+        self._als = None
 
     def has_factors(self) -> bool:
         return bool(getattr(self, "_F", None))
@@ -2183,6 +2184,147 @@ class SlimEngine:
         out = self.factor_topk_device(d_rows, len(rows), top_k, filter_interacted, d_mask, item_splits, vectors=vectors,
                                       vector_has=vector_has)
         return tuple(t.cpu().numpy() for t in out)
+
+    # ------------------------------------------------------------------------------ training the factor scorer (implicit ALS)
+    ALS_MAX_DIM = 64            # dim limit of rtrec_factor_gram / rtrec_factor_als_solve
+
+    def _als_check(self, what: str) -> None:
+        if not self._X:
+            raise RuntimeError(f"set_interactions() must be called before {what}")
+        if self.world_size > 1:
+            raise ValueError(f"{what} trains on one rank: with several ranks train on one and bring the vectors with set_factors()")
+        if self._W and getattr(self._W["dw"], "shard", None) is not None:
+            raise ValueError(f"{what} needs the whole catalogue on this rank, and W is column-sharded (shard_w)")
+        if not self.has_csc():
+            raise RuntimeError(f"{what} reads both orientations of X: set_interactions(need_csc=True)")
+
+    def _als_side(self, side: str):
+        """(R as (ptr, idx, val), its number of rows, the matrix the side's half-step writes, the fixed one) of the training state."""
+        if side not in ("user", "item"):
+            raise ValueError(f"side must be 'user' or 'item', got {side!r}")
+        X, T = self._X, self._als
+        if side == "user":
+            return (X["rptr"], X["rcol"], X["rval"]), self.n_users, T["P"], T["Q"]
+        return (X["cptr"], X["crow"], X["cval"]), self.n_items, T["Q"], T["P"]
+
+    def _als_order(self, side: str, ptr):
+        """Every row of the side as an int32 job list, the longest row first (a row is one sequential chain on one wave: the
+        long ones start first, as the scoring kernels do with d_row_order).  Kept beside X; the answer never depends on it."""
+        torch = self.be.torch
+        key = f"als_order_{side}"
+        if key not in self._X:
+            lens = (ptr[1:] - ptr[:-1]).to(torch.int64)
+            self._X[key] = torch.argsort(lens, descending=True, stable=True).to(torch.int32)
+        return self._X[key]
+
+    def als_begin(self, dim: int, regularization: float, alpha: float, item_vectors, user_vectors=None, user_status=None,
+                  item_status=None) -> None:
+        """Open the training state: two row-major device matrices P [n_users, dim] and Q [rows of item_vectors, dim] (float32
+        numbers), the regulariser and the confidence slope of the half-steps to come, and one status per row (1 = no vector
+        yet).  fit_factors opens it with seeded item vectors alone; a caller that resumes from finished vectors brings both
+        sides and their status."""
+        be, torch = self.be, self.be.torch
+        self._als_check("als_begin")
+        dim = int(dim)
+        if not 1 <= dim <= self.ALS_MAX_DIM:
+            raise ValueError(f"factor vectors of 1..{self.ALS_MAX_DIM} components can be trained, got {dim}")
+        reg, alpha = float(regularization), float(alpha)
+        if not reg >= 0.0 or not alpha > 0.0:
+            raise ValueError(f"regularization must be >= 0 and alpha > 0, got {regularization} and {alpha}")
+        Q = self._as_float32(item_vectors, "item_vectors")
+        if Q.ndim != 2 or Q.shape[1] != dim or Q.shape[0] > self.n_items:
+            raise ValueError(f"item_vectors must be [<= {self.n_items} items, {dim}], got {Q.shape}")
+        P = np.zeros((self.n_users, dim), np.float32)
+        su = np.ones(self.n_users, np.uint8)
+        if user_vectors is not None:
+            Pu = self._as_float32(user_vectors, "user_vectors")
+            if Pu.ndim != 2 or Pu.shape[1] != dim or Pu.shape[0] > self.n_users:
+                raise ValueError(f"user_vectors must be [<= {self.n_users} rows of X, {dim}], got {Pu.shape}")
+            P[:len(Pu)] = Pu
+            su[:len(Pu)] = 0 if user_status is None else np.asarray(user_status, np.uint8)
+        si = np.zeros(len(Q), np.uint8) if item_status is None else np.asarray(item_status, np.uint8)
+        if si.shape != (len(Q),):
+            raise ValueError(f"item_status must hold one entry per item vector ({len(Q)}), got {si.shape}")
+        self._als = {"P": be.to_dev(P), "Q": be.to_dev(Q), "dim": dim, "reg": reg, "alpha": alpha,
+                     "status": {"user": be.to_dev(su), "item": be.to_dev(si)}}
+
+    def als_half_step(self, side: str, rows: Optional[Sequence[int]] = None) -> Dict[int, int]:
+        """One half-step of the open training state: the Gram matrix of the FIXED side (csrc/factor_gram.hip), then the solve
+        of every row of `side` ("user": rows of X against the item vectors; "item": columns of X against the user vectors) or
+        of the distinct rows named, written in place (csrc/factor_als.hip; the comments of rtrec_factor_gram and
+        rtrec_factor_als_solve in include/rtrec_amd_ext.h are the contract).  Returns how many jobs ended with status 0
+        (solved), 1 (a row outside the side, or without a usable entry: its vector is zero) and 2 (breakdown: zero too)."""
+        be, torch = self.be, self.be.torch
+        self._als_check("als_half_step")
+        T = getattr(self, "_als", None)
+        if not T:
+            raise RuntimeError("als_begin() or fit_factors() must be called before als_half_step")
+        csr, n_rows, out, fixed = self._als_side(side)
+        n_rows = min(n_rows, int(out.shape[0]))            # (an item X has gained since the vectors were made has none yet)
+        dim = T["dim"]
+        gram = be.empty((dim, dim), torch.float32)
+        be.factor_gram(fixed, int(fixed.shape[0]), dim, T["reg"], gram)
+        if rows is None:
+            jobs = self._als_order(side, csr[0])
+            if int(jobs.numel()) != n_rows:
+                jobs = jobs[jobs < n_rows]
+        else:
+            r = np.unique(np.asarray(rows, dtype=np.int64).reshape(-1))
+            jobs = be.to_dev(r[(r >= 0) & (r < n_rows)].astype(np.int32))
+        n_jobs = int(jobs.numel())
+        status = be.zeros((n_jobs,), torch.uint8)
+        if n_jobs:
+            ptr = csr[0][:n_rows + 1].contiguous()
+            be.factor_als_solve(jobs, n_jobs, (ptr, csr[1], csr[2]), fixed, int(fixed.shape[0]), dim, gram, T["alpha"], out, status)
+            T["status"][side][jobs.to(torch.int64)] = status
+        counts = torch.bincount(status.to(torch.int64), minlength=3).cpu().numpy()
+        return {s: int(counts[s]) for s in range(3)}
+
+    def als_install(self) -> None:
+        """Make the training state the resident factor model, exactly as set_factors() leaves one: P row-major, Q transposed on
+        the device to component-major, user_index = -1 and item_mask = 0 where the last status is not 0, the item norms taken.
+        Nothing visits the host."""
+        be, torch = self.be, self.be.torch
+        T = getattr(self, "_als", None)
+        if not T:
+            raise RuntimeError("als_begin() or fit_factors() must be called before als_install")
+        n_items = int(self._W["n_items"]) if self._W else self.n_items
+        Q, si = T["Q"], T["status"]["item"]
+        if int(Q.shape[0]) != n_items:                      # the catalogue W covers and the trained items differ: cut or pad
+            Qn = be.zeros((n_items, T["dim"]), torch.float32)
+            sn = torch.ones((n_items,), dtype=torch.uint8, device=Q.device)
+            k = min(n_items, int(Q.shape[0]))
+            Qn[:k], sn[:k] = Q[:k], si[:k]
+            Q, si = Qn, sn
+        rows = torch.arange(self.n_users, dtype=torch.int32, device=Q.device)
+        index = torch.where(T["status"]["user"] == 0, rows, torch.full_like(rows, -1))
+        self._F = {"p": T["P"], "qt": Q.t().contiguous(), "index": index, "mask": (si == 0).to(torch.uint8), "dim": T["dim"],
+                   "n_p": self.n_users, "n_items": n_items}
+        self._take_item_norms(0)
+
+    def fit_factors(self, dim: int = 32, iterations: int = 15, regularization: float = 0.01, alpha: float = 1.0,
+                    seed: int = 0) -> Dict[str, Dict[int, int]]:
+        """Train the factor scorer on the resident X by implicit-feedback ALS (Hu, Koren, Volinsky): `iterations` times a user
+        half-step, then an item half-step.  Only the item matrix is initialised -- np.random.default_rng(seed)
+        .standard_normal((n_items, dim)).astype(float32) * float32(0.01), made on the host and uploaded once -- and the result
+        is installed as set_factors() would (als_install).  Deterministic: every operation of a half-step is pinned
+        (include/rtrec_amd_ext.h).  Returns the status counts of the last half-step of each side."""
+        if int(iterations) < 1:
+            raise ValueError(f"iterations must be at least 1, got {iterations}")
+        self._als_check("fit_factors")
+        Q0 = np.random.default_rng(seed).standard_normal((self.n_items, int(dim))).astype(np.float32) * np.float32(0.01)
+        self.als_begin(dim, regularization, alpha, Q0)
+        counts = {}
+        for _ in range(int(iterations)):
+            counts["user"] = self.als_half_step("user")
+            counts["item"] = self.als_half_step("item")
+        self.als_install()
+        return counts
+
+    def als_vectors(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The training state on the host: (P, user status, Q, item status)."""
+        T = self._als
+        return (T["P"].cpu().numpy(), T["status"]["user"].cpu().numpy(), T["Q"].cpu().numpy(), T["status"]["item"].cpu().numpy())
 
     # ------------------------------------------------------------------------------ similar items from the factor vectors
     SIMILAR_BLEND_MAX_LIST = 1024       # ka / kb limit of rtrec_similar_blend

@@ -26,6 +26,7 @@ class SLIM(BaseModel):
         self._dev_x: Optional[DeviceInteractions] = None        # X resident in HBM (utils/device_store.py)
         self._factors: Optional[Dict[str, np.ndarray]] = None   # vectors of a factor model the caller attached (attach_factors)
         self._factors_on_device: Any = None                     # (what the engine's resident copy was built for, has-vector mask)
+        self._factor_training: Optional[Dict[str, float]] = None   # regularization / alpha of the last fit_factors (not pickled)
 
     # ------------------------------------------------------------ device-resident X
     def _store_tag(self) -> Any:
@@ -1141,6 +1142,75 @@ class SLIM(BaseModel):
         self._factors = {"user_rows": uid[uid >= 0], "user_vectors": np.ascontiguousarray(P[uid >= 0]),
                          "item_rows": iid[iid >= 0], "item_vectors": np.ascontiguousarray(Q[iid >= 0])}
         self._factors_on_device = None
+        return self
+
+    FACTOR_TRAIN_MAX_DIM = 64   # dim limit of rtrec_factor_als_solve
+
+    def _take_trained_factors(self, eng: Any) -> None:
+        """The engine's training state as the vectors attach_factors() would have kept: one row per user / item whose last
+        solve ended with status 0, in ascending internal id."""
+        P, su, Q, si = eng.als_vectors()
+        urows, irows = np.flatnonzero(su == 0).astype(np.int64), np.flatnonzero(si == 0).astype(np.int64)
+        self._factors = {"user_rows": urows, "user_vectors": np.ascontiguousarray(P[urows]),
+                         "item_rows": irows, "item_vectors": np.ascontiguousarray(Q[irows])}
+        eng.als_install()
+        n_users, n_items = eng.n_users, self.model.n_items_fitted
+        if eng.has_factors() and eng._F["n_items"] == n_items:      # what _sync_factors would upload is resident already
+            self._factors_on_device = ((id(self._factors), n_users, n_items, id(eng)), su == 0)
+        else:
+            self._factors_on_device = None
+
+    def fit_factors(self, dim: int = 32, iterations: int = 15, regularization: float = 0.01, alpha: float = 1.0,
+                    seed: int = 0) -> "SLIM":
+        """Train the second scorer of the hybrid on the device, from the interactions this model holds: implicit-feedback
+        alternating least squares (Hu, Koren, Volinsky) with confidence 1 + alpha * r over the stored, positive interactions,
+        `iterations` times a user half-step and an item half-step, deterministic for a `seed` (SlimEngine.fit_factors; the
+        pinned arithmetic is the contract of rtrec_factor_gram / rtrec_factor_als_solve in include/rtrec_amd_ext.h).  The
+        reference's hybrid trains LightFM there; this is ALS and learns one vector per user and item -- tags still need
+        attach_feature_factors().  Leaves the model as attach_factors(users, P, items, Q) with the trained vectors would: a
+        user or item without a positive interaction has no vector.  Returns self."""
+        if not 1 <= int(dim) <= self.FACTOR_TRAIN_MAX_DIM:
+            raise ValueError(f"fit_factors trains vectors of 1..{self.FACTOR_TRAIN_MAX_DIM} components, got {dim}")
+        if int(iterations) < 1 or not float(regularization) >= 0.0 or not float(alpha) > 0.0:
+            raise ValueError(f"fit_factors needs iterations >= 1, regularization >= 0 and alpha > 0, got {iterations}, "
+                             f"{regularization} and {alpha}")
+        self._sync_interactions_csc()
+        eng = self.model.engine
+        eng.fit_factors(dim=int(dim), iterations=int(iterations), regularization=float(regularization), alpha=float(alpha), seed=seed)
+        self._factor_training = {"regularization": float(regularization), "alpha": float(alpha)}
+        self._take_trained_factors(eng)
+        return self
+
+    def update_factors(self, users: Iterable[Any]) -> "SLIM":
+        """The online counterpart of fit_factors, to be called after fit / partial_fit of new interactions: the rows of the named
+        users are solved again against the current item vectors (one Gram matrix, one solve over a job list), with the
+        regularization and alpha of the last fit_factors (its defaults after attach_factors or a pickle).  A user X knows
+        and the vectors do not yet gets one; users the model does not know are ignored; item vectors are not touched (an
+        item without one is skipped in every row).  RuntimeError without fitted or attached vectors."""
+        if self._factors is None:
+            raise RuntimeError("fit_factors() or attach_factors() must be called before update_factors.")
+        if self.has_feature_factors():
+            raise ValueError("update_factors solves one vector per user; attach_feature_factors() brought per-feature tables")
+        F = self._factors
+        dim = int(F["user_vectors"].shape[1])
+        if dim > self.FACTOR_TRAIN_MAX_DIM:
+            raise ValueError(f"update_factors solves vectors of 1..{self.FACTOR_TRAIN_MAX_DIM} components, the attached ones have {dim}")
+        self._sync_interactions_csc()
+        eng = self.model.engine
+        n_users, n_items = eng.n_users, eng.n_items
+        rows = self._ids_or_minus_one(list(users), self._known_user_id, n_users)
+        rows = np.unique(rows[rows >= 0])
+        P, su = np.zeros((n_users, dim), np.float32), np.ones(n_users, np.uint8)
+        ok = F["user_rows"] < n_users
+        P[F["user_rows"][ok]], su[F["user_rows"][ok]] = F["user_vectors"][ok], 0
+        Q, si = np.zeros((n_items, dim), np.float32), np.ones(n_items, np.uint8)
+        ok = F["item_rows"] < n_items
+        Q[F["item_rows"][ok]], si[F["item_rows"][ok]] = F["item_vectors"][ok], 0
+        par = getattr(self, "_factor_training", None) or {"regularization": 0.01, "alpha": 1.0}
+        eng.als_begin(dim, par["regularization"], par["alpha"], Q, user_vectors=P, user_status=su, item_status=si)
+        if len(rows):
+            eng.als_half_step("user", rows)
+        self._take_trained_factors(eng)
         return self
 
     def attach_feature_factors(self, users: Iterable[Any], user_tags: Iterable[Any], user_table: Any, items: Iterable[Any],

@@ -188,6 +188,17 @@ class Recommender:
                                           item_bias=item_bias)
         return self
 
+    def fit_factors(self, dim: int = 32, iterations: int = 15, regularization: float = 0.01, alpha: float = 1.0,
+                    seed: int = 0) -> "Recommender":
+        """Train the second scorer of recommend_hybrid on the device by implicit ALS (SLIM.fit_factors)."""
+        self.model.fit_factors(dim=dim, iterations=iterations, regularization=regularization, alpha=alpha, seed=seed)
+        return self
+
+    def update_factors(self, users: List[Any]) -> "Recommender":
+        """Solve the named users' vectors again after new interactions (SLIM.update_factors)."""
+        self.model.update_factors(users)
+        return self
+
     def detach_factors(self) -> "Recommender":
         self.model.detach_factors()
         return self

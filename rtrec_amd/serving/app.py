@@ -40,6 +40,9 @@ the GPU), POST /recommend (one user's top-k).  Differences, all forced by the de
     "score": ...}, ...]} (SLIM.similar_items_hybrid; a model without attached vectors is the shell's 500, and so is "item_tags"
     on a model without the tables of attach_feature_factors); same token check as /rerank, answered under the model lock, not
     coalesced;
+  * POST /fit_factors is an addition beside /fit (train the served model's second scorer on the device by implicit ALS, from
+    the interactions it holds): {"dim", "iterations", "regularization", "alpha", "seed"}, all optional -> {"message": "Factor
+    training successful"} (SLIM.fit_factors); same token check as /fit, answered under the model lock;
   * concurrent POST /recommend calls are coalesced (`RecommendCoalescer`): requests that arrive within a bounded
     wait (RTREC_AMD_COALESCE_MS, default 1 ms; 0 = only what queued up behind the model lock) share ONE
     recommend_batch launch per (top_k, filter_interacted) group; each caller gets exactly what its own
@@ -139,6 +142,14 @@ class HybridRequest(BaseModel):
     mnz: bool = False
     filter_interacted: bool = True
     user_tags: Optional[List[str]] = None
+
+
+class FitFactorsRequest(BaseModel):
+    dim: int = 32
+    iterations: int = 15
+    regularization: float = 0.01
+    alpha: float = 1.0
+    seed: int = 0
 
 
 class SimilarHybridRequest(BaseModel):
@@ -331,6 +342,14 @@ def build_router(gate: ModelGate) -> APIRouter:
         batch = [(row.user, row.item, row.timestamp, row.rating) for row in interactions]
         gate.call("Training", lambda m: m.fit(batch, progress_bar=False))
         return {"message": "Training successful"}
+
+    @api.post("/fit_factors")
+    def fit_factors(request: FitFactorsRequest, x_token: str = Header()):
+        _authorise(x_token)
+        gate.call("Factor training", lambda m: m.fit_factors(dim=request.dim, iterations=request.iterations,
+                                                             regularization=request.regularization, alpha=request.alpha,
+                                                             seed=request.seed))
+        return {"message": "Factor training successful"}
 
     @api.post("/recommend", response_model=RecommendationResponse)
     def recommend(request: RecommendationRequest, x_token: str = Header()):
