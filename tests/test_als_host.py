@@ -11,6 +11,7 @@ CSR R; an entry (i, val) is usable when 0 <= i < n_v and w = fl(alpha * val) > 0
 over the usable entries in storage order (lower triangle), rhs = fmaf(fl(1 + w), y_i[a], rhs[a]); a left-looking Cholesky whose
 every element is one fmaf chain over ascending k, a forward and a backward substitution, one division per component."""
 import ctypes
+import functools
 import io
 import os
 
@@ -142,6 +143,7 @@ def solve_plain(ptr, idx, val, V, G, alpha, out, job_rows=None):
 
 
 VARIANTS = ("unfused", "reverse", "right_looking", "float64", "w_other")
+TINY = F32(2.0 ** -126)                          # the smallest normal float32
 
 
 def solve_fast(ptr, idx, val, V, G, alpha, out, job_rows=None, variant=None):
@@ -151,8 +153,15 @@ def solve_fast(ptr, idx, val, V, G, alpha, out, job_rows=None, variant=None):
     entries last first; "right_looking" is the textbook outer-product Cholesky in float32 (A -= l l^T, a rounded product and a
     rounded difference: with fused updates the right-looking order gives the very chains of the left-looking one, element by
     element); "float64" builds A and rhs in a float64 accumulator and rounds once; "w_other" scales the other operand,
-    fmaf(y[a], fl(w * y[b]), A)."""
-    assert variant is None or variant in VARIANTS
+    fmaf(y[a], fl(w * y[b]), A).  "flush" (not one of VARIANTS: ordinary inputs do not show it, test_the_tiny_case_...) is a
+    kernel in flush-to-zero mode: denormal operands and results of the build and the factorisation become zero, and an entry
+    whose w flushes is not usable."""
+    assert variant is None or variant in VARIANTS or variant == "flush"
+    flush = variant == "flush"
+
+    def z(a):
+        return np.where(np.abs(a) < TINY, F32(0.0), a).astype(F32) if flush else a
+
     V, G = np.asarray(V, F32), np.asarray(G, F32)
     n_v, dim = V.shape
     n_rows = len(ptr) - 1
@@ -164,6 +173,8 @@ def solve_fast(ptr, idx, val, V, G, alpha, out, job_rows=None, variant=None):
             status[r] = 1
             continue
         cols, ws = _row_entries(ptr, idx, val, x, n_v, alpha)
+        if flush:
+            cols, ws = cols[ws >= TINY], ws[ws >= TINY]
         if not len(cols):
             status[r] = 1
             out[x, :dim] = 0
@@ -180,12 +191,12 @@ def solve_fast(ptr, idx, val, V, G, alpha, out, job_rows=None, variant=None):
         cols[a, :lens[a]], ws[a, :lens[a]] = entries[r]
     wide = variant == "float64"
     with np.errstate(all="ignore"):
-        A = np.broadcast_to(G, (J, dim, dim)).astype(np.float64 if wide else F32)
+        A = np.broadcast_to(z(G), (J, dim, dim)).astype(np.float64 if wide else F32)
         rhs = np.zeros((J, dim), np.float64 if wide else F32)
         for t in range(longest):
             n = int((lens > t).sum())
-            y, w = V[cols[:n, t]], ws[:n, t]
-            wy = w[:, None] * y
+            y, w = z(V[cols[:n, t]]), ws[:n, t]
+            wy = z(w[:, None] * y)
             c = (F32(1.0) + w)[:, None]
             if wide:
                 A[:n] += wy.astype(np.float64)[:, :, None] * y.astype(np.float64)[:, None, :]
@@ -197,8 +208,8 @@ def solve_fast(ptr, idx, val, V, G, alpha, out, job_rows=None, variant=None):
                 A[:n] = fma32(y[:, :, None], wy[:, None, :], A[:n])
                 rhs[:n] = fma32(c, y, rhs[:n])
             else:
-                A[:n] = fma32(wy[:, :, None], y[:, None, :], A[:n])
-                rhs[:n] = fma32(c, y, rhs[:n])
+                A[:n] = z(fma32(wy[:, :, None], y[:, None, :], A[:n]))
+                rhs[:n] = z(fma32(c, y, rhs[:n]))
         A, rhs = A.astype(F32), rhs.astype(F32)
         L = np.zeros((J, dim, dim), F32)
         broken = np.zeros(J, bool)
@@ -206,12 +217,12 @@ def solve_fast(ptr, idx, val, V, G, alpha, out, job_rows=None, variant=None):
             s = A[:, j:, j].copy()
             if variant != "right_looking":
                 for k in range(j):
-                    s = fma32(-L[:, j:, k], L[:, j, k][:, None], s)
+                    s = z(fma32(-L[:, j:, k], L[:, j, k][:, None], s))
             d = s[:, 0]
             broken |= ~((d > 0) & np.isfinite(d))
-            root = np.sqrt(d)
+            root = z(np.sqrt(d))
             L[:, j, j] = root
-            L[:, j + 1:, j] = s[:, 1:] / root[:, None]
+            L[:, j + 1:, j] = z(s[:, 1:] / root[:, None])
             if variant == "right_looking":
                 l = L[:, j + 1:, j]
                 A[:, j + 1:, j + 1:] = A[:, j + 1:, j + 1:] - l[:, :, None] * l[:, None, :]
@@ -305,6 +316,167 @@ def als_loss(X, P, Q, reg, alpha):
     return float((c * ((Xd > 0) - P @ Q.T) ** 2).sum() + reg * ((P ** 2).sum() + (Q ** 2).sum()))
 
 
+# ---------------------------------------------------------------------------------------------- adversarial inputs
+BREAK_LENGTHS = (0, 1, 2, 3, 63, 64, 65, 130)
+BLOCK_SEED = {1: 3, 5: 0}          # als_block_case's seed per dim where seed = dim lets a reversed two-entry row keep its bits
+# the rows of als_block_case: runs of ("s"kipped | "u"sable, how many) in storage order.  The kernel reads a row 64 entries at a
+# time (a BLOCK) and feeds the matrix cores two entries per step, the even one and the odd one
+BLOCK_ROWS = ((("s", 64), ("u", 5)),                       # a first block without a usable entry, then a real one
+              (("u", 64), ("s", 64), ("u", 1)),            # an all-skipped block between two real ones; the last one holds one entry
+              (("s", 130),),                               # nothing usable in three blocks: status 1, zeros
+              (("s", 63), ("u", 1)),                       # the only usable entry in lane 63 (the odd entry of the last step)
+              (("u", 1), ("s", 63)),                       # ... in lane 0
+              (("s", 64), ("s", 64), ("u", 2)),            # two all-skipped blocks first
+              (("u", 127),), (("u", 128),), (("u", 129),),           # the second block edge
+              (("u", 191),), (("u", 192),), (("u", 193),),           # the third
+              (("u", 64), ("s", 4), ("u", 1)),             # an odd count: the last entry, alone in its step, is its block's only usable one
+              (("u", 64), ("s", 70)))                      # the row ENDS with two all-skipped blocks: what was built must stand
+BLOCK_USABLE = tuple(sum(n for k, n in row if k == "u") for row in BLOCK_ROWS)
+
+
+def skipped_entries(n, n_v, start=0):
+    """(columns, values) of n entries no job may use, the kinds of als_case in turn from `start`: value 0, a negative one and NaN
+    on the poisoned row n_v - 1 of V, column -1, columns n_v and n_v + 7."""
+    k = (start + np.arange(n)) % 6
+    return np.array([n_v - 1, n_v - 1, n_v - 1, -1, n_v, n_v + 7], np.int64)[k], np.array([0.0, -2.0, np.nan, 1.0, 2.0, 3.0], F32)[k]
+
+
+def als_block_case(n_v, dim, seed):
+    """A hand-laid CSR whose rows are BLOCK_ROWS: whole 64-entry blocks of skipped entries before, between and behind usable
+    ones, a block's only usable entry in its first, last or odd last slot, and rows that end exactly at, one before and one
+    behind the second and third block edge.  Row n_v - 1 of V is NaN and named by skipped entries only.  n_v >= 195.  Returns
+    (ptr, idx, val, V); BLOCK_USABLE has the usable entries per row."""
+    rng = np.random.default_rng(seed)
+    V = (rng.standard_normal((n_v, dim)) * 0.3).astype(F32)
+    V[n_v - 1] = np.nan
+    ptr, idx, val = [0], [], []
+    for r, row in enumerate(BLOCK_ROWS):
+        for kind, n in row:
+            if kind == "u":
+                c, v = rng.choice(n_v - 1, size=n, replace=False), rng.integers(1, 6, n).astype(F32) * F32(0.5)
+            else:
+                c, v = skipped_entries(n, n_v, start=r + len(idx))
+            idx += c.tolist()
+            val += v.tolist()
+        ptr.append(len(idx))
+    return np.array(ptr, np.int32), np.array(idx, np.int32), np.array(val, F32), V
+
+
+BREAK_KINDS = ("neg", "inf", "nan")
+BREAK_REG, BREAK_ALPHA = 0.1, 0.7
+# t of als_break_case's kind "neg" per (dim, c) where 0.5 gives no mix of solved and broken rows: chosen with the host model
+# (test_break_cases_hold_solved_and_broken_rows asserts the mix for every pair of BREAK_GRID); None = no t gives one: at dim 64,
+# c = 32 every non-empty row breaks for t = 0.5, 0.25, 0.1, 0.01, 1e-3, 1e-6 and 0, and a larger t only takes more away
+BREAK_T = {(64, 32): None}
+BREAK_GRID = tuple((dim, c) for dim in (5, 32) for c in (0, 1, dim - 1)) + \
+    tuple((dim, c) for dim in (33, 48, 64) for c in sorted({0, 1, 31, 32, 33, dim - 1}) if c < dim)
+
+
+def als_break_case(dim, c, kind, t=None, n_rows=48, lengths=BREAK_LENGTHS):
+    """The rows of als_case (48 rows of 0 .. 130 entries, seed = dim, scale 0.3) with the Gram matrix of reg BREAK_REG doctored
+    at pivot c: "neg" G[c][c] = -t (a row whose own entries add less than t and the chain's squares to the pivot breaks at
+    column c, a longer one survives; t from BREAK_T, 0.5 where it has none), "inf" G[c][c] = +inf (every row breaks at c: d is
+    not finite), "nan" a NaN in the lower-triangle element G[c][c // 2] (it reaches d at column c through L[c][c // 2], or is d
+    itself).  To be solved with BREAK_ALPHA.  Returns (ptr, idx, val, V, G)."""
+    assert kind in BREAK_KINDS and 0 <= c < dim
+    ptr, idx, val, V = als_case(n_rows, 200, dim, seed=dim, lengths=lengths, scale=0.3)
+    G = gram_fast(np.nan_to_num(V), BREAK_REG)
+    if kind == "neg":
+        t = (BREAK_T.get((dim, c)) or 0.5) if t is None else t
+        G[c, c] = -F32(t)
+    elif kind == "inf":
+        G[c, c] = np.inf
+    else:
+        G[c, c // 2] = np.nan
+    return ptr, idx, val, V, G
+
+
+def als_tiny_case(dim, g=1e-38, alpha=1e-39):
+    """Denormals in every stage of a solve: the rows of als_case (seed 3, V ~ N(0, 1)) with every usable value 1, G = g I and
+    an alpha so small that w = fl(alpha * 1), fl(w * y), the pivots of the factorisation and the quotients are float32
+    denormals, while the solved components are as large as 3e38.  g = alpha = 1e-40 at dim 1: the factorisation succeeds and
+    the component overflows, the second way to status 2.  Returns (ptr, idx, val, V, G, alpha)."""
+    ptr, idx, val, V = als_case(48, 200, dim, seed=3, lengths=BREAK_LENGTHS)
+    with np.errstate(invalid="ignore"):
+        val = np.where(val > 0, F32(1.0), val).astype(F32)
+    return ptr, idx, val, V, np.eye(dim, dtype=F32) * F32(g), alpha
+
+
+def als_rounding_case(dim, side):
+    """The CSR of als_case (48 rows of BREAK_LENGTHS over 300 columns) on the vectors of rounding_vectors (2^24-sized
+    cancelling terms, midpoint products, denormals; `side` 0 or 1: its P or its Q) as V, row 299 NaN behind skipped entries as
+    ever: an unfused or reordered build shows.  Returns (ptr, idx, val, V, G) with reg 0.1."""
+    from tests.test_factor_host import rounding_vectors
+    ptr, idx, val, _ = als_case(48, 300, dim, seed=dim, lengths=BREAK_LENGTHS)
+    V = rounding_vectors(300, 300, dim, seed=dim)[side].copy()
+    V[299] = np.nan
+    return ptr, idx, val, V, gram_fast(np.nan_to_num(V), 0.1)
+
+
+def als_inf_case(dim):
+    """als_break_case's rows with an honest G and ONE value +inf, a usable entry in the middle of row 4 (63 entries): w = inf,
+    so that row's system is not finite (status 2, zeros) and no other row notices.  Returns (ptr, idx, val, V, G, the row)."""
+    ptr, idx, val, V = als_case(48, 200, dim, seed=dim, lengths=BREAK_LENGTHS, scale=0.3)
+    with np.errstate(invalid="ignore"):
+        e = next(e for e in range(ptr[4] + 30, ptr[5]) if val[e] > 0 and 0 <= idx[e] < 199)
+    val = val.copy()
+    val[e] = np.inf
+    return ptr, idx, val, V, gram_fast(np.nan_to_num(V), BREAK_REG), 4
+
+
+STRIDE_GRID = 1 << 18                 # the workgroups of the largest launch (csrc/factor_als.hip, kAlsMaxGrid): job b + 2^18 is
+STRIDE_SECOND = 300                   # the SECOND job of workgroup b; this many jobs have one
+STRIDE_LENGTHS = (0, 1, 2, 3, 5, 65)
+OUTSIDE = 3                           # the class of a job whose row lies outside R; the other classes are the status
+# (class of workgroup b's first job, class of its second one), in turn over b: a solve after each way a job can end -- solved,
+# broken in the middle of the factorisation, no usable entry, outside R -- and each other ending after them
+STRIDE_PAIRS = ((0, 0), (2, 0), (1, 0), (OUTSIDE, 0), (0, 2), (2, 2), (1, 2), (OUTSIDE, 2), (0, 1), (2, 1), (1, 1), (OUTSIDE, 1),
+                (0, OUTSIDE), (2, OUTSIDE))
+
+
+def als_stride_case(dim, c):
+    """2^18 + 300 jobs over DISTINCT rows, more than one launch has workgroups for, so that 300 workgroups run a second job.
+    R has 2^18 + 400 rows and row x is template x % 64: the 64 rows of als_break_case(dim, c, "neg") with STRIDE_LENGTHS, whose
+    doctored G leaves solved, empty and broken templates.  By the contract a job's result depends on its row alone, so the host
+    model solves the templates once.  The job list puts the pairs of STRIDE_PAIRS on workgroups 0 .. 299 (job b, then job
+    b + 2^18), fills the other slots with the remaining rows in a shuffled order and leaves about 100 rows unnamed; three more
+    slots in the middle name -1 and n_rows.  Returns (ptr, idx, val, V, G, jobs, template status, template vectors)."""
+    tp, ti, tv, V, G = als_break_case(dim, c, "neg", n_rows=64, lengths=STRIDE_LENGTHS)
+    t_out = np.zeros((64, dim), F32)
+    t_st = solve_fast(tp, ti, tv, V, G, BREAK_ALPHA, t_out)
+    n_jobs = STRIDE_GRID + STRIDE_SECOND
+    n_rows = n_jobs + 100
+    reps = -(-n_rows // 64)
+    ptr = np.r_[0, np.cumsum(np.tile(np.diff(tp), reps)[:n_rows])]
+    idx, val = np.tile(ti, reps)[:ptr[-1]], np.tile(tv, reps)[:ptr[-1]]
+    order = np.random.default_rng(dim).permutation(n_rows)
+    pools = [iter(order[t_st[order % 64] == k].tolist()) for k in range(3)]
+    outside = iter([-1, n_rows] * STRIDE_SECOND)
+    jobs = np.full(n_jobs, -7, np.int64)
+    for b in range(STRIDE_SECOND):
+        first, second = STRIDE_PAIRS[b % len(STRIDE_PAIRS)]
+        jobs[b] = next(outside) if first == OUTSIDE else next(pools[first])
+        jobs[b + STRIDE_GRID] = next(outside) if second == OUTSIDE else next(pools[second])
+    taken = np.zeros(n_rows, bool)
+    taken[jobs[(jobs >= 0) & (jobs < n_rows)]] = True
+    rest = order[~taken[order]]
+    jobs[jobs == -7] = rest[:(jobs == -7).sum()]
+    jobs[[1000, 70001, STRIDE_GRID - 1]] = [-1, n_rows, -1]
+    return ptr.astype(np.int32), idx, val, V, G, jobs.astype(np.int32), t_st, t_out
+
+
+def stride_classes(jobs, n_rows, t_st):
+    """The class per job of als_stride_case: its status by the templates, or OUTSIDE."""
+    jobs = np.asarray(jobs, np.int64)
+    inside = (jobs >= 0) & (jobs < n_rows)
+    return np.where(inside, t_st[np.where(inside, jobs, 0) % 64], OUTSIDE)
+
+
+def counts_of(status):
+    """[how many 0, 1, 2] of a status array."""
+    return np.bincount(np.asarray(status, np.int64), minlength=3).tolist()
+
+
 # ---------------------------------------------------------------------------------------------- the two models agree
 @pytest.mark.parametrize("dim", [1, 2, 5, 33])
 def test_both_models_agree_bit_for_bit(dim):
@@ -360,6 +532,171 @@ def test_each_pinned_operation_shows_in_the_bits():
         counts[variant] = int((bits(out) != bits(base)).sum())
     print(counts)
     assert all(counts[v] > 0 for v in VARIANTS), counts
+
+
+# ---------------------------------------------------------------------------------------------- the adversarial inputs have teeth
+def _solve(case, alpha, variant=None, jobs=None, plain=False):
+    """(status, out) of the host model on (ptr, idx, val, V, G); `out` starts as 7.0."""
+    ptr, idx, val, V, G = case
+    out = np.full((len(ptr) - 1, V.shape[1]), 7.0, F32)
+    if plain:
+        return solve_plain(ptr, idx, val, V, G, alpha, out, jobs), out
+    return solve_fast(ptr, idx, val, V, G, alpha, out, jobs, variant=variant), out
+
+
+@functools.lru_cache(maxsize=None)
+def break_reference(dim, c, kind):
+    """(the case, status, out) of als_break_case by the vectorised host model, computed once per process and read-only: the
+    check here and the device test share it."""
+    case = als_break_case(dim, c, kind)
+    st, out = _solve(case, BREAK_ALPHA)
+    for a in case + (st, out):
+        a.setflags(write=False)
+    return case, st, out
+
+
+def _same(a, b):
+    return np.array_equal(a[0], b[0]) and np.array_equal(bits(a[1]), bits(b[1]))
+
+
+@pytest.mark.parametrize("dim", [1, 5, 33, 64])
+def test_block_case_has_the_rows_it_claims_and_their_order_shows(dim):
+    """als_block_case from the host model alone: status 1 and zeros for the row of 130 skipped entries and 0 for every other
+    row, and taking the entries last first changes bits in EVERY row with two or more usable entries (and in no other): a kernel
+    that drops, doubles or misorders an entry at a block edge or around an all-skipped block cannot equal the model."""
+    ptr, idx, val, V = als_block_case(260, dim, BLOCK_SEED.get(dim, dim))
+    assert np.diff(ptr).tolist() == [sum(n for _, n in row) for row in BLOCK_ROWS]
+    assert [len(_row_entries(ptr, idx, val, x, 260, 0.7)[0]) for x in range(len(BLOCK_ROWS))] == list(BLOCK_USABLE)
+    case = (ptr, idx, val, V, gram_fast(np.nan_to_num(V), 0.1))
+    base, rev = _solve(case, 0.7), _solve(case, 0.7, "reverse")
+    assert base[0].tolist() == [0 if n else 1 for n in BLOCK_USABLE] and (base[1][2] == 0).all() and np.isfinite(base[1]).all()
+    changed = (bits(base[1]) != bits(rev[1])).any(axis=1)
+    assert changed.tolist() == [n >= 2 for n in BLOCK_USABLE], changed
+    if dim <= 5:
+        assert _same(_solve(case, 0.7, plain=True), base)
+
+
+def test_break_cases_hold_solved_and_broken_rows():
+    """als_break_case over BREAK_GRID from the host model alone.  "neg": solved and broken rows side by side for every (dim, c)
+    but (64, 32) (BREAK_T: no t gives a mix there, all 42 non-empty rows break); every row of ONE entry breaks, and at least three of the six
+    at column c itself (in float64 the leading c x c block of its system is positive definite and the next one is not; a large
+    y_c carries the others past c, and they break further on).  "inf" and "nan": every
+    non-empty row breaks.  Broken rows are zero.  Measured: 25/6/17 at (5, 0), 18/6/24 at (33, 0), 23/6/19 at (33, 32), 6/6/36 at
+    (64, 1), 0/6/42 at (64, 32)."""
+    for dim, c in BREAK_GRID:
+        for kind in BREAK_KINDS:
+            case, st, out = break_reference(dim, c, kind)
+            n0, n1, n2 = counts_of(st)
+            assert n1 == 6 and (out[st != 0] == 0).all() and np.isfinite(out).all(), (dim, c, kind)
+            if kind == "neg":
+                ptr, idx, val, V, G = case
+                G64 = np.tril(G.astype(np.float64)) + np.tril(G.astype(np.float64), -1).T
+                assert c == 0 or np.linalg.eigvalsh(G64[:c, :c]).min() > 1e-3      # (and a term w y y^T only adds to it)
+                at_c = 0
+                for x in range(1, 48, 8):                # the rows of one entry (plus skipped ones)
+                    cols, ws = _row_entries(ptr, idx, val, x, 200, BREAK_ALPHA)
+                    assert len(cols) == 1 and st[x] == 2, (dim, c, x)
+                    y = V[cols[0]].astype(np.float64)
+                    A = G64[:c + 1, :c + 1] + float(ws[0]) * np.outer(y[:c + 1], y[:c + 1])
+                    at_c += bool(A[c, c] - (A[c, :c] @ np.linalg.solve(A[:c, :c], A[:c, c]) if c else 0.0) < -1e-3)
+                assert at_c >= 3, (dim, c, at_c)
+            if kind == "neg" and BREAK_T.get((dim, c), 0.5) is not None:
+                assert n0 >= 1 and n2 >= 1, (dim, c, counts_of(st))
+            else:
+                assert (n0, n2) == (0, 42), (dim, c, kind, counts_of(st))
+    # the honest G solves every non-empty row: the doctored element alone breaks them
+    ptr, idx, val, V, _ = als_break_case(33, 32, "neg")
+    assert counts_of(_solve((ptr, idx, val, V, gram_fast(np.nan_to_num(V), BREAK_REG)), BREAK_ALPHA)[0]) == [42, 6, 0]
+    for dim, c, kind, jobs in ((5, 1, "neg", None), (5, 4, "nan", None), (5, 0, "inf", None), (33, 32, "neg", [0, 1, 2, 3, 4, 9]),
+                               (33, 31, "nan", [1, 2, 3])):
+        case = als_break_case(dim, c, kind)
+        assert _same(_solve(case, BREAK_ALPHA, jobs=jobs, plain=True), _solve(case, BREAK_ALPHA, jobs=jobs)), (dim, c, kind)
+
+
+STRIDE_CASES = ((5, 1), (40, 32))     # (dim, c): one tile and the three lower ones; the pivot doctored behind the first tile
+
+
+@pytest.mark.parametrize("dim, c", STRIDE_CASES)
+def test_stride_case_puts_every_pair_on_one_workgroup(dim, c):
+    """als_stride_case from the host model alone: the templates hold all three statuses, the rows named are distinct, every
+    pair of STRIDE_PAIRS occurs as (job b, job b + 2^18), and solving the tiled R itself for those 600 jobs gives what the
+    templates expand to."""
+    ptr, idx, val, V, G, jobs, t_st, t_out = als_stride_case(dim, c)
+    n_rows, jobs = len(ptr) - 1, jobs.astype(np.int64)
+    assert len(jobs) == STRIDE_GRID + STRIDE_SECOND and min(counts_of(t_st)) >= 5, counts_of(t_st)
+    inside = jobs[(jobs >= 0) & (jobs < n_rows)]
+    assert len(np.unique(inside)) == len(inside) and 0 < len(jobs) - len(inside) < 150 and n_rows - len(inside) >= 100
+    assert 3.0e6 < len(idx) < 4.0e6 and np.array_equal(np.diff(ptr)[64:128], np.diff(ptr)[:64])
+    cls = stride_classes(jobs, n_rows, t_st)
+    second = np.arange(STRIDE_GRID, STRIDE_GRID + STRIDE_SECOND)
+    assert set(zip(cls[second - STRIDE_GRID].tolist(), cls[second].tolist())) == set(STRIDE_PAIRS)
+    sel = np.r_[second - STRIDE_GRID, second]
+    out = np.full((n_rows, dim), 7.0, F32)
+    st = solve_fast(ptr, idx, val, V, G, BREAK_ALPHA, out, jobs[sel])
+    assert np.array_equal(st, np.where(cls[sel] == OUTSIDE, 1, cls[sel]))
+    named = jobs[sel][cls[sel] != OUTSIDE]
+    assert np.array_equal(bits(out[named]), bits(t_out[named % 64])) and (np.delete(out, named, axis=0) == 7.0).all()
+
+
+def test_the_tiny_case_is_denormal_at_every_stage_and_a_flushing_kernel_shows():
+    """als_tiny_case from the host model alone: w and G's pivots are denormal, the status mix is the measured one (g = 1e-38,
+    alpha = 1e-39: 42/6/0 at dim 1 and 5, 38/6/4 at dim 40; g = alpha = 1e-40 at dim 1: 7/6/35 -- the factorisation succeeds and
+    the component overflows), the solved components reach 1e38, and the "flush" variant of solve_fast -- denormal operands and
+    results of the build and the factorisation become zero -- changes the status of all 42 non-empty rows."""
+    for dim, g, a, mix in ((1, 1e-38, 1e-39, [42, 6, 0]), (5, 1e-38, 1e-39, [42, 6, 0]), (40, 1e-38, 1e-39, [38, 6, 4]),
+                           (1, 1e-40, 1e-40, [7, 6, 35])):
+        *case, alpha = als_tiny_case(dim, g, a)
+        assert 0 < F32(alpha) * F32(1.0) < TINY and 0 < case[4][0, 0] < TINY
+        base, flushed = _solve(case, alpha), _solve(case, alpha, "flush")
+        assert counts_of(base[0]) == mix, (dim, g, counts_of(base[0]))
+        assert np.abs(base[1][base[0] == 0]).max() > 1e38
+        assert ((base[0] != flushed[0]) | (bits(base[1]) != bits(flushed[1])).any(axis=1)).sum() == 42
+        if dim <= 5:
+            assert _same(_solve(case, alpha, plain=True), base)
+    # at dim 1 the overflow is the substitution's: the only pivot d = g + sum w y^2 is positive (denormal in most rows)
+    ptr, idx, val, V, G, alpha = als_tiny_case(1, 1e-40, 1e-40)
+    st = _solve((ptr, idx, val, V, G), alpha)[0]
+    pivots = []
+    for x in np.flatnonzero(st == 2):
+        cols, ws = _row_entries(ptr, idx, val, x, 200, alpha)
+        d = G[0, 0]
+        for i, w in zip(cols, ws):
+            d = fmaf(F32(w * V[i, 0]), V[i, 0], d)
+        pivots.append(d)
+    assert len(pivots) == 35 and 0 < min(pivots) and max(pivots) < 1e-36 and sum(d < TINY for d in pivots) >= 18
+    # ordinary inputs do not show a flush: the variant is not one of VARIANTS
+    case = als_break_case(5, 1, "neg")
+    assert _same(_solve(case, BREAK_ALPHA), _solve(case, BREAK_ALPHA, "flush"))
+
+
+@pytest.mark.parametrize("dim", [7, 32, 40, 64])
+def test_rounding_case_is_solved_and_an_unfused_build_shows(dim):
+    """als_rounding_case from the host model alone: all 42 non-empty rows are solved on either side's vectors, and the
+    "unfused" and "reverse" variants change output bits (measured: 20 .. 2228 and 146 .. 2127 components)."""
+    for side in (0, 1):
+        case = als_rounding_case(dim, side)
+        base = _solve(case, 0.7)
+        assert counts_of(base[0]) == [42, 6, 0], (dim, side)
+        for variant in ("unfused", "reverse"):
+            n = int((bits(base[1]) != bits(_solve(case, 0.7, variant)[1])).sum())
+            assert n >= 20, (dim, side, variant, n)
+        if dim == 7:
+            assert _same(_solve(case, 0.7, plain=True), base)
+
+
+@pytest.mark.parametrize("dim", [5, 33, 64])
+def test_one_infinite_value_breaks_its_row_alone(dim):
+    ptr, idx, val, V, G, row = als_inf_case(dim)
+    got = _solve((ptr, idx, val, V, G), BREAK_ALPHA)
+    honest = val.copy()
+    honest[np.isinf(val)] = 1.0
+    want = _solve((ptr, idx, honest, V, G), BREAK_ALPHA)
+    assert np.isinf(val).sum() == 1 and counts_of(want[0]) == [42, 6, 0] and counts_of(got[0]) == [41, 6, 1]
+    assert got[0][row] == 2 and (got[1][row] == 0).all()
+    others = np.arange(48) != row
+    assert np.array_equal(got[0][others], want[0][others]) and np.array_equal(bits(got[1][others]), bits(want[1][others]))
+    if dim == 5:
+        assert _same(_solve((ptr, idx, val, V, G), BREAK_ALPHA, plain=True), got)
 
 
 # ---------------------------------------------------------------------------------------------- accuracy

@@ -6,7 +6,10 @@ buffers carry a sentinel before every call: what a call must not touch keeps it.
 import numpy as np
 import pytest
 
-from tests.test_als_host import F32, als_case, bits, block_data, gram_fast, host_fit, solve_fast
+from tests.test_als_host import (BLOCK_SEED, BLOCK_USABLE, BREAK_ALPHA, BREAK_GRID, BREAK_KINDS, BREAK_LENGTHS, BREAK_T, F32, OUTSIDE,
+                                 STRIDE_CASES, STRIDE_GRID, STRIDE_PAIRS, STRIDE_SECOND, als_block_case, als_case, als_inf_case,
+                                 als_rounding_case, als_stride_case, als_tiny_case, bits, block_data, break_reference, counts_of,
+                                 gram_fast, half_step, host_fit, solve_fast, stride_classes)
 from tests.test_factor_host import rounding_vectors
 
 pytestmark = pytest.mark.gpu
@@ -18,13 +21,15 @@ def up(a, dt):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to("cuda:0")
 
 
-def run_gram(V, reg, pad=0):
-    """torch.ops.rtrec_amd.factor_gram on a host matrix; `pad` > 0: the stride is wider than dim, with NaN behind it."""
+def run_gram(V, reg, pad=0, n=None):
+    """torch.ops.rtrec_amd.factor_gram on a host matrix; `pad` > 0: the stride is wider than dim, with NaN behind it; `n`: n_v,
+    where the matrix handed in has more rows than the call may read."""
     import torch
     from rtrec_amd import ops  # noqa: F401  (registers torch.ops.rtrec_amd.*)
     V = np.asarray(V, F32)
-    n, dim = V.shape
-    Vd = np.concatenate([V, np.full((n, pad), np.nan, F32)], axis=1) if pad else V
+    rows, dim = V.shape
+    n = rows if n is None else n
+    Vd = np.concatenate([V, np.full((rows, pad), np.nan, F32)], axis=1) if pad else V
     gram = torch.full((dim, dim), SENTINEL, dtype=torch.float32, device="cuda:0")
     chunks = (n + 1023) // 1024
     ws = torch.full((chunks * dim * dim,), np.nan, dtype=torch.float32, device="cuda:0") if chunks else None
@@ -33,15 +38,17 @@ def run_gram(V, reg, pad=0):
     return gram.cpu().numpy()
 
 
-def run_solve(ptr, idx, val, V, G, alpha, jobs=None, pad=0):
+def run_solve(ptr, idx, val, V, G, alpha, jobs=None, pad=0, n_v=None):
     """torch.ops.rtrec_amd.factor_als_solve on host arrays: (status[n_jobs], out[n_rows, dim + pad]) with the sentinel wherever
-    the call wrote nothing; `pad` > 0 widens both strides (NaN behind V's components)."""
+    the call wrote nothing; `pad` > 0 widens both strides (NaN behind V's components); `n_v` where V has more rows than the
+    call may name."""
     import torch
     from rtrec_amd import ops  # noqa: F401
     V = np.asarray(V, F32)
-    n_v, dim = V.shape
+    rows, dim = V.shape
+    n_v = rows if n_v is None else n_v
     n_rows = len(ptr) - 1
-    Vd = np.concatenate([V, np.full((n_v, pad), np.nan, F32)], axis=1) if pad else V
+    Vd = np.concatenate([V, np.full((rows, pad), np.nan, F32)], axis=1) if pad else V
     n_jobs = n_rows if jobs is None else len(jobs)
     out = torch.full((n_rows, dim + pad), SENTINEL, dtype=torch.float32, device="cuda:0")
     status = torch.full((n_jobs,), 9, dtype=torch.uint8, device="cuda:0")
@@ -64,11 +71,12 @@ def assert_solved(got, want, what):
 
 
 # ---------------------------------------------------------------------------------------------- 1. the Gram matrix
-@pytest.mark.parametrize("dim", [1, 7, 32, 33, 64])
+@pytest.mark.parametrize("dim", [1, 7, 32, 33, 48, 63, 64])
 def test_gram_is_the_chunked_fmaf_chain_bit_for_bit(dim):
     """Cancelling 2^24 terms, midpoint products and denormals (rounding_vectors): another order of the rows, an unfused multiply,
-    a wider accumulator or another chunk size changes bits.  1023 / 1024 / 1025 rows stand on both sides of the chunk."""
-    for n in (1, 1023, 1024, 1025, 3000):
+    a wider accumulator or another chunk size changes bits.  1023 / 1024 / 1025 and 2048 / 2049 rows stand on both sides of a
+    chunk, 2 / 3 and 15 .. 18 rows around the group of 16 rows whose loads are issued together."""
+    for n in (1, 2, 3, 15, 16, 17, 18, 1023, 1024, 1025, 2048, 2049, 3000):
         V = rounding_vectors(n, 1, dim, seed=n + dim)[0]
         pad = 3 if n == 1025 else 0
         got, want = run_gram(V, 0.37, pad), gram_fast(V, 0.37)
@@ -168,3 +176,157 @@ def test_breakdown_is_a_status_never_a_fault():
         bad[3], bad[7], bad[-1] = 2 ** 31 - 1, -5, 10 ** 9
         bad = bad.astype(np.int32)
         assert_solved(run_solve(bad, idx, val, V, G, 1.0), host_solve(bad, idx, val, V, G, 1.0), "offsets out of range")
+
+
+# ---------------------------------------------------------------------------------------------- 3. a workgroup's second job
+@pytest.mark.parametrize("dim, c", STRIDE_CASES)
+def test_a_second_job_on_the_same_workgroup_starts_clean(dim, c):
+    """2^18 + 300 jobs (als_stride_case): more than a launch has workgroups, so workgroups 0 .. 299 run job b and then job
+    b + 2^18 -- the only place where LDS `A`, the accumulators, rhs and the flags of a job meet those of the job before.  The
+    job list lays every pair of STRIDE_PAIRS on one workgroup: a solve, a breakdown and an empty row after a solved job, after
+    one that broke in the middle of its factorisation (A half overwritten), after a row without a usable entry and after a row
+    outside R.  Every status, every vector and the sentinel in the rows no job names and behind dim are compared; the
+    expectation is the 64 templates expanded (a job's result depends on its row alone).  Without a job list job r is row r and
+    workgroup b runs the same template twice."""
+    ptr, idx, val, V, G, jobs, t_st, t_out = als_stride_case(dim, c)
+    n_rows = len(ptr) - 1
+    assert len(jobs) > STRIDE_GRID and min(counts_of(t_st)) >= 5
+    cls = stride_classes(jobs, n_rows, t_st)
+    second = np.arange(STRIDE_GRID, STRIDE_GRID + STRIDE_SECOND)
+    pairs = set(zip(cls[second - STRIDE_GRID].tolist(), cls[second].tolist()))
+    assert pairs == set(STRIDE_PAIRS) and {(0, 0), (2, 0), (1, 0), (OUTSIDE, 0), (0, 2)} <= pairs
+    named = jobs[cls != OUTSIDE].astype(np.int64)
+    want = np.full((n_rows, dim + 2), SENTINEL, F32)
+    want[named, :dim] = t_out[named % 64]
+    assert n_rows - len(named) >= 100
+    got = run_solve(ptr, idx, val, V, G, BREAK_ALPHA, jobs, pad=2)
+    assert_solved(got, (np.where(cls == OUTSIDE, 1, cls).astype(np.uint8), want), f"dim {dim}, {len(jobs)} jobs")
+    want[:, :dim] = np.tile(t_out, (n_rows // 64 + 1, 1))[:n_rows]
+    got = run_solve(ptr, idx, val, V, G, BREAK_ALPHA, pad=2)
+    assert_solved(got, (np.tile(t_st, n_rows // 64 + 1)[:n_rows], want), f"dim {dim}, one job per row")
+
+
+# ---------------------------------------------------------------------------------------------- 4. blocks of 64 entries
+@pytest.mark.parametrize("dim", [1, 32, 33, 48, 63, 64])
+def test_blocks_without_a_usable_entry_and_the_block_edges(dim):
+    """als_block_case: whole blocks of skipped entries before, between and after the usable ones, a block's only usable entry
+    in lane 0, in lane 63 or in the odd last slot, rows of exactly 127 .. 129 and 191 .. 193 usable entries -- with a shuffled
+    job list that also names two rows outside R, and without one; strides wider than dim."""
+    ptr, idx, val, V = als_block_case(260, dim, BLOCK_SEED.get(dim, dim))
+    G = gram_fast(np.nan_to_num(V), 0.1)
+    n = len(BLOCK_USABLE)
+    jobs = np.r_[np.arange(n), -1, n][np.random.default_rng(dim).permutation(n + 2)]
+    want = host_solve(ptr, idx, val, V, G, 0.7, jobs, pad=2)
+    assert want[0].tolist() == [1 if x in (-1, n) or not BLOCK_USABLE[x] else 0 for x in jobs]
+    assert_solved(run_solve(ptr, idx, val, V, G, 0.7, jobs, pad=2), want, f"dim {dim}")
+    want = host_solve(ptr, idx, val, V, G, 0.7, pad=2)
+    assert want[0].tolist() == [0 if u else 1 for u in BLOCK_USABLE]
+    assert_solved(run_solve(ptr, idx, val, V, G, 0.7, pad=2), want, f"dim {dim}, no job list")
+
+
+# ---------------------------------------------------------------------------------------------- 5. breakdown at every column
+@pytest.mark.parametrize("kind", BREAK_KINDS)
+@pytest.mark.parametrize("dim, c", BREAK_GRID)
+def test_breakdown_at_a_middle_pivot(dim, c, kind):
+    """als_break_case: G doctored at pivot c -- the first, the second and the last column, and for dim > 32 the columns 31, 32
+    and 33 where the factorisation leaves tile (0, 0) -- by a negative diagonal (rows break or survive by their length: both
+    must occur, but at dim 64, c = 32, where no t leaves a survivor, BREAK_T), by +inf on the diagonal and by a NaN in the
+    middle of row c.  One launch: solved and broken jobs side by side, broken rows all zero."""
+    (ptr, idx, val, V, G), st, out = break_reference(dim, c, kind)
+    n0, n1, n2 = counts_of(st)
+    if kind == "neg" and BREAK_T.get((dim, c), 0.5) is not None:
+        assert n0 >= 1 and n1 == 6 and n2 >= 1, (n0, n1, n2)
+    else:
+        assert (n0, n1, n2) == (0, 6, 42)
+    assert (out[st != 0] == 0).all()
+    got = run_solve(ptr, idx, val, V, G, BREAK_ALPHA)
+    assert_solved(got, (st, out), f"dim {dim}, c {c}, {kind}")
+    assert (got[1][got[0] != 0] == 0).all()
+
+
+# ---------------------------------------------------------------------------------------------- 6. denormals, rounding, inf
+@pytest.mark.parametrize("dim, g, alpha, mix", [(1, 1e-38, 1e-39, [42, 6, 0]), (5, 1e-38, 1e-39, [42, 6, 0]), (40, 1e-38, 1e-39, [38, 6, 4]),
+                                               (1, 1e-40, 1e-40, [7, 6, 35])])
+def test_denormals_are_kept_in_every_stage_of_the_solve(dim, g, alpha, mix):
+    """als_tiny_case: w, fl(w * y), the pivots and the quotients are float32 denormals and the solved components reach 3e38; a
+    kernel that flushes any of them gives other statuses (tests/test_als_host.py).  g = alpha = 1e-40: the factorisation
+    succeeds and the component overflows -- status 2 by the test after the substitutions."""
+    ptr, idx, val, V, G, alpha = als_tiny_case(dim, g, alpha)
+    want = host_solve(ptr, idx, val, V, G, alpha)
+    assert counts_of(want[0]) == mix
+    assert_solved(run_solve(ptr, idx, val, V, G, alpha), want, f"dim {dim}, g {g}")
+
+
+@pytest.mark.parametrize("dim", [7, 32, 40, 64])
+def test_the_build_is_the_fmaf_chain_on_rounding_sensitive_vectors(dim):
+    """als_rounding_case: 2^24-sized cancelling terms, midpoint products and denormals in V; all 42 non-empty rows are solved,
+    and an unfused or reordered build changes their bits (tests/test_als_host.py)."""
+    for side in (0, 1):
+        ptr, idx, val, V, G = als_rounding_case(dim, side)
+        want = host_solve(ptr, idx, val, V, G, 0.7)
+        assert counts_of(want[0]) == [42, 6, 0]
+        assert_solved(run_solve(ptr, idx, val, V, G, 0.7), want, f"dim {dim}, side {side}")
+
+
+@pytest.mark.parametrize("dim", [5, 33, 64])
+def test_one_infinite_value_breaks_its_row_alone(dim):
+    ptr, idx, val, V, G, row = als_inf_case(dim)
+    want = host_solve(ptr, idx, val, V, G, BREAK_ALPHA)
+    assert counts_of(want[0]) == [41, 6, 1] and want[0][row] == 2 and (want[1][row] == 0).all()
+    assert_solved(run_solve(ptr, idx, val, V, G, BREAK_ALPHA), want, f"dim {dim}")
+
+
+# ---------------------------------------------------------------------------------------------- 7. n_v below the tensor's rows
+@pytest.mark.parametrize("dim", [5, 40])
+def test_rows_of_v_behind_n_v_are_never_read(dim):
+    """V as handed in has 40 NaN rows behind n_v.  The solve skips every entry that names one (a fifth of the usable entries
+    are moved there) and equals the host model on V[:n_v]; the Gram matrix is that of V[:n_v], with n_v in the middle of a
+    group of 16 rows, at a chunk edge and one behind it."""
+    ptr, idx, val, V = als_case(48, 200, dim, seed=dim, lengths=BREAK_LENGTHS, scale=0.3)
+    rng = np.random.default_rng(dim)
+    idx = idx.copy()
+    move = np.flatnonzero((val > 0) & (idx >= 0) & (idx < 199) & (rng.random(len(idx)) < 0.2))
+    idx[move] = 200 + rng.integers(0, 40, len(move))
+    big = np.concatenate([V, np.full((40, dim), np.nan, F32)])
+    G = gram_fast(np.nan_to_num(V), 0.1)
+    want = host_solve(ptr, idx, val, V, G, 0.7, pad=2)
+    assert len(move) > 300 and counts_of(want[0])[0] >= 36 and counts_of(want[0])[2] == 0      # (a short row may lose every entry)
+    assert_solved(run_solve(ptr, idx, val, big, G, 0.7, pad=2, n_v=200), want, f"dim {dim}")
+    for n in (17, 1024, 1025):
+        Vn = np.concatenate([rounding_vectors(n, 1, dim, seed=n + dim)[0], np.full((40, dim), np.nan, F32)])
+        got, want_g = run_gram(Vn, 0.37, pad=1, n=n), gram_fast(Vn[:n], 0.37)
+        assert np.isfinite(want_g).all() and np.array_equal(bits(got), bits(want_g)), (dim, n)
+
+
+# ---------------------------------------------------------------------------------------------- 8. end to end, larger
+def larger_end_to_end(eng):
+    """The body of the test below on an engine (the CPU stand-in of tests/test_als_host.py runs it too)."""
+    X = block_data(0, clusters=4, items_per=30, users_per=275, rated=8)
+    item_lens = np.diff(X.tocsc().indptr)
+    assert X.shape == (1100, 120) and item_lens.min() >= 50 and (item_lens > 64).sum() >= 60      # two chunks of P; two entry blocks
+    eng.set_interactions(X.tocsc())
+    counts = eng.fit_factors(dim=40, iterations=2, regularization=0.01, alpha=1.0, seed=0)
+    P, Q, su, si = host_fit(X, 40, 2, 0.01, 1.0, 0)
+    assert (su == 0).all() and (si == 0).all()
+    gP, gsu, gQ, gsi = eng.als_vectors()
+    assert counts == {"user": {0: 1100, 1: 0, 2: 0}, "item": {0: 120, 1: 0, 2: 0}}
+    assert np.array_equal(gsu, su) and np.array_equal(gsi, si)
+    assert np.array_equal(bits(gP), bits(P)) and np.array_equal(bits(gQ), bits(Q))
+    # a half-step over named rows: duplicates and rows outside the side are dropped, the rest solved in ascending order
+    want = P.copy()
+    st = half_step(X, Q, 0.01, 1.0, want, job_rows=[5, 17, 900])
+    changed = (bits(want) != bits(P)).any(axis=1)
+    assert st.tolist() == [0, 0, 0] and np.flatnonzero(changed).tolist() == [5, 17, 900]
+    assert eng.als_half_step("user", rows=[5, 5, 900, -3, 10 ** 6, 17]) == {0: 3, 1: 0, 2: 0}
+    hP, hsu, hQ, hsi = eng.als_vectors()
+    assert np.array_equal(bits(hP), bits(want)) and np.array_equal(bits(hP[~changed]), bits(gP[~changed]))
+    assert np.array_equal(bits(hQ), bits(gQ)) and np.array_equal(hsu, su) and np.array_equal(hsi, si)
+
+
+def test_fit_factors_with_two_gram_chunks_and_two_entry_blocks():
+    """1,100 users x 120 items at dim 40 through SlimEngine.fit_factors: the item half-step's Gram matrix has two chunks, an
+    item's row 60 .. 90 entries (two blocks), the three lower tiles are live.  P, Q and the statuses equal host_fit's; then
+    als_half_step("user", rows=[5, 5, 900, -3, 10**6, 17]) equals the host half-step over rows 5, 17 and 900, every other row
+    keeps its bits, and the counts are returned."""
+    from rtrec_amd.engine import SlimEngine
+    larger_end_to_end(SlimEngine(device="cuda:0"))
