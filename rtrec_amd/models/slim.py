@@ -8,14 +8,36 @@ calls and scored in place by row id instead of being rebuilt and sliced per requ
 from __future__ import annotations
 
 import os
-from typing import Any, Dict, Iterable, List, Optional, Tuple
+from typing import Any, Dict, Iterable, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
+from .._native import TOPK_DENSE, TOPK_SPARSE
 from ..utils.device_store import DeviceInteractions
 from .base import BaseModel
 from .internal.slim_elastic import SLIMElastic
 from .. import settings
+
+
+class _UserBatch(NamedTuple):
+    """The users of a model-level batch call, split as recommend_batch splits them (SLIM._user_batch)."""
+    users: Any              # the int64 array of ids that pass through unmapped, else a list
+    B: int
+    uid: np.ndarray         # internal user id per user (0 for a cold one)
+    cold: np.ndarray        # nobody the model knows: the cold-start list
+    regular: np.ndarray     # a row of X: what the device pass serves
+
+    # the two derived views build a new array per access: a caller takes each once, outside its loops
+    @property
+    def rows(self) -> np.ndarray:
+        """The row of X per user as the kernels take it: int32, -1 for a user without one."""
+        return np.where(self.regular, self.uid, -1).astype(np.int32)
+
+    @property
+    def odd(self) -> np.ndarray:
+        """Known, but outside the matrix (a negative id, an id known only through register_user_feature): _recommend_odd_ids."""
+        return ~self.cold & ~self.regular
+
 
 class SLIM(BaseModel):
     def __init__(self, **kwargs: Any):
@@ -299,7 +321,6 @@ class SLIM(BaseModel):
         `diversity > 0`: known users are judged on recommend_diverse_batch(top_k=size, pool, diversity)'s lists instead, with
         its refusals.  `list_quality=True`: the same lists also go through list_quality_kernel (csrc/list_quality.hip) in the
         same pass, and a fifth element is returned: numpy (n, sim_sum, linked, weight_sum, exposure[W's n_items])."""
-        from .._native import TOPK_DENSE, TOPK_SPARSE
         from ..backend import HipBackend
         from ..utils.metrics import discount_tables, ground_truth_csr
         eng = self.model.engine
@@ -343,7 +364,7 @@ class SLIM(BaseModel):
         hot_rows = rows[hot]
         if len(hot_rows) and int(hot_rows.max()) >= n_users:
             raise ValueError("on_device evaluation: a user known only through register_user_feature is served by the host path only")
-        mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+        mode = self._topk_mode()
         top_k = min(size, n_items)
         self.model._sync_weights()
         if top_k < 1 or not eng.topk_supported(top_k, mode):
@@ -368,12 +389,8 @@ class SLIM(BaseModel):
                 pos = be.to_dev(np.flatnonzero(hot))
                 all_ids[pos, :top_k] = ids
                 all_cnt[pos] = cnt
-            if len(hot_rows) < n:
-                cold_list = self._recommend_cold_batch([None], top_k=size)[0][:size]
-                if cold_list:
-                    pos = be.to_dev(np.flatnonzero(~hot))
-                    all_ids[pos, :len(cold_list)] = be.to_dev(np.asarray(cold_list, dtype=np.int32))[None, :]
-                    all_cnt[pos] = len(cold_list)
+            # (every user here is hot or cold: negative ids and ids beyond the matrix were refused above)
+            self._fill_unserved_device(_UserBatch(eval_users, n, np.maximum(rows, 0), ~hot, hot), size, filter_interacted, all_ids, all_cnt)
             ids, cnt = all_ids, all_cnt
         discount, ideal = discount_tables(size)
         d_metrics = be.empty((n, 8), torch.float64)
@@ -413,11 +430,8 @@ class SLIM(BaseModel):
         valid up to counts[b], support = the number of contributing items of the pair (it may exceed top_m), unused slots
         hold -1 / -inf.  The id arrays hold INTERNAL item ids: for integer ids those are the raw ids, for a model with string
         ids map them with `model.item_ids.get`."""
-        from .._native import TOPK_DENSE, TOPK_SPARSE
-        if not self.model.is_fitted:
-            raise RuntimeError("Model must be fitted before calling explain_batch.")
-        arr = self._int_user_array(users)
-        users = arr if arr is not None else list(users)
+        self._require_fitted("explain_batch")
+        users = self._user_list(users)
         B, m = len(users), int(top_m)
         if items is not None:
             items = [list(row) for row in items]
@@ -434,36 +448,26 @@ class SLIM(BaseModel):
         contrib = np.full((B, K, m), -np.inf, dtype=np.float32)
         support = np.zeros((B, K), dtype=np.int32)
         eng = self.model.engine
-        n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
-        uid, cold = self._user_rows(users)
-        regular = ~cold & (uid >= 0) & (uid < n_users)
+        n_items = self.model.n_items_fitted
+        batch = self._user_batch(users)
+        regular = batch.regular
         if B:
             self.model._sync_weights()
             eng._whole_w("explain")                # a W that cannot be explained is refused whatever the batch holds
-        if items is not None:
+        if items is not None:                      # brought lists: nothing is filled in, a user without a row has no reasons
             for b, row in enumerate(items):
                 counts[b] = len(row)
                 ids[b, :len(row)] = self._ids_or_minus_one(row, self.item_ids.get_id, n_items)
             if regular.any():
                 self._sync_interactions()
-                r_ids[:], contrib[:], support[:] = eng.explain_rows(np.where(regular, uid, -1), ids, counts, m)
+                r_ids[:], contrib[:], support[:] = eng.explain_rows(batch.rows, ids, counts, m)
         elif B:
-            if cold.any():
-                cold_list = self._recommend_cold_batch([None], top_k=K)[0][:K]
-                ids[cold, :len(cold_list)] = np.asarray(cold_list, dtype=np.int64)[None, :]
-                counts[cold] = len(cold_list)
-            odd = ~cold & ~regular
-            if odd.any():
-                lists = self._recommend_odd_ids(uid[~cold], n_users, None, K, filter_interacted)
-                for b, row in zip(np.flatnonzero(~cold).tolist(), lists):
-                    if odd[b]:
-                        ids[b, :len(row)] = row
-                        counts[b] = len(row)
+            self._fill_unserved(batch, K, filter_interacted, ids, counts)      # (no scores: the reasons stay empty)
             k = min(K, n_items)
             if regular.any() and k >= 1:
                 self._sync_interactions()
-                rows = uid[regular].astype(np.int32)
-                mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+                rows = batch.uid[regular].astype(np.int32)
+                mode = self._topk_mode()
                 if eng.topk_supported(k, mode):
                     d_rows = eng._up(rows)
                     d_ids, _, d_cnt = eng.score_topk_device(None, len(rows), k, filter_interacted, mode, d_rows=d_rows)
@@ -519,15 +523,94 @@ class SLIM(BaseModel):
         """Internal id -> raw id: the identity for ids that pass through unmapped."""
         return (lambda i: i) if id_map.pass_through else id_map.get
 
-    def _user_rows(self, users: Any) -> Tuple[np.ndarray, np.ndarray]:
-        """(internal user id per user, cold mask): the hot / cold split of recommend_batch -- one compare for integer
-        pass-through ids, `_known_user_id` per user otherwise (with its "mixed types" error)."""
+    # ------------------------------------------------------------ what the model-level batch calls share
+    def _require_fitted(self, what: str) -> None:
+        if not self.model.is_fitted:
+            raise RuntimeError(f"Model must be fitted before calling {what}.")
+
+    def _topk_mode(self) -> int:
+        """The mode `recommend` ranks this model by: stored non-zero products for integer item ids, every item otherwise."""
+        return TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+
+    def _user_list(self, users: Any) -> Any:
+        """`users` as the int64 array of ids that pass through unmapped, else as a list: what len() and a second pass need."""
         arr = self._int_user_array(users)
-        if arr is not None:
-            return arr, arr > self.interactions.max_user_id
-        known = [self._known_user_id(u) for u in users]
-        cold = np.fromiter((u is None for u in known), dtype=bool, count=len(known))
-        return np.fromiter((0 if u is None else u for u in known), dtype=np.int64, count=len(known)), cold
+        return arr if arr is not None else list(users)
+
+    def _user_batch(self, users: Any) -> _UserBatch:
+        """The hot / cold split of recommend_batch -- one compare for integer pass-through ids, `_known_user_id` per user
+        otherwise (with its "mixed types" error) -- and who of the hot users has a row of X."""
+        users = self._user_list(users)
+        if isinstance(users, np.ndarray):
+            uid, cold = users, users > self.interactions.max_user_id
+        else:
+            known = [self._known_user_id(u) for u in users]
+            cold = np.fromiter((u is None for u in known), dtype=bool, count=len(known))
+            uid = np.fromiter((0 if u is None else u for u in known), dtype=np.int64, count=len(known))
+        regular = ~cold & (uid >= 0) & (uid < self.interactions.shape[0])
+        return _UserBatch(users, len(users), uid, cold, regular)
+
+    def _unserved_lists(self, batch: _UserBatch, top_k: int, filter_interacted: bool,
+                        cold_candidates: Optional[List[int]] = None, unserved: Optional[np.ndarray] = None):
+        """(positions in the batch, internal item ids) of the lists a device pass over the regular users leaves open: the
+        cold-start list once for all cold users (positions: an index array), then `_recommend_odd_ids`' list per user
+        outside the matrix (position: an int) -- asked for ALL known users, so that a negative id still wraps to a row of
+        the same batch, and raising its IndexError for an id beyond the matrix.  `unserved` (a mask) gets the cold-start
+        list instead of `cold`, among `cold_candidates`, and nobody is asked about then."""
+        cold = batch.cold if unserved is None else unserved
+        if cold.any():
+            yield np.flatnonzero(cold), self._recommend_cold_batch([None], candidate_item_ids=cold_candidates, top_k=top_k)[0][:top_k]
+        odd = batch.odd
+        if unserved is None and odd.any():
+            lists = self._recommend_odd_ids(batch.uid[~batch.cold], self.interactions.shape[0], None, top_k, filter_interacted)
+            for b, row in zip(np.flatnonzero(~batch.cold).tolist(), lists):
+                if odd[b]:
+                    yield b, row
+
+    def _fill_unserved(self, batch: _UserBatch, top_k: int, filter_interacted: bool, ids: np.ndarray, counts: np.ndarray,
+                       scores: Optional[np.ndarray] = None, cold_candidates: Optional[List[int]] = None,
+                       unserved: Optional[np.ndarray] = None) -> None:
+        """_unserved_lists into the padded host outputs `ids` [B, K] / `counts` [B]; the listed entries of `scores` get 0.0."""
+        for pos, row in self._unserved_lists(batch, top_k, filter_interacted, cold_candidates, unserved):
+            ids[pos, :len(row)] = np.asarray(row, dtype=np.int64)
+            counts[pos] = len(row)
+            if scores is not None:
+                scores[pos, :len(row)] = 0.0
+
+    def _fill_unserved_device(self, batch: _UserBatch, top_k: int, filter_interacted: bool, d_ids: Any, d_cnt: Any) -> None:
+        """_unserved_lists into the int32 device tensors `d_ids` [B, K] / `d_cnt` [B]: one upload per list (the cold-start
+        list is broadcast on the device) and none for an empty one."""
+        be = self.model.engine.be
+        for pos, row in self._unserved_lists(batch, top_k, filter_interacted):
+            if row:
+                at = pos if isinstance(pos, int) else be.to_dev(pos)
+                d_ids[at, :len(row)] = be.to_dev(np.asarray(row, dtype=np.int32))
+                d_cnt[at] = len(row)
+
+    @staticmethod
+    def _padded(B: int, K: int, *dtypes: Any) -> Tuple[np.ndarray, ...]:
+        """The [B, K] outputs of a batch call before anything is listed -- -1 for int64 ids, -inf for float values, 0 for an
+        int32 source -- and counts[B] = 0 behind them."""
+        empty = {np.int64: -1, np.float32: -np.inf, np.float64: -np.inf, np.int32: 0}
+        return tuple(np.full((B, K), empty[dt], dtype=dt) for dt in dtypes) + (np.zeros(B, dtype=np.int32),)
+
+    def _lists_tail(self, ids: np.ndarray, counts: np.ndarray, scores: Optional[np.ndarray] = None, id_map: Any = None,
+                    keep_raw: Optional[np.ndarray] = None) -> List[List[Any]]:
+        """The list form of padded outputs: per row the first counts[b] ids mapped to raw ids through `id_map` (default: the
+        item ids; the rows of the mask `keep_raw` stay as they are), as (id, score) tuples where `scores` is given.  One
+        tolist() per array, so the elements are Python ints and floats."""
+        id_map = self.item_ids if id_map is None else id_map
+        get = None if id_map.pass_through else id_map.get             # (ids that pass through unmapped are their own raw ids)
+        id_rows, cnts = ids.tolist(), counts.tolist()
+        sc_rows = None if scores is None else scores.tolist()
+        as_is = None if keep_raw is None or get is None else keep_raw.tolist()
+        out: List[List[Any]] = []
+        for b, n in enumerate(cnts):
+            row = id_rows[b][:n]
+            if get is not None and not (as_is and as_is[b]):
+                row = [get(i) for i in row]
+            out.append(row if sc_rows is None else list(zip(row, sc_rows[b])))
+        return out
 
     def rerank_batch(self, users: List[Any], candidates: List[List[Any]], top_k: Optional[int] = None,
                      filter_interacted: bool = False, ret_scores: bool = False, as_arrays: bool = False) -> Any:
@@ -554,10 +637,8 @@ class SLIM(BaseModel):
         Returns one list of raw item ids per user in rank order -- of (item, score) tuples with `ret_scores` -- or with
         `as_arrays=True` (ids[B, top_k], scores[B, top_k], counts[B]): row b is valid up to counts[b], unused slots hold
         -1 / -inf, and the ids are INTERNAL item ids (for integer ids the raw ids; map string ids with `model.item_ids.get`)."""
-        if not self.model.is_fitted:
-            raise RuntimeError("Model must be fitted before calling rerank_batch.")
-        arr = self._int_user_array(users)
-        users = arr if arr is not None else list(users)
+        self._require_fitted("rerank_batch")
+        users = self._user_list(users)
         B = len(users)
         lim = 2 ** 31 - 1
         if (isinstance(candidates, np.ndarray) and candidates.ndim == 2 and candidates.dtype.kind in "iu"
@@ -584,19 +665,16 @@ class SLIM(BaseModel):
             raise ValueError(f"rerank_batch ranks lists of up to {self.RERANK_MAX_LIST} candidates, got one of {K}: split it, or "
                              "score it with score_pairs and sort on the host")
         k = K if top_k is None else max(0, min(int(top_k), K))
-        out_ids = np.full((B, k), -1, dtype=np.int64)
-        out_sc = np.full((B, k), -np.inf, dtype=np.float32)
-        out_cnt = np.zeros(B, dtype=np.int32)
-        uid, cold = self._user_rows(users)
+        out_ids, out_sc, out_cnt = self._padded(B, k, np.int64, np.float32)
+        batch = self._user_batch(users)
+        cold = batch.cold
         if B:
             self.model._sync_weights()
             self.model.engine._whole_w("score_pairs")    # a W that cannot be served is refused whatever the batch holds
         hot = np.flatnonzero(~cold)
-        if len(hot) and k > 0:
+        if len(hot) and k > 0:                        # (a known user outside the matrix is scored as one without interactions)
             all_hot = len(hot) == B
-            h_ids, h_uid = (ids, uid) if all_hot else (np.ascontiguousarray(ids[hot]), uid[hot])
-            n_users = self.interactions.shape[0]
-            rows = np.where((h_uid >= 0) & (h_uid < n_users), h_uid, -1)
+            h_ids, rows = (ids, batch.rows) if all_hot else (np.ascontiguousarray(ids[hot]), batch.rows[hot])
             self._sync_interactions()
             scores, _, order, cnt = self.model.engine.score_pairs_rows(rows, h_ids, counts if all_hot else counts[hot], k,
                                                                        filter_interacted)
@@ -614,13 +692,8 @@ class SLIM(BaseModel):
             out_ids[b, :len(row)], out_sc[b, :len(row)], out_cnt[b] = row, 0.0, len(row)
         if as_arrays:
             return out_ids, out_sc, out_cnt
-        raw_of = self._raw_of(self.item_ids)
-        id_rows, sc_rows, cnts, is_cold = out_ids.tolist(), out_sc.tolist(), out_cnt.tolist(), cold.tolist()
-        out: List[Any] = []
-        for b in range(B):
-            items = id_rows[b][:cnts[b]] if is_cold[b] else [raw_of(i) for i in id_rows[b][:cnts[b]]]
-            out.append(list(zip(items, sc_rows[b][:cnts[b]])) if ret_scores else items)
-        return out
+        # a cold user's ids stay unmapped, as the reference's `recommend` returns its hot items (base.py:207-210)
+        return self._lists_tail(out_ids, out_cnt, out_sc if ret_scores else None, keep_raw=cold)
 
     def rerank(self, user: Any, candidates: List[Any], top_k: Optional[int] = None, filter_interacted: bool = False,
                ret_scores: bool = False) -> List[Any]:
@@ -677,8 +750,6 @@ class SLIM(BaseModel):
     def _catalogue_ranks(self, uid: np.ndarray, tg_ptr: np.ndarray, iid: np.ndarray, filter_interacted: bool):
         """(above, tied, score, competing) of SlimEngine.catalogue_ranks_rows for the internal user ids `uid` (a user without a
         row in X scores 0 everywhere) and internal item ids `iid` (-1: no column), in the mode `recommend` ranks this model by."""
-        from .._native import TOPK_DENSE, TOPK_SPARSE
-        mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
         self.model._sync_weights()
         self.model.engine._whole_w("catalogue_ranks")     # a W that cannot be served is refused whatever the batch holds
         if len(uid) == 0:
@@ -686,7 +757,7 @@ class SLIM(BaseModel):
         self._sync_interactions()
         n_users = self.interactions.shape[0]
         rows = np.where((uid >= 0) & (uid < n_users), uid, -1)
-        return self.model.engine.catalogue_ranks_rows(rows, tg_ptr, iid, filter_interacted, mode)
+        return self.model.engine.catalogue_ranks_rows(rows, tg_ptr, iid, filter_interacted, self._topk_mode())
 
     def rank_items_batch(self, users: List[Any], items: List[List[Any]], filter_interacted: bool = True,
                          as_arrays: bool = False) -> Any:
@@ -705,10 +776,8 @@ class SLIM(BaseModel):
         Returns one dict per user: {"items": the raw ids as given, "above": [...], "tied": [...], "score": [...],
         "competing": n} -- or with `as_arrays=True` (ptr[B + 1] int64, above int32, tied int32, score float64, competing[B]
         int32): user b's items are the slots ptr[b] .. ptr[b + 1], in the order given."""
-        if not self.model.is_fitted:
-            raise RuntimeError("Model must be fitted before calling rank_items_batch.")
-        arr = self._int_user_array(users)
-        users = arr if arr is not None else list(users)
+        self._require_fitted("rank_items_batch")
+        users = self._user_list(users)
         lists = [c.tolist() if isinstance(c, np.ndarray) else list(c) for c in items]
         B = len(users)
         if len(lists) != B:
@@ -717,7 +786,7 @@ class SLIM(BaseModel):
         np.cumsum([len(c) for c in lists], out=ptr[1:])
         flat = [x for c in lists for x in c]
         iid = self._ids_or_minus_one(flat, self.item_ids.get_id, self.model.n_items_fitted)
-        uid, cold = self._user_rows(users)
+        _, _, uid, cold, _ = self._user_batch(users)
         iid = np.where(np.repeat(cold, np.diff(ptr)), -1, iid)             # a cold user's items are nobody's
         above, tied, score, competing = self._catalogue_ranks(np.where(cold, -1, uid), ptr, iid, filter_interacted)
         competing = np.where(cold, 0, competing).astype(np.int32)
@@ -842,52 +911,27 @@ class SLIM(BaseModel):
         `rerank_batch(as_arrays=True)` returns (INTERNAL item ids, base scores, -1 / -inf behind counts[b]) plus the value the
         entry was chosen with and its penalty, i.e. how similar it is to what stands above it (-inf for the unchanged lists
         of unknown users)."""
-        from .._native import TOPK_DENSE, TOPK_SPARSE
         top_k, pool, lam = self._diverse_args("recommend_diverse_batch", top_k, pool, diversity)
-        arr = self._int_user_array(users)
-        users = arr if arr is not None else list(users)
-        B = len(users)
-        out_ids = np.full((B, top_k), -1, dtype=np.int64)
-        out_sc = np.full((B, top_k), -np.inf, dtype=np.float32)
-        out_val = np.full((B, top_k), -np.inf, dtype=np.float32)
-        out_pen = np.full((B, top_k), -np.inf, dtype=np.float32)
-        out_cnt = np.zeros(B, dtype=np.int32)
-        if B:
+        batch = self._user_batch(users)
+        out_ids, out_sc, out_val, out_pen, out_cnt = self._padded(batch.B, top_k, np.int64, np.float32, np.float32, np.float32)
+        if batch.B:                                # (an empty batch syncs nothing and asks nothing of W)
             eng = self.model.engine
-            n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
-            uid, cold = self._user_rows(users)
-            regular = ~cold & (uid >= 0) & (uid < n_users)
             self.model._sync_weights()
             eng._whole_w("diversify")              # a W that cannot be served is refused whatever the batch holds
-            mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+            mode = self._topk_mode()
             k_pool = self._pool_width("recommend_diverse_batch", pool, mode)
-            if cold.any():
-                cold_list = self._recommend_cold_batch([None], top_k=top_k)[0][:top_k]
-                out_ids[cold, :len(cold_list)] = np.asarray(cold_list, dtype=np.int64)[None, :]
-                out_sc[cold, :len(cold_list)] = 0.0
-                out_cnt[cold] = len(cold_list)
-            odd = ~cold & ~regular
-            if odd.any():
-                lists = self._recommend_odd_ids(uid[~cold], n_users, None, top_k, filter_interacted)
-                for b, row in zip(np.flatnonzero(~cold).tolist(), lists):
-                    if odd[b]:
-                        out_ids[b, :len(row)], out_sc[b, :len(row)], out_cnt[b] = row, 0.0, len(row)
-            if regular.any():
+            self._fill_unserved(batch, top_k, filter_interacted, out_ids, out_cnt, out_sc)
+            if batch.regular.any():
                 self._sync_interactions()
                 keep = min(top_k, k_pool)
-                g_ids, g_sc, cnt, value, pen = self._diverse_device(uid[regular].astype(np.int32), top_k, k_pool, lam, filter_interacted, mode)
-                pos = np.flatnonzero(regular)
+                g_ids, g_sc, cnt, value, pen = self._diverse_device(batch.uid[batch.regular].astype(np.int32), top_k, k_pool, lam,
+                                                                    filter_interacted, mode)
+                pos = np.flatnonzero(batch.regular)
                 out_ids[pos, :keep], out_sc[pos, :keep] = g_ids.cpu().numpy(), g_sc.cpu().numpy()
                 out_val[pos, :keep], out_pen[pos, :keep], out_cnt[pos] = value.cpu().numpy(), pen.cpu().numpy(), cnt.cpu().numpy()
         if as_arrays:
             return out_ids, out_sc, out_cnt, out_val, out_pen
-        raw_of = self._raw_of(self.item_ids)
-        id_rows, sc_rows, cnts = out_ids.tolist(), out_sc.tolist(), out_cnt.tolist()
-        out: List[Any] = []
-        for b in range(B):
-            items = [raw_of(i) for i in id_rows[b][:cnts[b]]]
-            out.append(list(zip(items, sc_rows[b][:cnts[b]])) if ret_scores else items)
-        return out
+        return self._lists_tail(out_ids, out_cnt, out_sc if ret_scores else None)
 
     def recommend_diverse(self, user: Any, top_k: int = 10, pool: int = 50, diversity: float = 0.3, filter_interacted: bool = True,
                           ret_scores: bool = False) -> List[Any]:
@@ -938,6 +982,14 @@ class SLIM(BaseModel):
         if not w >= 0.0:                                                  # (a NaN fails the compare)
             raise ValueError(f'{what}: weighting must be "contacts" or a non-negative number, got {weighting!r}')
         return False, w
+
+    @staticmethod
+    def _weight_factor(similarity_weight_factor: float, what: str) -> float:
+        """The k of the contacts rule weight = 2 n / (n + k), or its refusal."""
+        k = float(similarity_weight_factor)
+        if not k >= 0.0:                                                  # (a NaN fails the compare)
+            raise ValueError(f"{what}: similarity_weight_factor must not be negative or NaN, got {similarity_weight_factor}")
+        return k
 
     def _brought_lists(self, what: str, items: List[List[Any]], scores: List[List[float]], n_rows: Optional[int] = None):
         """(ids[B, K] int32, scores[B, K] float32, counts[B] int32) of the raw-id lists `items` with `scores`: ids the model does
@@ -1042,38 +1094,28 @@ class SLIM(BaseModel):
         Returns one list of raw item ids per user, or with `as_arrays=True` (ids[B, top_k] int64 INTERNAL item ids,
         value[B, top_k] float32, source[B, top_k] int32 -- 1: only the other scorer holds the item, 2: only SLIM, 3: both --
         counts[B]); -1 / -inf / 0 behind counts[b]."""
-        from .._native import TOPK_DENSE, TOPK_SPARSE
         what = "recommend_blended_batch"
         top_k = int(top_k)
         pool = top_k if pool is None else int(pool)
         if top_k < 1 or not 1 <= pool <= self.BLEND_MAX_LIST:
             raise ValueError(f"{what} needs top_k >= 1 and 1 <= pool <= {self.BLEND_MAX_LIST}, got top_k={top_k} and pool={pool}")
         contacts, weight = self._blend_weight(weighting, what)
-        k = float(similarity_weight_factor)
-        if not k >= 0.0:
-            raise ValueError(f"{what}: similarity_weight_factor must not be negative or NaN, got {similarity_weight_factor}")
-        if not self.model.is_fitted:
-            raise RuntimeError(f"Model must be fitted before calling {what}.")
-        arr = self._int_user_array(users)
-        users = arr if arr is not None else list(users)
+        k = self._weight_factor(similarity_weight_factor, what)
+        self._require_fitted(what)
+        users = self._user_list(users)
         B = len(users)
-        a_ids, a_sc, a_cnt = self._brought_lists(what, other_items, other_scores, B)
-        out_ids = np.full((B, top_k), -1, dtype=np.int64)
-        out_val = np.full((B, top_k), -np.inf, dtype=np.float32)
-        out_src = np.zeros((B, top_k), dtype=np.int32)
-        out_cnt = np.zeros(B, dtype=np.int32)
-        if B:
+        a_ids, a_sc, a_cnt = self._brought_lists(what, other_items, other_scores, B)      # (refused before the users are looked up)
+        out_ids, out_val, out_src, out_cnt = self._padded(B, top_k, np.int64, np.float32, np.int32)
+        if B:                                      # (an empty batch syncs nothing and asks nothing of W)
             eng = self.model.engine
-            n_users = self.interactions.shape[0]
-            uid, cold = self._user_rows(users)
-            regular = ~cold & (uid >= 0) & (uid < n_users)
+            batch = self._user_batch(users)
             self.model._sync_weights()
             eng._whole_w("blend")                  # a W that cannot be served is refused whatever the batch holds
-            mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+            mode = self._topk_mode()
             k_pool = self._pool_width(what, pool, mode)
             self._sync_interactions()
-            rows = np.where(regular, uid, -1).astype(np.int32)
-            b_ids, b_sc, b_cnt = self._slim_pool_device(rows, regular, k_pool, filter_interacted, mode)
+            rows = batch.rows                      # (a user without a row has an empty SLIM side: no list is filled in)
+            b_ids, b_sc, b_cnt = self._slim_pool_device(rows, batch.regular, k_pool, filter_interacted, mode)
             cn = self._contact_csr(contact_counts, eng.n_users) if contacts else None      # (one row per row of the resident X)
             keep = min(top_k, a_ids.shape[1] + k_pool)
             ids, value, source, count = eng.blend_device(eng._up(a_ids), eng._up(a_sc), eng._up(a_cnt), b_ids, b_sc, b_cnt, keep, weight,
@@ -1083,9 +1125,7 @@ class SLIM(BaseModel):
             out_src[:, :keep], out_cnt[:] = source.cpu().numpy(), count.cpu().numpy()
         if as_arrays:
             return out_ids, out_val, out_src, out_cnt
-        raw_of = self._raw_of(self.item_ids)
-        id_rows, cnts = out_ids.tolist(), out_cnt.tolist()
-        return [[raw_of(i) for i in id_rows[b][:cnts[b]]] for b in range(B)]
+        return self._lists_tail(out_ids, out_cnt)
 
     def recommend_blended(self, user: Any, other_items: List[Any], other_scores: List[float], top_k: int = 10, pool: Optional[int] = None,
                           weighting: Any = "contacts", contact_counts: Optional[Iterable[Tuple[Any, Any, int]]] = None,
@@ -1106,8 +1146,7 @@ class SLIM(BaseModel):
         contacts, w = self._blend_weight(weight, what)
         if contacts or int(top_k) < 1:
             raise ValueError(f"{what} takes a constant non-negative weight and top_k >= 1, got weight={weight!r} and top_k={top_k}")
-        if not self.model.is_fitted:
-            raise RuntimeError(f"Model must be fitted before calling {what}.")
+        self._require_fitted(what)
         A = self._brought_lists(what, items_a, scores_a)
         Bl = self._brought_lists(what, items_b, scores_b, len(A[0]))
         if not len(A[0]):
@@ -1115,8 +1154,7 @@ class SLIM(BaseModel):
         self.model._sync_weights()
         keep = min(int(top_k), A[0].shape[1] + Bl[0].shape[1])
         ids, value, _, count = self.model.engine.blend_lists(A[0], A[1], Bl[0], Bl[1], A[2], Bl[2], keep=keep, weight_b=w, mnz=mnz)
-        raw_of = self._raw_of(self.item_ids)
-        return [[(raw_of(int(i)), float(v)) for i, v in zip(ids[b, :count[b]], value[b, :count[b]])] for b in range(len(ids))]
+        return self._lists_tail(ids, count, value)
 
     # ------------------------------------------------------------ factor scorer and hybrid lists (the reference's hybrid, one pass)
     FACTOR_MAX_K = 128          # list length rtrec_factor_topk selects
@@ -1371,21 +1409,15 @@ class SLIM(BaseModel):
         if not 1 <= top_k <= self.FACTOR_MAX_K:
             raise ValueError(f"{what} needs 1 <= top_k <= {self.FACTOR_MAX_K} (what the factor kernel selects), got {top_k}")
         users_tags = self._checked_users_tags(what, users, users_tags)
-        if not self.model.is_fitted:
-            raise RuntimeError(f"Model must be fitted before calling {what}.")
+        self._require_fitted(what)
         if self._factors is None:
             raise RuntimeError(f"attach_factors() must be called before {what}.")
-        arr = self._int_user_array(users)
-        users = arr if arr is not None else list(users)
-        B = len(users)
-        out_ids = np.full((B, top_k), -1, dtype=np.int64)
-        out_sc = np.full((B, top_k), -np.inf, dtype=np.float32)
-        out_cnt = np.zeros(B, dtype=np.int32)
+        batch = self._user_batch(users)
+        B, uid, regular = batch.B, batch.uid, batch.regular
+        out_ids, out_sc, out_cnt = self._padded(B, top_k, np.int64, np.float32)
         if B:
             eng = self.model.engine
-            n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
-            uid, cold = self._user_rows(users)
-            regular = ~cold & (uid >= 0) & (uid < n_users)
+            n_items = self.model.n_items_fitted
             self.model._sync_weights()
             self._sync_interactions()
             has_vec = self._sync_factors(what)
@@ -1400,12 +1432,9 @@ class SLIM(BaseModel):
             if candidate_items is not None:
                 cand = self._ids_or_minus_one(candidate_items, self.item_ids.get_id, n_items)
                 cand = np.unique(cand[cand >= 0])
-            if not served.all():
-                cold_list = self._recommend_cold_batch([None], candidate_item_ids=None if cand is None else cand.tolist(),
-                                                       top_k=top_k)[0][:top_k]
-                out_ids[~served, :len(cold_list)] = np.asarray(cold_list, dtype=np.int64)[None, :]
-                out_sc[~served, :len(cold_list)] = 0.0
-                out_cnt[~served] = len(cold_list)
+            # whoever the factor pass does not serve -- no row, or a row without a vector -- gets the cold-start list
+            self._fill_unserved(batch, top_k, filter_interacted, out_ids, out_cnt, out_sc,
+                                cold_candidates=None if cand is None else cand.tolist(), unserved=~served)
             if served.any():
                 mask = None
                 if cand is not None:
@@ -1414,16 +1443,14 @@ class SLIM(BaseModel):
                 pos = np.flatnonzero(served)
                 if vec is not None:                           # (a user without a row of X: scored unfiltered, the cold start)
                     at = None if len(pos) == B else eng._up(pos.astype(np.int64))
-                    ids, sc, cnt = eng.factor_topk_rows(np.where(regular, uid, -1)[pos], top_k, filter_interacted, item_mask=mask,
+                    ids, sc, cnt = eng.factor_topk_rows(batch.rows[pos], top_k, filter_interacted, item_mask=mask,
                                                         vectors=vec if at is None else vec.index_select(0, at))
                 else:
                     ids, sc, cnt = eng.factor_topk_rows(uid[pos], top_k, filter_interacted, item_mask=mask)
                 out_ids[pos], out_sc[pos], out_cnt[pos] = ids, sc, cnt
         if as_arrays:
             return out_ids, out_sc, out_cnt
-        raw_of = self._raw_of(self.item_ids)
-        id_rows, cnts = out_ids.tolist(), out_cnt.tolist()
-        return [[raw_of(i) for i in id_rows[b][:cnts[b]]] for b in range(B)]
+        return self._lists_tail(out_ids, out_cnt)
 
     def recommend_factor(self, user: Any, top_k: int = 10, filter_interacted: bool = True,
                          candidate_items: Optional[List[Any]] = None, user_tags: Optional[List[Any]] = None) -> List[Any]:
@@ -1455,7 +1482,6 @@ class SLIM(BaseModel):
         Returns what `recommend_blended_batch` returns: one list of raw item ids per user, or with `as_arrays=True`
         (ids[B, top_k] int64 INTERNAL item ids, value[B, top_k] float32, source[B, top_k] int32 -- 1: only the factor scorer
         holds the item, 2: only SLIM, 3: both -- counts[B]); -1 / -inf / 0 behind counts[b]."""
-        from .._native import TOPK_DENSE, TOPK_SPARSE
         what = "recommend_hybrid_batch"
         top_k = int(top_k)
         pool = top_k if pool is None else int(pool)
@@ -1463,33 +1489,23 @@ class SLIM(BaseModel):
             raise ValueError(f"{what} needs top_k >= 1 and 1 <= pool <= {self.FACTOR_MAX_K}, got top_k={top_k} and pool={pool}: the "
                              f"factor kernel keeps each user's candidates in LDS and selects at most {self.FACTOR_MAX_K} per user")
         contacts, weight = self._blend_weight(weighting, what)
-        k = float(similarity_weight_factor)
-        if not k >= 0.0:
-            raise ValueError(f"{what}: similarity_weight_factor must not be negative or NaN, got {similarity_weight_factor}")
+        k = self._weight_factor(similarity_weight_factor, what)
         users_tags = self._checked_users_tags(what, users, users_tags)
-        if not self.model.is_fitted:
-            raise RuntimeError(f"Model must be fitted before calling {what}.")
+        self._require_fitted(what)
         if self._factors is None:
             raise RuntimeError(f"attach_factors() must be called before {what}.")
-        arr = self._int_user_array(users)
-        users = arr if arr is not None else list(users)
-        B = len(users)
-        out_ids = np.full((B, top_k), -1, dtype=np.int64)
-        out_val = np.full((B, top_k), -np.inf, dtype=np.float32)
-        out_src = np.zeros((B, top_k), dtype=np.int32)
-        out_cnt = np.zeros(B, dtype=np.int32)
-        if B:
+        batch = self._user_batch(users)
+        B, uid, regular = batch.B, batch.uid, batch.regular
+        out_ids, out_val, out_src, out_cnt = self._padded(B, top_k, np.int64, np.float32, np.int32)
+        if B:                                      # (an empty batch syncs nothing and asks nothing of W)
             eng = self.model.engine
-            n_users = self.interactions.shape[0]
-            uid, cold = self._user_rows(users)
-            regular = ~cold & (uid >= 0) & (uid < n_users)
             self.model._sync_weights()
             eng._whole_w("blend")
-            mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+            mode = self._topk_mode()
             k_pool = self._pool_width(what, pool, mode)
             self._sync_interactions()
             self._sync_factors(what)
-            rows = np.where(regular, uid, -1).astype(np.int32)
+            rows = batch.rows                      # (a user without a row has no side at all: no list is filled in)
             d_rows = eng._up(rows)
             if users_tags is None:
                 a_ids, a_sc, a_cnt = eng.factor_topk_device(d_rows, B, k_pool, filter_interacted)     # (row -1: an empty list)
@@ -1516,9 +1532,7 @@ class SLIM(BaseModel):
                 out_src[pos, :kc] = (np.arange(kc)[None, :] < c_cnt[:, None]).astype(np.int32)
         if as_arrays:
             return out_ids, out_val, out_src, out_cnt
-        raw_of = self._raw_of(self.item_ids)
-        id_rows, cnts = out_ids.tolist(), out_cnt.tolist()
-        return [[raw_of(i) for i in id_rows[b][:cnts[b]]] for b in range(B)]
+        return self._lists_tail(out_ids, out_cnt)
 
     def recommend_hybrid(self, user: Any, top_k: int = 10, pool: Optional[int] = None, weighting: Any = "contacts",
                          contact_counts: Optional[Iterable[Tuple[Any, Any, int]]] = None, similarity_weight_factor: float = 2.0,
@@ -1596,7 +1610,6 @@ class SLIM(BaseModel):
 
         Raises what recommend_diverse_batch raises when `diversity > 0`; with `diversity == 0`, `pool` is not read and top_k must
         be one the fused top-k kernels serve for this model."""
-        from .._native import TOPK_DENSE, TOPK_SPARSE
         from ..utils.metrics import quality_frame_columns, quality_summary
         what = "recommend_quality"
         lam: Optional[float] = None
@@ -1606,16 +1619,14 @@ class SLIM(BaseModel):
             top_k = int(top_k)
             if not 1 <= top_k <= self.QUALITY_MAX_LIST:
                 raise ValueError(f"{what} needs 1 <= top_k <= {self.QUALITY_MAX_LIST}, got top_k={top_k}")
-            if not self.model.is_fitted:
-                raise RuntimeError(f"Model must be fitted before calling {what}.")
-        arr = self._int_user_array(users)
-        users = arr if arr is not None else list(users)
+            self._require_fitted(what)
+        users = self._user_list(users)
         B = len(users)
         eng = self.model.engine
-        n_users, n_items = self.interactions.shape[0], self.model.n_items_fitted
-        self.model._sync_weights()
+        n_items = self.model.n_items_fitted
+        self.model._sync_weights()                                         # (W and the pool are checked for an empty batch too)
         dw = eng._whole_w("diversify" if lam is not None else "list_quality")
-        mode = TOPK_SPARSE if self.item_ids.pass_through else TOPK_DENSE
+        mode = self._topk_mode()
         k_pool = self._pool_width(what, pool, mode) if lam is not None else 0
         k = min(top_k, n_items)
         if lam is None and (k < 1 or not eng.topk_supported(k, mode)):
@@ -1625,26 +1636,13 @@ class SLIM(BaseModel):
         d_ids = torch.full((B, top_k), -1, dtype=torch.int32, device=be.device)
         d_cnt = be.zeros((B,), torch.int32)
         if B:
-            uid, cold = self._user_rows(users)
-            regular = ~cold & (uid >= 0) & (uid < n_users)
-            if regular.any():
-                ids, cnt = self._hot_lists_device(uid[regular], k, lam, k_pool, filter_interacted, mode)
-                pos = be.to_dev(np.flatnonzero(regular))
+            batch = self._user_batch(users)
+            if batch.regular.any():
+                ids, cnt = self._hot_lists_device(batch.uid[batch.regular], k, lam, k_pool, filter_interacted, mode)
+                pos = be.to_dev(np.flatnonzero(batch.regular))
                 d_ids[pos, :int(ids.shape[1])] = ids
                 d_cnt[pos] = cnt
-            if cold.any():                                                 # one upload, broadcast on the device
-                cold_list = self._recommend_cold_batch([None], top_k=top_k)[0][:top_k]
-                if cold_list:
-                    pos = be.to_dev(np.flatnonzero(cold))
-                    d_ids[pos, :len(cold_list)] = be.to_dev(np.asarray(cold_list, dtype=np.int32))[None, :]
-                    d_cnt[pos] = len(cold_list)
-            odd = ~cold & ~regular
-            if odd.any():
-                lists = self._recommend_odd_ids(uid[~cold], n_users, None, top_k, filter_interacted)
-                for b, row in zip(np.flatnonzero(~cold).tolist(), lists):
-                    if odd[b] and len(row):
-                        d_ids[b, :len(row)] = be.to_dev(np.asarray(row, dtype=np.int32))
-                        d_cnt[b] = len(row)
+            self._fill_unserved_device(batch, top_k, filter_interacted, d_ids, d_cnt)      # (after the device pass, as its IndexError was)
         exposure = be.zeros((dw.n_items,), torch.int32)
         out = eng.list_quality_device(d_ids, d_cnt, eng.item_novelty_device(), exposure)
         n, sim_sum, linked, weight_sum = (t.cpu().numpy() for t in out)
@@ -1695,11 +1693,7 @@ class SLIM(BaseModel):
         users, scores, counts, eligible = self.model.recommend_users_batch(q, top_n, filter_interacted, rows)
         if as_arrays:
             return users, scores, counts, eligible
-        raw_of = self._raw_of(self.user_ids)
-        user_rows, score_rows, cnts = users.tolist(), scores.tolist(), counts.tolist()
-        if ret_scores:
-            return [[(raw_of(u), s) for u, s in zip(user_rows[b][:cnts[b]], score_rows[b][:cnts[b]])] for b in range(len(items))]
-        return [[raw_of(u) for u in user_rows[b][:cnts[b]]] for b in range(len(items))]
+        return self._lists_tail(users, counts, scores if ret_scores else None, id_map=self.user_ids)
 
     def recommend_users(self, item: Any, top_n: int = 100, filter_interacted: bool = True,
                         candidate_users: Optional[List[Any]] = None, ret_scores: bool = False) -> List[Any]:
@@ -1779,17 +1773,13 @@ class SLIM(BaseModel):
         query_items = list(query_items)
         qid, vec, first = self._similar_query(what, query_items, query_items_tags, first_component)
         B = len(query_items)
-        out_ids = np.full((B, top_k), -1, dtype=np.int64)
-        out_sc = np.full((B, top_k), -np.inf, dtype=np.float32)
-        out_cnt = np.zeros(B, dtype=np.int32)
+        out_ids, out_sc, out_cnt = self._padded(B, top_k, np.int64, np.float32)
         if B:
             ids, sc, cnt, _ = self.model.engine.similar_factor_device(qid, top_k, first, vectors=vec, write_cosine=True)
             out_ids[:], out_sc[:], out_cnt[:] = ids.cpu().numpy(), sc.cpu().numpy(), cnt.cpu().numpy()
         if as_arrays:
             return out_ids, out_sc, out_cnt
-        raw_of = self._raw_of(self.item_ids)
-        id_rows, sc_rows, cnts = out_ids.tolist(), out_sc.tolist(), out_cnt.tolist()
-        return [[(raw_of(i), s) for i, s in zip(id_rows[b][:cnts[b]], sc_rows[b][:cnts[b]])] for b in range(B)]
+        return self._lists_tail(out_ids, out_cnt, out_sc)
 
     def similar_items_factor(self, query_item: Any, top_k: int = 10, query_item_tags: Optional[List[Any]] = None,
                              first_component: Optional[int] = None) -> List[Tuple[Any, float]]:
@@ -1825,10 +1815,7 @@ class SLIM(BaseModel):
         query_items = list(query_items)
         qid, vec, first = self._similar_query(what, query_items, query_items_tags, first_component)
         B = len(query_items)
-        out_ids = np.full((B, top_k), -1, dtype=np.int64)
-        out_val = np.full((B, top_k), -np.inf, dtype=np.float64)
-        out_src = np.zeros((B, top_k), dtype=np.int32)
-        out_cnt = np.zeros(B, dtype=np.int32)
+        out_ids, out_val, out_src, out_cnt = self._padded(B, top_k, np.int64, np.float64, np.int32)
         if B:
             keep = min(top_k, 2 * pool)
             ids, value, source, count = self.model.engine.similar_hybrid_device(qid, top_k, pool, first, vectors=vec)
@@ -1836,9 +1823,7 @@ class SLIM(BaseModel):
             out_src[:, :keep], out_cnt[:] = source.cpu().numpy(), count.cpu().numpy()
         if as_arrays:
             return out_ids, out_val, out_src, out_cnt
-        raw_of = self._raw_of(self.item_ids)
-        id_rows, val_rows, cnts = out_ids.tolist(), out_val.tolist(), out_cnt.tolist()
-        return [[(raw_of(i), v) for i, v in zip(id_rows[b][:cnts[b]], val_rows[b][:cnts[b]])] for b in range(B)]
+        return self._lists_tail(out_ids, out_cnt, out_val)
 
     def similar_items_hybrid(self, query_item: Any, top_k: int = 10, pool: Optional[int] = None,
                              query_item_tags: Optional[List[Any]] = None, first_component: Optional[int] = None

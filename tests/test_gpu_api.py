@@ -450,6 +450,16 @@ def test_hybrid_slimfm_call_sequence_on_the_gpu():
     replay(lambda cfg: SLIMElastic(cfg))
 
 
+def test_model_level_batch_calls_serve_cold_and_odd_users_on_the_gpu():
+    """The identities of tests/test_user_batch_host.py (who gets recommend_batch's list, the padding, the list tails) for the
+    integer-id and the string-id mix of regular, cold and out-of-matrix users, through the real backend."""
+    from rtrec_amd import SLIM
+    from tests.test_user_batch_host import build_case, check_mix
+    for kind in ("int", "str"):
+        c = build_case(kind, make=SLIM)
+        for name in ("mix with the last user", "mix without the last user") if kind == "int" else ("mix",):
+            check_mix(c, c.mixes[name])
+
 
 def test_custom_ops_refuse_mistyped_tensors():
     """csrc/torch_ops.cpp checks every pointer it hands to the C-ABI: a tensor of another dtype, a strided view or a host
