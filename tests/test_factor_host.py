@@ -265,6 +265,181 @@ def test_every_score_is_within_the_bound_of_a_chain_of_d_roundings():
         assert (np.abs(S - exact) <= gamma * mag * (1.0 + 1e-6)).all(), dim
 
 
+# ---------------------------------------------------------------------------------------------- cases for the device tests
+# The scan is instantiated per class of dim (8 / 32 / 128 B registers for dim <= 16 / 64 / 256) and of top_k (64 / 128 / 224 buffer
+# entries for top_k <= 16 / 64 / 128); its A operands are loaded 16 k-steps at a time.  These are the dims on both sides of a class
+# rule, and dims whose ceil(dim / 2) leaves the last group of 16 partly filled in the two larger classes.
+CLASS_DIMS = [15, 16, 17, 31, 32, 33, 63, 65, 129]
+# A case of more rows than a grid cap is built from 509 distinct pattern rows, row r carrying pattern r % 509: 65,536 % 509 = 384,
+# so the rows r and r + 65,536 that one workgroup serves never carry the same pattern, and the host model runs on 509 rows.
+PATTERNS = 509
+GRID_CAP = 65536
+
+
+def pattern_of(n_rows):
+    return np.arange(n_rows) % PATTERNS
+
+
+def tiled(want, n_rows):
+    """The answer for n_rows rows from the answer for the patterns."""
+    at = pattern_of(n_rows)
+    return tuple(None if a is None else np.asarray(a)[at] for a in want)
+
+
+def class_edge_case(dim, seed=0):
+    """40 jobs x 200 items whose LAST component decides the lists: a class rule one too generous drops exactly that one."""
+    rng = np.random.default_rng(900 + dim + seed)
+    P = rng.standard_normal((40, dim)).astype(F32)
+    Q = rng.standard_normal((200, dim)).astype(F32)
+    P[:, dim - 1] = F32(8.0) * rng.choice(np.array([1, -1], F32), 40)
+    return P, Q
+
+
+def operand_case(dim):
+    """test_identity_vectors_against_an_asymmetric_integer_matrix of tests/test_gpu_factor.py at any dim: P = unit vectors makes
+    score(u, i) = Q[i, u % dim], so every component -- the last one, behind which the padding begins, included -- is somebody's
+    whole score, and the transposed roles."""
+    n_items, n_users = 40, max(33, dim + 1)
+    i, c = np.meshgrid(np.arange(n_items), np.arange(dim), indexing="ij")
+    Q = (i * 37 + c * 3 + (i * c) % 5 - 400).astype(F32)
+    P = np.zeros((n_users, dim), F32)
+    P[np.arange(n_users), np.arange(n_users) % dim] = 1
+    u, c = np.meshgrid(np.arange(n_users), np.arange(dim), indexing="ij")
+    P2 = (u * 29 - c * 7 + (u * c) % 3).astype(F32)
+    Q2 = np.zeros((n_items, dim), F32)
+    Q2[np.arange(n_items), np.arange(n_items) % dim] = 1
+    return P, Q, P2, Q2
+
+
+def filter_case(dim, seed=66):
+    """The inputs of test_filter_mask_rows_strides_and_specials (tests/test_gpu_factor.py) at any dim >= 4: (P, Q, keyword
+    arguments, x_rows)."""
+    rng = np.random.default_rng(seed)
+    n_items, n_x = 300, 8
+    P = rng.standard_normal((6, dim)).astype(F32)
+    Q = rng.standard_normal((n_items, dim)).astype(F32)
+    P[4, 2], P[5, 1] = np.inf, np.nan
+    Q[10, 2], Q[11, 2], Q[12, 0], Q[13, 3], Q[14, 2] = 0.0, -2.0, np.nan, np.inf, -np.inf
+    p_index = np.array([0, 1, 2, 3, -1, 4, 5, 6])
+    free = host_model_fast(P, Q, 40, rows=np.arange(n_x), p_index=p_index, n_x_rows=n_x)
+    x_rows = [sorted(free[0][0, :30].tolist()), list(range(n_items)), [], sorted(rng.choice(n_items, 50, replace=False).tolist()), [],
+              sorted(rng.choice(n_items, 20, replace=False).tolist()), [3], []]
+    X = sp.csr_matrix((np.ones(sum(map(len, x_rows)), F32), np.concatenate([np.array(r, np.int64) for r in x_rows]),
+                       np.r_[0, np.cumsum([len(r) for r in x_rows])]), shape=(n_x, n_items))
+    rows = [0, 1, 2, 3, 4, 5, 6, 7, -1, n_x, 0, 3]
+    return P, Q, dict(rows=rows, p_index=p_index, n_x_rows=n_x, X=X, filter_interacted=True), x_rows
+
+
+MERGE_KINDS = ("chunk 0", "chunk 1", "short", "no vector", "both chunks")
+
+
+def merge_kind(ids, count, top_k, has_vector):
+    if not has_vector:
+        return 3
+    if count < top_k:
+        return 2
+    return 0 if (ids < 32).all() else 1 if (ids >= 32).all() else 4
+
+
+def merge_trip_case(seed=7, extra=40):
+    """More jobs than the merge kernel's grid (65,536 workgroups, one job per trip): 65,536 + 40 jobs over 64 items in two chunks
+    of one tile, dim 2, top_k 3.  The items of chunk 0 have a positive first component and those of chunk 1 a negative one, the
+    second component is 0 but at two admitted items (one per chunk).  A pattern's vector makes its merge take every entry from
+    chunk 0 ((a, 0), a > 0), every entry from chunk 1 ((-a, 0)), fewer than top_k entries in total ((0, +-inf): NaN against every 0,
+    +-inf against the two others; (NaN, 0): nothing), entries of both chunks (an ordinary vector), or it has no vector at all
+    (p_index -1).  Returns a dict: P, Q, mask, p_index, rows, n_x_rows, top_k, splits, kind (designed, per pattern)."""
+    rng = np.random.default_rng(seed)
+    n_rows, top_k = GRID_CAP + extra, 3
+    Q = np.zeros((64, 2), F32)
+    Q[:32, 0] = (1 + rng.random(32)).astype(F32)
+    Q[32:, 0] = -(1 + rng.random(32)).astype(F32)
+    Q[5, 1], Q[40, 1] = 1.0, 2.0
+    mask = (rng.random(64) < 0.6).astype(np.uint8)
+    mask[[5, 40, 0, 1, 2, 33, 34, 35]] = 1
+    kind = rng.integers(0, 5, PATTERNS)
+    kind[:5], kind[384:389] = [0, 1, 2, 3, 4], [3, 4, 1, 0, 2]
+    P = np.zeros((PATTERNS, 2), F32)
+    a = (0.5 + rng.random(PATTERNS)).astype(F32)
+    P[kind == 0, 0] = a[kind == 0]
+    P[kind == 1, 0] = -a[kind == 1]
+    short = np.flatnonzero(kind == 2)
+    P[short, 1] = rng.choice(np.array([np.inf, -np.inf], F32), len(short))
+    P[short[::3], 0], P[short[::3], 1] = np.nan, 0.0
+    both = kind == 4
+    P[both] = np.stack([rng.choice(np.array([0.25, -0.25], F32), both.sum()), F32(4.0) * a[both]], axis=1)       # items 40 and 5 lead
+    P[kind == 3] = a[kind == 3][:, None]                                    # (a vector nobody may read)
+    p_index = np.where(kind == 3, -1, np.arange(PATTERNS)).astype(np.int32)
+    return dict(P=P, Q=Q, mask=mask, p_index=p_index, rows=pattern_of(n_rows).astype(np.int32), n_x_rows=PATTERNS, top_k=top_k, splits=2,
+                kind=kind, n_rows=n_rows)
+
+
+def merge_trip_answer(case):
+    """(the host model's answer for the patterns, the kind of each pattern's answer)."""
+    want = host_model_fast(case["P"], case["Q"], case["top_k"], rows=np.arange(PATTERNS), p_index=case["p_index"], n_x_rows=PATTERNS,
+                           mask=case["mask"])
+    kinds = np.array([merge_kind(want[0][x, :want[2][x]], want[2][x], case["top_k"], case["p_index"][x] >= 0) for x in range(PATTERNS)])
+    return want, kinds
+
+
+@pytest.mark.parametrize("dim", CLASS_DIMS)
+def test_both_models_agree_on_the_class_edge_dims(dim):
+    """The rounding test's own shape (64 x 96) on the dims around the class rules: the fast model is the definition, every one
+    of the 6,144 scores is listed (none is NaN), and the last component -- the one a class rule one too generous drops -- moves
+    score bits in more than half of the rows."""
+    P, Q = rounding_vectors(64, 96, dim, seed=dim)
+    fast = host_model_fast(P, Q, 96)
+    assert_same(fast, host_model_plain(P, Q, 96), f"dim {dim}")
+    assert int(fast[2].sum()) == 64 * 96
+    S, less = host_scores(P, Q), host_scores(P[:, :dim - 1], Q[:, :dim - 1])
+    assert int((bits(S) != bits(less)).any(axis=1).sum()) > 32               # (a row whose last component is a denormal may keep its bits)
+
+
+@pytest.mark.parametrize("dim", [17, 65])
+def test_class_edge_case_is_the_definition_and_hangs_on_its_last_component(dim):
+    P, Q = class_edge_case(dim)
+    want = host_model_fast(P, Q, 65)
+    assert_same(want, host_model_plain(P, Q, 65), f"dim {dim}")
+    assert (want[2] == 65).all()
+    less = host_model_fast(P[:, :dim - 1], Q[:, :dim - 1], 17)
+    assert (less[0] != want[0][:, :17]).any(axis=1).all(), "dropping the last component must change every job's list"
+
+
+@pytest.mark.parametrize("dim", [13, 33])
+def test_operand_and_filter_cases_at_odd_dims(dim):
+    """Odd dims: the k-step of the last component has a zero half, behind which the padding begins."""
+    P, Q, P2, Q2 = operand_case(dim)
+    n_items = len(Q)
+    want = host_model_fast(P, Q, n_items)
+    assert_same(want, host_model_plain(P, Q, n_items), "P = I")
+    assert_same(host_model_fast(P2, Q2, n_items), host_model_plain(P2, Q2, n_items), "Q = I")
+    for u in range(len(P)):
+        assert np.array_equal(np.sort(want[1][u]), np.sort(Q[:, u % dim]))
+    assert len(P) > dim and dim % 2 == 1
+    P, Q, kw, x_rows = filter_case(dim)
+    want = host_model_plain(P, Q, 10, **kw)
+    assert_same(host_model_fast(P, Q, 10, **kw), want, "filter")
+    assert want[2].tolist() == [10, 0, 10, 10, 0, 10, 0, 0, 0, 0, 10, 10]
+    assert not set(want[0][0].tolist()) & set(x_rows[0]) and np.isposinf(want[1][5]).any()
+
+
+def test_merge_trip_case_is_the_definition_and_mixes_its_kinds_across_the_cap():
+    case = merge_trip_case()
+    want, kinds = merge_trip_answer(case)
+    kw = dict(rows=np.arange(PATTERNS), p_index=case["p_index"], n_x_rows=PATTERNS, mask=case["mask"])
+    assert_same(want, host_model_plain(case["P"], case["Q"], case["top_k"], **kw), "patterns")
+    assert np.array_equal(kinds, case["kind"]), "every pattern's answer is of the kind it was built for"
+    n_rows, at = case["n_rows"], case["rows"]
+    assert n_rows == GRID_CAP + 40 and GRID_CAP % PATTERNS == 384 and np.array_equal(at, np.arange(n_rows) % PATTERNS)
+    late, early = kinds[at[GRID_CAP:]], kinds[at[:n_rows - GRID_CAP]]
+    for k in (0, 1, 2, 3):                                                  # among the rows past the cap and among their partners
+        assert (late == k).any() and (early == k).any(), MERGE_KINDS[k]
+    assert int((late != early).sum()) >= 10
+    short = want[2][(kinds == 2)]
+    assert set(short.tolist()) == {0, 2}                                    # (NaN, 0): nothing; (0, +-inf): the two items with a second component
+    full = tiled(want, n_rows)
+    assert full[0].shape == (n_rows, 3) and np.array_equal(full[0][GRID_CAP + 3], want[0][387])
+
+
 # ---------------------------------------------------------------------------------------------- stack_bias
 def test_stack_bias_is_the_references_hstack():
     from rtrec_amd.utils.factors import stack_bias

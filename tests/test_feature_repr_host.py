@@ -118,6 +118,40 @@ def same_bits(a, b):
     return a.shape == b.shape and bool(((bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))).all())
 
 
+# ---------------------------------------------------------------------------------------------- more slots than one trip of the grid
+def grid_trip_case(layout, seed=31):
+    """65,537 jobs x width 256 = 16,777,472 slots, 256 more than the kernel's 65,536 workgroups x 256 threads: the slots of the
+    last job are second trips.  Four feature rows of 3, 0, 1 and 2 entries over a table of five features (PLAIN: dim_e 256, a
+    stacking layout: dim_e 254), the job rows drawn per pattern from those four, -1 and 4 (no row); pattern 0 names the full row
+    and pattern 384 -- job 65,536's -- the empty one.  (ptr, col, val, E, bias, job rows per pattern)."""
+    from tests.test_factor_host import PATTERNS
+    rng = np.random.default_rng(seed)
+    dim_e = 256 if layout == PLAIN else 254
+    ptr = np.array([0, 3, 3, 4, 6], np.int32)
+    col = np.array([4, 0, 2, 1, 3, 3], np.int32)
+    val = np.array([1.0, 2.0, 0.5, 3.0, 1.0, 1.0], F32)
+    E = (rng.standard_normal((5, dim_e)).astype(F32) + F32(3.0) * np.sign(rng.standard_normal((5, dim_e))).astype(F32)).astype(F32)
+    bias = (F32(2.0) + rng.random(5).astype(F32)).astype(F32)
+    jobs = rng.choice(np.array([0, 1, 2, 3, -1, 4], np.int32), PATTERNS).astype(np.int32)
+    jobs[0], jobs[384] = 0, 1
+    return ptr, col, val, E, bias, jobs
+
+
+@pytest.mark.parametrize("layout", [PLAIN, USER])
+def test_grid_trip_case_is_the_definition_and_its_last_job_differs_from_the_first(layout):
+    from tests.test_factor_host import GRID_CAP, PATTERNS, pattern_of
+    ptr, col, val, E, bias, jobs = grid_trip_case(layout)
+    want = repr_fast(ptr, col, val, E, bias, layout, jobs)
+    plain = repr_plain(ptr, col, val, E, bias, layout, jobs[:40])
+    assert same_bits(want[0][:40], plain[0]) and np.array_equal(want[1][:40], plain[1])
+    n_jobs, width = GRID_CAP + 1, want[0].shape[1]
+    assert width == 256 and n_jobs * width == GRID_CAP * 256 + 256 and pattern_of(n_jobs)[GRID_CAP] == 384 and len(jobs) == PATTERNS
+    first, last = 0, pattern_of(n_jobs)[GRID_CAP]
+    assert want[1][first] == 1 and want[1][last] == 0
+    assert (want[0][first] != want[0][last]).all(), "job 65,536 differs from job 0 in every slot"
+    assert set(want[1].tolist()) == {0, 1} and len({want[0][x].tobytes() for x in range(PATTERNS)}) == 4
+
+
 # ---------------------------------------------------------------------------------------------- order and rounding
 def adversarial_case(n_rows=300, n_features=50, dim=12, seed=5):
     """Feature rows of 1..12 entries (sorted distinct columns, values 1, 2 or 3) against a table whose ROWS span 2^-8 .. 2^8 in

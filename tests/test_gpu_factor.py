@@ -7,25 +7,30 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from tests.test_factor_host import (F32, HYBRID_CASES, assert_same, check_factor_and_hybrid, fitted_model, host_model_fast, host_model_plain,
-                                    host_scores, rounding_vectors)
+from tests.test_factor_host import (CLASS_DIMS, F32, GRID_CAP, HYBRID_CASES, assert_same, check_factor_and_hybrid, class_edge_case, filter_case,
+                                    fitted_model, host_model_fast, host_model_plain, host_scores, merge_trip_answer, merge_trip_case, operand_case,
+                                    rounding_vectors, tiled)
 
 pytestmark = pytest.mark.gpu
 
 
-def run_op(P, Q, top_k, rows=None, p_index=None, n_x_rows=None, X=None, mask=None, filter_interacted=False, splits=0, pad=0, seed=0):
+def run_op(P, Q, top_k, rows=None, p_index=None, n_x_rows=None, X=None, mask=None, filter_interacted=False, splits=0, pad=0, seed=0,
+           pad_value=None):
     """torch.ops.rtrec_amd.factor_topk on host arrays, as the host models take them.  `pad` > 0: both strides are wider than the
-    widths (and qt has rows beyond dim), with seeded values behind them."""
+    widths (and qt has rows beyond dim), with seeded values behind them, or `pad_value` in all three places (P's columns beyond
+    dim, qt's rows beyond dim, qt's columns beyond n_items): a finite pad times a zero operand leaves a score as it is, a NaN
+    does not."""
     import torch
     from rtrec_amd import ops  # noqa: F401  (registers torch.ops.rtrec_amd.*)
     P, Q = np.asarray(P, F32), np.asarray(Q, F32)
     dim, n_items = P.shape[1], len(Q)
     rng = np.random.default_rng(seed)
-    Pd = np.concatenate([P, rng.standard_normal((len(P), pad)).astype(F32) * 100], axis=1) if pad else P
+    behind = lambda *shape: rng.standard_normal(shape).astype(F32) * 100 if pad_value is None else np.full(shape, pad_value, F32)
+    Pd = np.concatenate([P, behind(len(P), pad)], axis=1) if pad else P
     Qt = np.ascontiguousarray(Q.T)
     if pad:
-        Qt = np.concatenate([Qt, rng.standard_normal((dim, pad)).astype(F32) * 100], axis=1)
-        Qt = np.concatenate([Qt, rng.standard_normal((pad, n_items + pad)).astype(F32) * 100], axis=0)
+        Qt = np.concatenate([Qt, behind(dim, pad)], axis=1)
+        Qt = np.concatenate([Qt, behind(pad, n_items + pad)], axis=0)
     if dim == 0 or Qt.shape[1] == 0:
         Qt = np.zeros((max(dim, 1), max(Qt.shape[1], 1)), F32)
     up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to("cuda:0")
@@ -74,7 +79,7 @@ def test_identity_vectors_against_an_asymmetric_integer_matrix():
 
 
 # ---------------------------------------------------------------------------------------------- 2. the rounding order
-@pytest.mark.parametrize("dim", [1, 2, 3, 12, 13, 64, 255, 256])
+@pytest.mark.parametrize("dim", [1, 2, 3, 12, 13, 64, 255, 256] + CLASS_DIMS)
 def test_scores_are_the_ascending_fmaf_chain_bit_for_bit(dim):
     """Decides between the MFMA and a VALU chain: every one of the 64 x 96 scores must carry the bits of
     fmaf(p[dim-1], q[dim-1], ... fmaf(p[0], q[0], +0)) on vectors where another order, an unfused multiply or a wider
@@ -104,9 +109,61 @@ def test_every_edge_of_the_tiling(edge_vectors, n_items):
     P, Q = edge_vectors[0], edge_vectors[1][:n_items]
     want = host_model_fast(P, Q, 128)
     for n_rows in (1, 31, 32, 33, 130):
-        for top_k in (1, 10, 64, 128):
+        for top_k in (1, 10, 16, 17, 64, 65, 128):
             for splits in (0, 1, 2, 7):
                 assert_same(run_op(P[:n_rows], Q, top_k, splits=splits), cut(want, n_rows, top_k), (n_items, n_rows, top_k, splits))
+
+
+@pytest.mark.parametrize("dim", [17, 65])
+def test_both_class_choices_change_in_one_call(dim):
+    """200 items x 40 jobs one past a dim class (17 > 16, 65 > 64) at top_k one past a k class (17 > 16, 65 > 64), in one chunk
+    and in three; the last component decides every list (tests/test_factor_host.py), so a rule that sends dim 17 to the 16-class
+    or dim 65 to the 64-class shows in every job."""
+    P, Q = class_edge_case(dim)
+    want = host_model_fast(P, Q, 65)
+    for top_k in (17, 65):
+        for splits in (1, 3):
+            assert_same(run_op(P, Q, top_k, splits=splits), cut(want, 40, top_k), (dim, top_k, splits))
+
+
+# ---------------------------------------------------------------------------------------------- 3b. NaN behind dim and behind n_items
+NAN_PAD = 32            # rows of qt behind dim: enough for every row a whole group of 16 k-steps could name (2 x 16 x 2 = 64 at dim 33)
+
+
+@pytest.mark.parametrize("dim", [13, 33])
+def test_nan_padding_is_never_read_into_a_score(dim):
+    """The operand-map case and the filter / mask / rows case with NaN in P's columns beyond dim, in qt's rows beyond dim and in
+    qt's columns beyond n_items: a load that misses its guard multiplies a finite pad by a zero operand and changes nothing, a
+    NaN pad poisons the score.  Odd dims: the last k-step has a zero half.  The expected answer is the unpadded one."""
+    P, Q, P2, Q2 = operand_case(dim)
+    n_items = len(Q)
+    nan = dict(pad=NAN_PAD, pad_value=np.nan)
+    want = host_model_fast(P, Q, n_items)
+    for splits in (1, 2):
+        assert_same(run_op(P, Q, n_items, splits=splits, **nan), want, ("P = I", splits))
+        assert_same(run_op(P2, Q2, n_items, splits=splits, **nan), host_model_fast(P2, Q2, n_items), ("Q = I", splits))
+    P, Q, kw, _ = filter_case(dim)
+    want = host_model_fast(P, Q, 10, **kw)
+    few = np.zeros(len(Q), np.uint8)
+    few[[3, 12, 77, 150, 299]] = 1
+    want_few = host_model_fast(P, Q, 10, mask=few, **kw)
+    for splits in (0, 1, 3):
+        assert_same(run_op(P, Q, 10, splits=splits, **nan, **kw), want, ("filter", splits))
+        assert_same(run_op(P, Q, 10, mask=few, splits=splits, **nan, **kw), want_few, ("filter and mask", splits))
+
+
+# ---------------------------------------------------------------------------------------------- 3c. the merge's second trip
+def test_the_merge_serves_more_jobs_than_its_grid():
+    """65,536 + 40 jobs in two chunks: the merge kernel's grid is capped at 65,536 workgroups, so the last 40 jobs are second
+    trips of the workgroups that served jobs 0 .. 39, and the two jobs of a workgroup differ in where their entries come from
+    (tests/test_factor_host.py, merge_trip_case)."""
+    case = merge_trip_case()
+    want, _ = merge_trip_answer(case)
+    n_rows = case["n_rows"]
+    assert n_rows > GRID_CAP
+    got = run_op(case["P"], case["Q"], case["top_k"], rows=case["rows"], p_index=case["p_index"], n_x_rows=case["n_x_rows"], mask=case["mask"],
+                 splits=case["splits"])
+    assert_same(got, tiled(want, n_rows), "merge, second trip")
 
 
 # ---------------------------------------------------------------------------------------------- 4. ties

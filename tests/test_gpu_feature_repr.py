@@ -9,7 +9,7 @@ import pytest
 
 from tests.test_factor_host import F32, bits
 from tests.test_feature_repr_host import (ITEM, PLAIN, USER, adversarial_case, check_engine_feature_factors, check_feature_api, check_serving,
-                                          feature_model, fma32, repr_fast, repr_plain, same_bits)
+                                          feature_model, fma32, grid_trip_case, repr_fast, repr_plain, same_bits)
 
 pytestmark = pytest.mark.gpu
 
@@ -117,6 +117,21 @@ def test_the_adversarial_case_of_the_host_file_and_denormals():
     got = run_op(ptr2, col2, val2, E2)
     check(got, repr_plain(ptr2, col2, val2, E2), "denormals")
     assert (got[0] > 0).all() and (got[0] < np.finfo(F32).tiny).all()
+
+
+@pytest.mark.parametrize("component_major", [False, True])
+@pytest.mark.parametrize("layout", [PLAIN, USER])
+def test_more_slots_than_one_trip_of_the_grid(layout, component_major):
+    """65,537 jobs x width 256: the 256 slots of the last job lie beyond 65,536 workgroups x 256 threads and are reached by the
+    grid stride; that job is empty where job 0 is full (tests/test_feature_repr_host.py, grid_trip_case).  The answer is the host
+    model's on the 509 patterns, tiled; the slots outside the written region must survive, as in every call of run_op."""
+    from tests.test_factor_host import GRID_CAP, pattern_of
+    ptr, col, val, E, bias, jobs = grid_trip_case(layout)
+    want = repr_fast(ptr, col, val, E, bias, layout, jobs)
+    n_jobs = GRID_CAP + 1
+    at = pattern_of(n_jobs)
+    got = run_op(ptr, col, val, E, bias, layout, jobs[at], n_jobs, component_major)
+    check(got, (want[0][at], want[1][at]), (layout, component_major))
 
 
 def test_empty_inputs_and_the_ops_own_checks():

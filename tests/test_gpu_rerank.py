@@ -12,7 +12,7 @@ from rtrec_amd import _native
 from tests.test_explain_host import bits, golden
 from tests.test_gpu_explain import LENGTHS, tie_case
 from tests.test_rerank_host import (assert_same, cpu_slim, golden_permuted_lists, golden_scoring, host_model, host_model_vectorised,
-                                    _batch)
+                                    pairs_trip_case, _batch)
 
 pytestmark = pytest.mark.gpu
 
@@ -189,6 +189,20 @@ def test_nan_and_infinite_scores():
     assert want[0][1].tolist() == [inf, inf, -inf, 0.0, inf] and want[2][1].tolist() == [4, 1, 0, 3, 2]
     for waves in WAVES:
         assert_same(run_op(X, W, None, ids, np.array([5, 5]), 5, 5, waves=waves), want, "nan / inf")
+
+
+# ---------------------------------------------------------------------------------------------- more rows than the grid
+@pytest.mark.parametrize("waves", WAVES)
+def test_more_list_rows_than_the_grid(waves):
+    """65,536 + 3 list rows onto 12 rows of X through row_ids: the grid is capped at 65,536 workgroups, so the last three rows are
+    second trips, and across the cap an unstaged row of X meets a staged one of one entry in both orders and a full list an empty
+    one (tests/test_rerank_host.py, pairs_trip_case): the staged row, the choice between LDS and global memory and the wave
+    counts' slots of a workgroup's first row must not reach its second.  list_k 5, top_k 3, filter_interacted."""
+    X, W, rows, ids, counts = pairs_trip_case()
+    want = host_model_vectorised(X, W, rows, ids, counts, 3, True)
+    at = np.arange(65536 + 3) % len(rows)
+    got = run_op(X, W, rows[at], ids[at], counts[at], 5, 3, True, waves=waves)
+    assert_same(got, tuple(w[at] for w in want), f"second trip, {waves} wave(s)")
 
 
 # ---------------------------------------------------------------------------------------------- CANDIDATES mode

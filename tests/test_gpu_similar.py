@@ -6,10 +6,11 @@ must be written)."""
 import numpy as np
 import pytest
 
-from tests.test_factor_host import F32, rounding_vectors
-from tests.test_similar_host import (FLT_MAX, assert_same_blend, assert_same_lists, check_serving_and_facade, check_similar_api, golden_answer,
-                                     golden_cases, golden_inputs, host_blend, host_norms_fast, host_norms_plain, host_similar_fast,
-                                     lists_of, one_scan_cases, special_vectors, dbits)
+from tests.test_factor_host import CLASS_DIMS, F32, GRID_CAP, PATTERNS, pattern_of, rounding_vectors, tiled
+from tests.test_similar_host import (FLT_MAX, assert_same_blend, assert_same_lists, blend_trip_case, caller_norms_case, check_serving_and_facade,
+                                     check_similar_api, golden_answer, golden_cases, golden_inputs, host_blend, host_norms_fast,
+                                     host_norms_plain, host_similar_fast, lists_of, one_scan_cases, query_norms_case, same_or_both_nan,
+                                     similar_class_case, similar_operand_case, similar_trip_case, special_vectors, dbits)
 
 pytestmark = pytest.mark.gpu
 
@@ -56,18 +57,21 @@ def test_norms_are_the_chain_and_a_correctly_rounded_root_bit_for_bit(dim):
 
 
 # ---------------------------------------------------------------------------------------------- 2. the cosine top-k
-def run_similar(Q, norms, queries, top_k, P=None, p_norms=None, mask=None, write_cosine=False, splits=0, pad=0, want_div=True, seed=0):
+def run_similar(Q, norms, queries, top_k, P=None, p_norms=None, mask=None, write_cosine=False, splits=0, pad=0, want_div=True, seed=0,
+                pad_value=None):
     """torch.ops.rtrec_amd.factor_similar_topk on host arrays, as the host models take them.  `pad` > 0: the strides are wider
-    than the widths (and qt has rows beyond dim), with seeded values behind them."""
+    than the widths (and qt has rows beyond dim), with seeded values behind them, or `pad_value` in all three places (qt's rows
+    beyond dim, qt's columns beyond n_items, p's columns beyond dim)."""
     import torch
     from rtrec_amd import ops  # noqa: F401
     Q = np.asarray(Q, F32)
     n_items, dim = Q.shape
     rng = np.random.default_rng(seed)
+    behind = lambda *shape: rng.standard_normal(shape).astype(F32) * 100 if pad_value is None else np.full(shape, pad_value, F32)
     Qt = np.ascontiguousarray(Q.T)
     if pad:
-        Qt = np.concatenate([Qt, rng.standard_normal((dim, pad)).astype(F32) * 100], axis=1)
-        Qt = np.concatenate([Qt, rng.standard_normal((pad, n_items + pad)).astype(F32) * 100], axis=0)
+        Qt = np.concatenate([Qt, behind(dim, pad)], axis=1)
+        Qt = np.concatenate([Qt, behind(pad, n_items + pad)], axis=0)
     n = len(P) if P is not None else len(queries)
     ids = torch.full((n, top_k), 12345, dtype=torch.int32, device="cuda:0")               # poisoned: every slot must be written
     scores = torch.full((n, top_k), 7.0, dtype=torch.float32, device="cuda:0")
@@ -79,7 +83,7 @@ def run_similar(Q, norms, queries, top_k, P=None, p_norms=None, mask=None, write
     if P is not None:
         Pd = np.asarray(P, F32)
         if pad:
-            Pd = np.concatenate([Pd, rng.standard_normal((n, pad)).astype(F32) * 100], axis=1)
+            Pd = np.concatenate([Pd, behind(n, pad)], axis=1)
         d_p, d_pn = _up(Pd, np.float32), _up(p_norms, np.float32)
     torch.ops.rtrec_amd.factor_similar_topk(None if queries is None else _up(queries, np.int32), d_p, d_pn, _up(Qt, np.float32), n_items, dim,
                                             _up(norms, np.float32), None if mask is None else _up(np.asarray(mask) != 0, np.uint8), top_k,
@@ -113,7 +117,7 @@ def test_operand_map_on_an_asymmetric_integer_matrix():
         assert q not in got[0][r].tolist() and got[0][r, -1] == -1 and np.isneginf(got[1][r, -1])
 
 
-@pytest.mark.parametrize("dim", [1, 2, 3, 12, 13, 64, 255, 256])
+@pytest.mark.parametrize("dim", [1, 2, 3, 12, 13, 64, 255, 256] + CLASS_DIMS)
 def test_every_s1_is_the_chain_and_one_division_bit_for_bit(dim):
     """Every s1 of 96 x 95 pairs must carry the bits of fl(chain / norm) on vectors where another order, an unfused multiply, a
     reciprocal or a wider accumulator changes them (tests/test_similar_host.py counts how often they do)."""
@@ -223,6 +227,76 @@ def test_the_two_entry_points_run_the_same_scan():
                 assert_same(sim[:3], want[top_k], what)
 
 
+# ---------------------------------------------------------------------------------------------- 2b. class edges, padding, norms, second trips
+@pytest.mark.parametrize("dim", [17, 65])
+def test_both_class_choices_change_in_one_similar_call(dim):
+    """200 items, 40 queries one past a dim class at top_k one past a k class, in one chunk and in three, with the cosine
+    division; the last component decides every list (tests/test_similar_host.py)."""
+    Q, norms, queries = similar_class_case(dim)
+    for cosine in (False, True):
+        want = host_similar_fast(Q, norms, queries, 65, write_cosine=cosine)
+        for top_k in (17, 65):
+            w = (want[0][:, :top_k], want[1][:, :top_k], np.minimum(want[2], top_k), want[3])
+            for splits in (1, 3):
+                same(run_similar(Q, norms, queries, top_k, write_cosine=cosine, splits=splits), w, (dim, top_k, splits, cosine))
+
+
+@pytest.mark.parametrize("dim", [13, 33])
+def test_nan_padding_is_never_read_into_an_s1(dim):
+    """The operand-map case with NaN in qt's rows beyond dim, in qt's columns beyond n_items and in the brought vectors' columns
+    beyond dim (tests/test_gpu_factor.py says why NaN, why odd dims and why 32 rows); the expected answer is the unpadded one."""
+    from tests.test_gpu_factor import NAN_PAD
+    Q, norms, queries = similar_operand_case(dim)
+    want = host_similar_fast(Q, norms, queries, 40)
+    for splits in (1, 2):
+        same(run_similar(Q, norms, queries, 40, splits=splits, pad=NAN_PAD, pad_value=np.nan), want, ("columns", splits))
+        same(run_similar(Q, norms, queries, 40, P=Q[queries], p_norms=norms[queries], splits=splits, pad=NAN_PAD, pad_value=np.nan), want,
+             ("brought", splits))
+
+
+def test_the_similar_merge_serves_more_jobs_than_its_grid():
+    """65,536 + 40 jobs in two chunks with write_cosine: the merge's grid is capped at 65,536 workgroups, and across the cap live
+    queries meet zero-norm and unknown ones in both orders (tests/test_similar_host.py, similar_trip_case) -- `live` and `total`
+    of a workgroup's first job must not reach its second.  Once with the queries' own columns, once with brought vectors."""
+    case = similar_trip_case()
+    Q, norms, at, n_rows = case["Q"], case["norms"], case["at"], case["n_rows"]
+    assert n_rows > GRID_CAP
+    want = host_similar_fast(Q, norms, case["queries"], 3, write_cosine=True)
+    same(run_similar(Q, norms, case["queries"][at], 3, write_cosine=True, splits=2), tiled(want, n_rows), "queries")
+    want = host_similar_fast(Q, norms, case["queries"], 3, P=case["P"], p_norms=case["p_norms"], write_cosine=True)
+    got = run_similar(Q, norms, case["queries"][at], 3, P=case["P"][at], p_norms=case["p_norms"][at], write_cosine=True, splits=2)
+    same(got, tiled(want, n_rows), "brought")
+
+
+@pytest.mark.parametrize("splits", [1, 3])
+def test_item_and_query_norms_are_the_callers(splits):
+    """NaN, +-inf, negative, -0.0 and denormal norms as divisors of s1 and as query norms (tests/test_similar_host.py,
+    caller_norms_case / query_norms_case): "s1 is not NaN" decides who competes and "a norm that is not > 0 empties a cosine list"
+    -- in the scan's epilogue (one chunk) and in the merge (three), which must agree with the host and so with each other."""
+    Q, norms, queries, _ = caller_norms_case()
+    for top_k in (20, 99):
+        for cosine in (False, True):
+            want = host_similar_fast(Q, norms, queries, top_k, write_cosine=cosine)
+            same_or_both_nan(run_similar(Q, norms, queries, top_k, write_cosine=cosine, splits=splits), want, (top_k, cosine))
+    Q, norms, P, p_norms = query_norms_case()
+    for cosine in (False, True):
+        want = host_similar_fast(Q, norms, None, 20, P=P, p_norms=p_norms, write_cosine=cosine)
+        same_or_both_nan(run_similar(Q, norms, None, 20, P=P, p_norms=p_norms, write_cosine=cosine, splits=splits), want, ("brought", cosine))
+
+
+@pytest.mark.parametrize("component_major", [False, True])
+def test_norms_of_more_vectors_than_one_trip_of_the_grid(component_major):
+    """65,536 workgroups x 256 threads + 300 vectors of dim 1: the last 300 are second trips.  The vectors repeat 509 patterns
+    of special_vectors (zero, denormal squares, overflow), so vector r and vector r + 16,777,216 differ."""
+    n = GRID_CAP * 256 + 300
+    V = special_vectors(PATTERNS, 1, seed=1)
+    want = host_norms_fast(V)
+    assert want[1] == 0 and np.isinf(want[5]) and (GRID_CAP * 256) % PATTERNS != 0
+    at = pattern_of(n)
+    got = run_norms(V[at], component_major, 0)
+    assert np.array_equal(got.view(np.int32), want[at].view(np.int32)), np.flatnonzero(got != want[at])[:5]
+
+
 # ---------------------------------------------------------------------------------------------- 3. the blend
 def run_blend(n_items, A, B, keep, a_div=None, exclude=None, waves=0, pad=0):
     import torch
@@ -302,6 +376,19 @@ def test_blend_contract_edges_on_the_device():
             got = run_blend(24, a, b, keep, waves=waves, **kw)
             assert_same_blend(got, want, (waves, keep, sorted(kw)))
             assert not np.isnan(got[1]).any()
+
+
+@pytest.mark.parametrize("waves", [1, 4])
+def test_the_blend_serves_more_rows_than_its_grid(waves):
+    """65,536 + 3 rows: the list stage's grid is capped at 65,536 workgroups, so the last three rows are second trips, and
+    across the cap a long union follows a short one and the reverse (tests/test_similar_host.py, blend_trip_case): holes, values
+    and lengths of a workgroup's first row must not reach its second."""
+    n_items, A, B, a_div, exclude, _ = blend_trip_case()
+    want = host_blend(n_items, A, B, 5, a_div=a_div, exclude=exclude)
+    n_rows = GRID_CAP + 3
+    at = pattern_of(n_rows)
+    got = run_blend(n_items, tuple(a[at] for a in A), tuple(b[at] for b in B), 5, a_div=a_div[at], exclude=exclude[at], waves=waves)
+    assert_same_blend(got, tiled(want, n_rows), f"second trip, {waves} wave(s)")
 
 
 # ---------------------------------------------------------------------------------------------- 4. the API on the device

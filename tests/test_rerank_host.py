@@ -101,6 +101,56 @@ def host_model_vectorised(X, W, rows, ids, counts, top_k, filter_interacted=Fals
     return scores, support, order, count
 
 
+PAIRS_TRIP_LENGTHS = [0, 1, 128, 129, 2048, 2049] * 2     # rows of X on both sides of the kernel's two staging limits (128 and 2,048 entries)
+
+
+def pairs_trip_case(seed=29):
+    """More list rows than the list stage's grid (65,536): the 509 patterns of a 65,536 + 3 row call (row r carries pattern
+    r % 509; tests/test_factor_host.py).  X has 12 rows of PAIRS_TRIP_LENGTHS entries over 4,000 items, W 40 stored columns of 30
+    weights (every column stores rows 0 .. 9, which every non-empty row of X holds some of); a pattern is a row of X, a list of 5
+    ids (some of them empty columns, -1 or beyond the catalogue) and a count of 0 .. 5.  Across the cap: row 0 is an unstaged row
+    (2,049 entries) and row 65,536 a staged one of one entry, rows 1 / 65,537 the reverse, row 2 a full list and row 65,538 an
+    empty one.  (X, W, rows, ids, counts) per pattern, list_k 5."""
+    rng = np.random.default_rng(seed)
+    I, P = 4000, 509
+    xi = [np.sort(np.r_[rng.choice(10, min(L, 1 + L // 256), replace=False), 10 + rng.choice(I - 10, L - min(L, 1 + L // 256), replace=False)])
+          for L in PAIRS_TRIP_LENGTHS]
+    X = sp.csr_matrix((rng.standard_normal(sum(PAIRS_TRIP_LENGTHS)).astype(np.float32), np.concatenate(xi).astype(np.int32),
+                       np.cumsum([0] + PAIRS_TRIP_LENGTHS)), shape=(len(PAIRS_TRIP_LENGTHS), I))
+    wi = [np.sort(np.r_[np.arange(10), 10 + rng.choice(I - 10, 20, replace=False)]) for _ in range(40)]
+    wptr = np.zeros(I + 1, np.int64)
+    wptr[1:41] = np.cumsum([len(w) for w in wi])
+    wptr[41:] = wptr[40]
+    W = sp.csc_matrix((rng.standard_normal(40 * 30).astype(np.float32), np.concatenate(wi).astype(np.int32), wptr), shape=(I, I))
+    rows = rng.integers(0, 12, P).astype(np.int32)
+    rows[::31] = rng.choice(np.array([-1, 12], np.int32), len(rows[::31]))
+    ids = rng.integers(0, 46, (P, 5)).astype(np.int32)
+    ids[rng.random((P, 5)) < 0.05] = -1
+    ids[rng.random((P, 5)) < 0.05] = I
+    counts = rng.integers(0, 6, P).astype(np.int32)
+    rows[[0, 1, 2]], rows[[384, 385, 386]] = [5, 7, 3], [1, 11, 2]
+    counts[[0, 1, 2]], counts[[384, 385, 386]] = [5, 5, 5], [5, 5, 0]
+    ids[[0, 1, 2, 384, 385, 386]] = np.stack([rng.permutation(40)[:5] for _ in range(6)])
+    return X, W, rows, ids, counts
+
+
+def test_pairs_trip_case_is_the_definition_and_crosses_the_staging_limits_across_the_cap():
+    X, W, rows, ids, counts = pairs_trip_case()
+    want = host_model_vectorised(X, W, rows, ids, counts, 3, True)
+    assert_same(want, host_model(X, W, rows, ids, counts, 3, True), "patterns")
+    lens = np.diff(X.indptr)
+    assert lens.tolist() == PAIRS_TRIP_LENGTHS and 65536 % 509 == 384
+    row_len = np.where((rows >= 0) & (rows < 12), lens[np.clip(rows, 0, 11)], 0)
+    assert set(row_len.tolist()) == set(PAIRS_TRIP_LENGTHS)
+    for limit in (128, 2048):                       # both launch widths: an unstaged row and a one-entry row share a workgroup, in both orders
+        assert row_len[0] > limit and row_len[384] == 1 and row_len[1] == 1 and row_len[385] > limit
+    assert counts[2] == 5 and counts[386] == 0 and want[3][2] == 3 and want[3][386] == 0
+    assert (want[1][[0, 1, 384, 385]] > 0).all() and (want[0][[0, 1, 384, 385]] != 0).all()      # every pair of those rows has support
+    filtered = sum(int(((want[1][x] >= 0) & np.isin(ids[x], X.indices[X.indptr[rows[x]]:X.indptr[rows[x] + 1]])).sum())
+                   for x in range(509) if 0 <= rows[x] < 12)
+    assert filtered > 50 and (want[3] < np.minimum(counts, 3)).any()                             # the filter decides lists
+
+
 def assert_same(got, want, what=""):
     names = ("scores", "support", "order", "count")
     for name, g, w in zip(names, got, want):

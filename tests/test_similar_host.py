@@ -393,6 +393,203 @@ def test_similar_with_unit_norms_is_the_factor_model():
             assert (want[10][0] == np.arange(160, 150, -1)).all() and (np.diff(host_scores(P, Q), axis=1) > 0).all()
 
 
+# ---------------------------------------------------------------------------------------------- cases for the device tests
+def same_or_both_nan(got, want, what=""):
+    """assert_same_lists for lists that may hold a NaN SCORE (fl(+-inf / +inf) with write_cosine and an infinite query norm): ids
+    and counts with ==, a score by its bits, a NaN by being one -- its sign and payload are not part of the contract (x86's
+    default NaN is negative, the device's positive)."""
+    g_ids, g_sc, g_cnt = [np.asarray(a) for a in got[:3]]
+    w_ids, w_sc, w_cnt = [np.asarray(a) for a in want[:3]]
+    assert np.array_equal(g_cnt, w_cnt), (what, "counts", g_cnt, w_cnt)
+    assert np.array_equal(g_ids, w_ids), (what, "ids", np.argwhere(g_ids != w_ids)[:5])
+    ok = (bits(g_sc) == bits(w_sc)) | (np.isnan(g_sc) & np.isnan(w_sc))
+    assert ok.all(), (what, "scores", np.argwhere(~ok)[:5])
+    if len(got) > 3 and got[3] is not None:
+        g, w = np.asarray(got[3], F32), np.asarray(want[3], F32)
+        assert ((g.view(np.int32) == w.view(np.int32)) | (np.isnan(g) & np.isnan(w))).all(), (what, "div")
+
+
+def similar_class_case(dim):
+    """tests/test_factor_host.py's class_edge_case as a similar-items call: 200 items, the first 40 as queries."""
+    from tests.test_factor_host import class_edge_case
+    _, Q = class_edge_case(dim)
+    Q[:, dim - 1] = F32(8.0) * np.where(np.arange(200) % 3 == 0, -1, 1).astype(F32)
+    return Q, host_norms_fast(Q), np.arange(40, dtype=np.int32)
+
+
+def similar_operand_case(dim):
+    """test_operand_map_on_an_asymmetric_integer_matrix of tests/test_gpu_similar.py at any dim."""
+    n_items = 40
+    i, c = np.meshgrid(np.arange(n_items), np.arange(dim), indexing="ij")
+    Q = (i * 37 + c * 3 + (i * c) % 5 - 400).astype(F32)
+    return Q, host_norms_fast(Q), np.r_[np.arange(n_items), [3]].astype(np.int32)
+
+
+ODD_NORMS = (np.nan, np.inf, None, 1e-45, -np.inf, -0.0)            # None: the item's own norm, negated
+
+
+def caller_norms_case(seed=12):
+    """The norms are the caller's: 100 items of dim 6 whose computed norms are overwritten at six items with NaN, +inf, a negated
+    value, a denormal (1e-45), -inf and -0.0; the queries are an ordinary item, those six and another ordinary one.  As a DIVISOR
+    of s1 they make NaN (never competes), +-0, a sign flip, +-inf (competes as a number: it leads or ends the list) and -+0; as a
+    QUERY norm with write_cosine only +inf and the denormal are > 0.  (Q, norms, queries, odd items)."""
+    rng = np.random.default_rng(seed)
+    Q = rng.standard_normal((100, 6)).astype(F32)
+    norms = host_norms_fast(Q)
+    odd = np.array([11, 23, 37, 52, 68, 90])
+    for i, v in zip(odd, ODD_NORMS):
+        norms[i] = -norms[i] if v is None else F32(v)
+    return Q, norms, np.r_[[3], odd, [77]].astype(np.int32), odd
+
+
+def query_norms_case(seed=12):
+    """caller_norms_case with brought vectors whose norms are the caller's too: NaN, +inf, a negative value, -0.0, a denormal and
+    two ordinary ones.  (Q, norms, P, p_norms)."""
+    Q, norms, _, _ = caller_norms_case(seed)
+    rng = np.random.default_rng(seed + 1)
+    P = rng.standard_normal((7, 6)).astype(F32)
+    p_norms = host_norms_fast(P)
+    p_norms[:5] = [np.nan, np.inf, -p_norms[2], -0.0, 1e-45]
+    return Q, norms, P, p_norms
+
+
+def similar_trip_case(seed=17, extra=40):
+    """More jobs than the similar merge kernel's grid (65,536): 65,536 + 40 jobs over 64 items (two chunks of one tile), dim 2,
+    top_k 3, write_cosine.  A pattern's query is a live item, the zero-norm item 7 (an empty cosine list) or outside the
+    catalogue (no vector); the brought vectors of the second form are ordinary or zero (norm 0).  Norms are zero or ordinary
+    here: the odd ones have caller_norms_case.  Returns a dict."""
+    from tests.test_factor_host import GRID_CAP, PATTERNS, pattern_of
+    rng = np.random.default_rng(seed)
+    n_rows = GRID_CAP + extra
+    Q = rng.standard_normal((64, 2)).astype(F32)
+    Q[7] = 0.0
+    norms = host_norms_fast(Q)
+    kind = rng.integers(0, 3, PATTERNS)                                 # 0 live, 1 the zero-norm item, 2 outside the catalogue
+    kind[:6], kind[384:390] = [0, 1, 0, 2, 1, 2], [1, 0, 2, 0, 0, 1]
+    live = rng.integers(0, 64, PATTERNS)
+    live[live == 7] = 8
+    outside = rng.choice(np.array([-1, 64, 2 ** 31 - 1, -2 ** 31]), PATTERNS)
+    queries = np.where(kind == 0, live, np.where(kind == 1, 7, outside)).astype(np.int32)
+    P = rng.standard_normal((PATTERNS, 2)).astype(F32)
+    P[kind != 0] = 0.0
+    return dict(Q=Q, norms=norms, queries=queries, P=P, p_norms=host_norms_fast(P), kind=kind, at=pattern_of(n_rows), n_rows=n_rows, top_k=3,
+                splits=2)
+
+
+def blend_trip_case(seed=23, extra=3):
+    """More rows than the list stage's grid (65,536): 65,536 + 3 rows of ka = kb = 4, keep 5, ids below 30.  The patterns: 0 full
+    lists with an id repeated in A, one shared with B and one of A's ids excluded (a hole); 1 an empty A; 2 an empty B; 3 a divisor
+    that is not > 0; 4 A cut at position 1 by a non-finite score.  Returns (n_items, A, B, a_div, exclude, kind), per pattern."""
+    from tests.test_factor_host import PATTERNS
+    rng = np.random.default_rng(seed)
+    n_items = 30
+    kind = rng.integers(0, 5, PATTERNS)
+    kind[:3], kind[384:387] = [0, 4, 3], [1, 0, 0]
+    both = np.stack([rng.permutation(n_items)[:8] for _ in range(PATTERNS)]).astype(np.int32)        # (disjoint before the repeats are made)
+    a_ids, b_ids = both[:, :4].copy(), both[:, 4:].copy()
+    a_ids[:, 2] = a_ids[:, 0]                                            # A repeats its first id
+    b_ids[:, 1] = a_ids[:, 1]                                            # ... and shares its second with B
+    desc = lambda: (-np.sort(-rng.standard_normal((PATTERNS, 4)), axis=1)).astype(F32)
+    a_sc, b_sc = desc(), desc()
+    a_cnt, b_cnt = np.full(PATTERNS, 4, np.int32), np.full(PATTERNS, 4, np.int32)
+    a_cnt[kind == 1], b_cnt[kind == 2], b_cnt[kind == 4] = 0, 0, 2
+    a_div = (0.5 + rng.random(PATTERNS)).astype(F32)
+    bad = np.flatnonzero(kind == 3)
+    a_div[bad] = np.array([0.0, -2.0, np.nan, -0.0], F32)[np.arange(len(bad)) % 4]
+    cut = np.flatnonzero(kind == 4)
+    a_sc[cut, 1] = np.array([np.inf, np.nan, -np.inf, -FLT_MAX], F32)[np.arange(len(cut)) % 4]
+    exclude = np.where(kind == 0, a_ids[:, 3], np.where(rng.random(PATTERNS) < 0.5, -1, b_ids[:, 0])).astype(np.int32)
+    return n_items, (a_ids, a_sc, a_cnt), (b_ids, b_sc, b_cnt), a_div, exclude, kind
+
+
+@pytest.mark.parametrize("dim", [15, 16, 17, 31, 32, 33, 63, 65, 129])
+def test_both_similar_models_agree_on_the_class_edge_dims(dim):
+    """The device rounding test's own case at the dims around the scan's class rules: the plain definition on 12 of its 96
+    queries, and the last component moves bits of s1 for most queries."""
+    _, Q = rounding_vectors(1, 96, dim, seed=dim)
+    Q[5] = 0.0
+    norms = host_norms_fast(Q)
+    some = np.arange(0, 96, 8, dtype=np.int32)
+    for cosine in (False, True):
+        fast = host_similar_fast(Q, norms, np.arange(96, dtype=np.int32), 95, write_cosine=cosine)
+        plain = host_similar_plain(Q, norms, some, 95, write_cosine=cosine)
+        assert_same_lists([a[some] for a in fast[:3]], plain, (dim, cosine))
+    with np.errstate(all="ignore"):
+        full, less = host_s1(Q, Q, norms), host_s1(Q[:, :dim - 1], Q[:, :dim - 1], norms)
+    assert int((bits(full) != bits(less)).any(axis=1).sum()) > 48
+
+
+@pytest.mark.parametrize("dim", [17, 65])
+def test_similar_class_case_hangs_on_its_last_component(dim):
+    Q, norms, queries = similar_class_case(dim)
+    want = host_similar_fast(Q, norms, queries, 65, write_cosine=True)
+    assert_same_lists(want, host_similar_plain(Q, norms, queries, 65, write_cosine=True), dim)
+    assert (want[2] == 65).all()
+    less = host_similar_fast(Q[:, :dim - 1], host_norms_fast(Q), queries, 17)
+    assert (less[0] != want[0][:, :17]).any(axis=1).all()
+
+
+@pytest.mark.parametrize("dim", [13, 33])
+def test_similar_operand_case_at_odd_dims(dim):
+    Q, norms, queries = similar_operand_case(dim)
+    want = host_similar_fast(Q, norms, queries, 40)
+    assert_same_lists(want, host_similar_plain(Q, norms, queries, 40), dim)
+    assert (want[2] == 39).all() and np.array_equal(want[3], norms[queries])
+
+
+def test_caller_norms_cases_are_the_definition_and_stay_odd():
+    Q, norms, queries, odd = caller_norms_case()
+    assert np.isnan(norms[odd[0]]) and np.isposinf(norms[odd[1]]) and norms[odd[2]] < 0 and 0 < norms[odd[3]] < 2.0 ** -126
+    assert np.isneginf(norms[odd[4]]) and norms[odd[5]] == 0 and np.signbit(norms[odd[5]])
+    for top_k in (20, 99):
+        for cosine in (False, True):
+            want = host_similar_fast(Q, norms, queries, top_k, write_cosine=cosine)
+            with np.errstate(over="ignore"):
+                same_or_both_nan(want, host_similar_plain(Q, norms, queries, top_k, write_cosine=cosine), (top_k, cosine))
+            listed = want[1][np.arange(top_k)[None, :] < want[2][:, None]]
+            assert np.isinf(listed).any(), "infinite scores must be listed"
+            if top_k == 20:                                                 # (fl(inf / inf) of the +inf query norm: two NaN scores)
+                assert (int(np.isinf(listed).sum()), int(np.isnan(listed).sum())) == ((23, 2) if cosine else (9, 0))
+            # nobody lists the NaN-norm item; the two items whose norm is a zero or a denormal lead or end every other live list
+            assert not (want[0] == odd[0]).any()
+            n = min(top_k, 98)                                              # 100 items less the query and the NaN-norm item
+            assert want[2].tolist() == ([n, 0, n, 0, n, 0, 0, n] if cosine else [n, min(top_k, 99), n, n, n, n, n, n])
+    Q, norms, P, p_norms = query_norms_case()
+    for cosine in (False, True):
+        want = host_similar_fast(Q, norms, None, 20, P=P, p_norms=p_norms, write_cosine=cosine)
+        with np.errstate(over="ignore"):
+            same_or_both_nan(want, host_similar_plain(Q, norms, None, 20, P=P, p_norms=p_norms, write_cosine=cosine), cosine)
+        assert want[2].tolist() == ([0, 20, 0, 0, 20, 20, 20] if cosine else [20] * 7)
+        assert np.array_equal(want[3].view(np.int32), p_norms.view(np.int32))
+
+
+def test_similar_trip_case_is_the_definition_and_sets_live_against_dead_across_the_cap():
+    from tests.test_factor_host import GRID_CAP, PATTERNS
+    case = similar_trip_case()
+    Q, norms, kind, at = case["Q"], case["norms"], case["kind"], case["at"]
+    want = host_similar_fast(Q, norms, case["queries"], 3, write_cosine=True)
+    assert_same_lists(want, host_similar_plain(Q, norms, case["queries"], 3, write_cosine=True), "queries")
+    assert np.array_equal(want[2], np.where(kind == 0, 3, 0))
+    brought = host_similar_fast(Q, norms, case["queries"], 3, P=case["P"], p_norms=case["p_norms"], write_cosine=True)
+    assert_same_lists(brought, host_similar_plain(Q, norms, case["queries"], 3, P=case["P"], p_norms=case["p_norms"], write_cosine=True), "brought")
+    assert np.array_equal(brought[2], np.where(kind == 0, 3, 0)) and len(kind) == PATTERNS
+    early, late = kind[at[:case["n_rows"] - GRID_CAP]] == 0, kind[at[GRID_CAP:]] == 0
+    assert (early & ~late).any() and (~early & late).any() and (early & late).any()
+    assert {1, 2} <= set(kind[at[GRID_CAP:]].tolist()) and {1, 2} <= set(kind[at[:40]].tolist())
+
+
+def test_blend_trip_case_is_the_definition_and_changes_the_unions_length_across_the_cap():
+    n_items, A, B, a_div, exclude, kind = blend_trip_case()
+    want = host_blend(n_items, A, B, 5, a_div=a_div, exclude=exclude)
+    assert_same_blend(want, host_blend(n_items, A, B, 5, a_div=a_div, exclude=exclude, row_fn=blend_row_plain), "patterns")
+    union = host_blend(n_items, A, B, 8, a_div=a_div, exclude=exclude)[3]
+    assert set(kind.tolist()) == {0, 1, 2, 3, 4}
+    assert (union[kind == 0] == 5).all() and (union[kind == 1] <= 4).all() and (union[kind == 3] <= 4).all() and (union[kind == 4] <= 3).all()
+    assert (want[2][kind == 0] == 3).any(), "an id of both lists"
+    early, late = union[:3], union[384:387]                             # rows 0 .. 2 and 65,536 .. 65,538 share their workgroups
+    assert (early != late).all() and (early > late).any() and (early < late).any()
+
+
 # ---------------------------------------------------------------------------------------------- pinning: what the roundings are worth
 def test_other_ways_to_divide_change_bits_of_s1():
     rng = np.random.default_rng(12)
