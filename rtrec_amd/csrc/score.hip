@@ -1179,13 +1179,17 @@ __device__ __forceinline__ float fr_kth_lane_best(float best, int kk) {
         kk -= 64;
         float v = best;
         for (int r = 0; r < kk; ++r) {
+            // (the maximum rides the DPP instruction itself: a lane without a source keeps its value, and no value here is
+            // a NaN, so neither a -inf fill nor a canonicalising v_max per stage is needed.  s_nop 1: a DPP operand
+            // written by the vector instruction before it)
             float t = v;
-            t = fmaxf(t, fr_dpp_f<0x111>(t, ninf));
-            t = fmaxf(t, fr_dpp_f<0x112>(t, ninf));
-            t = fmaxf(t, fr_dpp_f<0x114>(t, ninf));
-            t = fmaxf(t, fr_dpp_f<0x118>(t, ninf));
-            t = fmaxf(t, fr_dpp_f<0x142>(t, ninf));      // row_bcast:15
-            t = fmaxf(t, fr_dpp_f<0x143>(t, ninf));      // row_bcast:31
+            asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+                "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+                "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xf bank_mask:0xf\n\t"
+                "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xf bank_mask:0xf"
+                : "+v"(t));
             tau = readlane_f(t, 63);
             if (tau == ninf) break;                      // fewer than kk values
             const unsigned long long at = __ballot(v == tau);
@@ -1215,6 +1219,30 @@ __device__ __forceinline__ float fr_kth_lane_best(float best, int kk) {
     }
     return tau;
 }
+
+// Number of lanes whose value is LARGER than this lane's `v`: its rank among the 64 values, descending, where all of
+// them differ (equal values share a rank).  Straight-line: per lane t one v_readlane, one compare and one add -- no
+// branch, no DPP chain.  No value is a NaN.
+__device__ __forceinline__ int fr_lane_rank_above(float v) {
+    int rank = 0;
+#pragma unroll
+    for (int t = 0; t < 64; ++t) rank += readlane_f(v, t) > v ? 1 : 0;
+    return rank;
+}
+// The same with equal values told apart: of those the HIGHER lane ranks first (the ranks are a permutation of 0..63).
+// A loop of 64 rounds, for the rare wave that holds equal values.
+__device__ __forceinline__ int fr_lane_rank_ties(float v, int lane) {
+    int rank = 0;
+#pragma nounroll
+    for (int t = 0; t < 64; ++t) {
+        const float o = readlane_f(v, t);
+        rank += (o > v || (o == v && t > lane)) ? 1 : 0;
+    }
+    return rank;
+}
+// The forms of score_frows_kernel that fill an EMPTY list by rank (fr_lane_rank_above) instead of by insertion: all but
+// the 8-user form of 256-column tiles and 65+ rows of W, which sits at exactly 128 VGPRs and would spill two.
+template <int REGS, int XR, int UW> constexpr bool kFrRankFill = !(REGS == 4 && XR == 2 && UW == 8);
 
 // Compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{}).  The per-user
 // register arrays of the kernel below are indexed with these constants only, so every element is a scalar
@@ -1722,6 +1750,8 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
             }
 
             if (!(ft & (1 << 25))) continue;                 // the tile's slice continues in the next super-tile
+            // (diagnostic build: the sweep so far is PF_DENSE; the block below is PF_SELECT, a user's first fill PF_SPARSE)
+            PF_MARK(PF_DENSE)
             // ---- candidates, user after user: columns that beat the user's kk-th score and are not interacted ----
             fr_static_for<UW>([&](auto Uc) {
                 constexpr int u = decltype(Uc)::value;
@@ -1766,27 +1796,67 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                         });
                     }
                 }
-                if (thr == ninf) {
+                const int rel = lane - lb;
+                const bool in = rel >= 0 && rel < kk;
+                const bool fill = thr == ninf;
+                int skip_r = -1;           // first fill by rank: the register of the lane whose sum is placed already
+                if (fill) {
                     // The list is not full yet (first tile, or a user with few scored columns): everything
-                    // non-zero would pass.  Take the tile's own kk-th best admissible score (a bound from the
-                    // lane maxima) as the cut instead.
+                    // non-zero would pass.
                     PF_ADD(PF_N_OVERFLOW, 1)
+                    // the lane's largest admissible, non-zero sum and the register that holds it (of equal sums the later
+                    // register: the higher column)
                     float bm = ninf;
+                    int br = 0;
                     fr_static_for<REGS>([&](auto Rc) {
                         constexpr int r = decltype(Rc)::value;
                         const float v = acc[u][r];
                         const float vm = (v != 0.0f && !((ex[r] >> lane) & 1ull)) ? v : ninf;
-                        bm = vm > bm ? vm : bm;
+                        br = vm >= bm ? r : br;
+                        bm = vm >= bm ? vm : bm;
                     });
-                    // kk-th largest of the 64 lane maxima (the 16 quad maxima would do as a bound, but a loose one:
-                    // half the tile can lie above it); -inf: fewer than kk lanes hold a score, and everything
-                    // they hold (< kk * REGS <= kFrCandCap) fits the buffer
-                    const float t0 = fr_kth_lane_best(bm, 64 + kk);
-                    if (t0 != ninf) tcut = float_prev(t0);      // candidates are the values >= t0
+                    if (kFrRankFill<REGS, XR, UW> && readlane_i(lc4[g], lb) < 0) {
+                        // ---- the list is EMPTY: nothing needs inserting.  The kk best lane maxima, ordered as merge() orders
+                        //      (score, then higher column = higher lane), ARE the list: every lane takes its rank among the 64
+                        //      maxima in straight-line code, the first kk write themselves to the candidate buffer at their
+                        //      rank, and the list lanes read the buffer back.  What is left for merge() is a sum above the
+                        //      new kk-th entry that is not its lane's maximum (a second register of one lane: rare). ----
+                        const int n_val = static_cast<int>(__builtin_popcountll(__ballot(bm != ninf)));
+                        if (n_val == 0) return;                 // nothing admissible in this tile: the list stays empty
+                        const int col = t * TC + lane * REGS + br;
+                        int rank = fr_lane_rank_above(bm);
+                        bool mine = bm != ninf && rank < kk;
+                        if (mine) { cv[rank] = bm; cp[rank] = col; }
+                        // equal maxima among the first kk share a rank, and all but one of them lose their slot: they
+                        // read another lane's column back (through an index the compiler cannot match to the store's:
+                        // what the LDS holds, not what this lane wrote).  Rare: rank again with the lanes told apart.
+                        int slot = rank;
+                        asm volatile("" : "+v"(slot));
+                        if (__ballot(mine && cp[slot] != col)) {
+                            rank = fr_lane_rank_ties(bm, lane);
+                            mine = bm != ninf && rank < kk;
+                            if (mine) { cv[rank] = bm; cp[rank] = col; }
+                        }
+                        if (rel >= 0 && rel < min(n_val, kk)) {      // LDS operations of one wave execute in order
+                            ls4[g] = cv[rel];
+                            lc4[g] = cp[rel];
+                        }
+                        const float thr_new = readlane_f(ls4[g], lb + kk - 1);
+                        thrv = lane == u ? thr_new : thrv;
+                        tcut = thr_new;                         // -inf while fewer than kk lanes held a sum: every other sum is an extra
+                        skip_r = br;
+                        PF_ADD(PF_ROWPTR, min(n_val, kk)) PF_ADD(PF_RESET, min(n_val, kk))
+                    } else {
+                        // A partial list (a user with fewer than kk admissible columns so far).  Take the tile's own kk-th
+                        // best admissible score (a bound from the lane maxima) as the cut:
+                        // kk-th largest of the 64 lane maxima (the 16 quad maxima would do as a bound, but a loose one:
+                        // half the tile can lie above it); -inf: fewer than kk lanes hold a score, and everything
+                        // they hold (< kk * REGS <= kFrCandCap) fits the buffer
+                        const float t0 = fr_kth_lane_best(bm, 64 + kk);
+                        if (t0 != ninf) tcut = float_prev(t0);      // candidates are the values >= t0
+                    }
                 }
                 int nc = 0;
-                const int rel = lane - lb;
-                const bool in = rel >= 0 && rel < kk;
                 // merge the buffered candidates into the user's list (lane lb + j = rank j)
                 auto merge = [&]() {
                     const float myv = lane < nc ? cv[lane] : ninf;
@@ -1801,7 +1871,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                         // ties inside the fast pass order by higher column; exact ties are re-scored anyway
                         const bool better = in && ((s > v) || (s == v && c > col));
                         const int pos = static_cast<int>(__builtin_popcountll(__ballot(better)));
-                        PF_ADD(PF_N_SPARSE_ROWS, 1)
+                        PF_ADD(PF_N_SPARSE_ROWS, 1) PF_ADD(PF_RESET, fill ? 1 : 0)
                         const float s_up = fr_row_shift_up(s, ninf);
                         const int c_up = fr_row_shift_up(c, -1);
                         ls4[g] = !in || rel < pos ? s : (rel == pos ? v : s_up);
@@ -1815,7 +1885,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                     constexpr int r = decltype(Rc)::value;
                     const float v = acc[u][r];
                     // only non-zero sums compete (scipy keeps `!= 0`)
-                    unsigned long long m = __ballot(v > tcut && v != 0.0f);
+                    unsigned long long m = __ballot(v > tcut && v != 0.0f && r != skip_r);
                     if (!m) return;
                     m &= ~ex[r];
                     if (!m) return;
@@ -1827,9 +1897,12 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                         cp[pos] = t * TC + lane * REGS + r;
                     }
                     nc += cnt;
+                    PF_ADD(PF_ROWPTR, fill ? cnt : 0)
                 });
                 if (nc > 0) merge();
+                PF_MARK(fill ? PF_SPARSE : PF_SELECT)
             });
+            PF_MARK(PF_SELECT)
         }
         PF_MARK(PF_DENSE)
 #ifdef SCORE_PROFILE

@@ -465,3 +465,48 @@ def fr_exit_model(L: Dict[str, Any], W: sp.spmatrix, X: sp.csr_matrix, top_k: in
     later_tiles = [np.flatnonzero(last_super > s) for s in range(n_super)]
     return dict(scores=scores, l1=l1, sfx=sfx, thr_end=thr_end, closed=closed, depth=depth, depth_open=np.minimum(depth_open, n_super),
                 later_tiles=later_tiles, n_super=n_super, wtop=wtop, last_super=last_super)
+
+
+# ---- host model of score_frows_kernel's first fill (csrc/score.hip): an empty list is filled by rank, not by insertion ----
+def fr_first_fill_model(sums: np.ndarray, admissible: np.ndarray, kk: int) -> Dict[str, Any]:
+    """The list a user with an EMPTY list holds after one tile, as the kernel builds it.  `sums`: the tile's float32 sums,
+    64 * regs of them in layout order (lane = column // regs holds the `regs` consecutive columns lane * regs + r);
+    `admissible`: False for the interacted columns; a zero sum never competes.  Three steps, as in the kernel:
+      rank    every lane's largest admissible sum (of equal sums the later register: the higher column) takes
+              rank = #{lanes with a larger maximum, or an equal one and a higher lane}; lanes without a sum take none
+      place   the lanes of rank < kk are the list, in rank order
+      extras  every other admissible sum ABOVE the list's kk-th entry (-inf while the list is short) goes through
+              merge(): register after register, lanes ascending, inserted behind the entries that are larger or equal
+              with a higher column, and only while it beats the kk-th entry of the moment
+    Returns values [kk] (float32, -inf where empty), cols [kk] (tile-local, -1 where empty), n_ranked (lanes with a sum),
+    n_extras (sums handed to merge), n_inserted (those of them that entered)."""
+    sums = np.asarray(sums, dtype=np.float32)
+    regs = len(sums) // 64
+    assert regs in (2, 4) and len(sums) == 64 * regs and 1 <= kk <= 16
+    ninf = np.float32(-np.inf)
+    ok = np.asarray(admissible, dtype=bool) & (sums != 0)
+    vm = np.where(ok, sums, ninf).reshape(64, regs)
+    br = regs - 1 - np.argmax(vm[:, ::-1], axis=1)
+    lanes = np.arange(64)
+    bm = vm[lanes, br]
+    has = bm > ninf
+    rank = ((bm[None, :] > bm[:, None]) | ((bm[None, :] == bm[:, None]) & (lanes[None, :] > lanes[:, None]))).sum(axis=1)
+    values = np.full(kk, ninf, dtype=np.float32)
+    cols = np.full(kk, -1, dtype=np.int64)
+    sel = has & (rank < kk)
+    values[rank[sel]] = bm[sel]
+    cols[rank[sel]] = lanes[sel] * regs + br[sel]
+    cut = values[kk - 1]
+    n_extras = n_inserted = 0
+    for r in range(regs):
+        for lane in np.flatnonzero(ok.reshape(64, regs)[:, r] & (br != r) & (vm[:, r] > cut)):
+            v, c = vm[lane, r], int(lane) * regs + r
+            n_extras += 1
+            if not v > values[kk - 1]:
+                continue
+            pos = int(((values > v) | ((values == v) & (cols > c))).sum())
+            values[pos + 1:] = values[pos:-1].copy()
+            cols[pos + 1:] = cols[pos:-1].copy()
+            values[pos], cols[pos] = v, c
+            n_inserted += 1
+    return dict(values=values, cols=cols, n_ranked=int(has.sum()), n_extras=n_extras, n_inserted=n_inserted)

@@ -3,6 +3,10 @@
 Depth = the fragment at which a wave left its job (n_frags = it went to the end of W).  Beside the histogram the raw
 phase counters of the -DSCORE_PROFILE build are printed: wave ticks per phase, `n_dense` = (wave, row) pairs swept and
 `n_gather` = those of them that were fetched through the wave's row ring (the rows behind the resident head).
+In score_frows_kernel the tile loop is split three ways: `dense` = the sweep and the tile tests, `select` = the candidate
+block of users whose list is full, `sparse` = the candidate block of users whose kk-th entry is still empty (the first
+fill).  `n_overflow` counts those first fills, `rowptr` the candidates they buffered or placed, `reset` those of them that
+entered a list; `n_sparse_chunks` / `n_sparse_rows` count merge() rounds / insertions of every user.
 
 usage: RTREC_AMD_LIB=<a -DSCORE_PROFILE build> python tools/fr_exit_depth.py [bench.py arguments]
 Runs bench.py in this process, then reads the library's counters (rtrec_amd_fr_exit_depth, rtrec_amd_score_profile) and
