@@ -440,6 +440,64 @@ int rtrec_factor_als_solve(int32_t n_jobs, const int32_t *d_job_rows, int32_t n_
                            const float *d_r_val, int64_t nnz, const float *d_v, int64_t v_stride, int32_t n_v, int32_t dim,
                            const float *d_gram, float alpha, float *d_out, int64_t out_stride, uint8_t *d_status, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * FACTOR GRAM WIDE  (rtrec_factor_gram for vectors of up to 256 components.)
+ * The definition is rtrec_factor_gram's word for word -- chunks of 1024 rows, per element one fmaf chain over the chunk's
+ * ascending rows, the chunks added in ascending order with one rounded add each, reg added to the diagonal last -- for
+ * dim in 1..256.  RTREC_FACTOR_GRAM_WORKSPACE_BYTES and every argument rule are rtrec_factor_gram's.  For dim <= 64 the output
+ * equals rtrec_factor_gram's bit for bit; it is symmetric bit for bit for every dim.
+ * dim in 1..256: RTREC_ERR_UNSUPPORTED otherwise.  Negative n_v, v_stride < dim, a reg that is negative or NaN, NULL d_gram, NULL
+ * d_v or d_workspace with n_v > 0: RTREC_ERR_INVALID_ARG.  A workspace too small: RTREC_ERR_WORKSPACE.  No global state, no
+ * environment variable, no allocation, no synchronisation.  The results never depend on the grid or on scheduling.
+ * csrc/factor_gram.hip: factor_gram_wide_partial_kernel, one one-wave workgroup per (chunk, lower 32 x 32 tile), each one chain of
+ * v_mfma_f32_32x32x2_f32 over ascending rows; a tile below the diagonal is written twice, once transposed;
+ * factor_gram_sum_kernel adds the partials.  No atomics.
+ * ------------------------------------------------------------------------------------- */
+int rtrec_factor_gram_wide(int32_t n_v, const float *d_v, int64_t v_stride, int32_t dim, float reg, float *d_gram,
+                           void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * FACTOR ALS CG  (per row of R: a few conjugate-gradient steps on the system of rtrec_factor_als_solve, never forming its matrix.)
+ * The other second call of a half-step, for dim up to 256.  R, the jobs, V, the clamped offsets and the USABLE entries are
+ * rtrec_factor_als_solve's (0 <= i < n_v and w = fl(alpha * val) > 0; a skipped entry's row of V is never read), and so is the
+ * system of row x: A = G + sum_i w_i y_i y_i^T, b = sum_i (1 + w_i) y_i over the usable entries IN STORAGE ORDER.  d_gram must be
+ * symmetric bit for bit (both Gram calls guarantee it); for another matrix the result is unspecified, nothing is read out of
+ * range.  Every operation is pinned:
+ *   chain(u, v) s = +0.0f, then s = fmaf(u[c], v[c], s) for c = 0 .. dim-1 (rtrec_factor_topk's score)
+ *   tree(u, v)  q[c] = fl(u[c] * v[c]) for c < dim and +0.0f for dim <= c < D, D the least power of two >= dim; for
+ *               h = D/2, D/4, .., 1: q[c] = fl(q[c] + q[c + h]) for c < h; the result is q[0] (the xor-butterfly of a
+ *               cross-lane reduction: c pairs with c + h, not with a neighbour)
+ *   mat(v)[a]   s = +0.0f, then s = fmaf(G[a][b], v[b], s) for b ascending
+ *   start       x = the vector stored at d_out[x_row * out_stride + c]; with warm_start == 0, or when any stored component
+ *               is not finite, x = +0.0f throughout
+ *   residual    r[a] = -mat(x)[a]; then over the usable entries in storage order t = chain(y_i, x),
+ *               coef = fl(fl(1.0f + w) - fl(w * t)), r[a] = fmaf(coef, y_i[a], r[a]).  (From x = 0, r is
+ *               rtrec_factor_als_solve's rhs.)
+ *   first       p = r, rs = tree(r, r); if rs < 1e-20f the job is done: x stays as it is, status 0
+ *   step        cg_steps times: Ap = mat(p), then over the usable entries in storage order t = chain(y_i, p),
+ *               Ap[a] = fmaf(fl(w * t), y_i[a], Ap[a]); den = tree(p, Ap); if !(den > 0) or den is not finite the job BREAKS
+ *               DOWN; al = fl(rs / den), one correctly rounded division; x[a] = fmaf(al, p[a], x[a]);
+ *               r[a] = fmaf(-al, Ap[a], r[a]); rn = tree(r, r); if rn < 1e-20f stop; be = fl(rn / rs);
+ *               p[a] = fmaf(be, p[a], r[a]); rs = rn
+ * Float32 denormals are kept; nothing is contracted or reordered beyond what is written here.
+ * Out: the vector in place at d_out[x_row * out_stride + c], c in [0, dim), as rtrec_factor_als_solve writes it.  d_status[r]
+ * (uint8): 0 = finished; 1 = x_row lies outside [0, n_rows) (nothing of d_out is written), or the row has no usable entry (the
+ * vector is all +0.0f); 2 = breakdown, or a component of x that is not finite (the vector is all +0.0f).  d_out_rs[r] (may be
+ * NULL): the last tree(r, r) computed for the job, +0.0f for status 1.  Jobs must name distinct rows.  The sign of a zero is
+ * not part of the contract.
+ * dim in 1..256 and cg_steps in 1..64: RTREC_ERR_UNSUPPORTED otherwise.  RTREC_ERR_INVALID_ARG as rtrec_factor_als_solve:
+ * negative sizes, strides below dim, an alpha that is not > 0, NULL required arrays.  n_jobs == 0: RTREC_OK before any pointer
+ * check.  warm_start: 0 or not 0.  No global state, no environment variable, no allocation, no synchronisation.  The results
+ * never depend on the grid or on scheduling.
+ * csrc/factor_als_cg.hip, factor_als_cg_kernel: one workgroup of 1 / 2 / 4 waves per job, lane = component for x, r, p and Ap; the
+ * entries are taken 64 at a time, their rows of V staged in LDS; t with lane = entry, the updates with lane = component; mat
+ * reads row b of G (= column b, by the symmetry) coalesced.  No atomics.
+ * ------------------------------------------------------------------------------------- */
+int rtrec_factor_als_cg(int32_t n_jobs, const int32_t *d_job_rows, int32_t n_rows, const int32_t *d_r_ptr, const int32_t *d_r_idx,
+                        const float *d_r_val, int64_t nnz, const float *d_v, int64_t v_stride, int32_t n_v, int32_t dim,
+                        const float *d_gram, float alpha, int32_t cg_steps, int32_t warm_start, float *d_out, int64_t out_stride,
+                        uint8_t *d_status, float *d_out_rs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

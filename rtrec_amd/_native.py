@@ -61,6 +61,8 @@ EXT_EXPORTS = [
     "rtrec_similar_blend",
     "rtrec_factor_gram",
     "rtrec_factor_als_solve",
+    "rtrec_factor_gram_wide",
+    "rtrec_factor_als_cg",
 ]
 
 
@@ -253,6 +255,11 @@ def load() -> C.CDLL:
     L.rtrec_factor_als_solve.restype = C.c_int
     L.rtrec_factor_als_solve.argtypes = [i32, vp, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, i32, i32, vp, C.c_float, vp, C.c_int64,
                                          vp, vp]
+    L.rtrec_factor_gram_wide.restype = C.c_int
+    L.rtrec_factor_gram_wide.argtypes = [i32, vp, C.c_int64, i32, C.c_float, vp, vp, C.c_size_t, vp]
+    L.rtrec_factor_als_cg.restype = C.c_int
+    L.rtrec_factor_als_cg.argtypes = [i32, vp, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, i32, i32, vp, C.c_float, i32, i32, vp, C.c_int64,
+                                      vp, vp, vp]
     _lib = L
     return L
 

@@ -388,6 +388,20 @@ class HipBackend:
         self.ops.factor_als_solve(job_rows, int(n_jobs), r_csr[0], r_csr[1], r_csr[2], v, int(n_v), int(dim), gram, float(alpha),
                                   out, status)
 
+    def factor_gram_wide(self, v, n_v, dim, reg, gram):
+        """factor_gram for vectors of up to 256 components: the same definition, one MFMA chain per (chunk, lower 32 x 32 tile)
+        (csrc/factor_gram.hip, rtrec_factor_gram_wide; include/rtrec_amd_ext.h).  Equal to factor_gram bit for bit up to 64."""
+        chunks = (int(n_v) + self.GRAM_CHUNK - 1) // self.GRAM_CHUNK
+        ws = self.empty((chunks * int(dim) * int(dim) * 4,), self.torch.uint8) if chunks else None
+        self.ops.factor_gram_wide(v, int(n_v), int(dim), float(reg), gram, ws)
+
+    def factor_als_cg(self, job_rows, n_jobs, r_csr, v, n_v, dim, gram, alpha, cg_steps, warm_start, out, status, rs=None):
+        """Per job: `cg_steps` pinned conjugate-gradient steps on the system factor_als_solve factors, started from the vector
+        `out` holds (`warm_start`) or from zero, written in place; one uint8 `status` per job and, where `rs` is given, the last
+        squared residual norm (csrc/factor_als_cg.hip, rtrec_factor_als_cg; include/rtrec_amd_ext.h).  dim up to 256."""
+        self.ops.factor_als_cg(job_rows, int(n_jobs), r_csr[0], r_csr[1], r_csr[2], v, int(n_v), int(dim), gram, float(alpha),
+                               int(cg_steps), bool(warm_start), out, status, rs)
+
     def audience_workspace_bytes(self, n_users, n_q, top_n):
         return int(self.lib.rtrec_slim_audience_workspace_bytes(n_users, n_q, top_n))
 

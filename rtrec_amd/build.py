@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "librtrec_amd.so")
 SOURCES = ["score.hip", "fit.hip", "store_host.hip", "store_device.hip", "seg_build.hip", "score_refine.hip", "score_cands.hip", "fit_sgd.hip", "score_dense_fill.hip", "score_first_touch.hip", "ordered_fold.hip", "rank_metrics.hip", "explain.hip", "audience.hip", "score_pairs.hip", "diversify.hip", "list_quality.hip", "catalogue_ranks.hip", "blend.hip", "factor_topk.hip", "feature_repr.hip", "factor_norms.hip", "factor_similar.hip",
-           "similar_blend.hip", "factor_gram.hip", "factor_als.hip"]
+           "similar_blend.hip", "factor_gram.hip", "factor_als.hip", "factor_als_cg.hip"]
 # (the core header stays last: ops_stale reads HEADERS[-1]; the extension surface's header stands in front of it)
 HEADERS = ["common.hip.h", "row_lookup.hip.h", "score_seg.hip.h", "fold_spec.hip.h", "list_stage.hip.h", "factor_scan.hip.h", "factor_als.hip.h", os.path.join("..", "..", "include", "rtrec_amd_ext.h"),
            os.path.join("..", "..", "include", "rtrec_amd.h")]

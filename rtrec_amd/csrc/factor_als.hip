@@ -27,7 +27,8 @@
 // longest rows first, as the scoring kernels do with d_row_order.
 // Malformed input cannot read out of range: offsets are clamped to [0, nnz], columns outside [0, n_v) are skipped before any read
 // of V, a job row outside [0, n_rows) reads and writes nothing but its status.
-// Not built: a row split over several waves (it would change the definition), a conjugate-gradient solve, dim above 64.
+// Not built: a row split over several waves (it would change the definition).  dim above 64 is served by the conjugate-gradient
+// call beside this one (csrc/factor_als_cg.hip, rtrec_factor_als_cg), which never forms the row's matrix; this kernel stays at 64.
 // Measured: profiles/als_<workload>.json (tools/als_bench.py) where committed; DESIGN quotes it beside the computed bound.
 #include "factor_als.hip.h"
 

@@ -16,6 +16,8 @@
 // factor_gram_sum_kernel: one thread per element adds the partials in ascending chunk order and the diagonal's reg.
 // No atomics; the result does not depend on the grid.  Both launches happen in the one export, as rtrec_factor_topk launches
 // its merge.  Not measured on its own here; tools/als_bench.py times the call.
+// rtrec_factor_gram_wide (dim up to 256, the same definition and the same bits up to 64): factor_gram_wide_partial_kernel, one
+// one-wave workgroup per (chunk, lower 32 x 32 tile), then the same factor_gram_sum_kernel.
 #include "factor_als.hip.h"
 
 namespace rtrec {
@@ -81,8 +83,69 @@ __global__ __launch_bounds__(256) void factor_gram_sum_kernel(int n_chunks, int 
     gram[e] = g;
 }
 
+// rtrec_factor_gram_wide: one one-wave workgroup per (chunk, lower tile).  blockIdx.y counts the tiles (ti, tj), tj <= ti, row by
+// row; the chain of tile (ti, tj) is the one factor_gram_partial_kernel runs for (1, 0): the A operand brings components
+// 32 ti + j, the B operand 32 tj + j.  A diagonal tile is written once, whole (both triangles come out of the same products);
+// a tile below the diagonal twice, once transposed.
+__global__ __launch_bounds__(64) void factor_gram_wide_partial_kernel(int n_v, const float *__restrict__ v, long long v_stride,
+                                                                      int dim, float *__restrict__ part) {
+    constexpr int G = kAlsGroup;
+    const int lane = lane_id(), j = lane & 31, h = lane >> 5;
+    int ti = 0, tj = static_cast<int>(blockIdx.y);
+    while (tj > ti) tj -= ++ti;
+    const long long r0 = static_cast<long long>(blockIdx.x) * kAlsGramChunk;
+    long long r1 = r0 + kAlsGramChunk;
+    if (r1 > n_v) r1 = n_v;
+    const int ca = 32 * ti + j, cb = 32 * tj + j;
+    const bool ina = ca < dim, inb = cb < dim;
+    als_f32x16 acc;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) acc[g] = 0.0f;
+    for (long long rb = r0; rb < r1; rb += 2 * G) {
+        float ya[G], yb[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const long long r = rb + 2 * g + h;
+            const bool ok = r < r1;
+            ya[g] = (ok && ina) ? v[r * v_stride + ca] : 0.0f;
+            yb[g] = (ok && inb) ? v[r * v_stride + cb] : 0.0f;
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+            if (rb + 2 * g < r1) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ya[g], yb[g], acc, 0, 0, 0);
+    }
+    float *dst = part + static_cast<long long>(blockIdx.x) * dim * dim;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+        const int a = 32 * ti + als_acc_row(g, h);
+        if (a < dim && inb) {
+            dst[a * dim + cb] = acc[g];
+            if (ti != tj) dst[cb * dim + a] = acc[g];
+        }
+    }
+}
+
 }  // namespace
 }  // namespace rtrec
+
+extern "C" int rtrec_factor_gram_wide(int32_t n_v, const float *d_v, int64_t v_stride, int32_t dim, float reg, float *d_gram,
+                                      void *d_workspace, size_t workspace_bytes, void *stream) {
+    using namespace rtrec;
+    if (dim < 1 || dim > kAlsWideMaxDim) return RTREC_ERR_UNSUPPORTED;
+    if (n_v < 0 || v_stride < dim || !(reg >= 0.0f)) return RTREC_ERR_INVALID_ARG;
+    if (!d_gram || (n_v > 0 && (!d_v || !d_workspace))) return RTREC_ERR_INVALID_ARG;
+    if (workspace_bytes < RTREC_FACTOR_GRAM_WORKSPACE_BYTES(n_v, dim)) return RTREC_ERR_WORKSPACE;
+    const int n_chunks = static_cast<int>((static_cast<long long>(n_v) + kAlsGramChunk - 1) / kAlsGramChunk);
+    const int nt = (dim + 31) / 32;
+    (void)hipGetLastError();
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *part = static_cast<float *>(d_workspace);
+    if (n_chunks > 0)
+        hipLaunchKernelGGL(factor_gram_wide_partial_kernel, dim3(n_chunks, nt * (nt + 1) / 2), dim3(64), 0, st, n_v, d_v,
+                           static_cast<long long>(v_stride), dim, part);
+    hipLaunchKernelGGL(factor_gram_sum_kernel, dim3((dim * dim + 255) / 256), dim3(256), 0, st, n_chunks, dim, part, reg, d_gram);
+    return launch_status();
+}
 
 extern "C" int rtrec_factor_gram(int32_t n_v, const float *d_v, int64_t v_stride, int32_t dim, float reg, float *d_gram,
                                  void *d_workspace, size_t workspace_bytes, void *stream) {

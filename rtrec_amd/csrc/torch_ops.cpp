@@ -62,6 +62,8 @@ struct Abi {
     decltype(&rtrec_similar_blend) similar_blend = nullptr;
     decltype(&rtrec_factor_gram) factor_gram = nullptr;
     decltype(&rtrec_factor_als_solve) factor_als_solve = nullptr;
+    decltype(&rtrec_factor_gram_wide) factor_gram_wide = nullptr;
+    decltype(&rtrec_factor_als_cg) factor_als_cg = nullptr;
 };
 Abi g_abi;
 
@@ -854,6 +856,52 @@ void factor_als_solve(const OT &job_rows, int64_t n_jobs, const at::Tensor &r_pt
           "rtrec_factor_als_solve");
 }
 
+// factor_gram's arguments for dim in 1..256 (include/rtrec_amd_ext.h, "FACTOR GRAM WIDE").
+void factor_gram_wide(const at::Tensor &v, int64_t n_v, int64_t dim, double reg, at::Tensor gram, const OT &workspace) {
+    TORCH_CHECK(dim >= 1 && dim <= 256, "factor_gram_wide: dim must lie in 1..256, got ", dim);
+    TORCH_CHECK(n_v >= 0 && n_v <= INT32_MAX, "factor_gram_wide: n_v must lie in 0..2^31-1");
+    TORCH_CHECK(v.dim() == 2 && v.size(0) >= n_v && v.size(1) >= dim, "factor_gram_wide: v must be [>= n_v, >= dim]");
+    TORCH_CHECK(reg >= 0.0, "factor_gram_wide: reg must be a number >= 0, got ", reg);
+    TORCH_CHECK(gram.numel() == dim * dim, "factor_gram_wide: gram must be [dim, dim]");
+    const size_t need = RTREC_FACTOR_GRAM_WORKSPACE_BYTES(n_v, dim);
+    const size_t ws_bytes = has(workspace) ? static_cast<size_t>(workspace->numel()) * workspace->element_size() : 0;
+    TORCH_CHECK(ws_bytes >= need, "factor_gram_wide: the workspace holds ", ws_bytes, " bytes, RTREC_FACTOR_GRAM_WORKSPACE_BYTES(n_v, dim) = ", need);
+    one_device("factor_gram_wide", gram, {&v}, {&workspace});
+    check(abi().factor_gram_wide(static_cast<int32_t>(n_v), cptr<const float>(v), v.size(1), static_cast<int32_t>(dim),
+                                 static_cast<float>(reg), cptr<float>(gram), cptr<void>(workspace), ws_bytes, stream_of(gram)),
+          "rtrec_factor_gram_wide");
+}
+
+// factor_als_solve's arguments, plus the number of conjugate-gradient steps, whether `out` holds the start vectors, and rs
+// [n_jobs] float32 (absent: not wanted): the last squared residual norm per job (include/rtrec_amd_ext.h, "FACTOR ALS CG").
+void factor_als_cg(const OT &job_rows, int64_t n_jobs, const at::Tensor &r_ptr, const at::Tensor &r_idx, const at::Tensor &r_val,
+                   const at::Tensor &v, int64_t n_v, int64_t dim, const at::Tensor &gram, double alpha, int64_t cg_steps,
+                   bool warm_start, at::Tensor out, at::Tensor status, const OT &rs) {
+    TORCH_CHECK(dim >= 1 && dim <= 256, "factor_als_cg: dim must lie in 1..256, got ", dim);
+    TORCH_CHECK(cg_steps >= 1 && cg_steps <= 64, "factor_als_cg: cg_steps must lie in 1..64, got ", cg_steps);
+    TORCH_CHECK(n_jobs >= 0 && n_jobs <= INT32_MAX && n_v >= 0 && n_v <= INT32_MAX, "factor_als_cg: n_jobs and n_v must lie in 0..2^31-1");
+    TORCH_CHECK(r_ptr.numel() >= 1 && r_ptr.numel() - 1 <= INT32_MAX, "factor_als_cg: r_ptr must hold n_rows + 1 offsets");
+    const int64_t n_rows = r_ptr.numel() - 1;
+    TORCH_CHECK(r_val.numel() == r_idx.numel(), "factor_als_cg: r_val must hold one value per entry of r_idx");
+    TORCH_CHECK(v.dim() == 2 && v.size(0) >= n_v && v.size(1) >= dim, "factor_als_cg: v must be [>= n_v, >= dim]");
+    TORCH_CHECK(gram.numel() == dim * dim, "factor_als_cg: gram must be [dim, dim]");
+    TORCH_CHECK(alpha > 0.0, "factor_als_cg: alpha must be a number > 0, got ", alpha);
+    TORCH_CHECK(out.dim() == 2 && out.size(0) >= n_rows && out.size(1) >= dim, "factor_als_cg: out must be [>= n_rows, >= dim]");
+    TORCH_CHECK(!has(job_rows) || job_rows->numel() == n_jobs, "factor_als_cg: job_rows must hold one entry per job");
+    TORCH_CHECK(has(job_rows) || n_jobs <= n_rows, "factor_als_cg: without job_rows there is at most one job per row");
+    TORCH_CHECK(status.numel() >= n_jobs && (status.scalar_type() == at::kByte || status.scalar_type() == at::kBool),
+                "factor_als_cg: status must hold one uint8 / bool entry per job");
+    TORCH_CHECK(!has(rs) || rs->numel() >= n_jobs, "factor_als_cg: rs must hold one float32 entry per job");
+    one_device("factor_als_cg", out, {&r_ptr, &r_idx, &r_val, &v, &gram, &status}, {&job_rows, &rs});
+    check(abi().factor_als_cg(static_cast<int32_t>(n_jobs), cptr<const int32_t>(job_rows), static_cast<int32_t>(n_rows),
+                              cptr<const int32_t>(r_ptr), cptr<const int32_t>(r_idx), cptr<const float>(r_val), r_idx.numel(),
+                              cptr<const float>(v), v.size(1), static_cast<int32_t>(n_v), static_cast<int32_t>(dim),
+                              cptr<const float>(gram), static_cast<float>(alpha), static_cast<int32_t>(cg_steps), warm_start ? 1 : 0,
+                              cptr<float>(out), out.size(1), static_cast<uint8_t *>(cptr<void>(status)), cptr<float>(rs),
+                              stream_of(out)),
+          "rtrec_factor_als_cg");
+}
+
 }  // namespace
 
 // Bind the ops to a build of the C-ABI library (called once by rtrec_amd.ops with _native.lib_path()).
@@ -897,6 +945,8 @@ extern "C" int rtrec_ops_bind(const char *path) {
         bind_one(h, a.similar_blend, "rtrec_similar_blend");
         bind_one(h, a.factor_gram, "rtrec_factor_gram");
         bind_one(h, a.factor_als_solve, "rtrec_factor_als_solve");
+        bind_one(h, a.factor_gram_wide, "rtrec_factor_gram_wide");
+        bind_one(h, a.factor_als_cg, "rtrec_factor_als_cg");
         g_abi = a;
         return 0;
     } catch (const std::exception &) {
@@ -987,6 +1037,9 @@ TORCH_LIBRARY(rtrec_amd, m) {
     m.def("factor_gram(Tensor v, int n_v, int dim, float reg, Tensor(a!) gram, Tensor(b!)? workspace) -> ()");
     m.def("factor_als_solve(Tensor? job_rows, int n_jobs, Tensor r_ptr, Tensor r_idx, Tensor r_val, Tensor v, int n_v, int dim, "
           "Tensor gram, float alpha, Tensor(a!) out, Tensor(b!) status) -> ()");
+    m.def("factor_gram_wide(Tensor v, int n_v, int dim, float reg, Tensor(a!) gram, Tensor(b!)? workspace) -> ()");
+    m.def("factor_als_cg(Tensor? job_rows, int n_jobs, Tensor r_ptr, Tensor r_idx, Tensor r_val, Tensor v, int n_v, int dim, "
+          "Tensor gram, float alpha, int cg_steps, bool warm_start, Tensor(a!) out, Tensor(b!) status, Tensor(c!)? rs) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
@@ -1023,4 +1076,6 @@ TORCH_LIBRARY_IMPL(rtrec_amd, CUDA, m) {
     m.impl("similar_blend", &similar_blend);
     m.impl("factor_gram", &factor_gram);
     m.impl("factor_als_solve", &factor_als_solve);
+    m.impl("factor_gram_wide", &factor_gram_wide);
+    m.impl("factor_als_cg", &factor_als_cg);
 }

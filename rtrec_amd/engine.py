@@ -2186,7 +2186,24 @@ class SlimEngine:
         return tuple(t.cpu().numpy() for t in out)
 
     # ------------------------------------------------------------------------------ training the factor scorer (implicit ALS)
-    ALS_MAX_DIM = 64            # dim limit of rtrec_factor_gram / rtrec_factor_als_solve
+    ALS_MAX_DIM = 64            # dim limit of rtrec_factor_gram / rtrec_factor_als_solve (solver="cholesky")
+    ALS_CG_MAX_DIM = 256        # dim limit of rtrec_factor_gram_wide / rtrec_factor_als_cg (solver="cg"): what the scorer serves
+    ALS_CG_MAX_STEPS = 64       # cg_steps limit of rtrec_factor_als_cg
+    ALS_SOLVERS = ("cholesky", "cg")
+
+    @classmethod
+    def als_solver_check(cls, dim: int, solver: str, cg_steps: int) -> None:
+        """ValueError unless `solver` is known, `dim` lies within its limit and, for "cg", `cg_steps` in 1..64."""
+        if solver not in cls.ALS_SOLVERS:
+            raise ValueError(f"solver must be one of {cls.ALS_SOLVERS}, got {solver!r}")
+        if solver == "cholesky":
+            if not 1 <= dim <= cls.ALS_MAX_DIM:
+                raise ValueError(f"factor vectors of 1..{cls.ALS_MAX_DIM} components can be trained, got {dim}")
+            return
+        if not 1 <= dim <= cls.ALS_CG_MAX_DIM:
+            raise ValueError(f"factor vectors of 1..{cls.ALS_CG_MAX_DIM} components can be trained with solver='cg', got {dim}")
+        if not 1 <= int(cg_steps) <= cls.ALS_CG_MAX_STEPS:
+            raise ValueError(f"cg_steps must lie in 1..{cls.ALS_CG_MAX_STEPS}, got {cg_steps}")
 
     def _als_check(self, what: str) -> None:
         if not self._X:
@@ -2218,16 +2235,16 @@ class SlimEngine:
         return self._X[key]
 
     def als_begin(self, dim: int, regularization: float, alpha: float, item_vectors, user_vectors=None, user_status=None,
-                  item_status=None) -> None:
+                  item_status=None, *, solver: str = "cholesky", cg_steps: int = 3) -> None:
         """Open the training state: two row-major device matrices P [n_users, dim] and Q [rows of item_vectors, dim] (float32
         numbers), the regulariser and the confidence slope of the half-steps to come, and one status per row (1 = no vector
         yet).  fit_factors opens it with seeded item vectors alone; a caller that resumes from finished vectors brings both
-        sides and their status."""
+        sides and their status.  `solver` names how the half-steps to come solve a row: "cholesky" (dim up to 64, exact) or
+        "cg" (dim up to 256: `cg_steps` conjugate-gradient steps per row and half-step, warm-started from the row's vector)."""
         be, torch = self.be, self.be.torch
         self._als_check("als_begin")
         dim = int(dim)
-        if not 1 <= dim <= self.ALS_MAX_DIM:
-            raise ValueError(f"factor vectors of 1..{self.ALS_MAX_DIM} components can be trained, got {dim}")
+        self.als_solver_check(dim, solver, cg_steps)
         reg, alpha = float(regularization), float(alpha)
         if not reg >= 0.0 or not alpha > 0.0:
             raise ValueError(f"regularization must be >= 0 and alpha > 0, got {regularization} and {alpha}")
@@ -2246,14 +2263,16 @@ class SlimEngine:
         if si.shape != (len(Q),):
             raise ValueError(f"item_status must hold one entry per item vector ({len(Q)}), got {si.shape}")
         self._als = {"P": be.to_dev(P), "Q": be.to_dev(Q), "dim": dim, "reg": reg, "alpha": alpha,
-                     "status": {"user": be.to_dev(su), "item": be.to_dev(si)}}
+                     "status": {"user": be.to_dev(su), "item": be.to_dev(si)}, "solver": solver, "cg_steps": int(cg_steps)}
 
     def als_half_step(self, side: str, rows: Optional[Sequence[int]] = None) -> Dict[int, int]:
         """One half-step of the open training state: the Gram matrix of the FIXED side (csrc/factor_gram.hip), then the solve
         of every row of `side` ("user": rows of X against the item vectors; "item": columns of X against the user vectors) or
         of the distinct rows named, written in place (csrc/factor_als.hip; the comments of rtrec_factor_gram and
         rtrec_factor_als_solve in include/rtrec_amd_ext.h are the contract).  Returns how many jobs ended with status 0
-        (solved), 1 (a row outside the side, or without a usable entry: its vector is zero) and 2 (breakdown: zero too)."""
+        (solved), 1 (a row outside the side, or without a usable entry: its vector is zero) and 2 (breakdown: zero too).
+        With the state's solver "cg" the second call is rtrec_factor_als_cg (csrc/factor_als_cg.hip), warm-started from the
+        vectors the state holds, and the Gram call is rtrec_factor_gram_wide above 64 components."""
         be, torch = self.be, self.be.torch
         self._als_check("als_half_step")
         T = getattr(self, "_als", None)
@@ -2263,7 +2282,7 @@ class SlimEngine:
         n_rows = min(n_rows, int(out.shape[0]))            # (an item X has gained since the vectors were made has none yet)
         dim = T["dim"]
         gram = be.empty((dim, dim), torch.float32)
-        be.factor_gram(fixed, int(fixed.shape[0]), dim, T["reg"], gram)
+        (be.factor_gram if dim <= self.ALS_MAX_DIM else be.factor_gram_wide)(fixed, int(fixed.shape[0]), dim, T["reg"], gram)
         if rows is None:
             jobs = self._als_order(side, csr[0])
             if int(jobs.numel()) != n_rows:
@@ -2275,7 +2294,11 @@ class SlimEngine:
         status = be.zeros((n_jobs,), torch.uint8)
         if n_jobs:
             ptr = csr[0][:n_rows + 1].contiguous()
-            be.factor_als_solve(jobs, n_jobs, (ptr, csr[1], csr[2]), fixed, int(fixed.shape[0]), dim, gram, T["alpha"], out, status)
+            if T.get("solver", "cholesky") == "cg":
+                be.factor_als_cg(jobs, n_jobs, (ptr, csr[1], csr[2]), fixed, int(fixed.shape[0]), dim, gram, T["alpha"],
+                                 T["cg_steps"], True, out, status)
+            else:
+                be.factor_als_solve(jobs, n_jobs, (ptr, csr[1], csr[2]), fixed, int(fixed.shape[0]), dim, gram, T["alpha"], out, status)
             T["status"][side][jobs.to(torch.int64)] = status
         counts = torch.bincount(status.to(torch.int64), minlength=3).cpu().numpy()
         return {s: int(counts[s]) for s in range(3)}
@@ -2303,17 +2326,20 @@ class SlimEngine:
         self._take_item_norms(0)
 
     def fit_factors(self, dim: int = 32, iterations: int = 15, regularization: float = 0.01, alpha: float = 1.0,
-                    seed: int = 0) -> Dict[str, Dict[int, int]]:
+                    seed: int = 0, *, solver: str = "cholesky", cg_steps: int = 3) -> Dict[str, Dict[int, int]]:
         """Train the factor scorer on the resident X by implicit-feedback ALS (Hu, Koren, Volinsky): `iterations` times a user
         half-step, then an item half-step.  Only the item matrix is initialised -- np.random.default_rng(seed)
         .standard_normal((n_items, dim)).astype(float32) * float32(0.01), made on the host and uploaded once -- and the result
         is installed as set_factors() would (als_install).  Deterministic: every operation of a half-step is pinned
-        (include/rtrec_amd_ext.h).  Returns the status counts of the last half-step of each side."""
+        (include/rtrec_amd_ext.h).  `solver="cg"` runs `cg_steps` conjugate-gradient steps per row and half-step instead of
+        the Cholesky solve, each warm-started from the last half-step's vector (the first user half-step from zero), and
+        trains up to 256 components.  Returns the status counts of the last half-step of each side."""
         if int(iterations) < 1:
             raise ValueError(f"iterations must be at least 1, got {iterations}")
         self._als_check("fit_factors")
+        self.als_solver_check(int(dim), solver, cg_steps)
         Q0 = np.random.default_rng(seed).standard_normal((self.n_items, int(dim))).astype(np.float32) * np.float32(0.01)
-        self.als_begin(dim, regularization, alpha, Q0)
+        self.als_begin(dim, regularization, alpha, Q0, solver=solver, cg_steps=cg_steps)
         counts = {}
         for _ in range(int(iterations)):
             counts["user"] = self.als_half_step("user")

@@ -48,7 +48,7 @@ class SLIM(BaseModel):
         self._dev_x: Optional[DeviceInteractions] = None        # X resident in HBM (utils/device_store.py)
         self._factors: Optional[Dict[str, np.ndarray]] = None   # vectors of a factor model the caller attached (attach_factors)
         self._factors_on_device: Any = None                     # (what the engine's resident copy was built for, has-vector mask)
-        self._factor_training: Optional[Dict[str, float]] = None   # regularization / alpha of the last fit_factors (not pickled)
+        self._factor_training: Optional[Dict[str, float]] = None   # regularization / alpha (/ solver, cg_steps) of the last fit_factors
 
     # ------------------------------------------------------------ device-resident X
     def _store_tag(self) -> Any:
@@ -1182,7 +1182,17 @@ class SLIM(BaseModel):
         self._factors_on_device = None
         return self
 
-    FACTOR_TRAIN_MAX_DIM = 64   # dim limit of rtrec_factor_als_solve
+    FACTOR_TRAIN_MAX_DIM = 64   # dim limit of rtrec_factor_als_solve (the default solver)
+    FACTOR_TRAIN_CG_MAX_DIM = 256   # dim limit of rtrec_factor_als_cg (solver="cg")
+
+    @classmethod
+    def _factor_solver_check(cls, what: str, dim: int, solver: str, cg_steps: int) -> None:
+        if solver not in ("cholesky", "cg"):
+            raise ValueError(f"{what}: solver must be 'cholesky' or 'cg', got {solver!r}")
+        if solver == "cg" and not 1 <= int(dim) <= cls.FACTOR_TRAIN_CG_MAX_DIM:
+            raise ValueError(f"{what} solves vectors of 1..{cls.FACTOR_TRAIN_CG_MAX_DIM} components with solver='cg', got {dim}")
+        if solver == "cg" and not 1 <= int(cg_steps) <= 64:
+            raise ValueError(f"{what}: cg_steps must lie in 1..64, got {cg_steps}")
 
     def _take_trained_factors(self, eng: Any) -> None:
         """The engine's training state as the vectors attach_factors() would have kept: one row per user / item whose last
@@ -1199,39 +1209,52 @@ class SLIM(BaseModel):
             self._factors_on_device = None
 
     def fit_factors(self, dim: int = 32, iterations: int = 15, regularization: float = 0.01, alpha: float = 1.0,
-                    seed: int = 0) -> "SLIM":
+                    seed: int = 0, *, solver: str = "cholesky", cg_steps: int = 3) -> "SLIM":
         """Train the second scorer of the hybrid on the device, from the interactions this model holds: implicit-feedback
         alternating least squares (Hu, Koren, Volinsky) with confidence 1 + alpha * r over the stored, positive interactions,
         `iterations` times a user half-step and an item half-step, deterministic for a `seed` (SlimEngine.fit_factors; the
         pinned arithmetic is the contract of rtrec_factor_gram / rtrec_factor_als_solve in include/rtrec_amd_ext.h).  The
         reference's hybrid trains LightFM there; this is ALS and learns one vector per user and item -- tags still need
         attach_feature_factors().  Leaves the model as attach_factors(users, P, items, Q) with the trained vectors would: a
-        user or item without a positive interaction has no vector.  Returns self."""
-        if not 1 <= int(dim) <= self.FACTOR_TRAIN_MAX_DIM:
+        user or item without a positive interaction has no vector.  `solver="cholesky"` (the default) solves every row's system
+        exactly and trains up to 64 components; `solver="cg"` runs `cg_steps` (1..64) conjugate-gradient steps per row and
+        half-step, warm-started from the row's last vector, as `implicit` does by default, and trains up to 256 components
+        (rtrec_factor_als_cg).  Returns self."""
+        self._factor_solver_check("fit_factors", dim, solver, cg_steps)
+        if solver == "cholesky" and not 1 <= int(dim) <= self.FACTOR_TRAIN_MAX_DIM:
             raise ValueError(f"fit_factors trains vectors of 1..{self.FACTOR_TRAIN_MAX_DIM} components, got {dim}")
         if int(iterations) < 1 or not float(regularization) >= 0.0 or not float(alpha) > 0.0:
             raise ValueError(f"fit_factors needs iterations >= 1, regularization >= 0 and alpha > 0, got {iterations}, "
                              f"{regularization} and {alpha}")
         self._sync_interactions_csc()
         eng = self.model.engine
-        eng.fit_factors(dim=int(dim), iterations=int(iterations), regularization=float(regularization), alpha=float(alpha), seed=seed)
+        eng.fit_factors(dim=int(dim), iterations=int(iterations), regularization=float(regularization), alpha=float(alpha), seed=seed,
+                        solver=solver, cg_steps=int(cg_steps))
         self._factor_training = {"regularization": float(regularization), "alpha": float(alpha)}
+        if solver != "cholesky":                 # (a dict without a solver means Cholesky: an old pickle, attach_factors)
+            self._factor_training.update(solver=solver, cg_steps=int(cg_steps))
         self._take_trained_factors(eng)
         return self
 
-    def update_factors(self, users: Iterable[Any]) -> "SLIM":
+    def update_factors(self, users: Iterable[Any], *, solver: Optional[str] = None, cg_steps: Optional[int] = None) -> "SLIM":
         """The online counterpart of fit_factors, to be called after fit / partial_fit of new interactions: the rows of the named
         users are solved again against the current item vectors (one Gram matrix, one solve over a job list), with the
         regularization and alpha of the last fit_factors (its defaults after attach_factors or a pickle).  A user X knows
         and the vectors do not yet gets one; users the model does not know are ignored; item vectors are not touched (an
-        item without one is skipped in every row).  RuntimeError without fitted or attached vectors."""
+        item without one is skipped in every row).  `solver` / `cg_steps` default to those of the last fit_factors (Cholesky
+        after attach_factors); `solver="cg"` re-solves vectors of up to 256 components, each warm-started from the user's
+        present vector.  RuntimeError without fitted or attached vectors."""
         if self._factors is None:
             raise RuntimeError("fit_factors() or attach_factors() must be called before update_factors.")
         if self.has_feature_factors():
             raise ValueError("update_factors solves one vector per user; attach_feature_factors() brought per-feature tables")
         F = self._factors
         dim = int(F["user_vectors"].shape[1])
-        if dim > self.FACTOR_TRAIN_MAX_DIM:
+        par = getattr(self, "_factor_training", None) or {"regularization": 0.01, "alpha": 1.0}
+        solver = par.get("solver", "cholesky") if solver is None else solver
+        cg_steps = par.get("cg_steps", 3) if cg_steps is None else cg_steps
+        self._factor_solver_check("update_factors", dim, solver, cg_steps)
+        if solver == "cholesky" and dim > self.FACTOR_TRAIN_MAX_DIM:
             raise ValueError(f"update_factors solves vectors of 1..{self.FACTOR_TRAIN_MAX_DIM} components, the attached ones have {dim}")
         self._sync_interactions_csc()
         eng = self.model.engine
@@ -1244,8 +1267,8 @@ class SLIM(BaseModel):
         Q, si = np.zeros((n_items, dim), np.float32), np.ones(n_items, np.uint8)
         ok = F["item_rows"] < n_items
         Q[F["item_rows"][ok]], si[F["item_rows"][ok]] = F["item_vectors"][ok], 0
-        par = getattr(self, "_factor_training", None) or {"regularization": 0.01, "alpha": 1.0}
-        eng.als_begin(dim, par["regularization"], par["alpha"], Q, user_vectors=P, user_status=su, item_status=si)
+        eng.als_begin(dim, par["regularization"], par["alpha"], Q, user_vectors=P, user_status=su, item_status=si, solver=solver,
+                      cg_steps=int(cg_steps))
         if len(rows):
             eng.als_half_step("user", rows)
         self._take_trained_factors(eng)
@@ -1838,6 +1861,8 @@ class SLIM(BaseModel):
                 "item_ids": self.item_ids, "feature_store": self.feature_store}
         if self._factors is not None:           # (only when attached: a model without vectors serialises as it always did)
             data["factors"] = self._factors
+            if (getattr(self, "_factor_training", None) or {}).get("solver", "cholesky") != "cholesky":
+                data["factor_training"] = dict(self._factor_training)      # (only for a solver an old pickle cannot mean)
         return data
 
     @classmethod
@@ -1849,4 +1874,5 @@ class SLIM(BaseModel):
         instance.item_ids = data["item_ids"]
         instance.feature_store = data["feature_store"]
         instance._factors = data.get("factors")
+        instance._factor_training = data.get("factor_training")
         return instance

@@ -34,6 +34,8 @@ is written on top of them; they are also the interface for callers that already 
     torch.ops.rtrec_amd.similar_blend       (extension surface) per row: two lists cut, the query taken out, min-max normalised, summed per id in float64, re-ranked
     torch.ops.rtrec_amd.factor_gram         (extension surface) V^T V + reg I of one side's vectors in chunks of 1024 rows (f32 MFMA = the fmaf chain), the partials added in order
     torch.ops.rtrec_amd.factor_als_solve    (extension surface) per row of R: G + sum w y y^T on the f32 MFMA, a pinned Cholesky solve, written in place; one status per job
+    torch.ops.rtrec_amd.factor_gram_wide    (extension surface) factor_gram for vectors of up to 256 components: one MFMA chain per (chunk, lower 32 x 32 tile)
+    torch.ops.rtrec_amd.factor_als_cg       (extension surface) per row of R: pinned conjugate-gradient steps on the same system, never formed; dim up to 256, warm start
 
 The registration lives in csrc/torch_ops.cpp (TORCH_LIBRARY / TORCH_LIBRARY_IMPL: librtrec_amd_ops.so, built by
 rtrec_amd/build.py with the host compiler); importing this module loads it and binds it to the C-ABI library
@@ -71,13 +73,14 @@ EXPORT_OF = {"column_sqnorms": "rtrec_slim_column_sqnorms", "fit_workspace_init"
 
 # The extension surface (include/rtrec_amd_ext.h, _native.EXT_EXPORTS): the same rules -- one op per kernel-launching export
 EXT_OPS = ["diversify_lists", "list_quality", "catalogue_ranks", "blend_lists", "factor_topk", "feature_repr",
-           "factor_norms", "factor_similar_topk", "similar_blend", "factor_gram", "factor_als_solve"]
+           "factor_norms", "factor_similar_topk", "similar_blend", "factor_gram", "factor_als_solve", "factor_gram_wide", "factor_als_cg"]
 EXT_EXPORT_OF = {"diversify_lists": "rtrec_slim_diversify_lists", "list_quality": "rtrec_slim_list_quality",
                  "catalogue_ranks": "rtrec_slim_catalogue_ranks", "blend_lists": "rtrec_slim_blend_lists",
                  "factor_topk": "rtrec_factor_topk", "feature_repr": "rtrec_feature_repr",
                  "factor_norms": "rtrec_factor_norms", "factor_similar_topk": "rtrec_factor_similar_topk",
                  "similar_blend": "rtrec_similar_blend", "factor_gram": "rtrec_factor_gram",
-                 "factor_als_solve": "rtrec_factor_als_solve"}
+                 "factor_als_solve": "rtrec_factor_als_solve", "factor_gram_wide": "rtrec_factor_gram_wide",
+                 "factor_als_cg": "rtrec_factor_als_cg"}
 
 
 def _load() -> None:

@@ -189,14 +189,16 @@ class Recommender:
         return self
 
     def fit_factors(self, dim: int = 32, iterations: int = 15, regularization: float = 0.01, alpha: float = 1.0,
-                    seed: int = 0) -> "Recommender":
-        """Train the second scorer of recommend_hybrid on the device by implicit ALS (SLIM.fit_factors)."""
-        self.model.fit_factors(dim=dim, iterations=iterations, regularization=regularization, alpha=alpha, seed=seed)
+                    seed: int = 0, *, solver: str = "cholesky", cg_steps: int = 3) -> "Recommender":
+        """Train the second scorer of recommend_hybrid on the device by implicit ALS (SLIM.fit_factors); solver="cg" trains up
+        to 256 components by `cg_steps` conjugate-gradient steps per row."""
+        self.model.fit_factors(dim=dim, iterations=iterations, regularization=regularization, alpha=alpha, seed=seed,
+                               solver=solver, cg_steps=cg_steps)
         return self
 
-    def update_factors(self, users: List[Any]) -> "Recommender":
+    def update_factors(self, users: List[Any], *, solver: Optional[str] = None, cg_steps: Optional[int] = None) -> "Recommender":
         """Solve the named users' vectors again after new interactions (SLIM.update_factors)."""
-        self.model.update_factors(users)
+        self.model.update_factors(users, solver=solver, cg_steps=cg_steps)
         return self
 
     def detach_factors(self) -> "Recommender":

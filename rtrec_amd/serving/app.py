@@ -41,7 +41,7 @@ the GPU), POST /recommend (one user's top-k).  Differences, all forced by the de
     on a model without the tables of attach_feature_factors); same token check as /rerank, answered under the model lock, not
     coalesced;
   * POST /fit_factors is an addition beside /fit (train the served model's second scorer on the device by implicit ALS, from
-    the interactions it holds): {"dim", "iterations", "regularization", "alpha", "seed"}, all optional -> {"message": "Factor
+    the interactions it holds): {"dim", "iterations", "regularization", "alpha", "seed", "solver", "cg_steps"}, all optional -> {"message": "Factor
     training successful"} (SLIM.fit_factors); same token check as /fit, answered under the model lock;
   * concurrent POST /recommend calls are coalesced (`RecommendCoalescer`): requests that arrive within a bounded
     wait (RTREC_AMD_COALESCE_MS, default 1 ms; 0 = only what queued up behind the model lock) share ONE
@@ -150,6 +150,8 @@ class FitFactorsRequest(BaseModel):
     regularization: float = 0.01
     alpha: float = 1.0
     seed: int = 0
+    solver: str = "cholesky"
+    cg_steps: int = 3
 
 
 class SimilarHybridRequest(BaseModel):
@@ -348,7 +350,8 @@ def build_router(gate: ModelGate) -> APIRouter:
         _authorise(x_token)
         gate.call("Factor training", lambda m: m.fit_factors(dim=request.dim, iterations=request.iterations,
                                                              regularization=request.regularization, alpha=request.alpha,
-                                                             seed=request.seed))
+                                                             seed=request.seed, solver=request.solver,
+                                                             cg_steps=request.cg_steps))
         return {"message": "Factor training successful"}
 
     @api.post("/recommend", response_model=RecommendationResponse)
