@@ -1243,6 +1243,14 @@ __device__ __forceinline__ int fr_lane_rank_ties(float v, int lane) {
 // The forms of score_frows_kernel that fill an EMPTY list by rank (fr_lane_rank_above) instead of by insertion: all but
 // the 8-user form of 256-column tiles and 65+ rows of W, which sits at exactly 128 VGPRs and would spill two.
 template <int REGS, int XR, int UW> constexpr bool kFrRankFill = !(REGS == 4 && XR == 2 && UW == 8);
+// Of those, the forms that rank STRIDED groups instead of lanes: group g = register r of the lane kFrGroupStep * r below g,
+// i.e. the columns REGS * ((g - kFrGroupStep * r) & 63) + r of the tile.  A lane holds REGS consecutive columns, and the
+// layout puts columns with the same row pattern side by side: a tile's best sums often share a lane.  Registers r and r + d
+// of one strided group lie 64 d - d columns apart (64 (REGS - d) + d where the lane wraps): never closer than 63 columns.
+// The 8-user form of 256-column tiles and up to 64 rows of W keeps the lanes as well: it compiles to 128 VGPRs without a
+// spill, but ran c4 8 % slower with strided groups (the cause is not established).
+template <int REGS> constexpr int kFrGroupStep = 64 / REGS;
+template <int REGS, int XR, int UW> constexpr bool kFrGroupFill = kFrRankFill<REGS, XR, UW> && !(REGS == 4 && UW == 8);
 
 // Compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{}).  The per-user
 // register arrays of the kernel below are indexed with these constants only, so every element is a scalar
@@ -1800,62 +1808,6 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                 const bool in = rel >= 0 && rel < kk;
                 const bool fill = thr == ninf;
                 int skip_r = -1;           // first fill by rank: the register of the lane whose sum is placed already
-                if (fill) {
-                    // The list is not full yet (first tile, or a user with few scored columns): everything
-                    // non-zero would pass.
-                    PF_ADD(PF_N_OVERFLOW, 1)
-                    // the lane's largest admissible, non-zero sum and the register that holds it (of equal sums the later
-                    // register: the higher column)
-                    float bm = ninf;
-                    int br = 0;
-                    fr_static_for<REGS>([&](auto Rc) {
-                        constexpr int r = decltype(Rc)::value;
-                        const float v = acc[u][r];
-                        const float vm = (v != 0.0f && !((ex[r] >> lane) & 1ull)) ? v : ninf;
-                        br = vm >= bm ? r : br;
-                        bm = vm >= bm ? vm : bm;
-                    });
-                    if (kFrRankFill<REGS, XR, UW> && readlane_i(lc4[g], lb) < 0) {
-                        // ---- the list is EMPTY: nothing needs inserting.  The kk best lane maxima, ordered as merge() orders
-                        //      (score, then higher column = higher lane), ARE the list: every lane takes its rank among the 64
-                        //      maxima in straight-line code, the first kk write themselves to the candidate buffer at their
-                        //      rank, and the list lanes read the buffer back.  What is left for merge() is a sum above the
-                        //      new kk-th entry that is not its lane's maximum (a second register of one lane: rare). ----
-                        const int n_val = static_cast<int>(__builtin_popcountll(__ballot(bm != ninf)));
-                        if (n_val == 0) return;                 // nothing admissible in this tile: the list stays empty
-                        const int col = t * TC + lane * REGS + br;
-                        int rank = fr_lane_rank_above(bm);
-                        bool mine = bm != ninf && rank < kk;
-                        if (mine) { cv[rank] = bm; cp[rank] = col; }
-                        // equal maxima among the first kk share a rank, and all but one of them lose their slot: they
-                        // read another lane's column back (through an index the compiler cannot match to the store's:
-                        // what the LDS holds, not what this lane wrote).  Rare: rank again with the lanes told apart.
-                        int slot = rank;
-                        asm volatile("" : "+v"(slot));
-                        if (__ballot(mine && cp[slot] != col)) {
-                            rank = fr_lane_rank_ties(bm, lane);
-                            mine = bm != ninf && rank < kk;
-                            if (mine) { cv[rank] = bm; cp[rank] = col; }
-                        }
-                        if (rel >= 0 && rel < min(n_val, kk)) {      // LDS operations of one wave execute in order
-                            ls4[g] = cv[rel];
-                            lc4[g] = cp[rel];
-                        }
-                        const float thr_new = readlane_f(ls4[g], lb + kk - 1);
-                        thrv = lane == u ? thr_new : thrv;
-                        tcut = thr_new;                         // -inf while fewer than kk lanes held a sum: every other sum is an extra
-                        skip_r = br;
-                        PF_ADD(PF_ROWPTR, min(n_val, kk)) PF_ADD(PF_RESET, min(n_val, kk))
-                    } else {
-                        // A partial list (a user with fewer than kk admissible columns so far).  Take the tile's own kk-th
-                        // best admissible score (a bound from the lane maxima) as the cut:
-                        // kk-th largest of the 64 lane maxima (the 16 quad maxima would do as a bound, but a loose one:
-                        // half the tile can lie above it); -inf: fewer than kk lanes hold a score, and everything
-                        // they hold (< kk * REGS <= kFrCandCap) fits the buffer
-                        const float t0 = fr_kth_lane_best(bm, 64 + kk);
-                        if (t0 != ninf) tcut = float_prev(t0);      // candidates are the values >= t0
-                    }
-                }
                 int nc = 0;
                 // merge the buffered candidates into the user's list (lane lb + j = rank j)
                 auto merge = [&]() {
@@ -1881,25 +1833,116 @@ __global__ __launch_bounds__(kFrWaves * 64, 4) void score_frows_kernel(FrArgs a)
                     const float thr_new = readlane_f(ls4[g], lb + kk - 1);
                     thrv = lane == u ? thr_new : thrv;
                 };
-                fr_static_for<REGS>([&](auto Rc) {
-                    constexpr int r = decltype(Rc)::value;
-                    const float v = acc[u][r];
-                    // only non-zero sums compete (scipy keeps `!= 0`)
-                    unsigned long long m = __ballot(v > tcut && v != 0.0f && r != skip_r);
-                    if (!m) return;
-                    m &= ~ex[r];
-                    if (!m) return;
-                    const int cnt = static_cast<int>(__builtin_popcountll(m));
-                    if (nc + cnt > kFrCandCap) merge();      // the buffer holds one ballot's worth (64): make room first
-                    if ((m >> lane) & 1ull) {
-                        const int pos = nc + lane_prefix(m);
-                        cv[pos] = v;
-                        cp[pos] = t * TC + lane * REGS + r;
+                // buffer the sums above the cut, register after register, and merge them.  Grouped (a first fill ranked over
+                // strided groups): `xv` holds the ROTATED admissible sums, register r of the lane kFrGroupStep<REGS> * r below.
+                auto scan = [&](auto Gc, const vec &xv) {
+                    constexpr bool grouped = decltype(Gc)::value;
+                    fr_static_for<REGS>([&](auto Rc) {
+                        constexpr int r = decltype(Rc)::value;
+                        const float v = xv[r];
+                        // only non-zero sums compete (scipy keeps `!= 0`)
+                        unsigned long long m = __ballot(v > tcut && (grouped || v != 0.0f) && r != skip_r);
+                        if (!m) return;
+                        if constexpr (!grouped) {
+                            m &= ~ex[r];
+                            if (!m) return;
+                        }
+                        const int cnt = static_cast<int>(__builtin_popcountll(m));
+                        if (nc + cnt > kFrCandCap) merge();      // the buffer holds one ballot's worth (64): make room first
+                        if ((m >> lane) & 1ull) {
+                            const int pos = nc + lane_prefix(m);
+                            const int src = grouped ? ((lane - kFrGroupStep<REGS> * r) & 63) : lane;
+                            cv[pos] = v;
+                            cp[pos] = t * TC + src * REGS + r;
+                        }
+                        nc += cnt;
+                        PF_ADD(PF_ROWPTR, fill ? cnt : 0)
+                    });
+                    if (nc > 0) merge();
+                };
+                if (fill) {
+                    // The list is not full yet (first tile, or a user with few scored columns): everything
+                    // non-zero would pass.
+                    PF_ADD(PF_N_OVERFLOW, 1)
+                    // the lane's admissible, non-zero sums, its largest and the register that holds it (of equal sums the later
+                    // register: the higher column)
+                    vec vm;
+                    fr_static_for<REGS>([&](auto Rc) {
+                        constexpr int r = decltype(Rc)::value;
+                        const float v = acc[u][r];
+                        vm[r] = (v != 0.0f && !((ex[r] >> lane) & 1ull)) ? v : ninf;
+                    });
+                    const bool empty = kFrRankFill<REGS, XR, UW> && readlane_i(lc4[g], lb) < 0;
+                    constexpr bool grouped = kFrGroupFill<REGS, XR, UW>;
+                    if (grouped && empty) {
+                        // ---- strided groups: register r moves up by kFrGroupStep * r lanes (wrapping), so that lane g holds
+                        //      group g = the columns REGS * ((g - kFrGroupStep * r) & 63) + r.  REGS neighbouring columns, which
+                        //      tend to carry their tile's best sums together, fall into REGS groups and are ranked side by
+                        //      side.  ds_bpermute_b32: one instruction per register, all in flight behind one wait, no LDS
+                        //      memory touched ----
+                        fr_static_for<REGS>([&](auto Rc) {
+                            constexpr int r = decltype(Rc)::value;
+                            if constexpr (r > 0)
+                                vm[r] = __int_as_float(__builtin_amdgcn_ds_bpermute(((lane - kFrGroupStep<REGS> * r) & 63) << 2, __float_as_int(vm[r])));
+                        });
                     }
-                    nc += cnt;
-                    PF_ADD(PF_ROWPTR, fill ? cnt : 0)
-                });
-                if (nc > 0) merge();
+                    float bm = ninf;
+                    int br = 0;
+                    fr_static_for<REGS>([&](auto Rc) {
+                        constexpr int r = decltype(Rc)::value;
+                        br = vm[r] >= bm ? r : br;
+                        bm = vm[r] >= bm ? vm[r] : bm;
+                    });
+                    if (empty) {
+                        // ---- the list is EMPTY: nothing needs inserting.  The kk best group maxima (a group: a strided group where
+                        //      kFrGroupFill holds, else the lane's own REGS columns: the 8-user form <4,1,8>), ordered by (score, then
+                        //      higher group), ARE the list: every lane takes its rank among the 64 maxima in straight-line
+                        //      code, the first kk write themselves to the candidate buffer at their rank, and the list lanes
+                        //      read the buffer back.  What is left for merge() is a sum above the new kk-th entry that is
+                        //      not its group's maximum (rare with strided groups). ----
+                        const int n_val = static_cast<int>(__builtin_popcountll(__ballot(bm != ninf)));
+                        if (n_val == 0) return;                 // nothing admissible in this tile: the list stays empty
+                        const int src = grouped ? ((lane - kFrGroupStep<REGS> * br) & 63) : lane;
+                        const int col = t * TC + src * REGS + br;
+                        int rank = fr_lane_rank_above(bm);
+                        bool mine = bm != ninf && rank < kk;
+                        if (mine) { cv[rank] = bm; cp[rank] = col; }
+                        // equal maxima among the first kk share a rank, and all but one of them lose their slot: they
+                        // read another lane's column back (through an index the compiler cannot match to the store's:
+                        // what the LDS holds, not what this lane wrote).  Rare: rank again with the lanes told apart.
+                        int slot = rank;
+                        asm volatile("" : "+v"(slot));
+                        if (__ballot(mine && cp[slot] != col)) {
+                            rank = fr_lane_rank_ties(bm, lane);
+                            mine = bm != ninf && rank < kk;
+                            if (mine) { cv[rank] = bm; cp[rank] = col; }
+                        }
+                        if (rel >= 0 && rel < min(n_val, kk)) {      // LDS operations of one wave execute in order
+                            ls4[g] = cv[rel];
+                            lc4[g] = cp[rel];
+                        }
+                        const float thr_new = readlane_f(ls4[g], lb + kk - 1);
+                        thrv = lane == u ? thr_new : thrv;
+                        tcut = thr_new;                         // -inf while fewer than kk groups held a sum: every other sum is an extra
+                        skip_r = br;
+                        PF_ADD(PF_ROWPTR, min(n_val, kk)) PF_ADD(PF_RESET, min(n_val, kk))
+                        if constexpr (grouped) {
+                            // the extras in group coordinates, from the rotated copies (admissibility is inside them already)
+                            scan(std::true_type{}, vm);
+                            PF_MARK(PF_SPARSE)
+                            return;
+                        }
+                    } else {
+                        // A partial list (a user with fewer than kk admissible columns so far).  Take the tile's own kk-th
+                        // best admissible score (a bound from the lane maxima) as the cut:
+                        // kk-th largest of the 64 lane maxima (the 16 quad maxima would do as a bound, but a loose one:
+                        // half the tile can lie above it); -inf: fewer than kk lanes hold a score, and everything
+                        // they hold (< kk * REGS <= kFrCandCap) fits the buffer
+                        const float t0 = fr_kth_lane_best(bm, 64 + kk);
+                        if (t0 != ninf) tcut = float_prev(t0);      // candidates are the values >= t0
+                    }
+                }
+                scan(std::false_type{}, acc[u]);
                 PF_MARK(fill ? PF_SPARSE : PF_SELECT)
             });
             PF_MARK(PF_SELECT)

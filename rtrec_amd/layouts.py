@@ -468,24 +468,35 @@ def fr_exit_model(L: Dict[str, Any], W: sp.spmatrix, X: sp.csr_matrix, top_k: in
 
 
 # ---- host model of score_frows_kernel's first fill (csrc/score.hip): an empty list is filled by rank, not by insertion ----
-def fr_first_fill_model(sums: np.ndarray, admissible: np.ndarray, kk: int) -> Dict[str, Any]:
+def fr_fill_group_columns(regs: int, strided: bool) -> np.ndarray:
+    """[64, regs] tile-local column of register r of group g.  Lane groups: g * regs + r, a lane's own consecutive columns.
+    Strided groups: regs * ((g - (64 // regs) * r) % 64) + r, register r of the lane 64 // regs * r places below g."""
+    g, r = np.arange(64)[:, None], np.arange(regs)[None, :]
+    return regs * ((g - (64 // regs) * r) % 64) + r if strided else g * regs + r
+
+
+def fr_first_fill_model(sums: np.ndarray, admissible: np.ndarray, kk: int, strided: bool = False) -> Dict[str, Any]:
     """The list a user with an EMPTY list holds after one tile, as the kernel builds it.  `sums`: the tile's float32 sums,
     64 * regs of them in layout order (lane = column // regs holds the `regs` consecutive columns lane * regs + r);
-    `admissible`: False for the interacted columns; a zero sum never competes.  Three steps, as in the kernel:
-      rank    every lane's largest admissible sum (of equal sums the later register: the higher column) takes
-              rank = #{lanes with a larger maximum, or an equal one and a higher lane}; lanes without a sum take none
-      place   the lanes of rank < kk are the list, in rank order
+    `admissible`: False for the interacted columns; a zero sum never competes.  The 64 GROUPS the ranking runs over are
+    the lanes (`strided` False: the 8-user form of 256-column tiles and up to 64 rows of W, and every form before round 12)
+    or the strided groups of fr_fill_group_columns (every other form that ranks at all: the 8-user form of 256-column
+    tiles and 65+ rows still fills by insertion).  Three steps, as in the kernel:
+      rank    every group's largest admissible sum (of equal sums the later register) takes
+              rank = #{groups with a larger maximum, or an equal one and a higher group index}; groups without a sum take none
+      place   the groups of rank < kk are the list, in rank order
       extras  every other admissible sum ABOVE the list's kk-th entry (-inf while the list is short) goes through
-              merge(): register after register, lanes ascending, inserted behind the entries that are larger or equal
+              merge(): register after register, groups ascending, inserted behind the entries that are larger or equal
               with a higher column, and only while it beats the kk-th entry of the moment
-    Returns values [kk] (float32, -inf where empty), cols [kk] (tile-local, -1 where empty), n_ranked (lanes with a sum),
+    Returns values [kk] (float32, -inf where empty), cols [kk] (tile-local, -1 where empty), n_ranked (groups with a sum),
     n_extras (sums handed to merge), n_inserted (those of them that entered)."""
     sums = np.asarray(sums, dtype=np.float32)
     regs = len(sums) // 64
     assert regs in (2, 4) and len(sums) == 64 * regs and 1 <= kk <= 16
     ninf = np.float32(-np.inf)
-    ok = np.asarray(admissible, dtype=bool) & (sums != 0)
-    vm = np.where(ok, sums, ninf).reshape(64, regs)
+    gcol = fr_fill_group_columns(regs, strided)
+    ok = (np.asarray(admissible, dtype=bool) & (sums != 0))[gcol]
+    vm = np.where(ok, sums[gcol], ninf)
     br = regs - 1 - np.argmax(vm[:, ::-1], axis=1)
     lanes = np.arange(64)
     bm = vm[lanes, br]
@@ -495,12 +506,12 @@ def fr_first_fill_model(sums: np.ndarray, admissible: np.ndarray, kk: int) -> Di
     cols = np.full(kk, -1, dtype=np.int64)
     sel = has & (rank < kk)
     values[rank[sel]] = bm[sel]
-    cols[rank[sel]] = lanes[sel] * regs + br[sel]
+    cols[rank[sel]] = gcol[lanes[sel], br[sel]]
     cut = values[kk - 1]
     n_extras = n_inserted = 0
     for r in range(regs):
-        for lane in np.flatnonzero(ok.reshape(64, regs)[:, r] & (br != r) & (vm[:, r] > cut)):
-            v, c = vm[lane, r], int(lane) * regs + r
+        for lane in np.flatnonzero(ok[:, r] & (br != r) & (vm[:, r] > cut)):
+            v, c = vm[lane, r], int(gcol[lane, r])
             n_extras += 1
             if not v > values[kk - 1]:
                 continue
