@@ -720,6 +720,14 @@ int rtrec_rank_metrics(int32_t n_rows, int32_t size, const int32_t *d_ids, int32
  *   reasons             the top_m contributing items by c descending, among equal c the LOWER item id first; every stored
  *                       intersection takes part, negative ones included -> d_out_items / d_out_contrib [n_rows][list_k][top_m],
  *                       unused slots -1 / -inf (the padding of rtrec_slim_score_topk)
+ * Values that are no ordinary numbers (rtrec_slim_score_pairs' rule, so that NaN means the same in every ranking kernel):
+ *   NaN     a NaN contribution (a NaN rating or weight, inf * 0 with a stored zero) counts in support and is never a reason:
+ *           its slot stays padding.  With s = the number of contributions that are numbers, slots [min(s, top_m), top_m) are
+ *           padding.  No output ever holds a NaN
+ *   +-inf   contributions that are numbers: +inf comes first, -inf last but LISTED, with an id >= 0, unlike padding.  A finite
+ *           product that overflows is +-inf and ties with a true one
+ *   zeros   equal contributions go to the lower item id, +0.0 against -0.0 included, and each keeps its own sign bit in
+ *           d_out_contrib.  Denormal products are kept, not flushed; a product below the denormals rounds to a signed zero
  * Invariant for a float32 W: adding all contributions of a pair in ascending j, sequentially in float32 from 0.0f, gives
  * exactly the score rtrec_slim_score_topk reports for the pair (scipy's csr_matmat order).
  * A list slot at or beyond d_counts[r], an item id outside [0, n_items) (-1 included) and a row id outside [0, n_x_rows) (a
@@ -752,8 +760,14 @@ int rtrec_slim_explain_topk(int32_t n_rows, const int32_t *d_row_ids, const int3
  *                       negative scores take part); with filter_interacted != 0, u is not stored in column i of X; with
  *                       d_user_mask != NULL (int32 words, bit u & 31 of word u >> 5, (n_users + 31) / 32 words), its bit is set
  *   audience            the top_n eligible users by score descending, among equal scores the LOWER user row first
+ *   NaN, +-inf, zeros   a user whose score is NaN (a NaN rating, inf - inf in the middle of the sum, inf * 0 with a stored zero)
+ *                       counts in eligible -- support is structural, so eligible stays the item's reach -- and is never listed
+ *                       (rtrec_slim_score_pairs' rule).  +-inf scores are numbers; ties, theirs included, go to the lower user
+ *                       row wherever the rows lie.  A sum that starts from +0.0f never gives -0.0f (a lone -0.0f product scores
+ *                       +0.0f and ties with 1 - 1 and with 1 * 0); denormal sums are kept, not flushed.  No output holds a NaN
  * Per query item: d_out_users[q][top_n] (unused slots -1), d_out_scores[q][top_n] (unused slots -inf), d_out_count[q] =
- * min(top_n, eligible), d_out_eligible[q] = the full number of eligible users, the reach of the item (it may exceed top_n).
+ * min(top_n, the eligible users whose score is a number), d_out_eligible[q] = the full number of eligible users, the reach of
+ * the item (it may exceed top_n, and it exceeds d_out_count[q] below top_n when scores are NaN).
  * A query id outside [0, n_items) has no column: count 0, eligible 0.  Repeated query items are answered independently.  CSC
  * offsets are clamped to [0, xc_nnz] / [0, wc_nnz] and rows outside [0, n_users) are skipped, so a malformed matrix gives wrong
  * answers, never an out-of-range read.  A score whose bit pattern is 0xffffffff (a NaN payload float32 arithmetic does not

@@ -15,7 +15,9 @@
 //     wave's LDS operations execute in issue order and the accesses are volatile, so the compiler keeps the read-modify-writes
 //     in column order: no float atomics, no barrier between columns.  The first 64 entries of the next column are loaded while
 //     the current column is applied.
-//   * The users stored in column i of X are cleared (filter_interacted), then those outside the bitmap.
+//   * The users stored in column i of X are cleared (filter_interacted), then those outside the bitmap.  What is left is
+//     eligible and counted.  A NaN accumulator (rerank's rule: counted, never listed) is cleared after it was counted, so the
+//     selection sees numbers only and is told how many; +-inf are numbers.
 //   * Selection: a radix select (8 bits a pass) on the UNIQUE key  [order-preserving score bits | 8191 - local row], so the
 //     top_n-th key is an exact threshold: everything at or above it is taken -- the lower row first among equal scores -- and
 //     the <= 1024 winners are sorted by a bitonic network in LDS.  -0.0f is keyed as +0.0f (an accumulation that starts from
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(kAudThreads) void audience_tile_kernel(
     __shared__ int bounds[kAudWaves + 1][kAudCols];
     __shared__ float wv[kAudCols];
     __shared__ SelectShared sh;
-    __shared__ int misc[3];                                               // the filter's segment, the number of eligible users
+    __shared__ int misc[4];                                               // the filter's segment, eligible users, those with a number
     const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
     const int q = static_cast<int>(blockIdx.x % static_cast<unsigned>(n_q));      // tile-major: the workgroups in flight share
     const int tile = static_cast<int>(blockIdx.x / static_cast<unsigned>(n_q));   // one slice of X's popular columns in L2
@@ -165,7 +167,7 @@ __global__ __launch_bounds__(kAudThreads) void audience_tile_kernel(
         return;
     }
     for (int i = tid; i < kAudTile; i += kAudThreads) acc[i] = kNoSupport;
-    if (tid == 0) misc[2] = 0;
+    if (tid == 0) { misc[2] = 0; misc[3] = 0; }
     __syncthreads();
 
     volatile uint32_t *vacc = acc + wave * kAudSub;                       // this wave's rows; volatile: column order is kept
@@ -221,14 +223,17 @@ __global__ __launch_bounds__(kAudThreads) void audience_tile_kernel(
         }
         __syncthreads();
     }
-    int mine = 0;
+    int mine = 0, numbers = 0;                                            // eligible users; those of them whose score is no NaN
     for (int i = tid; i < kAudTile; i += kAudThreads) {
-        if (acc[i] == kNoSupport) continue;
+        const uint32_t a = acc[i];
+        if (a == kNoSupport) continue;
         const long long u = tile_lo + i;                                  // < n_users: only such rows were accumulated
-        if (user_mask && !((static_cast<uint32_t>(user_mask[u >> 5]) >> (u & 31)) & 1u)) acc[i] = kNoSupport; else ++mine;
+        if (user_mask && !((static_cast<uint32_t>(user_mask[u >> 5]) >> (u & 31)) & 1u)) { acc[i] = kNoSupport; continue; }
+        ++mine;
+        if ((a & 0x7fffffffu) > 0x7f800000u) acc[i] = kNoSupport; else ++numbers;     // a NaN score: counted, never a key
     }
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
-    if (lane == 0 && mine) atomicAdd(&misc[2], mine);
+    for (int d = 32; d >= 1; d >>= 1) { mine += __shfl_xor(mine, d, 64); numbers += __shfl_xor(numbers, d, 64); }
+    if (lane == 0 && mine) { atomicAdd(&misc[2], mine); atomicAdd(&misc[3], numbers); }
     __syncthreads();
     const int eligible = misc[2];
 
@@ -237,7 +242,7 @@ __global__ __launch_bounds__(kAudThreads) void audience_tile_kernel(
         if (a == kNoSupport) return 0ull;
         return (1ull << 45) | (static_cast<unsigned long long>(score_key(a)) << 13) | static_cast<unsigned long long>(kAudTile - 1 - i);
     };
-    const int cnt = select_sorted<48>(key, kAudTile, eligible, top_n, win, sh);
+    const int cnt = select_sorted<48>(key, kAudTile, misc[3], top_n, win, sh);
     for (int k = tid; k < cnt; k += kAudThreads) {
         const unsigned long long kk = win[k];
         const uint32_t u = static_cast<uint32_t>(tile_lo) + static_cast<uint32_t>(kAudTile - 1 - static_cast<int>(kk & (kAudTile - 1)));

@@ -9,9 +9,13 @@
 // (K = 50 in every benchmark configuration), so a pair is an intersection of <= K column entries with the sorted row:
 //   lanes take the column's entries (strided by 64 when the column is longer), each binary-searches its j in the row --
 //   through the wave's registers (ds_bpermute) when the row has at most 64 entries, in memory otherwise -- and forms the
-//   product on a hit; __ballot + popcount give the support; top_m rounds of wave_best pick the reasons, each round excluding
-//   what the previous winner beats (similar_topk_kernel's scheme: nothing is stored besides the last winner).  A column of
-//   at most 64 entries is probed once and kept in registers; a longer one is probed again every round.
+//   product on a hit; __ballot + popcount of the hits give the support; top_m rounds of wave_best pick the reasons, each
+//   round excluding what the previous winner beats (similar_topk_kernel's scheme: nothing is stored besides the last winner).
+//   A column of at most 64 entries is probed once and kept in registers; a longer one is probed again every round.
+// A NaN product counts in the support and is never a candidate (rerank's rule): cand_better is a strict total order only
+// over numbers, so no NaN may reach it.  +-inf are numbers; +0.0f and -0.0f compare equal and go by item id, each written
+// with its own sign bit.  The rounds end when no candidate is left, so a pair's slots from the number of its non-NaN
+// contributions on stay padding.
 // Malformed input cannot read out of range: CSR / CSC offsets are clamped to the arrays' lengths, a row id outside
 // [0, n_x_rows) is an empty row and an item id outside [0, n_items) has no column.
 #include "list_stage.hip.h"
@@ -28,11 +32,12 @@ struct ExplainRow {
     float reg_val;
 };
 
-// The candidate of column entry (j, w): id = j on a hit, -1 otherwise.  aux = ~j: among equal contributions the LOWER item
-// id wins (cand_better prefers the larger aux).  Called by all 64 lanes together (the register search shuffles).
-__device__ __forceinline__ Cand<float> explain_probe(const ExplainRow &row, bool valid, int j, float w) {
+// The candidate of column entry (j, w): id = j on a hit whose product is a number, -1 otherwise; `hit` says whether j is
+// stored in the row at all (the support counts hits).  aux = ~j: among equal contributions the LOWER item id wins
+// (cand_better prefers the larger aux).  Called by all 64 lanes together (the register search shuffles).
+__device__ __forceinline__ Cand<float> explain_probe(const ExplainRow &row, bool valid, int j, float w, bool &hit) {
     Cand<float> x; x.id = -1; x.score = -__builtin_huge_valf(); x.aux = 0u;
-    bool hit = false;
+    hit = false;
     float xv = 0.0f;
     if (row.in_regs) {
         int pos = 0;                                                      // number of row entries < j (<= 63 when j is present)
@@ -53,7 +58,10 @@ __device__ __forceinline__ Cand<float> explain_probe(const ExplainRow &row, bool
             if (m < j) lo = mid + 1; else hi = mid;
         }
     }
-    if (hit) { x.id = j; x.score = __fmul_rn(xv, w); x.aux = 0xffffffffu - static_cast<uint32_t>(j); }
+    if (hit) {
+        const float c = __fmul_rn(xv, w);
+        if (c == c) { x.id = j; x.score = c; x.aux = 0xffffffffu - static_cast<uint32_t>(j); }
+    }
     return x;
 }
 
@@ -86,8 +94,9 @@ __global__ __launch_bounds__(64) void explain_topk_kernel(
             int support = 0;
             if (one && e > s) {
                 const bool valid = s + lane < e;
-                mine = explain_probe(row, valid, valid ? wc_row[s + lane] : -1, valid ? wc_val[s + lane] : 0.0f);
-                support = __popcll(__ballot(mine.id >= 0));
+                bool hit;
+                mine = explain_probe(row, valid, valid ? wc_row[s + lane] : -1, valid ? wc_val[s + lane] : 0.0f, hit);
+                support = __popcll(__ballot(hit));
             }
             Cand<float> last; last.id = -1; last.score = ninf; last.aux = 0u;
             int my_id = -1;
@@ -99,8 +108,9 @@ __global__ __launch_bounds__(64) void explain_topk_kernel(
                 } else {
                     for (long long base = s; base < e; base += 64) {
                         const bool valid = base + lane < e;
-                        const Cand<float> x = explain_probe(row, valid, valid ? wc_row[base + lane] : -1, valid ? wc_val[base + lane] : 0.0f);
-                        if (m == 0) support += __popcll(__ballot(x.id >= 0));
+                        bool hit;
+                        const Cand<float> x = explain_probe(row, valid, valid ? wc_row[base + lane] : -1, valid ? wc_val[base + lane] : 0.0f, hit);
+                        if (m == 0) support += __popcll(__ballot(hit));
                         if (last.id >= 0 && !cand_better(last, x)) continue;
                         if (cand_better(x, b)) b = x;
                     }

@@ -421,7 +421,8 @@ class SLIM(BaseModel):
         Per (user, item) the contributing items are the j stored in both the user's row of X and column i of W, the
         contribution of j is the float32 product x_uj * w_ji (one rounding), and the reasons are the `top_m` (1..32)
         contributing items by contribution descending, the lower item id first among equal ones; negative contributions take
-        part (filter by sign if only positive reasons are wanted).  For a float32 W, adding ALL contributions of a pair in
+        part (filter by sign if only positive reasons are wanted).  A contribution that is NaN (an infinite rating next to a
+        zero weight) counts in the support and is never a reason; +-inf are numbers.  For a float32 W, adding ALL contributions of a pair in
         ascending item order in float32 gives exactly the score `recommend` ranks it by.  Unknown users get their cold-start
         list with empty reasons; users outside the matrix follow `recommend_batch`'s rules for the list and get empty reasons.
 
@@ -484,7 +485,7 @@ class SLIM(BaseModel):
             return ids, counts, r_ids, contrib, support
         raw_of = self._raw_of(self.item_ids)
         id_rows, cnts, reason_rows, contrib_rows = ids.tolist(), counts.tolist(), r_ids.tolist(), contrib.tolist()
-        n_reasons = np.minimum(support, m).tolist()
+        n_reasons = (r_ids >= 0).sum(axis=2).tolist()      # the reasons present: a NaN contribution counts in support, not here
         out_rows: List[List[Tuple[Any, List[Tuple[Any, float]]]]] = []
         for b in range(B):
             row = []

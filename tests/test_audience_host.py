@@ -6,7 +6,9 @@ The kernel itself is in tests/test_gpu_audience.py.
 The definition (include/rtrec_amd.h, "AUDIENCE OF AN ITEM"): score(u, i) is the float32 sum of fl32(x_uj * w_ji) over the j stored
 in both row u of X and column i of W, added from 0.0f in ascending j; eligible are the users with at least one such j, not stored
 in column i of X (filter_interacted), inside the candidate set; the audience is the top_n of them by score descending, the lower
-user row first among equal scores."""
+user row first among equal scores.  A user whose score is NaN counts in eligible and is never listed; +-inf are numbers.  The
+value-edge cases (`edge_case`) and the mutated models that show they bite follow the definition's tests;
+tests/test_gpu_audience.py runs the same cases on the kernels."""
 import os
 import re
 
@@ -15,7 +17,7 @@ import pytest
 import scipy.sparse as sp
 
 from tests.cpu_backend import OracleBackend
-from tests.test_explain_host import bits, golden, ordered_sum, pair_contributions
+from tests.test_explain_host import INF, NNAN, PNAN, bits, golden, ordered_sum, p2, pair_contributions
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
@@ -29,14 +31,17 @@ def accumulate(Xc: sp.csc_matrix, W: sp.csc_matrix, i: int):
         j, w = int(W.indices[p]), np.float32(W.data[p])
         s, e = Xc.indptr[j], Xc.indptr[j + 1]
         r = Xc.indices[s:e]
-        acc[r] = acc[r] + Xc.data[s:e].astype(np.float32) * w            # one rounded multiply, one rounded add
+        with np.errstate(all="ignore"):                                  # inf * 0, inf - inf, underflow: the values under test
+            acc[r] = acc[r] + Xc.data[s:e].astype(np.float32) * w        # one rounded multiply, one rounded add
         touched[r] = True
     return acc, touched
 
 
 def host_model(Xc, W, items, top_n, filter_interacted=True, candidates=None):
     """THE DEFINITION: (users[n, top_n] int32, scores[n, top_n] float32, count[n], eligible[n]), -1 / -inf padded.  Xc / W are
-    CSC with sorted indices; `candidates` a bool array over the user rows or None; an item outside [0, n_items) is empty."""
+    CSC with sorted indices; `candidates` a bool array over the user rows or None; an item outside [0, n_items) is empty.  A
+    user whose score is NaN counts in eligible (support is structural) and is never listed: count = min(top_n, the eligible
+    users whose score is a number); +-inf are numbers."""
     n, rows = len(items), np.arange(Xc.shape[0])
     users, scores = np.full((n, top_n), -1, np.int32), np.full((n, top_n), -np.inf, np.float32)
     count, eligible = np.zeros(n, np.int32), np.zeros(n, np.int32)
@@ -49,8 +54,10 @@ def host_model(Xc, W, items, top_n, filter_interacted=True, candidates=None):
         if candidates is not None:
             ok &= candidates
         el = rows[ok]
+        eligible[b] = len(el)                                            # NaN scores included
+        el = el[~np.isnan(acc[el])]
         order = el[np.lexsort((el, -acc[el]))][:top_n]                   # score descending, then the lower user row
-        eligible[b], count[b] = len(el), len(order)
+        count[b] = len(order)
         users[b, :len(order)], scores[b, :len(order)] = order, acc[order]
     return users, scores, count, eligible
 
@@ -144,6 +151,221 @@ def test_tie_rule_lower_user_row_first_zero_and_negative_scores_take_part():
     cand = np.array([0, 0, 1, 1, 1, 1, 1, 1], bool)
     users, _, count, eligible = host_model(Xc, W, [3, 0, -1, 4], 3, candidates=cand)
     assert users.tolist() == [[7, 2, 3], [-1] * 3, [-1] * 3, [-1] * 3] and count.tolist() == [3, 0, 0, 0] and eligible.tolist() == [3, 0, 0, 0]
+
+
+# ---------------------------------------------------------------------------------------------- the value edges: the cases
+E = "E"                # a row token: ("E", d) is row edge + d, edge = the last row of the first tile when there are two tiles
+o = None                # not stored
+D = p2(-100)           # times the weight 2^-40: the denormal 2^-140
+
+# name -> (the three weights of the query column's active entries in ascending item id,
+#          {user row: its three ratings on those items}, the rows that interacted with the query item itself).
+# Every 0.0 below is a STORED zero.
+SCORE_SETS = {
+    "nan_rating": ((1, 1, 1), {1: (2, o, o), 2: (PNAN, 1, o), 3: (1, o, o), 4: (NNAN, o, 1), 5: (3, o, o), 6: (o, o, NNAN), 7: (1, PNAN, 1),
+                               (E, -1): (5, o, o), (E, 0): (PNAN, o, o), (E, 1): (5, o, o), (E, 2): (o, NNAN, o)}, {2, (E, 0)}),
+    "inf_minus_inf": ((1, -1, 1), {2: (INF, INF, 7), 4: (INF, o, 7), 6: (o, INF, 7), 8: (1, 1, 1), 9: (2, o, o), 10: (-3, o, o),
+                                   (E, -2): (INF, INF, 1), (E, -1): (o, INF, o), (E, 0): (INF, o, o), (E, 1): (INF, o, 1), (E, 2): (o, INF, 3),
+                                   (E, 3): (INF, INF, o)}, {2}),
+    "inf_times_zero": ((0.0, 1, 2), {1: (INF, 1, o), 2: (-INF, o, 1), 3: (5, 1, o), 4: (o, 2, o), 5: (o, o, -1), (E, 0): (INF, o, o),
+                                     (E, 1): (7, o, o)}, {1}),
+    "zero_times_inf": ((INF, 1, 1), {1: (0.0, 1, o), 2: (1, o, o), 3: (-1, o, o), 4: (o, 1, 1), (E, 0): (0.0, o, o), (E, 1): (2, o, o)}, set()),
+    # 11 eligible, 3 of them numbers: with top_n = 5 there is no fifth key to find
+    "few_numbers": ((1, 1, 1), {1: (PNAN, o, o), 2: (NNAN, o, o), 3: (PNAN, 1, o), 4: (o, NNAN, o), 5: (1, o, PNAN), 6: (1, o, o), 7: (NNAN, o, o),
+                                8: (PNAN, o, o), (E, 0): (2, o, o), (E, 1): (2, o, o), (E, 2): (PNAN, o, o)}, {7}),
+    "all_nan": ((1, NNAN, 1), {3: (o, 1, o), 5: (1, 1, 1), (E, 0): (o, 2, o), (E, 1): (o, 1, o)}, set()),
+    # -1 * 0 = -0.0 alone in its sum: 0 + -0 = +0.0, tying with 1 - 1 and with 1 * 0
+    "signed_zero": ((0.0, 1, -1), {2: (o, 2, o), 3: (o, 1, 1), 5: (-1, o, o), 7: (1, o, o), 9: (o, o, 2), (E, 0): (-2, o, o), (E, 1): (o, 3, 3)}, set()),
+    # the zero-score users sit on lower rows than the positive denormal and on higher rows than the negative one
+    "denormals": ((p2(-40), p2(-40), 1), {1: (o, o, 0.0), 2: (o, o, 0.0), 3: (D, D, o), 4: (D, o, o), 6: (-D, o, o), 7: (-D, -D, o), 8: (o, o, 0.0),
+                                          (E, -1): (o, o, 0.0), (E, 0): (D, o, o), (E, 1): (D, o, o), (E, 2): (-D, o, 0.0)}, set()),
+}
+# the users the definition lists, whole (top_n = 1024), per set: e = edge
+EXPECTED_USERS = {
+    "nan_rating": lambda e: [e - 1, e + 1, 5, 1, 3], "inf_minus_inf": lambda e: [4, e, e + 1, 9, 8, 10, 6, e - 1, e + 2],
+    "inf_times_zero": lambda e: [4, 3, e + 1, 5], "zero_times_inf": lambda e: [2, e + 1, 4, 3], "few_numbers": lambda e: [e, e + 1, 6],
+    "all_nan": lambda e: [], "signed_zero": lambda e: [2, 3, 5, 7, e, e + 1, 9], "denormals": lambda e: [3, 4, e, e + 1, 1, 2, 8, e - 1, 6, e + 2, 7],
+}
+EDGE_TOP_N = (1, 5, 1024)
+MANY_NANS = (100, 1130)           # the rows of the "many_nans" item: 1,030 NaN scores in one tile (as many as there are users)
+
+
+def edge_case(two_tiles):
+    """(Xc csc, W csc, query items, mask, cases) from raw (data, indices, indptr) arrays, so that stored zeros survive: 300 users
+    (one tile) or 8,192 + 300 (two; the edge rows 8,191 and 8,192 then carry the tied and the NaN scores, so the merge kernel
+    sees them from different tiles).  Every score set is asked about twice: through a column of W of its 3 active entries, and
+    through one of 60 entries -- 55 fillers, a stored-zero product of every user of the set at position 55 (the last of the
+    first round of 56 columns), one more filler, the active entries at positions 57..59: the accumulator crosses a round and
+    arrives as +0.0, so both columns give the set's users the same scores.  Rows 60..89 rate the fillers only.  "many_nans" has
+    more NaN users than top_n = 1024 can be (in the two-tile matrix) beside ten numbers.  mask: a candidate set that leaves out
+    NaN users, numbers and the edge row.  cases[name] = (query item with 3 entries, with 60, the set's expected users)."""
+    U = 8192 + 300 if two_tiles else 300
+    edge = 8191 if two_tiles else 255
+    row = lambda t: t if isinstance(t, int) else edge + t[1]
+    sets = dict(SCORE_SETS)
+    nan_rows = range(MANY_NANS[0], min(MANY_NANS[1], U))
+    sets["many_nans"] = ((1, 1, 1), {**{r: ((PNAN, NNAN)[r & 1], o, o) for r in nan_rows}, **{20 + k: (k - 4, o, o) for k in range(10)}}, set())
+    n_fill, S = 56, len(sets)
+    first_gate, second_filler, first_active, first_query = 55, 55 + S, 56 + S, 56 + 4 * S
+    I = first_query + 2 * S
+    cols = {j: {} for j in range(I)}                                      # X by column: {row: value}
+    rng = np.random.default_rng(23)
+    for j in list(range(55)) + [second_filler]:
+        for r in rng.choice(np.arange(60, 90), 6, replace=False):
+            cols[j][int(r)] = np.float32(rng.integers(-4, 5))
+    wcols, items, cases = {}, [], {}
+    for s, (name, (w, users, interacted)) in enumerate(sets.items()):
+        gate, act = first_gate + s, [first_active + 3 * s + t for t in range(3)]
+        q3, q60 = first_query + 2 * s, first_query + 2 * s + 1
+        for t, x in users.items():
+            cols[gate][row(t)] = np.float32(0.0)
+            for a, v in zip(act, x):
+                if v is not None:
+                    cols[a][row(t)] = np.float32(v)
+        for t in interacted:
+            cols[q3][row(t)] = cols[q60][row(t)] = np.float32(1.0)
+        wcols[q3] = [(a, np.float32(v)) for a, v in zip(act, w)]
+        wcols[q60] = [(j, np.float32(1 + j % 3)) for j in range(55)] + [(gate, np.float32(1.0)), (second_filler, np.float32(-2.0))] + wcols[q3]
+        assert len(wcols[q60]) == 60 and [j for j, _ in wcols[q60]] == sorted(j for j, _ in wcols[q60])
+        items += [q3, q60]
+        want = (lambda e: list(range(29, 19, -1))) if name == "many_nans" else EXPECTED_USERS[name]
+        cases[name] = (q3, q60, want(edge))
+    xptr = np.zeros(I + 1, np.int64)
+    xptr[1:] = np.cumsum([len(cols[j]) for j in range(I)])
+    xrow = np.array([r for j in range(I) for r in sorted(cols[j])], np.int32)
+    xval = np.array([cols[j][r] for j in range(I) for r in sorted(cols[j])], np.float32)
+    Xc = sp.csc_matrix((xval, xrow, xptr.astype(np.int32)), shape=(U, I))
+    wptr = np.zeros(I + 1, np.int64)
+    wptr[1:] = np.cumsum([len(wcols.get(j, ())) for j in range(I)])
+    W = sp.csc_matrix((np.array([v for j in range(I) for _, v in wcols.get(j, ())], np.float32),
+                       np.array([i for j in range(I) for i, _ in wcols.get(j, ())], np.int32), wptr.astype(np.int32)), shape=(I, I))
+    assert Xc.nnz == len(xval) and W.nnz == 63 * S and Xc.has_sorted_indices and W.has_sorted_indices      # no zero was dropped
+    mask = np.ones(U, bool)
+    mask[[2, 4, 5, edge, 101, 22]] = False
+    return Xc, W, np.array(items, np.int32), mask, cases
+
+
+def same(a, b):
+    return np.array_equal(a[0], b[0]) and np.array_equal(bits(a[1]), bits(b[1])) and np.array_equal(a[2], b[2]) and np.array_equal(a[3], b[3])
+
+
+@pytest.mark.parametrize("two_tiles", [False, True])
+def test_edge_cases_give_the_expected_audiences_under_the_definition(two_tiles):
+    Xc, W, items, mask, cases = edge_case(two_tiles)
+    X = Xc.tocsr()                                                       # (scipy keeps the stored zeros)
+    assert X.nnz == Xc.nnz and np.isnan(Xc.data).any() and np.isinf(Xc.data).any() and (Xc.data == 0).any() and (W.data == 0).any()
+    users, scores, count, eligible = host_model(Xc, W, items, 1024, filter_interacted=False)
+    assert not np.isnan(scores).any()                                    # under the rule no output holds a NaN
+    edge = 8191 if two_tiles else 255
+    for name, (q3, q60, want) in cases.items():
+        a, b = int(np.flatnonzero(items == q3)[0]), int(np.flatnonzero(items == q60)[0])
+        assert users[a, :count[a]].tolist() == want and (users[a, count[a]:] == -1).all(), name
+        n_set = eligible[a]
+        assert eligible[b] == n_set + 30 and count[b] == count[a] + 30    # the 60-entry column adds the 30 filler users ...
+        of_set = ~np.isin(users[b, :count[b]], np.arange(60, 90))
+        assert users[b, :count[b]][of_set].tolist() == want, name         # ... and gives the set's users the same order and scores
+        assert np.array_equal(bits(scores[b, :count[b]][of_set]), bits(scores[a, :count[a]]))
+    q = lambda name: int(np.flatnonzero(items == cases[name][0])[0])
+    assert (eligible[q("few_numbers")], count[q("few_numbers")]) == (11, 3) and (eligible[q("all_nan")], count[q("all_nan")]) == (4, 0)
+    n_nan = min(MANY_NANS[1], Xc.shape[0]) - MANY_NANS[0]
+    assert (eligible[q("many_nans")], count[q("many_nans")]) == (n_nan + 10, 10) and (n_nan > 1024) == two_tiles
+    assert bits(scores[q("signed_zero"), 1:6]).tolist() == [0] * 5        # -0.0 alone, 1 - 1 and 1 * 0: all +0.0
+    assert bits(scores[q("denormals"), :11]).tolist() == [0x400, 0x200, 0x200, 0x200, 0, 0, 0, 0, 0x80000200, 0x80000200, 0x80000400]
+    assert scores[q("inf_minus_inf"), :9].tolist() == [np.inf] * 3 + [2, 1, -3] + [-np.inf] * 3
+    # the accumulator model is the per-pair definition on these values too: the ordered float32 sum of the pair's products
+    for name, (q3, q60, _) in cases.items():
+        for item in (q3, q60):
+            acc, touched = accumulate(Xc, W, item)
+            for u in np.flatnonzero(touched)[:40]:
+                j, c = pair_contributions(X, W, int(u), item)
+                with np.errstate(all="ignore"):
+                    s = ordered_sum(c)
+                assert len(j) >= 1 and (np.isnan(s) and np.isnan(acc[u]) or bits(s) == bits(acc[u])), (name, item, u)
+    # the filter, the candidate set and top_n change what they should
+    f = host_model(Xc, W, items, 5)
+    m = host_model(Xc, W, items, 5, False, mask)
+    assert f[3][q("nan_rating")] == eligible[q("nan_rating")] - 2 and f[3][q("few_numbers")] == 10 and f[2][q("few_numbers")] == 3
+    assert m[3][q("nan_rating")] == eligible[q("nan_rating")] - 4 and m[0][q("nan_rating"), :3].tolist() == [edge - 1, edge + 1, 1]
+
+
+def test_existing_fixtures_hold_no_nan_and_keep_their_answers_under_the_rule():
+    _, Xc, W, _, _, _ = golden_csc()
+    assert np.isfinite(Xc.data).all() and np.isfinite(W.data).all()
+    old = mutant_model(Xc, W, np.arange(W.shape[1]), 1024, "nan_listed_last")       # the definition before the rule
+    assert same(old, host_model(Xc, W, np.arange(W.shape[1]), 1024))
+
+
+# ---------------------------------------------------------------------------------------------- mutated models: the cases bite
+DEFECTS = ("nan_listed_last", "nan_by_sign_bit", "denormals_flushed", "ties_to_the_higher_row", "nan_dropped_from_eligible")
+
+
+def _flush(v):
+    return np.where(np.abs(v) < p2(-126), np.copysign(np.float32(0), v), v).astype(np.float32)
+
+
+def mutant_model(Xc, W, items, top_n, defect, filter_interacted=True, candidates=None):
+    """host_model with one defect built in."""
+    assert defect in DEFECTS
+    n, rows = len(items), np.arange(Xc.shape[0])
+    users, scores = np.full((n, top_n), -1, np.int32), np.full((n, top_n), -np.inf, np.float32)
+    count, eligible = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    for b, i in enumerate(int(x) for x in items):
+        if not 0 <= i < W.shape[1]:
+            continue
+        if defect == "denormals_flushed":                                # every product and every sum
+            acc, ok = np.zeros(Xc.shape[0], np.float32), np.zeros(Xc.shape[0], bool)
+            for p in range(W.indptr[i], W.indptr[i + 1]):
+                j, w = int(W.indices[p]), np.float32(W.data[p])
+                r = Xc.indices[Xc.indptr[j]:Xc.indptr[j + 1]]
+                with np.errstate(all="ignore"):
+                    acc[r] = _flush(acc[r] + _flush(Xc.data[Xc.indptr[j]:Xc.indptr[j + 1]].astype(np.float32) * w))
+                ok[r] = True
+        else:
+            acc, ok = accumulate(Xc, W, i)
+        if filter_interacted:
+            ok[Xc.indices[Xc.indptr[i]:Xc.indptr[i + 1]]] = False
+        if candidates is not None:
+            ok &= candidates
+        el = rows[ok]
+        eligible[b] = len(el)
+        if defect == "nan_dropped_from_eligible":
+            eligible[b] = int((~np.isnan(acc[el])).sum())
+        if defect == "nan_by_sign_bit":                                  # the kernel's key before the rule: the raw bits, order-preserving
+            u = bits(acc[el]).astype(np.int64)
+            u[u == 0x80000000] = 0
+            order = el[np.lexsort((el, -np.where(u & 0x80000000, 0xffffffff - u, u | 0x80000000)))][:top_n]
+        else:
+            if defect != "nan_listed_last":
+                el = el[~np.isnan(acc[el])]
+            order = el[np.lexsort((-el if defect == "ties_to_the_higher_row" else el, -acc[el]))][:top_n]
+        count[b] = len(order)
+        users[b, :len(order)], scores[b, :len(order)] = order, acc[order]
+    return users, scores, count, eligible
+
+
+# defect -> (a score set, its 3- or 60-entry column, the matrix) that must tell it from the definition
+CAUGHT_BY = {
+    "nan_listed_last": ("few_numbers", 3, False), "nan_by_sign_bit": ("nan_rating", 60, True), "denormals_flushed": ("denormals", 60, False),
+    "ties_to_the_higher_row": ("inf_minus_inf", 3, True), "nan_dropped_from_eligible": ("all_nan", 3, True),
+}
+
+
+@pytest.mark.parametrize("defect", DEFECTS)
+def test_every_defect_is_told_from_the_definition_by_a_named_case(defect):
+    name, length, two_tiles = CAUGHT_BY[defect]
+    Xc, W, items, mask, cases = edge_case(two_tiles)
+    seen = set()
+    for top_n in EDGE_TOP_N:
+        want, got = host_model(Xc, W, items, top_n), mutant_model(Xc, W, items, top_n, defect)
+        for set_name, (q3, q60, _) in cases.items():
+            for L, item in ((3, q3), (60, q60)):
+                b = int(np.flatnonzero(items == item)[0])
+                if not same(tuple(a[b:b + 1] for a in want), tuple(a[b:b + 1] for a in got)):
+                    seen.add((set_name, L, top_n))
+    print(f"{defect}: seen by {sorted(seen)}")
+    assert any(s[:2] == (name, length) for s in seen)
+    if defect == "ties_to_the_higher_row":                               # the tie that straddles the two tiles decides top_n = 5
+        assert ("inf_minus_inf", 3, 5) in seen
 
 
 # ---------------------------------------------------------------------------------------------- model / facade, end to end

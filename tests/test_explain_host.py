@@ -4,7 +4,9 @@ with `explain_topk` supplied by the host model; the registration of the op.  The
 
 The definition (include/rtrec_amd.h, "EXPLANATIONS"): for a user row u and an item i the contributing items are the j stored in
 both row u of X and column i of W, c(j) = float32(x_uj) * float32(w_ji) in float32, support = their number, reasons = the top_m
-by c descending, the lower item id first among equal c."""
+by c descending, the lower item id first among equal c.  A NaN contribution counts in support and is never a reason; +-inf
+are numbers; +0.0 and -0.0 are equal and each keeps its sign bit.  The value-edge cases (`edge_case`) and the mutated models
+that show they bite are at the end of the definition's section; tests/test_gpu_explain.py runs the same cases on the kernel."""
 import os
 import re
 
@@ -26,12 +28,15 @@ def pair_contributions(X: sp.csr_matrix, W: sp.csc_matrix, row: int, item: int):
     xs, xv = X.indices[X.indptr[row]:X.indptr[row + 1]], X.data[X.indptr[row]:X.indptr[row + 1]].astype(np.float32)
     wj, ww = W.indices[W.indptr[item]:W.indptr[item + 1]], W.data[W.indptr[item]:W.indptr[item + 1]].astype(np.float32)
     common, xi, wi = np.intersect1d(xs, wj, assume_unique=True, return_indices=True)
-    return common.astype(np.int64), xv[xi] * ww[wi]                     # float32 * float32: one rounding
+    with np.errstate(all="ignore"):                                     # inf * 0, overflow, underflow: the values under test
+        return common.astype(np.int64), xv[xi] * ww[wi]                 # float32 * float32: one rounding
 
 
 def host_model(X, W, rows, ids, counts, top_m):
     """THE DEFINITION: (reason_items[B, k, top_m] int32, contributions[B, k, top_m] float32, support[B, k] int32), -1 / -inf
-    padded.  A slot at or beyond counts[b], an item outside [0, n_items) and a row outside [0, n_users) are empty."""
+    padded.  A slot at or beyond counts[b], an item outside [0, n_items) and a row outside [0, n_users) are empty.  A NaN
+    contribution counts in support and is never a reason: the reasons are ranked among the contributions that are numbers
+    (+-inf included; +0.0 == -0.0, so the two go by item id), and the slots from their number on are padding."""
     ids = np.asarray(ids)
     B, k = ids.shape
     items = np.full((B, k, top_m), -1, np.int32)
@@ -40,8 +45,9 @@ def host_model(X, W, rows, ids, counts, top_m):
     for b in range(B):
         for p in range(min(max(int(counts[b]), 0), k)):
             j, c = pair_contributions(X, W, int(rows[b]), int(ids[b, p]))
+            support[b, p] = len(j)                                      # NaN contributions included
+            j, c = j[~np.isnan(c)], c[~np.isnan(c)]
             order = np.lexsort((j, -c))[:top_m]                         # c descending, then the lower item id
-            support[b, p] = len(j)
             items[b, p, :len(order)], contrib[b, p, :len(order)] = j[order], c[order]
     return items, contrib, support
 
@@ -72,11 +78,15 @@ def host_model_vectorised(X, W, rows, ids, counts, top_m, chunk=8192):
         key = r[pb][pair] * I + j
         pos = np.minimum(np.searchsorted(xkey, key), len(xkey) - 1)
         hit = xkey[pos] == key
-        pair, j, c = pair[hit], j[hit], xval[pos[hit]] * W.data[off[hit]].astype(np.float32)
-        sup = np.bincount(pair, minlength=len(item))
+        with np.errstate(all="ignore"):
+            pair, j, c = pair[hit], j[hit], xval[pos[hit]] * W.data[off[hit]].astype(np.float32)
+        sup = np.bincount(pair, minlength=len(item))                    # NaN contributions included
+        number = ~np.isnan(c)
+        pair, j, c = pair[number], j[number], c[number]
+        numbers = np.bincount(pair, minlength=len(item))
         order = np.lexsort((j, -c, pair))
         pair, j, c = pair[order], j[order], c[order]
-        rank = np.arange(len(pair)) - (np.cumsum(sup) - sup)[pair]
+        rank = np.arange(len(pair)) - (np.cumsum(numbers) - numbers)[pair]
         keep = rank < top_m
         items[s + pb[pair[keep]], pp[pair[keep]], rank[keep]] = j[keep]
         contrib[s + pb[pair[keep]], pp[pair[keep]], rank[keep]] = c[keep]
@@ -172,6 +182,267 @@ def test_tie_rule_lower_item_id_first_and_negative_contributions_take_part():
         assert contrib[0, 0].tolist() == [1.0, 1.0, 1.0, 1.0, -4.0, -np.inf]
 
 
+# ---------------------------------------------------------------------------------------------- the value edges: the cases
+PNAN, NNAN = (np.float32(v) for v in np.array([0x7fc00000, 0xffc00000], np.uint32).view(np.float32))     # the two default quiet NaNs
+INF = np.float32(np.inf)
+
+
+def p2(e):
+    return np.float32(2.0 ** e)
+
+
+# name -> the (x_uj, w_ji) of the contributing items in ascending item id.  Every zero below is a STORED zero.
+VALUE_SETS = {
+    "nan_lowest": [(PNAN, 1), (1, 2), (1, 1), (1, .5), (1, 3), (1, -2)],
+    "nan_middle": [(1, 2), (1, 1), (1, NNAN), (1, .5), (1, 3), (1, -2)],
+    "nan_highest": [(1, 2), (1, 1), (1, .5), (1, 3), (1, -2), (NNAN, 1)],
+    "two_nans": [(PNAN, 1), (1, 2), (1, 1), (1, 0), (PNAN, 1), (1, 3), (1, -2)],       # c = nan 2 1 0 nan 3 -2: the butterfly's smallest failure
+    "two_nans_adjacent": [(1, 3), (PNAN, 1), (1, NNAN), (1, 1), (1, 5)],
+    "all_nan": [(PNAN, 1), (1, NNAN), (INF, 0)],
+    "made_and_given_nans": [(INF, 0), (1, 2), (PNAN, 1), (1, -1), (NNAN, 1), (-INF, 0), (1, 5), (0, INF), (1, PNAN), (0, -INF), (-4, 1)],
+    "infinities": [(1, 1), (INF, 1), (INF, -1), (1, 2), (1, INF), (1, -3), (-INF, 2), (1, 0)],   # c = 1 inf -inf 2 inf -3 -inf 0
+    "signed_zeros_minus_first": [(-1, 0), (1, 0), (1, 1)],                             # c = -0 +0 1
+    "signed_zeros_plus_first": [(1, 0), (-1, 0), (1, -1)],                             # c = +0 -0 -1
+    "denormals": [(p2(-100), p2(-60)), (p2(-100), p2(-40)), (1, 0), (-p2(-100), p2(-40)), (-p2(-100), p2(-60)), (1, -1)],
+    "overflow_ties_inf": [(p2(100), p2(100)), (INF, 1), (1, 3), (INF, 2), (p2(100), p2(100))],   # c = inf inf 3 inf inf
+}
+# what the definition says about them, item ids as positions in the value set (top_m = 32: the whole list)
+EXPECTED_ORDER = {
+    "nan_lowest": [4, 1, 2, 3, 5], "nan_middle": [4, 0, 1, 3, 5], "nan_highest": [3, 0, 1, 2, 4], "two_nans": [5, 1, 2, 3, 6],
+    "two_nans_adjacent": [4, 0, 3], "all_nan": [], "made_and_given_nans": [6, 1, 3, 10], "infinities": [1, 4, 3, 0, 7, 5, 2, 6],
+    "signed_zeros_minus_first": [2, 0, 1], "signed_zeros_plus_first": [0, 1, 2], "denormals": [1, 0, 2, 4, 3, 5],
+    "overflow_ties_inf": [0, 1, 3, 4, 2],
+}
+EDGE_ITEMS = 400
+ISSUE_J = [0, 1, 2, 9, 11, 17, 21]                                      # the "two_nans" values on these literal ids: a 7-lane column
+
+
+def _spread(m, residue):
+    """m distinct item ids = residue (mod 3) spread evenly over [0, EDGE_ITEMS)."""
+    return (3 * np.round(np.linspace(0, 132, m)).astype(np.int64) + residue) if m else np.empty(0, np.int64)
+
+
+def _sorted_entries(j_a, v_a, j_b, v_b):
+    j, v = np.concatenate([j_a, j_b]), np.concatenate([np.asarray(v_a, np.float32), np.asarray(v_b, np.float32)])
+    order = np.argsort(j, kind="stable")
+    assert len(np.unique(j)) == len(j)
+    return j[order], v[order]
+
+
+def edge_case():
+    """(X csr, W csc, rows, ids[n, 4], counts, cases): one matrix pair from raw (data, indices, indptr) arrays -- stored zeros
+    survive -- that runs every value set through the kernel's four search paths.  Per value set of n contributing items
+    (ids = 0 mod 3, the first 0 and the last 396) there is a row of X of 64 and one of 65 entries (search in registers /
+    in memory; the other entries have ids = 1 mod 3) and a column of W of 64, 65 and 130 entries (one probe / a probe per
+    round; the other entries have ids = 2 mod 3, so they never meet the row's): the contributing items are exactly the
+    value set's, in the first and the last lane of a probe and, for the 130-entry column, in all three probes.  The sets of
+    three values also get a row and a column of 3 entries.  Row r explains its set's columns: ids[r], counts[r].
+    cases[(name, row_len, col_len)] = (r, slot, the contributing ids)."""
+    x_rows, w_cols, lists, cases = [], [], [], {}
+    for name, pairs in VALUE_SETS.items():
+        n = len(pairs)
+        J = _spread(n, 0)
+        col_lens = ([3] if n == 3 else []) + [64, 65, 130]
+        cols = []
+        for L in col_lens:
+            j, v = _sorted_entries(J, [w for _, w in pairs], _spread(L - n, 2), np.full(L - n, 0.75))
+            if L == 130:
+                at = np.flatnonzero(np.isin(j, J))
+                assert at[0] == 0 and ((at >= 64) & (at < 128)).any() and (at >= 128).any(), (name, at)
+            cols.append(len(w_cols))
+            w_cols.append((j, v))
+        for L in ([3] if n == 3 else []) + [64, 65]:
+            for slot, Lc in enumerate(col_lens):
+                cases[(name, L, Lc)] = (len(x_rows), slot, J)
+            x_rows.append(_sorted_entries(J, [x for x, _ in pairs], _spread(L - n, 1), np.full(L - n, 1.5)))
+            lists.append(cols)
+    J = np.array(ISSUE_J, np.int64)
+    cases[("two_nans_literal", 7, 7)] = (len(x_rows), 0, J)
+    x_rows.append((J, np.array([x for x, _ in VALUE_SETS["two_nans"]], np.float32)))
+    lists.append([len(w_cols)])
+    w_cols.append((J, np.array([w for _, w in VALUE_SETS["two_nans"]], np.float32)))
+
+    def raw(entries, n_major):
+        ptr = np.zeros(n_major + 1, np.int64)
+        ptr[1:len(entries) + 1] = np.cumsum([len(j) for j, _ in entries])
+        ptr[len(entries) + 1:] = ptr[len(entries)]
+        return np.concatenate([v for _, v in entries]), np.concatenate([j for j, _ in entries]).astype(np.int32), ptr.astype(np.int32)
+
+    X = sp.csr_matrix(raw(x_rows, len(x_rows)), shape=(len(x_rows), EDGE_ITEMS))
+    W = sp.csc_matrix(raw(w_cols, EDGE_ITEMS), shape=(EDGE_ITEMS, EDGE_ITEMS))
+    assert len(w_cols) <= EDGE_ITEMS and X.has_sorted_indices and W.has_sorted_indices
+    assert X.nnz == sum(len(j) for j, _ in x_rows) and W.nnz == sum(len(j) for j, _ in w_cols)          # no zero was dropped
+    ids = np.full((len(x_rows), 4), -1, np.int32)
+    for r, cols in enumerate(lists):
+        ids[r, :len(cols)] = cols
+    return X, W, np.arange(len(x_rows)), ids, np.array([len(c) for c in lists], np.int32), cases
+
+
+EDGE_TOP_M = (1, 4, 32)
+
+
+def same(a, b):
+    return np.array_equal(a[0], b[0]) and np.array_equal(bits(a[1]), bits(b[1])) and np.array_equal(a[2], b[2])
+
+
+def test_edge_cases_definition_vectorised_model_and_the_expected_lists():
+    X, W, rows, ids, counts, cases = edge_case()
+    assert X.shape[0] < 40 and len(cases) > 60 and sorted({k[1] for k in cases}) == [3, 7, 64, 65] and sorted({k[2] for k in cases}) == [3, 7, 64, 65, 130]
+    assert np.isnan(X.data).any() and np.isnan(W.data).any() and np.isinf(X.data).any() and (W.data == 0).any() and (X.data == 0).any()
+    for top_m in EDGE_TOP_M:
+        a, b = host_model(X, W, rows, ids, counts, top_m), host_model_vectorised(X, W, rows, ids, counts, top_m, chunk=5)
+        assert same(a, b)
+        assert not np.isnan(a[1]).any()                                  # under the rule no output holds a NaN
+        assert np.isneginf(a[1][a[0] < 0]).all() and (np.sort(a[0] < 0, axis=2) == (a[0] < 0)).all()      # padding is -inf and trails
+    items, contrib, support = a                                          # top_m = 32
+    for (name, Lr, Lc), (r, slot, J) in cases.items():
+        pairs = VALUE_SETS[name.replace("_literal", "")]
+        want = EXPECTED_ORDER[name.replace("_literal", "")]
+        assert support[r, slot] == len(pairs), (name, Lr, Lc)
+        assert items[r, slot, :len(want)].tolist() == J[want].tolist() and (items[r, slot, len(want):] == -1).all(), (name, Lr, Lc)
+        with np.errstate(all="ignore"):
+            c = np.array([np.float32(x) * np.float32(w) for x, w in pairs], np.float32)
+        assert np.array_equal(bits(contrib[r, slot, :len(want)]), bits(c[want])) and np.isneginf(contrib[r, slot, len(want):]).all()
+    r, slot, _ = cases[("signed_zeros_minus_first", 3, 3)]
+    assert bits(contrib[r, slot, :3]).tolist() == [0x3f800000, 0x80000000, 0x00000000]           # each zero keeps its sign bit
+    r, slot, _ = cases[("denormals", 64, 130)]
+    assert bits(contrib[r, slot, :6]).tolist() == [0x00000200, 0, 0, 0x80000000, 0x80000200, 0xbf800000]   # 2^-140 is kept, 2^-160 is 0
+    r, slot, _ = cases[("infinities", 65, 65)]
+    assert contrib[r, slot, :8].tolist() == [np.inf, np.inf, 2, 1, 0, -3, -np.inf, -np.inf] and (items[r, slot, 6:8] >= 0).all()
+
+
+def test_existing_fixtures_hold_no_nan_and_keep_their_answers_under_the_rule():
+    X, W, users, ids, _ = golden()
+    z = np.load(os.path.join(G, "partial_fit.npz"))
+    assert np.isfinite(X.data).all() and np.isfinite(W.data).all() and np.isfinite(z["v"]).all()
+    old = mutant_model(X, W, users, ids, np.full(len(users), 10), 32, "nan_listed_last")      # the definition before the rule
+    assert same(old, host_model(X, W, users, ids, np.full(len(users), 10), 32))
+
+
+# ---------------------------------------------------------------------------------------------- mutated models: the cases bite
+def _better(a, b):
+    """cand_better of csrc/common.hip.h on (score, aux, id) triples: a NaN score is neither above nor below."""
+    if a[2] < 0:
+        return False
+    if b[2] < 0:
+        return True
+    if a[0] > b[0]:
+        return True
+    if a[0] < b[0]:
+        return False
+    if a[1] != b[1]:
+        return a[1] > b[1]
+    return a[2] > b[2]
+
+
+def butterfly_pair(col_j, col_c, top_m):
+    """The kernel BEFORE the rule re-enacted lane by lane on one pair: col_j / col_c are the column's entries in storage order
+    (j = -1: not in the row), a NaN product is a candidate like any other.  64 lanes, the xor butterfly of wave_best, each
+    lane keeping its own view of the last winner; lane m's view of round m is what is written."""
+    none = (-np.inf, 0, -1)
+    cands = [(float(c), 0xffffffff - int(j), int(j)) if j >= 0 else none for j, c in zip(col_j, col_c)]
+    support = sum(j >= 0 for j in col_j)
+    one = len(cands) <= 64
+    last, live = [none] * 64, [True] * 64
+    out_j, out_c = [-1] * top_m, [np.float32(-np.inf)] * top_m
+    for m in range(min(top_m, support)):
+        b = [none] * 64
+        for lane in range(64):
+            if not live[lane]:
+                continue
+            for base in range(0, len(cands), 64):
+                x = cands[base + lane] if base + lane < len(cands) else none
+                if last[lane][2] >= 0 and not _better(last[lane], x):
+                    continue
+                if one:
+                    b[lane] = x
+                elif _better(x, b[lane]):
+                    b[lane] = x
+        for step in (32, 16, 8, 4, 2, 1):
+            b = [b[l ^ step] if _better(b[l ^ step], b[l]) else b[l] for l in range(64)]
+        for lane in range(64):
+            if live[lane] and b[lane][2] < 0:
+                live[lane] = False
+            elif live[lane]:
+                last[lane] = b[lane]
+        if live[m]:
+            out_j[m], out_c[m] = b[m][2], np.float32(b[m][0])
+    return out_j, out_c, support
+
+
+DEFECTS = ("nan_listed_last", "nan_by_sign_bit", "nan_equal_to_everything", "denormals_flushed", "minus_zero_written_as_plus_zero",
+           "ties_to_the_higher_id", "nan_dropped_from_support")
+
+
+def mutant_model(X, W, rows, ids, counts, top_m, defect):
+    """host_model with one defect built in."""
+    assert defect in DEFECTS
+    ids = np.asarray(ids)
+    B, k = ids.shape
+    items = np.full((B, k, top_m), -1, np.int32)
+    contrib = np.full((B, k, top_m), -np.inf, np.float32)
+    support = np.zeros((B, k), np.int32)
+    for b in range(B):
+        for p in range(min(max(int(counts[b]), 0), k)):
+            j, c = pair_contributions(X, W, int(rows[b]), int(ids[b, p]))
+            support[b, p] = len(j)
+            if defect == "nan_equal_to_everything":
+                item = int(ids[b, p])
+                if not 0 <= item < W.shape[1]:
+                    continue
+                col = W.indices[W.indptr[item]:W.indptr[item + 1]].astype(np.int64)
+                full = np.full(len(col), np.float32(0))
+                full[np.isin(col, j)] = c
+                r, v, _ = butterfly_pair(np.where(np.isin(col, j), col, -1), full, top_m)
+                items[b, p], contrib[b, p] = r, v
+                continue
+            if defect == "denormals_flushed":
+                c = np.where(np.abs(c) < p2(-126), np.copysign(np.float32(0), c), c).astype(np.float32)
+            if defect == "nan_dropped_from_support":
+                support[b, p] = int((~np.isnan(c)).sum())
+            if defect == "nan_by_sign_bit":                             # the order-preserving key of the raw bits
+                u = bits(c).astype(np.int64)
+                key = np.where(u & 0x80000000, 0xffffffff - u, u | 0x80000000)
+                order = np.lexsort((j, -key))[:top_m]
+            else:
+                if defect != "nan_listed_last":
+                    j, c = j[~np.isnan(c)], c[~np.isnan(c)]
+                order = np.lexsort((-j if defect == "ties_to_the_higher_id" else j, -c))[:top_m]
+            items[b, p, :len(order)], contrib[b, p, :len(order)] = j[order], c[order]
+            if defect == "minus_zero_written_as_plus_zero":
+                contrib[b, p][contrib[b, p] == 0] = 0.0
+    return items, contrib, support
+
+
+# defect -> a case that must tell it from the definition (every defect is also run over all cases: which ones see it is printed)
+CAUGHT_BY = {
+    "nan_listed_last": ("nan_lowest", 64, 64), "nan_by_sign_bit": ("made_and_given_nans", 65, 130),
+    "nan_equal_to_everything": ("two_nans_literal", 7, 7), "denormals_flushed": ("denormals", 64, 65),
+    "minus_zero_written_as_plus_zero": ("signed_zeros_minus_first", 3, 3), "ties_to_the_higher_id": ("infinities", 65, 64),
+    "nan_dropped_from_support": ("all_nan", 3, 130),
+}
+
+
+@pytest.mark.parametrize("defect", DEFECTS)
+def test_every_defect_is_told_from_the_definition_by_a_named_case(defect):
+    X, W, rows, ids, counts, cases = edge_case()
+    top_m = 32
+    if defect == "nan_equal_to_everything":                              # the lane-by-lane re-enactment: one-probe columns only
+        keep = sorted({r for (_, _, Lc), (r, _, _) in cases.items() if Lc <= 7} | {cases[k][0] for k in cases if k[2] == 64})
+        rows, ids, counts = rows[keep], ids[keep].copy(), counts[keep]
+        ids[W.indptr[np.maximum(ids, 0) + 1] - W.indptr[np.maximum(ids, 0)] > 64] = -1
+        cases = {k: (keep.index(r), slot, J) for k, (r, slot, J) in cases.items() if r in keep and ids[keep.index(r), slot] >= 0}
+    want, got = host_model(X, W, rows, ids, counts, top_m), mutant_model(X, W, rows, ids, counts, top_m, defect)
+    seen = sorted(k for k, (r, slot, _) in cases.items()
+                  if not (np.array_equal(want[0][r, slot], got[0][r, slot]) and np.array_equal(bits(want[1][r, slot]), bits(got[1][r, slot]))
+                          and want[2][r, slot] == got[2][r, slot]))
+    print(f"{defect}: seen by {len(seen)} of {len(cases)} cases, value sets {sorted({k[0] for k in seen})}")
+    assert CAUGHT_BY[defect] in seen
+    if defect == "nan_equal_to_everything":                              # the failure the rule was written for: item 17 twice, 21 lost
+        r, slot, _ = cases[("two_nans_literal", 7, 7)]
+        assert got[0][r, slot, :7].tolist() == [0, 17, 1, 2, 9, 11, 17] and want[0][r, slot, :7].tolist() == [17, 1, 2, 9, 21, -1, -1]
+
+
 # ---------------------------------------------------------------------------------------------- model / facade, end to end
 def _int_model():
     z = np.load(os.path.join(G, "partial_fit.npz"))
@@ -248,6 +519,24 @@ def test_slim_explain_batch_sparse_mode_integer_ids():
             m.explain_batch(users[:2], **kw)
     with pytest.raises(ValueError, match="one list per user"):
         m.explain_batch(users[:2], items=[[1]])
+
+
+def test_explain_batch_list_form_counts_the_reasons_present_when_a_contribution_is_nan():
+    m, batch = _int_model()
+    users = sorted({u for u, _, _, _ in batch})[:40]
+    recs = m.recommend_batch(users, top_k=5)
+    ids, counts, r_ids, contrib, support = m.explain_batch(users, items=recs, top_m=3, as_arrays=True)
+    b, p = next((b, p) for b in range(len(users)) for p in range(counts[b]) if 2 <= support[b, p] <= 3)
+    before = m.explain_batch([users[b]], items=[[recs[b][p]]], top_m=3)[0][0][1]
+    assert len(before) == support[b, p]
+    W = sp.csc_matrix(m.model.item_similarity, dtype=np.float32)
+    W[int(r_ids[b, p, 0]), int(ids[b, p])] = np.nan                      # the strongest reason's weight: its contribution is NaN
+    assert W.nnz == m.model.item_similarity.nnz
+    m.model.item_similarity = W
+    after = m.explain_batch([users[b]], items=[[recs[b][p]]], top_m=3)
+    assert after == [[(recs[b][p], before[1:])]]                         # one reason fewer, no padding slot read as a reason
+    a = m.explain_batch([users[b]], items=[[recs[b][p]]], top_m=3, as_arrays=True)
+    assert a[4][0, 0] == support[b, p] and (a[2][0, 0] >= 0).sum() == support[b, p] - 1 and not np.isnan(a[3]).any()
 
 
 def test_slim_explain_batch_dense_mode_string_ids():

@@ -9,7 +9,7 @@ import scipy.sparse as sp
 
 from rtrec_amd import _native
 from rtrec_amd import ops as _ops  # noqa: F401  (registers torch.ops.rtrec_amd.*)
-from tests.test_audience_host import golden_csc, host_model
+from tests.test_audience_host import EDGE_TOP_N, edge_case, golden_csc, host_model
 from tests.test_explain_host import bits
 
 pytestmark = pytest.mark.gpu
@@ -106,6 +106,65 @@ def test_ties_at_the_boundary_go_to_the_lower_user_row():
         for f in (True, False):
             want = prefix(full, top_n) if f else host_model(Xc, W, np.arange(I), top_n, False)
             assert_same(run_op(Xc, W, np.arange(I), top_n, f), want, f"ties n={top_n} filter={f}")
+
+
+# ---------------------------------------------------------------------------------------------- 2b. the value edges
+@pytest.fixture(scope="module", params=[False, True], ids=["one_tile", "two_tiles"])
+def edges(request):
+    return edge_case(request.param)
+
+
+@pytest.mark.parametrize("top_n", EDGE_TOP_N)
+def test_nan_inf_signed_zero_and_denormal_scores(edges, top_n):
+    """tests/test_audience_host.py's edge_case, every score set through a column of W of 3 and of 60 entries: a NaN score counts
+    in eligible and is never listed, however it was made and whatever its sign bit; +-inf are numbers and tie by row across
+    the tile boundary; -0.0 alone in its sum scores +0.0; denormal sums keep their place.  Then with the filter and the
+    candidate set removing NaN users, and through a workspace that holds one query item per pass."""
+    Xc, W, items, mask, cases = edges
+    one = int(_native.load().rtrec_slim_audience_workspace_bytes(Xc.shape[0], 1, top_n))
+    for what, f, m, ws_bytes in (("no filter", False, None, None), ("filter", True, None, None), ("candidates", False, mask, None),
+                                 ("filter and candidates", True, mask, None), ("one item per pass", True, None, one)):
+        want = host_model(Xc, W, items, top_n, f, m)
+        got = run_op(Xc, W, items, top_n, f, m, ws_bytes=ws_bytes)
+        bad = sorted((name, L) for name, (q3, q60, _) in cases.items() for L, q in ((3, q3), (60, q60))
+                     for b in np.flatnonzero(items == q)
+                     if not (np.array_equal(got[0][b], want[0][b]) and np.array_equal(bits(got[1][b]), bits(want[1][b]))
+                             and got[2][b] == want[2][b] and got[3][b] == want[3][b]))
+        print(f"top_n={top_n}, {what}: {len(bad)} of {len(items)} query items differ: {bad}")
+        assert not bad, f"top_n={top_n}, {what}: these (score set, column length) differ from the definition: {bad}"
+        assert_same(got, want, f"edges n={top_n} {what}")
+        assert not np.isnan(got[1]).any()                                # under the rule no output holds a NaN
+    assert (want[3] > want[2]).any() and (want[2] < min(top_n, 3)).any()
+
+
+def test_engine_audience_items_counts_but_never_lists_a_nan_score_from_infinite_ratings():
+    from rtrec_amd.engine import SlimEngine
+    rng = np.random.default_rng(37)
+    U, I = 9000, 48                                                      # two tiles
+    X = sp.random(U, I, density=0.3, random_state=rng, format="csr", dtype=np.float32)
+    X.data[:] = rng.integers(1, 6, X.nnz).astype(np.float32)
+    X.data[rng.choice(X.nnz, 4000, replace=False)] = np.repeat(np.array([np.inf, -np.inf], np.float32), 2000)   # infinite ratings
+    W = sp.random(I, I, density=0.3, random_state=rng, format="csc", dtype=np.float32)
+    W.data[:] = rng.choice(np.array([-1.0, -0.5, 0.5, 1.0, 2.0], np.float32), W.nnz)
+    Xc = X.tocsc()
+    Xc.sort_indices(); X.sort_indices(); W.sort_indices()
+    eng = SlimEngine(device="cuda:0")
+    eng.set_interactions(Xc, X)
+    eng.set_weights(W)
+    for top_n, f in ((1, True), (40, True), (1024, False)):
+        want = host_model(Xc, W, np.arange(I), top_n, f)
+        got = eng.audience_items(np.arange(I), top_n, f)
+        assert_same(got, want, f"engine, infinite ratings n={top_n}")
+        assert not np.isnan(got[1]).any()
+    cand = np.zeros(U, bool)                                             # 1,000 candidates around the tile boundary: whole audiences fit
+    cand[7700:8700] = True                                               # into top_n, so a listed NaN could not hide behind the cut
+    want = host_model(Xc, W, np.arange(I), 1024, False, cand)
+    got = eng.audience_items(np.arange(I), 1024, False, candidate_rows=np.flatnonzero(cand))
+    assert_same(got, want, "engine, infinite ratings, candidates")
+    assert not np.isnan(got[1]).any() and (want[3] < 1024).all() and (want[2] < want[3]).sum() > I // 2
+    full = host_model(Xc, W, np.arange(I), U, False)
+    assert ((full[3] - full[2]) > 10).sum() > I // 2                     # inf - inf happened: NaN scores, eligible and not listed
+    assert np.isposinf(full[1][:, 1]).sum() > I // 2 and np.isneginf(full[1][np.arange(I), full[2] - 1]).sum() > I // 2   # inf ties at both ends
 
 
 # ---------------------------------------------------------------------------------------------- 3. lengths

@@ -8,7 +8,7 @@ import pytest
 import scipy.sparse as sp
 
 from rtrec_amd import _native
-from tests.test_explain_host import bits, golden, host_model, host_model_vectorised, ordered_sum
+from tests.test_explain_host import EDGE_TOP_M, bits, edge_case, golden, host_model, host_model_vectorised, ordered_sum
 
 pytestmark = pytest.mark.gpu
 
@@ -132,6 +132,57 @@ def test_row_ids_padding_holes_and_strides():
     # no rows at all: nothing is launched, nothing is written
     empty = run_op(X, W, np.empty(0, np.int32), np.empty((0, 10), np.int32), np.empty(0, np.int32), 10, 4)
     assert empty[0].shape == (0, 10, 4) and empty[2].shape == (0, 10)
+
+
+# ---------------------------------------------------------------------------------------------- the value edges
+@pytest.fixture(scope="module")
+def edges():
+    return edge_case()
+
+
+def differing_cases(got, want, cases):
+    return sorted(k for k, (r, slot, _) in cases.items()
+                  if not (np.array_equal(got[0][r, slot], want[0][r, slot]) and np.array_equal(bits(got[1][r, slot]), bits(want[1][r, slot]))
+                          and got[2][r, slot] == want[2][r, slot]))
+
+
+@pytest.mark.parametrize("top_m", EDGE_TOP_M)
+def test_nan_inf_signed_zero_and_denormal_contributions_on_all_four_search_paths(edges, top_m):
+    """tests/test_explain_host.py's edge_case: every value set through rows of 3 / 64 / 65 entries (search in registers / in
+    memory) and columns of 3 / 64 / 65 / 130 entries (one probe / a probe per round, hits in all three probes).  A NaN
+    contribution counts in support and is never a reason; +-inf are numbers; each zero keeps its sign bit; 2^-140 is kept."""
+    X, W, rows, ids, counts, cases = edges
+    want = host_model(X, W, rows, ids, counts, top_m)
+    got = run_op(X, W, None, ids, counts, 4, top_m)
+    bad = differing_cases(got, want, cases)
+    print(f"top_m={top_m}: {len(bad)} of {len(cases)} cases differ: {bad}")
+    assert not bad, f"top_m={top_m}: {len(bad)} of {len(cases)} cases differ from the definition: {bad}"
+    assert_same(got, want, f"edges m={top_m}")
+    assert not np.isnan(got[1]).any()                                    # under the rule no output holds a NaN
+    back = np.arange(len(rows))[::-1].copy()                             # the same pairs through row ids, the last row first
+    assert_same(run_op(X, W, back, ids[back], counts[back], 4, top_m), tuple(a[back] for a in want), f"edges by row id m={top_m}")
+
+
+def test_engine_explain_rows_lists_infinite_contributions_as_numbers():
+    from rtrec_amd.engine import SlimEngine
+    rng = np.random.default_rng(31)
+    U, I = 60, 48
+    X = sp.random(U, I, density=0.4, random_state=rng, format="csr", dtype=np.float32)
+    X.data[:] = rng.integers(1, 6, X.nnz).astype(np.float32)
+    X.data[rng.choice(X.nnz, 40, replace=False)] = np.repeat(np.array([np.inf, -np.inf], np.float32), 20)     # infinite ratings
+    W = sp.random(I, I, density=0.3, random_state=rng, format="csc", dtype=np.float32)
+    W.data[:] = rng.choice(np.array([-1.0, -0.5, 0.5, 1.0, 2.0], np.float32), W.nnz)
+    X.sort_indices(); W.sort_indices()
+    eng = SlimEngine(device="cuda:0")
+    eng.set_interactions(X.tocsc(), X)
+    eng.set_weights(W)
+    ids = np.stack([rng.permutation(I)[:8] for _ in range(U)]).astype(np.int32)
+    want = host_model(X, W, np.arange(U), ids, np.full(U, 8), 32)
+    listed = want[0] >= 0
+    assert (np.isposinf(want[1]) & listed).sum() > 10 and (np.isneginf(want[1]) & listed).sum() > 10      # -inf with an id: a reason, not padding
+    got = eng.explain_rows(np.arange(U), ids, None, 32)
+    assert_same(got, want, "engine, infinite ratings")
+    assert not np.isnan(got[1]).any()
 
 
 def test_op_refuses_bad_ranges_and_mistyped_tensors():
