@@ -336,12 +336,13 @@ class SLIMElastic:
                     sc = S[q].copy()
                     if filter_interacted:
                         sc[own] = -np.inf
+                    sc[np.isnan(sc)] = -np.inf       # a NaN score is never listed (include/rtrec_amd.h), nor is -inf
                     top = np.argsort(sc, kind="stable")[-top_k:][::-1]
                     top = top[sc[top] != -np.inf]
                     sel, val = top, sc[top]
                 else:
                     sc = S[q]
-                    nz = sc != 0
+                    nz = (sc != 0) & (sc > -np.inf)      # (NaN > -inf is false: neither NaN nor -inf is listed)
                     if filter_interacted:
                         nz[own] = False
                     cols = np.flatnonzero(nz)

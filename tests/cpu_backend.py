@@ -120,8 +120,17 @@ class OracleBackend:
             if sc64 is not None:
                 sc64.copy_(torch.from_numpy(o_sc.astype(np.float64)))
             return
-        o_ids, o_sc, o_cnt = so.recommend_batch(Xall[rsel], Wr, top_k=top_k, filter_interacted=filter_interacted,
-                                                dense=(mode == 1), use_f64=bool(acc_f64))
+        Xsel = Xall[rsel]
+        dt = np.float64 if acc_f64 else np.float32
+        with np.errstate(all="ignore"):
+            P = sp.csr_matrix(Xsel.astype(dt) @ Wr.astype(dt))     # scipy's csr_matmat: the product the reference ranks
+        if np.isfinite(P.data).all():
+            o_ids, o_sc, o_cnt = so.recommend_batch(Xsel, Wr, top_k=top_k, filter_interacted=filter_interacted,
+                                                    dense=(mode == 1), use_f64=bool(acc_f64))
+        else:
+            # A score is NaN or infinite: the oracle's insertion order defines nothing once a NaN arrives.  The rule of
+            # include/rtrec_amd.h on scipy's own product: NaN and -inf are never listed, +inf is a number.
+            o_ids, o_sc, o_cnt = self._lists_of_product(P, Xsel, top_k, filter_interacted, mode == 1)
         ids.copy_(torch.from_numpy(o_ids)); sc.copy_(torch.from_numpy(o_sc)); cnt.copy_(torch.from_numpy(o_cnt))
         aux.zero_()
         if mode == 0:
@@ -140,6 +149,38 @@ class OracleBackend:
             aux.copy_(torch.from_numpy(o_aux))
         if sc64 is not None:
             sc64.copy_(torch.from_numpy(o_sc.astype(np.float64)))
+
+    @staticmethod
+    def _lists_of_product(P, Xsel, top_k, filter_interacted, dense):
+        """(ids, float32 scores, counts) from the rows of the product P = X W as scipy leaves them: a row's stored entries are
+        its non-zero sums, LAST touched column first (csr_matmat's linked list) -- the list slim_elastic.py:782-818 sorts with
+        a stable sorted(reverse=True).  DENSE (:744-779): every column, ties to the higher id."""
+        B, n_cols = P.shape
+        o_ids = np.full((B, top_k), -1, np.int32)
+        o_sc = np.full((B, top_k), -np.inf, np.float32)
+        o_cnt = np.zeros(B, np.int32)
+        for r in range(B):
+            cols, vals = P.indices[P.indptr[r]:P.indptr[r + 1]], P.data[P.indptr[r]:P.indptr[r + 1]]
+            own = Xsel.indices[Xsel.indptr[r]:Xsel.indptr[r + 1]]
+            if dense:
+                sc = np.zeros(n_cols, P.dtype)
+                sc[cols] = vals
+                if filter_interacted:
+                    sc[own] = -np.inf
+                keep = np.flatnonzero(sc > -np.inf)                 # (NaN > -inf is false)
+                order = keep[np.lexsort((-keep, -sc[keep]))][:top_k]
+                sel, val = order, sc[order]
+            else:
+                keep = (vals != 0) & (vals > -np.inf)
+                if filter_interacted:
+                    keep &= ~np.isin(cols, own)
+                cols, vals = cols[keep], vals[keep]
+                order = np.argsort(-vals, kind="stable")[:top_k]
+                sel, val = cols[order], vals[order]
+            n = len(sel)
+            with np.errstate(over="ignore"):
+                o_ids[r, :n], o_sc[r, :n], o_cnt[r] = sel, val.astype(np.float32), n
+        return o_ids, o_sc, o_cnt
 
     def score_rows(self, n_rows, row_ids, xb, n_items, col_lo, lay, acc_f64, out):
         Wr = self._shard_w(n_items, col_lo, lay)
