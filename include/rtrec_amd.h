@@ -398,25 +398,30 @@ size_t rtrec_slim_score_workspace_bytes(int32_t n_rows, int32_t n_tiles, int32_t
  * matrix, slim_elastic.py:252).
  * Limits: top_k <= 1023 and n_tiles * (top_k + 1) <= 1024 (RTREC_ERR_UNSUPPORTED otherwise); up to
  * top_k = 63 the selection is a two-pass threshold filter, beyond that one scan per result.
- * Values that are no ordinary numbers.  PRECONDITION, every form of this call (tiled, feature-row, segment) and the steps
- * behind it (rtrec_slim_refine_topk_f64, rtrec_slim_dense_fill, rtrec_slim_merge_topk): no score of the call and no
- * partial sum of one leaves the finite range -- no NaN or infinite rating or weight, no inf * 0 with a stored zero, no
- * overflowing product or sum (3e38 * 10 is +inf, and with signed weights inf - inf follows).  n_max * max|x| * max|w| <
- * 2^127, evaluated in float64 over the longest scored row and the stored ratings and weights, is sufficient.  The caller
- * vouches for it.  Outside it the result is UNSPECIFIED and, for a NaN score, unsafe -- a known defect of the tiled
- * selection (csrc/score.hip, select_topk): rank_and_store ranks a candidate by the number of better ones, every comparison
- * with a NaN is false, so all NaN candidates of a tile take rank 0 yet are counted, emit_result emits result slots that
- * were never written, and their contents index d_col_ids.  Signed zeros and denormals are inside the contract and stay as
- * they are.
- * The rule the call is to follow once that selection is repaired is the one of the other ranking kernels
- * (rtrec_slim_score_pairs below), written out as a plain definition and held to the reference wherever the reference is
- * defined in tests/test_score_values_host.py: a column whose score is NaN is never listed, in any mode, with float32 or
+ * Values that are no ordinary numbers.  The TILED form of this call (the d_tile_ptr / d_w_col / d_w_val layout: what runs when
+ * opts names no feature-row and no segment layout) follows one rule, the rule of the other ranking kernels
+ * (rtrec_slim_score_pairs below), written out as a plain definition in tests/test_score_values_host.py and held to the
+ * reference wherever the reference is defined: a column whose score is NaN is never listed, in any mode, with float32 or
  * float64 accumulators -- it takes no slot, d_out_count counts the listed columns only, the first-touch keys of the other
  * columns are what they would be anyway, and no output holds a NaN; +inf is a number, listed first, ties among +inf by the
  * mode's tie rule; -inf is never listed (DENSE mode: the reference marks filtered columns with -inf and drops them; SPARSE
  * mode: the reference's sorted() would list it last, but -inf is this call's mark of an own item and of an empty slot in
  * every selection and merge -- what telling the two apart would cost has not been measured, so the weaker rule is the
- * one stated); a finite sum that overflows is +-inf and ranks as such. */
+ * one stated); a finite sum that overflows is +-inf and ranks as such; an own item (filter_interacted) stays out whatever
+ * its sum meets; signed zeros and denormals stay as they are.  d_out_aux holds a first-touch key only in the rows whose
+ * leading top_k + 1 scores hold an exact tie (the rows the exact-tie pass re-scores), 0 elsewhere.  The selection admits a
+ * column only if its key is a number above -inf, so every result slot below a returned count has been written
+ * (csrc/score.hip, select_topk).  Dense blocks: a zero of d_dense_val means "W stores nothing here" -- a
+ * row segment that stores a zero must stay in the CSR part (the layout builders of rtrec_amd/layouts.py see to it) -- and
+ * an infinite or NaN rating adds nothing to such a column.
+ * PRECONDITION of the FAST forms (feature-row and segment layouts through opts) and of the steps behind them
+ * (rtrec_slim_refine_topk_f64, rtrec_slim_dense_fill): no score of the call and no partial sum of one leaves the finite
+ * range -- no NaN or infinite rating or weight, no inf * 0 with a stored zero, no overflowing product or sum (3e38 * 10 is
+ * +inf, and with signed weights inf - inf follows).  n_max * max|x| * max|w| < 2^127, evaluated in float64 over the longest
+ * scored row and the stored ratings and weights, is sufficient.  At the C ABI the caller vouches for it and the result is
+ * UNSPECIFIED outside it; the Python engine checks exactly this condition (score_plan.values_ordinary) and sends a call
+ * that fails it to the tiled form.  rtrec_slim_merge_topk keeps its own NaN precondition; this call never hands it a
+ * NaN. */
 int rtrec_slim_score_topk(int32_t n_rows, const int32_t *d_row_ids,
                           const int32_t *d_xb_ptr, const int32_t *d_xb_col, const float *d_xb_val,
                           int32_t n_items, int32_t n_cols, int32_t col_offset,

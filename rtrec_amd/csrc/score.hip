@@ -137,7 +137,9 @@ __device__ __forceinline__ double untouched_value(double) { return __longlong_as
 __device__ __forceinline__ bool is_untouched(float v) { return __float_as_uint(v) == 0x80000000u; }
 __device__ __forceinline__ bool is_untouched(double v) { return static_cast<unsigned long long>(__double_as_longlong(v)) == 0x8000000000000000ull; }
 
-// Key of an accumulator for selection: invalid columns map to -inf.
+// Key of an accumulator for selection: invalid columns map to -inf.  A NaN accumulator keeps its NaN key; ADMISSION is
+// `key > -inf` everywhere in select_topk, which is false for -inf and for NaN alike, so neither ever becomes a candidate
+// (the value rule of include/rtrec_amd.h: NaN never listed or counted, -inf never listed, +inf a number like any other).
 template <typename ACC>
 __device__ __forceinline__ ACC sel_key(ACC v, bool zero_is_valid) {
     return (!zero_is_valid && v == ACC(0)) ? NegInf<ACC>::value() : v;
@@ -208,6 +210,9 @@ __device__ __forceinline__ int select_topk(const ScoreArgs &a, const TileLds<ACC
     // light user's touched list is mostly its own, excluded, items), and in SPARSE mode without
     // first-touch tracking every aux is 0, so the comparison is (score, id) alone.  Selection is the
     // per-user cost of a pass (C2: 43 % of it), and it is VALU-issue bound.
+    // No candidate is a NaN (admission), and two candidates name different columns, so (score, aux, id) orders the held
+    // candidates totally: their ranks are 0 .. n_have - 1, each once, and every slot below the returned min(n_have, kk)
+    // is written (layouts.select_topk_model is the host model of this function).
     auto rank_and_store = [&](bool have, const Cand<ACC> &mine) {
         const bool use_aux = FT || a.mode == RTREC_TOPK_CANDIDATES;
         unsigned long long m = __ballot(have);
@@ -235,7 +240,7 @@ __device__ __forceinline__ int select_topk(const ScoreArgs &a, const TileLds<ACC
         bool have = false;
         if (lane < n_idx) {
             const int c = idx(lane);
-            if (sel_key(acc[c], zero_valid) != ninf) { mine = make_cand(c); have = true; }
+            if (sel_key(acc[c], zero_valid) > ninf) { mine = make_cand(c); have = true; }
         }
         return rank_and_store(have, mine);
     }
@@ -249,7 +254,7 @@ __device__ __forceinline__ int select_topk(const ScoreArgs &a, const TileLds<ACC
             Cand<ACC> b; b.id = -1; b.score = ninf; b.aux = 0u;
             for (int t = lane; t < n_idx; t += 64) {
                 const int c = idx(t);
-                if (sel_key(acc[c], zero_valid) == ninf) continue;
+                if (!(sel_key(acc[c], zero_valid) > ninf)) continue;
                 const Cand<ACC> x = make_cand(c);
                 if (last.id >= 0 && !cand_better(last, x)) continue;
                 if (cand_better(x, b)) b = x;
@@ -321,7 +326,7 @@ __device__ __forceinline__ int select_topk(const ScoreArgs &a, const TileLds<ACC
                 hit[j] = false;
                 if (c < n_idx) {
                     const ACC k = sel_key(acc[c], zero_valid);
-                    hit[j] = (k != ninf) && (k >= tau);
+                    hit[j] = (k > ninf) && (k >= tau);
                 }
                 any = any || hit[j];
             }
@@ -344,7 +349,7 @@ __device__ __forceinline__ int select_topk(const ScoreArgs &a, const TileLds<ACC
         if (t < n_idx) {
             c = idx(t);
             const ACC k = sel_key(acc[c], zero_valid);
-            hit = (k != ninf) && (k >= tau);
+            hit = (k > ninf) && (k >= tau);
         }
         const unsigned long long m = __ballot(hit);
         if (m) {
@@ -385,7 +390,7 @@ __device__ __forceinline__ int select_topk(const ScoreArgs &a, const TileLds<ACC
         Cand<ACC> b; b.id = -1; b.score = ninf; b.aux = 0u;
         for (int t = lane; t < n_idx; t += 64) {
             const int c = idx(t);
-            if (sel_key(acc[c], zero_valid) == ninf) continue;
+            if (!(sel_key(acc[c], zero_valid) > ninf)) continue;
             const Cand<ACC> x = make_cand(c);
             if (last.id >= 0 && !cand_better(last, x)) continue;   // strictly below `last`
             if (cand_better(x, b)) b = x;
@@ -443,10 +448,13 @@ __device__ __forceinline__ void emit_result(const ScoreArgs &a, const TileLds<AC
 // TOUCH: the value read back tells whether this is the first contribution to the column; such
 // columns are appended to tlist.  FT: the first-touch position of the column is recorded.
 // PREFILTER (sparse kernel, filter_interacted): the user's own items are taken out of the race while
-// their row headers are loaded -- the accumulator of an interacted column is set to -inf (an
-// absorbing value: -inf + p = -inf) and the column joins the touched list so that it is reset with
-// the rest.  This replaces a separate pass (two dependent global loads per job) after the
-// accumulation; scores of the other columns are untouched.
+// their row headers are loaded -- the accumulator of an interacted column is set to -inf and the
+// column joins the touched list so that it is reset with the rest.  -inf absorbs every finite and
+// every -inf product (-inf + p = -inf); a +inf or NaN product (an infinite weight or rating on an
+// own item) turns it into NaN, and NaN absorbs everything.  Neither -inf nor NaN is admitted by
+// select_topk (`key > -inf`), so an own item stays out whatever is added to it.  This replaces a
+// separate pass (two dependent global loads per job) after the accumulation; scores of the other
+// columns are untouched.
 template <typename ACC, bool FT, bool TOUCH, bool PREFILTER = false>
 __device__ __forceinline__ int accumulate_tile(const ScoreArgs &a, const TileLds<ACC> &L, int a0, int n_a, int tile,
                                                int t0, int ncol PF_PARAMS) {
@@ -542,10 +550,26 @@ __device__ __forceinline__ int accumulate_tile(const ScoreArgs &a, const TileLds
 #pragma unroll
             for (int j = 0; j < kRowGroup; ++j) {
                 if (dd[j] >= 0) {
-                    // dense block: 4 consecutive accumulators per lane and step.  x * 0 is +-0 and
-                    // never changes a sum, so the zero padding is inert.
+                    // dense block: 4 consecutive accumulators per lane and step.  For a FINITE rating x * 0 is
+                    // +-0 and never changes a sum, so the zero padding is inert.
                     const float *dv = a.dense_val + static_cast<size_t>(dd[j]) * a.tile_cols;
                     const ACC xj = xx[j];
+                    if (!__builtin_isfinite(xj)) {
+                        // An infinite or NaN rating (wave-uniform: xj was read from one lane) would make a NaN of every
+                        // padded column, which W does not store: a plain column loop adds only where the block is
+                        // non-zero.  The layout builders keep a row segment with a STORED zero out of the dense blocks
+                        // (layouts.py), so a zero in a block is always padding; a stored zero times inf is a NaN the
+                        // reference computes too, and it comes from the CSR part of the tile.
+                        for (int c = lane; c < a.tile_cols; c += 64) {
+                            const float w = dv[c];
+                            if (w != 0.0f) {
+                                const ACC old = acc[c];
+                                if (FT && is_untouched(old)) L.ft[c] = ps[j];
+                                acc[c] = old + prod(xj, w);
+                            }
+                        }
+                        continue;
+                    }
                     if (!FT && sizeof(ACC) == 4) {
                         // float tile: whole-vector arithmetic (v_pk_mul_f32 / v_pk_add_f32 on the
                         // registers the 128-bit loads filled, no repacking moves) and a two-stage

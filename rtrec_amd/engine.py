@@ -779,6 +779,38 @@ class SlimEngine:
             W["w_min_ok"] = bool(not dw.lossy and (dw.nnz == 0 or float(dw.vals.min()) >= self.F64_REFINE_MIN_VALUE))
         return W["w_min_ok"] and self._f64_refine_x_ok(xb)
 
+    def _w_absmax(self) -> Optional[float]:
+        """max |w| over the stored weights (NaN when one of them is a NaN; None for an empty W); cached per weights, beside
+        w_min_ok."""
+        W = self._W
+        if "w_absmax" not in W:
+            dw: DeviceWeights = W["dw"]
+            W["w_absmax"] = float(dw.vals.abs().max()) if dw.nnz else None
+        return W["w_absmax"]
+
+    def _x_bound(self, xb) -> Optional[Tuple[int, float]]:
+        """(ratings in the longest row, max |x|) of the batch matrix (NaN when a rating is a NaN; None without a rating):
+        one reduction and one read-back, cached for the resident X beside rval_min_ok -- its longest row bounds every row
+        list scored from it -- and computed once per call for a batch that is not resident."""
+        ptr, _col, val = xb
+        resident = self._X.get("rval") is val
+        if resident and "rval_bound" in self._X:
+            return self._X["rval_bound"]
+        bound = None
+        if val.numel() and ptr.numel() > 1:
+            torch = self.be.torch
+            n_max, x_max = torch.stack([(ptr[1:] - ptr[:-1]).max().double(), val.abs().max().double()]).tolist()
+            bound = (int(n_max), float(x_max))
+        if resident:
+            self._X["rval_bound"] = bound
+        return bound
+
+    def _values_ordinary(self, xb) -> bool:
+        """The finite-range PRECONDITION of the fast kernels (include/rtrec_amd.h), checked: n_max * max|x| * max|w| < 2^127."""
+        xbound = self._x_bound(xb)
+        n_max, x_max = xbound if xbound is not None else (0, None)
+        return score_plan.values_ordinary(n_max, x_max, self._w_absmax())
+
     def _seg_form(self) -> Optional[Dict[str, Any]]:
         """The segment layout of this rank's shard as a layout dict ({"sg": ..., "n_cols": ...}), or None."""
         W, be = self._W, self.be
@@ -854,7 +886,16 @@ class SlimEngine:
         shard (_fast_layout) merged in when compact."""
         W, be = self._W, self.be
         if compact:
-            self._fast_layout()               # (sets n_active, which the tile width of a compacted layout depends on)
+            # (sets n_active, which the tile width of a compacted layout depends on.)  A W with a NaN or an infinite weight
+            # never takes a fast pass (score_plan.values_ordinary), so no fast form of it is built either: its builders and
+            # their bounds are written for ordinary numbers.  The active columns are counted directly then.
+            w_max = self._w_absmax()
+            if w_max is None or w_max < score_plan.VALUE_LIMIT:
+                self._fast_layout()
+            elif "n_active" not in W:
+                dw0: DeviceWeights = W["dw"]
+                sel = (dw0.cols >= W["col_lo"]) & (dw0.cols < W["col_hi"])
+                W["n_active"] = int(be.torch.unique(dw0.cols[sel]).numel())
         tile = self._tile_width(compact, top_k)
         key = (compact, tile)
         if key not in W["layouts"]:
@@ -866,7 +907,7 @@ class SlimEngine:
                                            compact=compact, dense_fill=DENSE_ROW_FILL if compact else None)
                 if lay is not None and compact:
                     W["n_active"] = lay["n_cols"]
-                    fast = self._fast_layout()
+                    fast = W.get("fast")                      # (built above, unless W holds a NaN or an infinite weight)
                     if fast is not None:
                         lay.update({k: v for k, v in fast.items() if k != "n_cols"})
             W["layouts"][key] = lay
@@ -931,6 +972,7 @@ class SlimEngine:
             seg_supported=bool(getattr(be, "supports_seg_layout", False)),
             dense_fill_ok=lambda: self._dense_fill_ok(xb), f64_w_ok=self._f64_refine_w_ok,
             f64_x_ok=lambda: self._f64_refine_x_ok(xb), f64_refine_mode=self._f64_refine_mode,
+            values_ordinary=lambda: self._values_ordinary(xb),
             limits=score_plan.Limits(self.FR_SMALL_BATCH, self.FR_MIN_ROWS, self.FR_MAX_TOP_K, self.SG_MAX_TOP_K))
         req = score_plan.plan_fast_layout(facts)
         fast = None

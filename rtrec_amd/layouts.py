@@ -59,11 +59,14 @@ def build_tiled_w(W_csc: sp.csc_matrix, col_lo: int, col_hi: int, tile_cols: int
     key = (tile * n_items + rows)[order]
     cnt = np.bincount(key, minlength=n_tiles * n_items)
     # (tile, row) segments that fill at least `dense_fill` of the tile are stored as zero-padded
-    # dense vectors: the kernel then updates 4 accumulators per lane and instruction
+    # dense vectors: the kernel then updates 4 accumulators per lane and instruction.  A segment that STORES a zero stays
+    # in the CSR part: in a dense block a zero means "not stored" (the kernel leaves such a column alone when the rating
+    # is infinite or NaN, and never lets it count as a first touch), while a stored zero takes part like any weight
     dense_idx = dense_val = None
     kl, vl = kloc[order], vals[order]
     if dense_fill is not None:
-        dense_keys = np.flatnonzero(cnt >= max(64, int(dense_fill * tile_cols)))
+        zeros = np.bincount(key[vl == 0], minlength=n_tiles * n_items)
+        dense_keys = np.flatnonzero((cnt >= max(64, int(dense_fill * tile_cols))) & (zeros == 0))
         if dense_keys.size:
             dense_idx = np.full(n_tiles * n_items, -1, dtype=np.int32)
             dense_idx[dense_keys] = np.arange(dense_keys.size, dtype=np.int32)
@@ -357,7 +360,8 @@ def build_tiled_w_device(torch, rows, cols, vals, n_items: int, col_lo: int, col
     cnt = torch.bincount(seg, minlength=n_tiles * n_items)
     dense_idx = dense_val = None
     if dense_fill is not None:
-        dense_keys = torch.nonzero(cnt >= max(64, int(dense_fill * S))).view(-1)
+        zeros = torch.bincount(seg[vl == 0], minlength=n_tiles * n_items)      # a segment with a stored zero stays CSR
+        dense_keys = torch.nonzero((cnt >= max(64, int(dense_fill * S))) & (zeros == 0)).view(-1)
         if dense_keys.numel():
             dense_idx = torch.full((n_tiles * n_items,), -1, dtype=torch.int32, device=dev)
             dense_idx[dense_keys] = torch.arange(dense_keys.numel(), dtype=torch.int32, device=dev)
@@ -521,3 +525,130 @@ def fr_first_fill_model(sums: np.ndarray, admissible: np.ndarray, kk: int, strid
             values[pos], cols[pos] = v, c
             n_inserted += 1
     return dict(values=values, cols=cols, n_ranked=int(has.sum()), n_extras=n_extras, n_inserted=n_inserted)
+
+
+# ---- host model of select_topk (csrc/score.hip): admission, rank by count, the returned count ----
+SEL_LIST_CAP = 256          # kListCap of csrc/score.hip
+
+
+def _cand_better(a, b) -> bool:
+    """cand_better of csrc/common.hip.h on (score, aux, id) triples; id < 0: no candidate.  Every compare with a NaN is false."""
+    if a[2] < 0:
+        return False
+    if b[2] < 0:
+        return True
+    if a[0] > b[0]:
+        return True
+    if a[0] < b[0]:
+        return False
+    if a[1] != b[1]:
+        return a[1] > b[1]
+    return a[2] > b[2]
+
+
+def select_topk_model(keys: np.ndarray, ids: np.ndarray, aux: Optional[np.ndarray], kk: int, whole_tile: bool = False,
+                      old_admission: bool = False) -> Dict[str, Any]:
+    """One call of select_topk as the wave runs it.  `keys`: sel_key of the columns idx(0 .. n_idx) in the order the wave
+    visits them (the accumulator, or -inf for a zero sum where zeros do not compete; float32 or float64, NaN allowed); `ids`:
+    their layout columns, distinct; `aux`: first-touch or candidate ranks (None: the (score, id) compare of SPARSE mode
+    without first-touch tracking); `whole_tile`: IdxAll (4 columns per lane and step) rather than a list.
+    ADMISSION is `key > -inf` (false for -inf and NaN); `old_admission` is the test the kernel had before, `key != -inf`, which
+    lets a NaN in.  The branches are the kernel's: n_idx <= 64 ranks what the lanes hold; kk > 64 scans once per result; else
+    pass 1 (lane bests, tau from the quad maxima for kk <= 16 or the 64 lane bests), pass 2 (admitted keys >= tau into the
+    list), then rank (<= 64 of them), extraction from the list (<= 256) or bounded scans (mass ties).
+    Returns slot_id / slot_score / slot_aux [count] (slot_id -2 where a slot below the count was NEVER WRITTEN), count (what
+    the function returns), unwritten (those slots), collisions (candidates that wrote a slot another one wrote too)."""
+    keys, ids = np.asarray(keys), np.asarray(ids, dtype=np.int64)
+    n_idx = len(keys)
+    ninf = keys.dtype.type(-np.inf)
+    use_aux = aux is not None
+    aux = np.asarray(aux, dtype=np.int64) if use_aux else np.zeros(n_idx, dtype=np.int64)
+    with np.errstate(invalid="ignore"):
+        admit = (keys != ninf) if old_admission else (keys > ninf)
+    cap = max(int(kk), 1)
+    slot_id = np.full(cap, -2, dtype=np.int64)
+    slot_sc = np.full(cap, ninf, dtype=keys.dtype)
+    slot_aux = np.zeros(cap, dtype=np.int64)
+    state = dict(collisions=0)
+
+    def finish(count):
+        unwritten = [s for s in range(count) if slot_id[s] == -2]
+        return dict(slot_id=slot_id[:count], slot_score=slot_sc[:count], slot_aux=slot_aux[:count], count=int(count),
+                    unwritten=unwritten, collisions=state["collisions"])
+
+    def rank_and_store(held):                      # held: positions (into keys) of the candidates the lanes hold, <= 64
+        s, a, i = keys[held], aux[held], ids[held]
+        with np.errstate(invalid="ignore"):
+            gt, eq = s[None, :] > s[:, None], s[None, :] == s[:, None]           # [me, other]
+            if use_aux:
+                lt = s[None, :] < s[:, None]
+                tie = ~gt & ~lt                                                      # cand_better falls through (NaN too)
+                better = gt | (tie & ((a[None, :] > a[:, None]) | ((a[None, :] == a[:, None]) & (i[None, :] > i[:, None]))))
+            else:
+                better = gt | (eq & (i[None, :] > i[:, None]))
+        rank = better.sum(axis=1)
+        written = set()
+        for j in np.flatnonzero(rank < kk):
+            r = int(rank[j])
+            state["collisions"] += int(r in written)
+            written.add(r)
+            slot_id[r], slot_sc[r], slot_aux[r] = i[j], s[j], a[j]
+        return finish(min(len(held), kk))
+
+    def scans(pool, bounded):
+        """One wave-wide arg-max per result over the admitted columns of `pool`; bounded: strictly below the previous
+        result (the kk > 64 and mass-tie forms), else the found column leaves the list."""
+        pool = [int(p) for p in pool]
+        with np.errstate(invalid="ignore"):
+            clean = not np.isnan(keys[pool]).any() if pool else True
+        if clean:         # no NaN: cand_better is a total order on distinct columns, so the scans emit the sorted prefix
+            order = sorted(pool, key=lambda p: (keys[p], aux[p], ids[p]), reverse=True)[:kk]
+            for r, p in enumerate(order):
+                slot_id[r], slot_sc[r], slot_aux[r] = ids[p], keys[p], aux[p]
+            return finish(len(order))
+        last, n_out, alive = None, 0, list(pool)
+        for r in range(kk):
+            lane_best = [(ninf, 0, -1, -1)] * 64
+            for t, p in enumerate(alive):
+                x = (keys[p], aux[p], ids[p], p)
+                if bounded and last is not None and not _cand_better(last, x):
+                    continue
+                if _cand_better(x, lane_best[t % 64]):
+                    lane_best[t % 64] = x
+            c = list(lane_best)
+            for m in (32, 16, 8, 4, 2, 1):          # wave_best: xor butterfly
+                c = [c[l ^ m] if _cand_better(c[l ^ m], c[l]) else c[l] for l in range(64)]
+            w = c[0]
+            if w[2] < 0:
+                break
+            last = w
+            if not bounded:
+                alive = [p for p in alive if ids[p] != w[2]]
+            slot_id[r], slot_sc[r], slot_aux[r] = w[2], w[0], w[1]
+            n_out = r + 1
+        return finish(n_out)
+
+    pos = np.arange(n_idx)
+    if n_idx <= 64:
+        return rank_and_store(pos[admit])
+    if kk > 64:
+        return scans(pos[admit], bounded=True)
+    # pass 1: a lane's best key (`k > best`: a NaN never becomes a lane best)
+    lane_of = (pos // 4) % 64 if whole_tile else pos % 64
+    best = np.full(64, ninf, dtype=keys.dtype)
+    with np.errstate(invalid="ignore"):
+        ok = keys > ninf
+    np.maximum.at(best, lane_of[ok], keys[ok])
+    if kk <= 16:
+        q = best.reshape(16, 4).max(axis=1)
+        tau = np.sort(q)[::-1][kk - 1]
+    else:
+        tau = np.sort(best)[::-1][kk - 1]
+    with np.errstate(invalid="ignore"):
+        hit = admit & (keys >= tau)
+    clist = pos[hit]
+    if len(clist) <= 64:
+        return rank_and_store(clist)
+    if len(clist) <= SEL_LIST_CAP:
+        return scans(clist, bounded=False)
+    return scans(pos[admit], bounded=True)

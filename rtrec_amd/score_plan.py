@@ -8,9 +8,13 @@ now two pure steps with the engine's side effects (building a layout, launching 
     lay  = <engine builds / fetches that layout>
     plan = choose_path(facts, req, has_fr, has_sg, tiled_exists)
 
-`facts` holds everything the decision reads.  The four data-dependent facts (are W's weights / X's ratings positive ...)
-cost a device reduction when asked for the first time, so they are passed as zero-argument callables and only called where
-the old short-circuit evaluation called them.  tests/test_host_logic.py checks both functions over the full cross product
+`facts` holds everything the decision reads.  The five data-dependent facts (are W's weights / X's ratings positive, are
+all values ordinary ...) cost a device reduction when asked for the first time, so they are passed as zero-argument callables
+and only called where the decision needs them: `values_ordinary` only where a fast form would otherwise be asked for.
+
+The fast kernels (feature rows, segments, float64 refine, dense fill) keep a finite-range PRECONDITION at the C ABI
+(include/rtrec_amd.h); the tiled kernel follows the value rule for NaN, +-inf and overflow.  `values_ordinary` is the
+engine's check of that precondition: when it is false no fast layout is wanted and every row takes Path.TILED.  tests/test_host_logic.py checks both functions over the full cross product
 of their inputs against an explicit table and a set of invariants -- on the CPU, without a GPU.
 
 Semantics being served: rtrec/models/internal/slim_elastic.py:782-818 (SPARSE: int ids, only stored products compete),
@@ -21,9 +25,22 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 from enum import Enum
-from typing import Callable
+from typing import Callable, Optional
 
 TOPK_SPARSE, TOPK_DENSE, TOPK_CANDIDATES = 0, 1, 2          # rtrec_topk_mode of include/rtrec_amd.h
+
+
+VALUE_LIMIT = 2.0 ** 127
+
+
+def values_ordinary(n_max: int, x_absmax: Optional[float], w_absmax: Optional[float]) -> bool:
+    """The sufficient condition of include/rtrec_amd.h for "no score and no partial sum leaves the finite range": n_max * max|x|
+    * max|w| < 2^127 in float64, with n_max the ratings of the longest scored row.  A NaN or an infinity on either side fails
+    the comparison (0 * inf is a NaN too: a stored zero rating against an infinite weight); None stands for a side without a
+    stored value -- no product exists then."""
+    if x_absmax is None or w_absmax is None:
+        return True
+    return bool(float(n_max) * float(x_absmax) * float(w_absmax) < VALUE_LIMIT)
 
 
 class Path(Enum):
@@ -62,6 +79,10 @@ class ScoreFacts:
     f64_w_ok: Callable[[], bool]           # float64 W: float32-valued, positive weights
     f64_x_ok: Callable[[], bool]           # ratings positive
     f64_refine_mode: Callable[[], int]     # 0: no refine step, 1: positive W, 2: signed W (absolute slack)
+    # n_max * max|x| * max|w| < 2^127 in float64 (false as well when a rating or a weight is NaN or infinite): no score can
+    # leave the finite float32 range, the precondition of every fast kernel
+    # (defaults to "ordinary": a caller that states nothing vouches for the precondition, as every caller did before the fact existed)
+    values_ordinary: Callable[[], bool] = lambda: True
     limits: Limits = Limits()
 
 
@@ -89,6 +110,12 @@ class Plan:
 def plan_fast_layout(f: ScoreFacts) -> FastRequest:
     L = f.limits
     sparse, dense = f.mode == TOPK_SPARSE, f.mode == TOPK_DENSE
+    # a fast form can be asked for at all: only then is the value fact worth its reduction, and it goes first -- the other
+    # facts' thresholds (min >= ...) mean nothing for a NaN
+    fast_kernel_on = f.feature_rows_on or (f.seg_layout_on and f.seg_supported)
+    if not ((sparse or (dense and f.dense_fast_on and f.lazy_tiled)) and f.hip and f.nonempty_shard and fast_kernel_on
+            and f.values_ordinary()):
+        return FastRequest(False, False, f.top_k, False, False)
     dense_fill = bool(dense and f.hip and f.dense_fast_on and f.dense_fill_on and f.lazy_tiled and not f.acc_f64
                       and f.top_k <= L.dense_fill_max_top_k and f.dense_fill_ok())
     dense_fast = bool(dense and f.hip and f.dense_fast_on and f.lazy_tiled and (not f.acc_f64 or f.f64_w_ok())

@@ -1049,8 +1049,9 @@ def _facts(**kw):
     from rtrec_amd import score_plan as sp_
     d = dict(mode=sp_.TOPK_SPARSE, hip=True, acc_f64=False, top_k=10, n_rows=100_000, full_range=True, nonempty_shard=True,
              dense_fast_on=True, dense_fill_on=True, lazy_tiled=True, feature_rows_on=True, seg_layout_on=True, seg_supported=True,
-             dense_fill_ok=lambda: True, f64_w_ok=lambda: True, f64_x_ok=lambda: True, f64_refine_mode=lambda: 1)
-    for k in ("dense_fill_ok", "f64_w_ok", "f64_x_ok", "f64_refine_mode"):
+             dense_fill_ok=lambda: True, f64_w_ok=lambda: True, f64_x_ok=lambda: True, f64_refine_mode=lambda: 1,
+             values_ordinary=lambda: True)
+    for k in ("dense_fill_ok", "f64_w_ok", "f64_x_ok", "f64_refine_mode", "values_ordinary"):
         if k in kw and not callable(kw[k]):
             v = kw[k]
             kw[k] = (lambda v=v: v)
@@ -1106,6 +1107,17 @@ def test_score_plan_explicit_table():
         # --- CANDIDATES (bulk form): always the tiled kernel
         (dict(mode=C), dict(), (Path.TILED, "tiled", 10, False)),
         (dict(mode=C, acc_f64=True), dict(), (Path.TILED, "tiled", 10, False)),
+        # --- a NaN, an infinity or a possible overflow among the values: the tiled kernel (it follows the value rule), whatever else holds
+        (dict(values_ordinary=False), dict(), (Path.TILED, "tiled", 10, False)),
+        (dict(values_ordinary=False), dict(tiled=True), (Path.TILED, "tiled", 10, False)),
+        (dict(values_ordinary=False), dict(has_fr=False, has_sg=True), (Path.TILED, "tiled", 10, False)),
+        (dict(values_ordinary=False, n_rows=100), dict(), (Path.TILED, "tiled", 10, False)),
+        (dict(values_ordinary=False, acc_f64=True), dict(), (Path.TILED, "tiled", 10, False)),
+        (dict(values_ordinary=False, acc_f64=True, f64_w_ok=False, f64_refine_mode=2), dict(has_fr=False, has_sg=True), (Path.TILED, "tiled", 10, False)),
+        (dict(values_ordinary=False, mode=D), dict(), (Path.TILED, "tiled", 10, False)),
+        (dict(values_ordinary=False, mode=D, full_range=False), dict(), (Path.TILED, "tiled", 10, False)),
+        (dict(values_ordinary=False, mode=D, acc_f64=True), dict(), (Path.TILED, "tiled", 10, False)),
+        (dict(values_ordinary=False, mode=C), dict(), (Path.TILED, "tiled", 10, False)),
     ]
     for kw, lay, want in T:
         req, plan = _plan(**lay, **kw)
@@ -1114,6 +1126,10 @@ def test_score_plan_explicit_table():
     assert _plan(mode=D, full_range=False)[1].fill and _plan(mode=D)[1].fill                     # (fill also completes short lists on a full range)
     assert not _plan(mode=D, dense_fill_on=False)[1].fill and not _plan()[1].fill
     assert _plan(acc_f64=True, f64_x_ok=False, f64_refine_mode=1)[1].f64_signed and not _plan(acc_f64=True)[1].f64_signed
+    # ... and with values that are not ordinary no fast layout is even asked for, no fill, no refine
+    for kw in (dict(), dict(mode=D), dict(mode=D, full_range=False), dict(acc_f64=True), dict(n_rows=100)):
+        req, plan = _plan(values_ordinary=False, **kw)
+        assert not req.want and not req.dense_fast and not req.dense_fill and not plan.fill and not plan.f64_signed and not plan.lazy
 
 
 def test_score_plan_invariants_over_the_cross_product():
@@ -1122,23 +1138,24 @@ def test_score_plan_invariants_over_the_cross_product():
     import itertools
     from rtrec_amd.score_plan import Path, TOPK_DENSE as D, TOPK_SPARSE as S
     n = 0
-    for (mode, hip, f64, top_k, n_rows, full, nonempty, dfast, dfill, lazy, fr_on, sg_on, sg_sup, fill_ok, w_ok, x_ok, rmode, has_fr, has_sg, tiled) in \
+    for (mode, hip, f64, top_k, n_rows, full, nonempty, dfast, dfill, lazy, fr_on, sg_on, sg_sup, fill_ok, w_ok, x_ok, rmode, has_fr, has_sg, tiled, ordinary) in \
             itertools.product((0, 1, 2), (True, False), (False, True), (10, 15, 16, 63, 64), (100, 100_000), (True, False), (True, False),
                               (True, False), (True, False), (True, False), (True, False), (True, False), (True,), (True, False),
-                              (True, False), (True, False), (0, 1, 2), (True, False), (True, False), (True, False)):
+                              (True, False), (True, False), (0, 1, 2), (True, False), (True, False), (True, False), (True, False)):
         if w_ok and rmode == 0:
             continue                    # (a positive float32-valued W always has a refine mode)
         calls = []
         fact = lambda name, v: (lambda: (calls.append(name), v)[1])
         f = _facts(mode=mode, hip=hip, acc_f64=f64, top_k=top_k, n_rows=n_rows, full_range=full, nonempty_shard=nonempty,
                    dense_fast_on=dfast, dense_fill_on=dfill, lazy_tiled=lazy, feature_rows_on=fr_on, seg_layout_on=sg_on, seg_supported=sg_sup,
-                   dense_fill_ok=fact("fill", fill_ok), f64_w_ok=fact("w", w_ok), f64_x_ok=fact("x", x_ok), f64_refine_mode=fact("m", rmode))
+                   dense_fill_ok=fact("fill", fill_ok), f64_w_ok=fact("w", w_ok), f64_x_ok=fact("x", x_ok), f64_refine_mode=fact("m", rmode),
+                   values_ordinary=fact("v", ordinary))
         from rtrec_amd import score_plan as sp_
         req = sp_.plan_fast_layout(f)
         got_fr, got_sg = (has_fr, has_sg) if req.want else (False, False)
         plan = sp_.choose_path(f, req, got_fr, got_sg, tiled)
         n += 1
-        ctx = (mode, hip, f64, top_k, n_rows, full, nonempty, dfast, dfill, lazy, fr_on, sg_on, fill_ok, w_ok, x_ok, rmode, has_fr, has_sg, tiled, plan)
+        ctx = (mode, hip, f64, top_k, n_rows, full, nonempty, dfast, dfill, lazy, fr_on, sg_on, fill_ok, w_ok, x_ok, rmode, has_fr, has_sg, tiled, ordinary, plan)
         assert not (plan.use_fr and plan.use_sg), ctx
         assert plan.kernel == ("feature_rows" if plan.use_fr else "segments" if plan.use_sg else "tiled"), ctx
         assert (plan.path is Path.TILED) == (plan.kernel == "tiled"), ctx
@@ -1165,7 +1182,20 @@ def test_score_plan_invariants_over_the_cross_product():
             assert "w" not in calls and "x" not in calls and "m" not in calls, ctx      # float32 W: no float64 fact is ever computed
         if mode != D:
             assert "fill" not in calls, ctx
-    assert n > 100_000
+        # the value fact: false -> the tiled kernel for every row, no fast layout wanted and no other fact computed; it is
+        # asked at most once per call, and only where a fast form could otherwise be asked for
+        if not ordinary and "v" in calls:
+            assert plan.path is Path.TILED and not req.want and not plan.lazy and not plan.fill and calls == ["v"], ctx
+        if plan.path is not Path.TILED:
+            assert ordinary and calls.count("v") == 1, ctx
+        assert calls.count("v") <= 1, ctx
+        if "v" in calls:
+            assert hip and nonempty and (mode == S or (mode == D and dfast and lazy)) and (fr_on or (sg_on and sg_sup)), ctx
+        else:
+            assert not req.want, ctx
+        if not ordinary:
+            assert plan == sp_.Plan(Path.TILED, "tiled", False, False, top_k, False, False, False), ctx
+    assert n > 200_000
 
 
 # ---- the fit's decision as pure functions (rtrec_amd/fit_plan.py): explicit table + invariants over a cross product ----

@@ -4,8 +4,9 @@
 The definition is held to the oracle (oracle.recommend_batch, the restated reference) bit for bit wherever the oracle is defined --
 no NaN score -- and the builders assert, from the definition alone, that their rows hold what their names claim.  Mutated copies
 of the definition show which value set catches which defect (MUTANTS).  The CPU paths -- the tests' stand-in backend and
-SLIMElastic._topk_host -- are held to the rule on the value sets.  The device kernels are NOT run on them here: for the tiled
-selection a NaN score is outside the stated precondition, and unsafe.
+SLIMElastic._topk_host -- are held to the rule on the value sets.  The device runs the same sets against the same definition
+in tests/test_gpu_score_values.py (the tiled kernel follows the rule; the engine keeps such calls off the fast kernels), and
+tests/test_score_selection_host.py holds a host model of the tiled selection to it.
 
 The rule: a column whose score is NaN is never listed, takes no slot and is not counted; +inf is a number and is listed first, ties
 by the mode's tie rule; -inf is never listed (`minus_inf_listed=False`) although the reference's SPARSE `sorted` lists it last
